@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the GP log-likelihood hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg4|cfg2|cfg3|cfg5] [--evals-per-gpu E]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg4|cfg2|cfg3|cfg5] [--evals-per-gpu E] [--dump-outputs DIR]
 
 metric   : GP log-lik evals/sec (n x n fp64, batched over the hyperparameter grid)
 workload : cfg4 (default) = BASELINE config 4, the configuration the north_star's MFMA
@@ -474,7 +474,35 @@ def parse_args():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the product path).  gloo: rehearsal of the N > 1 code path on "
                          "a box with fewer GPUs than ranks (ranks share devices, results gathered through host memory)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (every rank's results, gathered) "
+                         "as DIR/<name>.npy in float64, for output-by-output comparison of two builds")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20140107
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as out_dir/<name>.npy in float64.  An array that does not fit the 64 MB budget left is replaced
+    by a fixed, seeded sample of its flattened elements, written with the sampled indices (<name>_index.npy, in
+    ascending order, also float64) so that two dumps of the same arguments compare element by element."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_MAX_BYTES - 2 * 128 * len(arrays)             # room for the .npy headers of every file that may be written
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > left:
+            k = left // 16                                     # the sample and its indices, 8 bytes each
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a.ravel()[idx]
+            left -= idx.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def main():
@@ -667,6 +695,9 @@ def run_loglik_workload(c):
         step()
     fence(torch, dist, world)
     elapsed = time.perf_counter() - t0
+    last = None
+    if args.dump_outputs:   # what the last timed step computed, copied before anything runs again
+        last = {"loglik": d_ll.cpu().numpy(), "beta": d_beta.cpu().numpy(), "status": d_st.cpu().numpy()}
     timing = h.get_timing()
     h.enable_timing(False)
     t0 = time.perf_counter()
@@ -765,7 +796,20 @@ def run_loglik_workload(c):
         if sec_in is not None:
             out["secondary"] = secondary_items(c, h, sec_in, cpu_sec, X, y, P, K, sigma2)
         print(json.dumps(out), flush=True)
+    if last is not None:
+        gather_and_dump(dist, world, rank, args.dump_outputs, last)
     h.close()
+
+
+def gather_and_dump(dist, world, rank, out_dir, local):
+    """Every rank's slice of each output, concatenated in rank order along the sharded (last) axis -- the shards are
+    contiguous -- and written by rank 0."""
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, local)
+        local = {k: np.concatenate([p[k] for p in parts], axis=-1) for k in local}
+    if rank == 0:
+        dump_outputs(out_dir, local)
 
 
 def small_roofline(ach, launches, fused_ms):
@@ -1145,6 +1189,10 @@ def run_predict_workload(c):
         step()
     fence(torch, dist, world)
     elapsed = time.perf_counter() - t0
+    last = None
+    if args.dump_outputs:   # the tables of the last timed step; beta and status are those of its last set's launch
+        tab = table.cpu().numpy()
+        last = {"mean": tab[:M], "var": tab[M:], "beta": d_beta.cpu().numpy(), "status": d_st.cpu().numpy()}
     timing = h.get_timing()
     h.enable_timing(False)
     t0 = time.perf_counter()
@@ -1181,6 +1229,8 @@ def run_predict_workload(c):
             out["cpu_baseline"] = {"value": cpu5["all_cores"], "unit": cpu5["unit"], "cores": cpu5["cores"], "kind": "port",
                                    "sample": cpu5["sample"], "one_core": cpu5["one_core"], "model": cpu_model()}
         print(json.dumps(out), flush=True)
+    if last is not None:
+        gather_and_dump(dist, world, rank, args.dump_outputs, last)
     h.close()
 
 

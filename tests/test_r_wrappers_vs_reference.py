@@ -1,38 +1,28 @@
 """r/ccgp.R cannot run in this container (no R).  Its wrappers around the scripts' own compare.GP / prediction / factors.frame
-assume things about those scripts; this test READS the eight reference scripts (text only -- nothing is copied, nothing is
-executed) where /root/reference exists and checks every assumption:
+assume things about those scripts; this test checks every assumption against tests/golden/r_script_facts.json, the record
+of those facts read off the eight reference scripts by tests/golden/make_r_script_facts.py (argument lists, column names,
+counts and pattern checks -- no script text):
   * every `a$name` the compare.GP / prediction wrappers read is a formal argument of that script's own definition
     (the wrappers bind arguments with match.call against those formals);
   * each script's `prediction` body contains exactly ONE `apply(pars.frame, 1, predict.post` -- the call the wrapper answers
     from the batched table by swapping `apply` in the function's environment;
   * the leading columns factors.frame builds are (p, theta1, theta2[, lambda]), then beta: what .ccgp.layout / the shim's
     LAYOUT_* and `pars[o + 1] is beta` rely on (HX:631-643, ANI:572-592, D1:750-781);
-  * logpost / factors / predict.post / Mixed.corr.* signatures match the definitions r/ccgp.R overrides them with.
-Skipped where the reference is absent (the GPU box)."""
+  * logpost / factors / predict.post / Mixed.corr.* signatures match the definitions r/ccgp.R overrides them with."""
+import json
 import os
 import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-SCRIPTS = {
-    "HX": "Heat Exchanger Emulator/Combined GP Heat Exchanger.R",
-    "GV": "Ground Vibrations Emulator/Combined GP Ground Vibrations.R",
-    "ISO": "2D Codes and Designs/2D Combined GP Isotropic Public.R",
-    "ADV": "2D Codes and Designs/2D Combined GP Isotropic Advanced.R",
-    "ANI": "2D Codes and Designs/2D Combined GP Anisotropic Public.R",
-    "BSQ": "Batch Sequential ME Designs/Batch Sequential ME Design.R",
-    "D1": "1D Codes and Designs/1D Combined GP Public.R",
-    "D1F": "1D Codes and Designs/1D Combined GP Two Families Public.R",
-}
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference scripts not present on this machine")
+with open(os.path.join(ROOT, "tests", "golden", "r_script_facts.json")) as _fh:
+    FACTS = json.load(_fh)
+SCRIPTS = sorted(FACTS)
 
 
-def script(tag):
-    with open(os.path.join(REF, SCRIPTS[tag]), encoding="latin-1") as fh:
-        return fh.read()
+def test_the_record_covers_the_eight_scripts():
+    assert SCRIPTS == ["ADV", "ANI", "BSQ", "D1", "D1F", "GV", "HX", "ISO"]
 
 
 def definition(src, name):
@@ -68,14 +58,12 @@ def rsrc():
     return re.sub(r"^  (compare\.GP|prediction|factors\.frame) <- function", r"\1 <- function", src, flags=re.M)
 
 
-@pytest.mark.parametrize("tag", sorted(SCRIPTS))
+@pytest.mark.parametrize("tag", SCRIPTS)
 def test_wrapped_arguments_are_formals_of_the_script(rsrc, tag):
-    src = script(tag)
     for fn, alternatives in (("compare.GP", {"D.test": "D.new", "D.new": "D.test"}), ("prediction", {})):
-        d = definition(src, fn)
-        if d is None:
-            assert tag == "BSQ" and False, "%s has no %s" % (tag, fn)
-        formals = set(d[0])
+        d = FACTS[tag]["formals"][fn]
+        assert d is not None, "%s has no %s" % (tag, fn)
+        formals = set(d)
         for name in wrapper_reads(rsrc, fn):
             if name == "nu":                 # read through .ccgp.nu(a): NULL where the script has no nu
                 continue
@@ -87,25 +75,24 @@ def test_wrapped_arguments_are_formals_of_the_script(rsrc, tag):
             assert "nu" not in formals
 
 
-@pytest.mark.parametrize("tag", sorted(SCRIPTS))
+@pytest.mark.parametrize("tag", SCRIPTS)
 def test_prediction_has_exactly_one_apply_over_the_frame(tag):
-    formals, body = definition(script(tag), "prediction")
-    calls = re.findall(r"apply\s*\(\s*pars\.frame\s*,\s*1\s*,\s*predict\.post", body)
-    assert len(calls) == 1, "%s: %d apply(pars.frame, 1, predict.post ...) calls" % (tag, len(calls))
-    assert len(re.findall(r"\bapply\s*\(", body)) == 1          # the wrapper swaps EVERY apply in that environment
+    formals, facts = FACTS[tag]["formals"]["prediction"], FACTS[tag]["prediction"]
+    calls = facts["apply_over_frame_calls"]
+    assert calls == 1, "%s: %d apply(pars.frame, 1, predict.post ...) calls" % (tag, calls)
+    assert facts["apply_calls"] == 1          # the wrapper swaps EVERY apply in that environment
     assert "pars.frame" in formals and "x.new" in formals and "D.train" in formals and "sigma2" in formals
     # what comes back is transposed into an S x 2 frame named mean / var: the 2 x S block the wrapper returns fits
-    assert re.search(r"data\.frame\s*\(\s*t\s*\(\s*apply", body) and re.search(r'c\("mean",\s*"var"\)', body)
+    assert facts["returns_transposed_mean_var_frame"]
 
 
-@pytest.mark.parametrize("tag", sorted(SCRIPTS))
+@pytest.mark.parametrize("tag", SCRIPTS)
 def test_frame_columns_are_the_layout_the_shim_indexes(rsrc, tag):
-    formals, body = definition(script(tag), "factors.frame")
-    m = re.search(r'names\(samp\)\s*<-\s*c\(([^)]*)\)', body)
-    cols = [c.strip().strip('"') for c in m.group(1).split(",")]
+    formals, facts = FACTS[tag]["formals"]["factors.frame"], FACTS[tag]["factors.frame"]
+    cols = facts["samp_columns"]
     want = ["p", "theta1", "theta2", "lambda"] if tag == "ANI" else ["p", "theta1", "theta2"]
     assert cols == want, (tag, cols)
-    assert re.search(r"return\s*\(\s*cbind\s*\(\s*samp\s*,\s*beta\s*,\s*prediction\.factors\s*,\s*R\.Inv\s*\)\s*\)", body)
+    assert facts["returns_samp_beta_factors_rinv"]
     # r/ccgp.R: layout 2 (four leading columns, anisotropic rates) for ANI only; ADV's frame is (p, theta1, theta2) like HX's
     lay = re.search(r"\.ccgp\.layout\s*<-\s*switch\(ccgp\.script,\s*([^)]*)\)", rsrc).group(1)
     table = dict((k.strip(), v.strip()) for k, v in (e.split("=") for e in lay.split(",") if "=" in e))
@@ -114,7 +101,7 @@ def test_frame_columns_are_the_layout_the_shim_indexes(rsrc, tag):
     assert got == {"ANI": "2L", "D1": "3L", "D1F": "4L"}.get(tag, "0L"), (tag, got)
     # y.train and D.train are formals factors.frame hands on to factors(): the wrapper's attribute comes from there
     assert "y.train" in formals and "D.train" in formals
-    assert re.search(r"factors\s*,\s*n\.train\s*=\s*n\.train\s*,\s*y\.train\s*=\s*y\.train", body.replace("\n", " "))
+    assert facts["passes_n_train_y_train_to_factors"]
 
 
 def test_where_each_predict_post_finds_beta_and_its_second_scale():
@@ -123,31 +110,29 @@ def test_where_each_predict_post_finds_beta_and_its_second_scale():
     -- the inconsistency LAYOUT_ADV_WRITTEN reproduces on request and the batched path resolves towards the training kernel."""
     shim = open(os.path.join(ROOT, "r", "ccgp_shim.c")).read()
     assert re.search(r"layout == LAYOUT_ANI \? 4 : 3;\s*/\* pars\[o \+ 1\] is beta", shim)
-    for tag in sorted(SCRIPTS):
-        _, body = definition(script(tag), "predict.post")
+    for tag in SCRIPTS:
         col = 5 if tag == "ANI" else 4
-        assert re.search(r"beta\s*<-\s*as\.numeric\(pars\[%d\]\)" % col, body), (tag, col)
-    _, adv = definition(script("ADV"), "predict.post")
-    assert re.search(r"lambda\s*<-\s*as\.numeric\(pars\[3\]\)", adv) and "theta1*(1+lambda)" in adv.replace(" ", "")
+        assert FACTS[tag]["predict.post"]["beta_column"] == col, (tag, col)
+    adv = FACTS["ADV"]["predict.post"]
+    assert adv["lambda_column"] == 3 and adv["scales_theta1_by_one_plus_lambda"]
     assert re.search(r"layout == LAYOUT_ADV_WRITTEN \? t1 \* \(1\.0 \+ t2\) : t2", shim)
 
 
-@pytest.mark.parametrize("tag", sorted(SCRIPTS))
+@pytest.mark.parametrize("tag", SCRIPTS)
 def test_overridden_signatures_match(tag):
     """The argument lists r/ccgp.R defines for this script's variant against the script's own."""
-    src = script(tag)
     want = {
         "logpost": {"HX": 6, "ADV": 6, "D1": 5, "D1F": 5}.get(tag, 4),
         "factors": 3,
         "predict.post": 5 if tag in ("D1", "D1F") else 4,
     }
     for fn, nargs in want.items():
-        d = definition(src, fn)
+        d = FACTS[tag]["formals"][fn]
         assert d is not None, (tag, fn)
-        assert len(d[0]) == nargs, (tag, fn, d[0])
-    f, _ = definition(src, "factors")
+        assert len(d) == nargs, (tag, fn, d)
+    f = FACTS[tag]["formals"]["factors"]
     assert f == ["MCMC.data", "n.train", "y.train"]
-    f, _ = definition(src, "predict.post")
+    f = FACTS[tag]["formals"]["predict.post"]
     assert f[:4] == ["x.new", "D.train", "pars", "sigma2"]
 
 
@@ -157,27 +142,19 @@ def test_metro_loop_is_what_the_block_wise_metro_assumes(rsrc, tag):
     exactly  u <- runif(1)  and then  rmnorm(1, as.vector(theta.old), sqrt(2)*pars$v)  per iteration, in this order, accepts on
     R > log(u) with R = l.cand$val - l.old$val, and runs Geweke's test on the first column of the last samp.size accepted draws
     whenever (k-1) >= samp.size & (k-1) %% batch.size == 0 -- and if every call site passes Metro's arguments by position."""
-    src = script(tag)
-    formals, body = definition(src, "Metro")
-    flat = re.sub(r"\s+", "", body)
+    formals, facts = FACTS[tag]["formals"]["Metro"], FACTS[tag]["Metro"]
     assert formals[:8] == ["start", "N", "samp.size", "batch.size", "alpha", "D.train", "sigma2", "y"]
     assert len(formals) == (10 if tag in ("HX", "ADV") else 9), formals
-    i_u, i_c = flat.index("u<-runif(1)"), flat.index("theta.candidate<-rmnorm(1,as.vector(theta.old),sqrt(2)*pars$v)")
-    assert 0 < i_u < i_c and flat.count("runif(") == 1 and flat.count("rmnorm(") == 1 and "rnorm(" not in flat.replace("rmnorm(", "")
-    assert "R<-l.cand$val-l.old$val" in flat and "if(R>log(u))" in flat
-    assert "while(k<=N&pv<alpha)" in flat
-    assert "if((k-1)>=samp.size&(k-1)%%batch.size==0)" in flat
-    assert "geweke.diag(mcmc(samp[(k-samp.size):(k-1)]))$z" in flat
-    assert ("est<-laplace(logpost.val,start)" in flat or "est<-laplace(logpost.val,start,...)" in flat) and "pars<-list(mu=est$mode,v=est$var)" in flat
-    assert "theta.old<-pars$mu" in flat and "k=1" in flat
-    tail = "R.Inv=R.Inv[(k-samp.size):(k-1)]" + (",logpost=log.posterior[(k-samp.size):(k-1)]" if tag == "BSQ" else "") + "))"
-    assert flat.rstrip("}").endswith(tail)        # the list r/ccgp.R's Metro returns (it always adds BSQ's `logpost`)
+    assert facts["draws_runif_then_rmnorm_only"]
+    assert facts["accepts_on_log_ratio"]
+    assert facts["loops_while_k_le_N_and_pv_lt_alpha"]
+    assert facts["geweke_every_batch_after_samp_size"]
+    assert facts["geweke_on_last_samp_size_draws"]
+    assert facts["starts_from_laplace_mode"]
+    assert facts["returns_last_samp_size_with_rinv"]        # the list r/ccgp.R's Metro returns (it always adds BSQ's `logpost`)
     assert "logpost = log.posterior[(k - samp.size):(k - 1)]" in open(os.path.join(ROOT, "r", "ccgp.R")).read()
     # every call of Metro in the script passes its arguments by position
-    for m in re.finditer(r"\bMetro\s*\(([^)]*)\)", src):
-        if "function" in src[max(0, m.start() - 12):m.start()]:
-            continue
-        assert "=" not in m.group(1), m.group(0)
+    assert facts["every_call_passes_arguments_by_position"]
     # r/ccgp.R's replacement takes the same number of arguments
     r_formals = re.search(r"Metro <- function\(([^)]*)\)\s*\n\s*\.ccgp\.Metro\(start, N, samp\.size, batch\.size, alpha, D\.train, sigma2, y,\s*\n\s*c\(\.ccgp\.prior",
                           open(os.path.join(ROOT, "r", "ccgp.R")).read())
