@@ -579,3 +579,179 @@ def test_function_2d(x, y, code):
     if code == 5:
         return math.sin(9 * x - 4.5) / (9 * x - 4.5) * math.sin(12 * y - 6) / (12 * y - 6)
     raise ValueError(code)
+
+
+# --------------------------------------------------------------------------- analytic gradient, extended precision
+# The reference has no gradient (HX:493 differences numerically), so the library's ccgp_loglik_grad_batch is held against
+# the closed form it implements.  With Sigma = sigma2 sum_c w_c^2 R_c (the mixed matrix of mixed_corr_matrix_general times
+# sigma2 sum_c w_c^2), alpha = Sigma^-1 (y - beta 1) and M = (alpha alpha' - Sigma^-1) / 2, the profiled log-likelihood has
+#   d/dw_q     = sum_ab M_ab  2 sigma2 w_q R_q,ab
+#   d/dtheta_qk = sum_ab M_ab (-sigma2 w_q^2 (x_ak - x_bk)^2 R_q,ab)
+# (beta is stationary, so its own derivative drops out).  Evaluated in np.longdouble through the hand-written Cholesky
+# below, or in fp64 through LAPACK; nothing here calls the device library.
+LONGDOUBLE_EPS_MAX = 1e-18
+# The per-component acceptance band of a device gradient (tests/test_gpu_gradient_exact.py states why this C):
+#   |g_dev[j] - g_ref[j]| <= GRAD_TOL_C * eps * cond1(R) * (1 + rho) * scale[j],   rho = expanded_form_magnitude(...)
+GRAD_TOL_C = 128.0
+
+
+def expanded_form_magnitude(X, row, K, d):
+    """rho = max_c,a 2 sum_k theta_ck x_ak^2: the size of the terms of the expanded exponent u_a + u_b - 2 sum_k theta_k x_ak x_bk
+    (HX:352-355) that the device, like the reference scripts, evaluates.  Its absolute rounding, ~eps rho, is a relative
+    perturbation of every kernel value that no algorithm downstream can undo."""
+    X = np.asarray(X, dtype=np.float64)
+    _, Th = unpack_params(row, K, d)
+    return float(2.0 * ((X ** 2) @ np.asarray(Th, dtype=np.float64).T).max())
+
+
+def grad_tolerance(scale, kappa, rho=0.0, c=GRAD_TOL_C):
+    return c * np.finfo(np.float64).eps * kappa * (1.0 + rho) * np.asarray(scale, dtype=np.float64)
+
+
+def require_extended_precision():
+    """The long-double reference is only worth its name where long double is wider than fp64 (x87 80-bit: eps 1.1e-19)."""
+    eps = float(np.finfo(np.longdouble).eps)
+    if eps > LONGDOUBLE_EPS_MAX:
+        raise RuntimeError("np.longdouble has eps %.3g > %.0e on this host: the extended-precision gradient reference "
+                           "is unavailable (no fall-back to fp64)" % (eps, LONGDOUBLE_EPS_MAX))
+
+
+def _chol_inverse(A, dtype):
+    """(Sigma^-1, log det Sigma) of a symmetric positive definite A.  fp64: LAPACK (dpotrf / dpotri).  long double: a
+    column Cholesky, then L^-1 by forward substitution on the identity and Sigma^-1 = L^-T L^-1, vectorised over rows."""
+    if dtype == np.float64:
+        c, low = sla.cho_factor(np.asarray(A, dtype=np.float64), lower=True)
+        inv, info = sla.lapack.dpotri(c, lower=1)
+        if info != 0:
+            raise np.linalg.LinAlgError("dpotri failed")
+        inv = np.tril(inv) + np.tril(inv, -1).T
+        return inv, 2.0 * float(np.log(np.diag(c)).sum())
+    require_extended_precision()
+    A = np.asarray(A, dtype=dtype)
+    n = A.shape[0]
+    L = np.zeros((n, n), dtype=dtype)
+    for j in range(n):
+        v = A[j:, j] - L[j:, :j] @ L[j, :j]
+        if not v[0] > 0:
+            raise np.linalg.LinAlgError("not positive definite at pivot %d" % j)
+        L[j, j] = np.sqrt(v[0])
+        L[j + 1:, j] = v[1:] / L[j, j]
+    Z = np.zeros((n, n), dtype=dtype)           # Z = L^-1, lower triangular
+    for i in range(n):
+        Z[i, :i] = -(L[i, :i] @ Z[:i, :i]) / L[i, i]
+        Z[i, i] = dtype(1) / L[i, i]
+    return Z.T @ Z, dtype(2) * np.log(np.diag(L)).sum()
+
+
+def _sq_dist(X, k, dtype):
+    x = np.asarray(X[:, k], dtype=dtype)
+    return (x[:, None] - x[None, :]) ** 2
+
+
+def component_corr(X, theta_c, dtype=np.float64):
+    """R_c in the direct squared-difference form (exp(-sum_k theta_ck (x_ak - x_bk)^2)), in dtype."""
+    X = np.asarray(X, dtype=np.float64)
+    acc = np.zeros((X.shape[0], X.shape[0]), dtype=dtype)
+    for k in range(X.shape[1]):
+        acc += dtype(theta_c[k]) * _sq_dist(X, k, dtype)
+    return np.exp(-acc)
+
+
+def loglik_grad_parts(X, y, row, K, d, sigma2, dtype=np.float64):
+    """The pieces of the closed form in dtype: dict(Sigma, Sinv, Rc (list), M, alpha, u, loglik, beta).  u = Sigma^-1 1 /
+    1' Sigma^-1 1 are the weights with beta = u' y.  Raises LinAlgError on a matrix that is not positive definite."""
+    X = np.asarray(X, dtype=np.float64)
+    yv = np.asarray(y, dtype=dtype).reshape(-1)
+    n = yv.shape[0]
+    w, Th = unpack_params(row, K, d)
+    s2 = dtype(sigma2)
+    Rc = [component_corr(X, Th[c], dtype) for c in range(K)]
+    Sigma = np.zeros((n, n), dtype=dtype)
+    for c in range(K):
+        Sigma += (s2 * dtype(w[c]) ** 2) * Rc[c]
+    Sinv, logdet = _chol_inverse(Sigma, dtype)
+    s1 = Sinv.sum(axis=0)
+    u = s1 / s1.sum()
+    beta = u @ yv
+    alpha = Sinv @ (yv - beta)
+    q = (yv - beta) @ alpha
+    ll = -(dtype(n) * dtype(LOG_2PI) + logdet + q) / dtype(2)
+    M = (np.outer(alpha, alpha) - Sinv) / dtype(2)
+    return dict(Sigma=Sigma, Sinv=Sinv, Rc=Rc, M=M, alpha=alpha, u=u, loglik=ll, beta=beta)
+
+
+def grad_from_parts(parts, X, row, K, d, sigma2, weights=None):
+    """(grad, scale) from the closed form: grad[j] = sum_ab W_ab M_ab dSigma_j,ab, scale[j] = sum_ab W_ab |M_ab| |dSigma_j,ab|.
+    weights: an n x n array W (default all ones); the test of the tolerance passes altered weights to model kernel bugs."""
+    X = np.asarray(X, dtype=np.float64)
+    M, Rc = parts["M"], parts["Rc"]
+    dtype = M.dtype.type
+    WM = M if weights is None else M * weights
+    aWM = np.abs(WM)
+    w, _ = unpack_params(row, K, d)
+    s2 = dtype(sigma2)
+    P = K + K * d
+    grad = np.zeros(P, dtype=dtype)
+    scale = np.zeros(P, dtype=dtype)
+    for q in range(K):
+        dw = dtype(2) * s2 * dtype(w[q]) * Rc[q]
+        grad[q] = (WM * dw).sum()
+        scale[q] = (aWM * np.abs(dw)).sum()
+        cq = -s2 * dtype(w[q]) ** 2
+        for k in range(d):
+            dt = cq * (_sq_dist(X, k, dtype) * Rc[q])
+            grad[K + q * d + k] = (WM * dt).sum()
+            scale[K + q * d + k] = (aWM * np.abs(dt)).sum()
+    return grad, scale
+
+
+def loglik_grad_exact(X, y, row, K, d, sigma2, dtype=np.float64):
+    """Closed-form gradient of the profiled log-likelihood with respect to the raw C-ABI row (w_1..w_K, theta_c,k).
+    Returns (loglik, beta, grad, scale), all float64 arrays / scalars rounded from dtype (np.float64: LAPACK; np.longdouble:
+    the hand-written Cholesky, about 1e-19 relative).  scale[j] = sum_ab |M_ab| |dSigma_ab / d row_j| is the cancellation-free
+    size of component j: a perturbation of every term of the sum by a relative eps moves grad[j] by at most eps * scale[j]."""
+    dtype = np.dtype(dtype).type
+    parts = loglik_grad_parts(X, y, row, K, d, sigma2, dtype)
+    grad, scale = grad_from_parts(parts, X, row, K, d, sigma2)
+    return float(parts["loglik"]), float(parts["beta"]), grad.astype(np.float64), scale.astype(np.float64)
+
+
+def loglik_beta_scales(parts, y):
+    """Cancellation-free sizes of the log-likelihood and beta, in the sense of loglik_grad_exact's scale:
+    loglik: n/2 + (|alpha|' |Sigma| |alpha|) / 2 (the log-determinant and the quadratic form); beta: sum_i |u_i| |y_i|."""
+    n = parts["alpha"].shape[0]
+    a = np.abs(parts["alpha"])
+    s_ll = 0.5 * n + 0.5 * float(a @ np.abs(parts["Sigma"]) @ a)
+    s_beta = float(np.abs(parts["u"]) @ np.abs(np.asarray(y, dtype=np.float64).reshape(-1)))
+    return s_ll, s_beta
+
+
+def cond1(A, A_inv):
+    """1-norm condition number ||A||_1 ||A^-1||_1 from an accurate inverse."""
+    return float(np.abs(np.asarray(A, np.float64)).sum(axis=0).max() * np.abs(np.asarray(A_inv, np.float64)).sum(axis=0).max())
+
+
+def solve_inverse_exact(R, dtype=np.longdouble):
+    """R^-1 of a symmetric positive definite R (solve(R), HX:454, for the matrices the device inverts) in dtype through
+    _chol_inverse.  Returns the dtype array."""
+    dtype = np.dtype(dtype).type
+    inv, _ = _chol_inverse(np.asarray(R, dtype=dtype), dtype)
+    return inv
+
+
+def conditioned_row(X, K, d, rng, kappa_max=1e8):
+    """A random anisotropic draw (w_1..w_K, theta_c,k) for the gradient tests whose mixed matrix has cond1 <= kappa_max:
+    length scales spread over a factor 20 around the design spacing (n^(-1/d)), the last component rough, then every theta
+    scaled up by 1.5 until the fp64 1-norm condition number is within bound.  Returns (row, cond1)."""
+    X = np.asarray(X, dtype=np.float64)
+    n = X.shape[0]
+    rough = 2.0 * n ** (2.0 / d) / d
+    w = 0.2 + 0.6 * rng.random(K)
+    Th = rough * np.exp(rng.uniform(np.log(0.05), 0.0, size=(K, d)))
+    Th[-1] = rng.uniform(rough, 2.0 * rough, d)
+    for _ in range(200):
+        kappa = float(np.linalg.cond(mixed_corr_matrix_general(X, w, Th), 1))
+        if kappa <= kappa_max:
+            return np.concatenate([w, Th.ravel()]), kappa
+        Th = Th * 1.5
+    raise RuntimeError("no draw with cond1 <= %g" % kappa_max)

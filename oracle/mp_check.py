@@ -129,3 +129,34 @@ def halton2(i):
         i >>= 1
         f /= 2
     return r
+
+
+def loglik_grad(X, y, w, Theta, sigma2):
+    """50-digit gradient of the profiled log-likelihood with respect to (w_1..w_K, theta_c,k), as in
+    ccgp_oracle.loglik_grad_exact but from this module's own pieces: Sigma^-1 = L^-T L^-1 through forward(),
+    alpha = Sigma^-1 (y - beta 1), M = (alpha alpha' - Sigma^-1) / 2, summed over the lower triangle, every off-diagonal
+    pair twice and the diagonal once (the pairs the device visits).  Returns a list of mpf."""
+    n, K, d = len(y), len(w), len(Theta[0])
+    Xm = _mpf_matrix(X)
+    wm = [mp.mpf(float(v)) for v in w]
+    Tm = _mpf_matrix(Theta)
+    s2 = mp.mpf(float(sigma2))
+    Rc = [[[mp.exp(-sum(Tm[c][k] * (Xm[i][k] - Xm[j][k]) ** 2 for k in range(d))) for j in range(n)] for i in range(n)]
+          for c in range(K)]
+    S = [[s2 * sum(wm[c] ** 2 * Rc[c][i][j] for c in range(K)) for j in range(n)] for i in range(n)]
+    L = cholesky(S)
+    Z = [forward(L, [mp.mpf(1) if r == i else mp.mpf(0) for r in range(n)]) for i in range(n)]   # column i of L^-1
+    Sinv = [[sum(Z[i][r] * Z[j][r] for r in range(n)) for j in range(n)] for i in range(n)]
+    ym = [mp.mpf(float(v)) for v in y]
+    s1 = [sum(row) for row in Sinv]
+    beta = sum(a * b for a, b in zip(s1, ym)) / sum(s1)
+    alpha = [sum(Sinv[i][j] * (ym[j] - beta) for j in range(n)) for i in range(n)]
+    g = [mp.mpf(0)] * (K + K * d)
+    for i in range(n):
+        for j in range(i + 1):
+            m = (alpha[i] * alpha[j] - Sinv[i][j]) / 2 * (2 if i != j else 1)
+            for c in range(K):
+                g[c] += m * 2 * s2 * wm[c] * Rc[c][i][j]
+                for k in range(d):
+                    g[K + c * d + k] -= m * s2 * wm[c] ** 2 * (Xm[i][k] - Xm[j][k]) ** 2 * Rc[c][i][j]
+    return g

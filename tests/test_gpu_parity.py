@@ -1145,6 +1145,10 @@ def test_small_n_gradient_pass_structure(handle, n, d, K):
     assert ll[0] == pytest.approx(orc.loglik_general(X, y, w, T, 0.8)[0], rel=1e-9)
     fd = orc.loglik_grad_fd(X, y, row, K, d, 0.8)
     np.testing.assert_allclose(grad[0], fd, rtol=5e-5, atol=5e-5 * np.abs(fd).max())
+    w1, T1 = orc.unpack_params(row * 1.01, K, d)
+    assert ll[1] == pytest.approx(orc.loglik_general(X, y, w1, T1, 0.8)[0], rel=1e-9)
+    fd1 = orc.loglik_grad_fd(X, y, row * 1.01, K, d, 0.8)
+    np.testing.assert_allclose(grad[1], fd1, rtol=5e-5, atol=5e-5 * np.abs(fd1).max())
 
 
 # ------------------------------------------------------------------------------- a10 / a11: kept-factor prediction (round 5)

@@ -240,3 +240,112 @@ def test_log_likeli_of_the_1d_scripts_known_answer():
     r = y - beta
     s2 = (r @ np.linalg.solve(R, r)) / 8
     assert orc.log_likeli_1d(nu, 0.25, X, y) == pytest.approx(np.log(w).sum() + 8 * math.log(s2), rel=1e-9)
+
+
+# --------------------------------------------------------------------------- exact gradient reference (host only)
+LD_EPS = float(np.finfo(np.longdouble).eps)
+F64_EPS = float(np.finfo(np.float64).eps)
+
+
+def _grad_case(n, d, K, seed, sigma2=1.3):
+    from conftest import synthetic_design
+    X, y = synthetic_design(n, d, seed=seed)
+    row, _ = orc.conditioned_row(X, K, d, np.random.default_rng(seed), kappa_max=1e6)
+    return X, y, row, sigma2
+
+
+def test_host_has_extended_precision():
+    """The gradient reference needs np.longdouble wider than fp64; it never falls back quietly."""
+    orc.require_extended_precision()
+
+
+@pytest.mark.parametrize("n,d,K", [(12, 1, 1), (17, 4, 1), (20, 1, 3), (24, 4, 3)])
+def test_exact_gradient_fp64_longdouble_and_50_digits_agree(n, d, K):
+    orc.require_extended_precision()
+    X, y, row, s2 = _grad_case(n, d, K, seed=100 + n)
+    parts = orc.loglik_grad_parts(X, y, row, K, d, s2, np.longdouble)
+    kappa = orc.cond1(parts["Sigma"], parts["Sinv"])
+    ll_ld, beta_ld, g_ld, scale = orc.loglik_grad_exact(X, y, row, K, d, s2, np.longdouble)
+    ll_64, beta_64, g_64, _ = orc.loglik_grad_exact(X, y, row, K, d, s2, np.float64)
+    w, Th = orc.unpack_params(row, K, d)
+    g_mp = np.array([float(v) for v in mp_check.loglik_grad(X, y, w, Th, s2)])
+    ll_mp, beta_mp = (float(v) for v in mp_check.loglik(X, y, w, Th, s2))
+    # long double against 50 digits: a few long-double ulps of cond x scale (plus the fp64 rounding of the results)
+    assert np.all(np.abs(g_ld - g_mp) <= 64 * LD_EPS * kappa * scale + 2 * F64_EPS * np.abs(g_mp)), (g_ld - g_mp) / scale
+    assert ll_ld == pytest.approx(ll_mp, rel=1e-15) and beta_ld == pytest.approx(beta_mp, rel=1e-14, abs=1e-15)
+    # the fp64 closed form (LAPACK) meets the same band the device is held to
+    assert np.all(np.abs(g_64 - g_mp) <= orc.grad_tolerance(scale, kappa)), (g_64 - g_mp) / scale
+    assert ll_64 == pytest.approx(ll_mp, rel=1e-12) and beta_64 == pytest.approx(beta_mp, rel=1e-11, abs=1e-13)
+
+
+@pytest.mark.parametrize("n,d,K", [(60, 3, 2), (33, 5, 4)])
+def test_exact_gradient_against_central_differences(n, d, K):
+    """Central differences with step h_j = 1e-6 max(1, |row_j|) reach about 1e-7 of scale[j] (truncation) plus the
+    cancellation of two log-likelihoods, ~10 eps |ll| / h_j; the closed form must sit inside that in every component."""
+    X, y, row, s2 = _grad_case(n, d, K, seed=7 * n)
+    ll, _, g, scale = orc.loglik_grad_exact(X, y, row, K, d, s2, np.longdouble)
+    fd = orc.loglik_grad_fd(X, y, row, K, d, s2)
+    h = 1e-6 * np.maximum(1.0, np.abs(row))
+    assert np.all(np.abs(fd - g) <= 1e-7 * scale + 10 * F64_EPS * max(1.0, abs(ll)) / h)
+
+
+def _rejected(g_mut, g_ref, scale, kappa, X, row, K, d):
+    rho = orc.expanded_form_magnitude(X, row, K, d)
+    return bool(np.any(np.abs(g_mut - g_ref) > orc.grad_tolerance(scale, kappa, rho)))
+
+
+def _mutation_case(n, d, K, seed):
+    X, y, row, s2 = _grad_case(n, d, K, seed)
+    parts = orc.loglik_grad_parts(X, y, row, K, d, s2, np.longdouble)
+    kappa = orc.cond1(parts["Sigma"], parts["Sinv"])
+    g, scale = orc.grad_from_parts(parts, X, row, K, d, s2)
+    return X, row, s2, parts, kappa, g, scale
+
+
+def test_gradient_tolerance_rejects_the_kernel_bugs_it_is_meant_to_catch():
+    """The band of tests/test_gpu_gradient_exact.py must be able to fail: each model of a plausible kernel bug, applied to
+    the reference formula, moves at least one component outside it."""
+    orc.require_extended_precision()
+    # diagonal pairs weighted 1 instead of 1/2 (the full sum counts each diagonal term twice)
+    for n, d, K in [(40, 3, 2), (130, 2, 1)]:
+        X, row, s2, parts, kappa, g, scale = _mutation_case(n, d, K, seed=n)
+        W = np.ones((n, n)) + np.eye(n)
+        gm, _ = orc.grad_from_parts(parts, X, row, K, d, s2, weights=W)
+        assert _rejected(gm, g, scale, kappa, X, row, K, d), "diagonal weight"
+    # one lower 64 x 64 tile block of M dropped or doubled at n = 193 (three full row blocks and a one-row ragged one)
+    n, d, K = 193, 3, 2
+    X, row, s2, parts, kappa, g, scale = _mutation_case(n, d, K, seed=193)
+    for (I, J) in [(1, 0), (2, 2), (3, 0), (3, 3)]:
+        for factor in (0.0, 2.0):
+            W = np.ones((n, n))
+            W[64 * I:64 * I + 64, 64 * J:64 * J + 64] = factor
+            W[64 * J:64 * J + 64, 64 * I:64 * I + 64] = factor
+            gm, _ = orc.grad_from_parts(parts, X, row, K, d, s2, weights=W)
+            assert _rejected(gm, g, scale, kappa, X, row, K, d), ("tile", I, J, factor)
+    # a padded dimension slot clamped to kk = d - 1 accumulating into dimension d - 1 (d = 5: a KG = 4 pass pads 3 slots)
+    n, d, K = 50, 5, 2
+    X, row, s2, parts, kappa, g, scale = _mutation_case(n, d, K, seed=5)
+    gm = g.copy()
+    for q in range(K):
+        gm[K + q * d + d - 1] += g[K + q * d + d - 1]
+    assert _rejected(gm, g, scale, kappa, X, row, K, d), "padded dimension"
+    # the last component group (components 6, 7 of K = 8 in groups of three) never contracted
+    n, d, K = 40, 4, 8
+    X, row, s2, parts, kappa, g, scale = _mutation_case(n, d, K, seed=8)
+    gm = g.copy()
+    for q in (6, 7):
+        gm[q] = 0.0
+        gm[K + q * d:K + (q + 1) * d] = 0.0
+    assert _rejected(gm, g, scale, kappa, X, row, K, d), "component group"
+
+
+def test_exact_inverse_against_lapack():
+    orc.require_extended_precision()
+    X, y, row, s2 = _grad_case(70, 3, 2, seed=70)
+    w, Th = orc.unpack_params(row, 2, 3)
+    R = orc.mixed_corr_matrix_general(X, w, Th)
+    Rinv = orc.solve_inverse_exact(R)
+    kappa = orc.cond1(R, Rinv)
+    assert np.abs(np.asarray(Rinv @ R.astype(np.longdouble) - np.eye(70), dtype=np.float64)).max() <= 70 * 70 * LD_EPS * kappa
+    bound = np.abs(np.asarray(Rinv, np.float64)) @ np.abs(R) @ np.abs(np.asarray(Rinv, np.float64))
+    assert np.all(np.abs(np.linalg.inv(R) - np.asarray(Rinv, np.float64)) <= 16 * 70 * F64_EPS * bound)
