@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the GP log-likelihood hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg4|cfg2|cfg3|cfg5] [--evals-per-gpu E] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg4|cfg2|cfg3|cfg5] [--evals-per-gpu E] [--dump-outputs DIR] [--full]
 
 metric   : GP log-lik evals/sec (n x n fp64, batched over the hyperparameter grid)
 workload : cfg4 (default) = BASELINE config 4, the configuration the north_star's MFMA
@@ -17,6 +17,12 @@ step     : one pass of the hot path over this rank's batch -- covariance build, 
 One rank per GPU.  Under torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE set) this process IS a rank; a plain
 `python bench.py --gpus N` with N > 1 starts the N ranks itself as fresh child processes before touching the GPU.
 Rank 0 prints ONE JSON line.
+plain run: inputs, warm-up, the K timed steps, --dump-outputs, the result line (the roofline comes from the events of
+           the timed steps themselves).
+--full   : everything else as well -- the CPU baselines and the secondary workloads (N = 1; --no-cpu-baseline and
+           --no-secondary leave them out), the K steps again without events (notiming_ms_per_step), one step with every
+           launch group timed (kernel_ms_per_step), and the checks of what was timed: failed / non-finite results, the
+           all-gather against every rank's slice, cfg4's CPU potrf digest (the run aborts on a mismatch).
 """
 import argparse
 import json
@@ -469,8 +475,11 @@ def parse_args():
     ap.add_argument("--ws-limit-gib", type=float, default=0.0,
                     help="cap the device scratch (ccgp_set_workspace_limit) to force multi-chunk batches")
     ap.add_argument("--n", type=int, default=4096, help="cfg4 matrix order (parity/debug runs only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the secondary workloads, the per-kernel breakdown, the no-event region and "
+                         "the checks of the timed results (see the module docstring); a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary workloads")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the product path).  gloo: rehearsal of the N > 1 code path on "
                          "a box with fewer GPUs than ranks (ranks share devices, results gathered through host memory)")
@@ -623,11 +632,11 @@ def run_loglik_workload(c):
     gat = shard.RowGatherer(units, tail=(unit_rows,), dtype=torch.float64, device=gdev) if world > 1 else None
     h_ll = torch.empty(B, dtype=torch.float64).pin_memory() if host_gather else None
 
-    # CPU legs first (rank 0, N = 1 only), so that the GPU legs that follow are one contiguous stretch of device work
+    # CPU legs first (--full, rank 0, N = 1 only), so that the GPU legs that follow are one contiguous stretch of device work
     cpu_main, cpu_sec, sec_in = None, {}, None
-    if rank == 0 and world == 1 and args.workload == "cfg4" and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and args.workload == "cfg4" and not args.no_secondary:
         sec_in = {"cfg2": cfg2_inputs(), "cfg3": cfg3_inputs(), "cfg5": cfg5_inputs()}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_main = cpu_baseline(args.workload, X, y, P, K, sigma2, mode, tau2)
         if sec_in is not None:
             X2, y2, P2, K2, s22 = sec_in["cfg2"]
@@ -678,9 +687,9 @@ def run_loglik_workload(c):
     warm_up(torch, dist, world, step, args.warmup,
             (lambda: h.loglik_batch_dev(dX, n, d, dy, K, dP, B, sigma2, mode, tau2, d_ll, d_beta, d_st)) if n <= 128 else None)
     # HIP events inside the timed region only around the launches of the roofline kernel (two event records
-    # per launch are not free: 96 launch groups per step); the per-kernel breakdown comes from one extra,
-    # untimed step afterwards, and a second region of the same K steps WITHOUT any event gives the cost of the
-    # in-region events (notiming_ms_per_step).
+    # per launch are not free: 96 launch groups per step); with --full the per-kernel breakdown comes from one
+    # extra, untimed step afterwards, and a second region of the same K steps WITHOUT any event gives the cost of
+    # the in-region events (notiming_ms_per_step).
     if n <= 128:
         main_id = "fused"
     else:   # which kind of sweep the library runs for this chunk: one untimed probe step with every group timed
@@ -700,37 +709,40 @@ def run_loglik_workload(c):
         last = {"loglik": d_ll.cpu().numpy(), "beta": d_beta.cpu().numpy(), "status": d_st.cpu().numpy()}
     timing = h.get_timing()
     h.enable_timing(False)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence(torch, dist, world)
-    elapsed_notiming = time.perf_counter() - t0
-    h.enable_timing(True)
-    step()
-    fence(torch, dist, world)
-    breakdown = h.get_timing()
-    h.enable_timing(False)
     elapsed = max_over_ranks(torch, dist, world, gdev, elapsed)
-    elapsed_notiming = max_over_ranks(torch, dist, world, gdev, elapsed_notiming)
-    if world > 1:
-        # every rank now holds every shard's log-likelihoods: check the gather against the local slice
-        full = gathered[0].reshape(-1)
-        assert full.shape[0] == total and torch.equal(full[lo:hi].to(dev), d_ll), "all-gather mismatch"
-    bad = int((d_st != 0).sum().item())
-    finite = bool(torch.isfinite(d_ll).all().item())
-    # what was just timed, against CPU potrf + forward solves of the same draws (tests/golden/make_cfg4_digest.py)
-    digest_ok = None
-    if args.workload == "cfg4" and n == 4096 and total <= 512:
-        try:
-            with open(os.path.join(ROOT, "tests", "golden", "cfg4_loglik_512.json")) as fh:
-                ref = json.load(fh)
-            got_ll, got_b = d_ll.cpu().numpy(), d_beta.cpu().numpy()
-            digest_ok = bool(np.allclose(got_ll, np.array(ref["loglik"])[lo:hi], rtol=1e-9, atol=0.0) and
-                             np.allclose(got_b, np.array(ref["beta"])[lo:hi], rtol=1e-7, atol=1e-10))
-        except FileNotFoundError:
-            digest_ok = None
-        if digest_ok is False and not os.environ.get("CCGP_BENCH_ALLOW_MISMATCH"):   # (timing ablations set it)
-            raise SystemExit("bench.py: rank %d log-likelihoods differ from tests/golden/cfg4_loglik_512.json" % rank)
+    checked = {}
+    if args.full:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence(torch, dist, world)
+        elapsed_notiming = time.perf_counter() - t0
+        h.enable_timing(True)
+        step()
+        fence(torch, dist, world)
+        breakdown = h.get_timing()
+        h.enable_timing(False)
+        elapsed_notiming = max_over_ranks(torch, dist, world, gdev, elapsed_notiming)
+        if world > 1:
+            # every rank now holds every shard's log-likelihoods: check the gather against the local slice
+            full = gathered[0].reshape(-1)
+            assert full.shape[0] == total and torch.equal(full[lo:hi].to(dev), d_ll), "all-gather mismatch"
+        bad = int((d_st != 0).sum().item())
+        finite = bool(torch.isfinite(d_ll).all().item())
+        # what was just timed, against CPU potrf + forward solves of the same draws (tests/golden/make_cfg4_digest.py)
+        digest_ok = None
+        if args.workload == "cfg4" and n == 4096 and total <= 512:
+            try:
+                with open(os.path.join(ROOT, "tests", "golden", "cfg4_loglik_512.json")) as fh:
+                    ref = json.load(fh)
+                got_ll, got_b = d_ll.cpu().numpy(), d_beta.cpu().numpy()
+                digest_ok = bool(np.allclose(got_ll, np.array(ref["loglik"])[lo:hi], rtol=1e-9, atol=0.0) and
+                                 np.allclose(got_b, np.array(ref["beta"])[lo:hi], rtol=1e-7, atol=1e-10))
+            except FileNotFoundError:
+                digest_ok = None
+            if digest_ok is False and not os.environ.get("CCGP_BENCH_ALLOW_MISMATCH"):   # (timing ablations set it)
+                raise SystemExit("bench.py: rank %d log-likelihoods differ from tests/golden/cfg4_loglik_512.json" % rank)
+        checked = {"failed_evals": bad, "all_finite": finite, "matches_cpu_potrf_digest": digest_ok}
 
     if rank == 0:
         value = total * args.steps / elapsed
@@ -743,14 +755,16 @@ def run_loglik_workload(c):
             "config": {"workload": wl_name, "n": n, "d": d, "K": K, "evals_total": total,
                        "evals_per_gpu": B, "parallelism": "grid sharded over %d GPU(s), one all-gather%s" % (
                            world, " (gloo rehearsal, ranks share devices)" if host_gather else ""),
-                       "failed_evals": bad, "all_finite": finite,
-                       "matches_cpu_potrf_digest": digest_ok},
-            "notiming_ms_per_step": 1e3 * elapsed_notiming / args.steps,
-            "notiming_note": "the same K steps again with no HIP event in the region (value / ms_per_step are the "
-                             "region WITH the events around the roofline kernel's launches)",
-            "kernel_ms_per_step": {k: v[0] for k, v in breakdown.items() if v[1]},
-            "kernel_ms_per_step_source": "one extra step with every launch group timed (outside the timed region)",
+                       **checked},
         }
+        if args.full:
+            out.update({
+                "notiming_ms_per_step": 1e3 * elapsed_notiming / args.steps,
+                "notiming_note": "the same K steps again with no HIP event in the region (value / ms_per_step are the "
+                                 "region WITH the events around the roofline kernel's launches)",
+                "kernel_ms_per_step": {k: v[0] for k, v in breakdown.items() if v[1]},
+                "kernel_ms_per_step_source": "one extra step with every launch group timed (outside the timed region)",
+            })
         if n > 128 and main_id == "sweep":
             # the scheduled sweep: ONE launch per chunk holds every update, diagonal and panel-solve tile, so the kernel is
             # priced with the factorisation's whole algorithmic count n^3 / 3 per matrix ("only the n^3/3 potrf
@@ -1163,12 +1177,11 @@ def run_predict_workload(c):
                       table[off:off + m], table[M + off:M + off + m]))
         off += m
     cpu5 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu5 = cpu_predict_sample(sets, P5)
     h = api.Handle(local)
     h.set_stream(torch.cuda.current_stream().cuda_stream)
     full = [None]
-    bad = [0]
 
     def compute():
         for (a1, a2, a3, n5, m5, o_m, o_v) in dsets:
@@ -1195,18 +1208,19 @@ def run_predict_workload(c):
         last = {"mean": tab[:M], "var": tab[M:], "beta": d_beta.cpu().numpy(), "status": d_st.cpu().numpy()}
     timing = h.get_timing()
     h.enable_timing(False)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence(torch, dist, world)
-    elapsed_notiming = time.perf_counter() - t0
     elapsed = max_over_ranks(torch, dist, world, gdev, elapsed)
-    elapsed_notiming = max_over_ranks(torch, dist, world, gdev, elapsed_notiming)
-    bad[0] = int((d_st != 0).sum().item())
-    got = full[0]
-    assert tuple(got.shape) == (2 * M, S), got.shape
-    assert torch.equal(got[:, lo:hi].to(dev), table), "all-gather mismatch"
-    finite = bool(torch.isfinite(got).all().item())
+    checked = {}
+    if args.full:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence(torch, dist, world)
+        elapsed_notiming = time.perf_counter() - t0
+        elapsed_notiming = max_over_ranks(torch, dist, world, gdev, elapsed_notiming)
+        got = full[0]
+        assert tuple(got.shape) == (2 * M, S), got.shape
+        assert torch.equal(got[:, lo:hi].to(dev), table), "all-gather mismatch"
+        checked = {"failed_draws": int((d_st != 0).sum().item()), "all_finite": bool(torch.isfinite(got).all().item())}
     if rank == 0:
         pairs = S * M
         fused_ms, fl = timing["fused"]
@@ -1222,9 +1236,10 @@ def run_predict_workload(c):
                           "draws_total": S, "draws_per_gpu": Sl, "test_points_total": M,
                           "parallelism": "draws sharded over %d GPU(s), one all-gather of the S x M x 2 table%s" % (
                               world, " (gloo rehearsal, ranks share devices)" if host_gather else ""),
-                          "gathered_bytes": int(2 * M * S * 8), "failed_draws": bad[0], "all_finite": finite},
-               "notiming_ms_per_step": 1e3 * elapsed_notiming / args.steps,
+                          "gathered_bytes": int(2 * M * S * 8), **checked},
                "roofline": small_roofline(ach, fl, fused_ms)}
+        if args.full:
+            out["notiming_ms_per_step"] = 1e3 * elapsed_notiming / args.steps
         if cpu5 is not None:
             out["cpu_baseline"] = {"value": cpu5["all_cores"], "unit": cpu5["unit"], "cores": cpu5["cores"], "kind": "port",
                                    "sample": cpu5["sample"], "one_core": cpu5["one_core"], "model": cpu_model()}

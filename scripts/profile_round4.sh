@@ -9,13 +9,13 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python3 $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 300 $OUT/bench_default.json; echo
-python3 $R/bench.py --evals-total 64 --steps 10 --no-cpu-baseline --no-secondary > $OUT/bench_slice64.json 2> $OUT/bench_slice64.err
-python3 $R/bench.py --workload cfg2 --steps 10 --warmup 2 > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
-python3 $R/bench.py --workload cfg3 --steps 10 --warmup 2 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
-python3 $R/bench.py --workload cfg3 --small-grid16 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg3_grid16.json 2> $OUT/bench_cfg3_grid16.err
-python3 $R/bench.py --workload cfg5 --steps 10 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+python3 $R/bench.py --full --evals-total 64 --steps 10 --no-cpu-baseline --no-secondary > $OUT/bench_slice64.json 2> $OUT/bench_slice64.err
+python3 $R/bench.py --full --workload cfg2 --steps 10 --warmup 2 > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+python3 $R/bench.py --full --workload cfg3 --steps 10 --warmup 2 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
+python3 $R/bench.py --full --workload cfg3 --small-grid16 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg3_grid16.json 2> $OUT/bench_cfg3_grid16.err
+python3 $R/bench.py --full --workload cfg5 --steps 10 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
 $R/tests/hip/valu_rates > $OUT/valu_f64_rates.txt 2>&1
 $R/tests/hip/mfma_valu_overlap > $OUT/mfma_valu_overlap.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
@@ -28,7 +28,7 @@ timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRB
 # alternating bench lines, kernel stats and the two traffic passes of the fused data flow beside the default ones above
 : > $OUT/fused_cov_ab.txt
 for o in "" "--fused-cov" "" "--fused-cov"; do
-  python3 $R/bench.py --steps 5 --no-cpu-baseline --no-secondary $o 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --steps 5 --no-cpu-baseline --no-secondary $o 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-16s %7.2f ms per step  %s  digest %s' % ('$o' or 'default', d['ms_per_step'], {k: round(v, 2) for k, v in d['kernel_ms_per_step'].items()}, d['config']['matches_cpu_potrf_digest']))" >> $OUT/fused_cov_ab.txt

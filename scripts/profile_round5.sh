@@ -12,17 +12,17 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
 export CCGP_SCHED_TIMEOUT_MS=10000
-python3 $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 400 $OUT/bench_default.json; echo
 N="--no-cpu-baseline --no-secondary"
-python3 $R/bench.py --evals-total 64 --steps 10 $N > $OUT/bench_slice64.json 2> $OUT/bench_slice64.err
-python3 $R/bench.py --evals-total 64 --steps 10 $N --sched 0 > $OUT/bench_slice64_sched0.json 2> $OUT/bench_slice64_sched0.err
-python3 $R/bench.py --steps 5 $N --sched 1 > $OUT/bench_sched1.json 2> $OUT/bench_sched1.err
-python3 $R/bench.py --evals-total 64 --steps 10 $N > $OUT/bench_slice64_b.json 2> /dev/null
-python3 $R/bench.py --evals-total 64 --steps 10 $N --sched 0 > $OUT/bench_slice64_sched0_b.json 2> /dev/null
-python3 $R/bench.py --workload cfg2 --steps 10 --warmup 2 > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
-python3 $R/bench.py --workload cfg3 --steps 10 --warmup 2 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
-python3 $R/bench.py --workload cfg5 --steps 10 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+python3 $R/bench.py --full --evals-total 64 --steps 10 $N > $OUT/bench_slice64.json 2> $OUT/bench_slice64.err
+python3 $R/bench.py --full --evals-total 64 --steps 10 $N --sched 0 > $OUT/bench_slice64_sched0.json 2> $OUT/bench_slice64_sched0.err
+python3 $R/bench.py --full --steps 5 $N --sched 1 > $OUT/bench_sched1.json 2> $OUT/bench_sched1.err
+python3 $R/bench.py --full --evals-total 64 --steps 10 $N > $OUT/bench_slice64_b.json 2> /dev/null
+python3 $R/bench.py --full --evals-total 64 --steps 10 $N --sched 0 > $OUT/bench_slice64_sched0_b.json 2> /dev/null
+python3 $R/bench.py --full --workload cfg2 --steps 10 --warmup 2 > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+python3 $R/bench.py --full --workload cfg3 --steps 10 --warmup 2 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
+python3 $R/bench.py --full --workload cfg5 --steps 10 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
 for a in "64 2 11" "64 1 11" "512 1 11" "512 2 11"; do set -- $a; python3 $R/scripts/r05_sched_profile.py $1 $2 $3 > $OUT/sched_account_$1_sched$2.json 2> /dev/null; done
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary"

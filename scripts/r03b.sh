@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd $R
 timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1 || { tail -40 $OUT/pytest_gpu.log; exit 1; }
 tail -3 $OUT/pytest_gpu.log
-timeout -k 10 600 python3 bench.py --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
 python3 - <<PY
 import json
 r=json.loads(open("$OUT/bench_default.json").read().strip().splitlines()[-1])
@@ -14,7 +14,7 @@ print("cfg4", round(r["value"],1), "evals/s", round(r["ms_per_step"],2), "ms", r
 for s in r["secondary"]:
     print(s["workload"][:40], round(s.get("ms_per_pass",0),3), "ms", s.get("end_to_end",{}).get("ms_per_call", s.get("end_to_end",{}).get("ms_per_pass")))
 PY
-timeout -k 10 300 python3 bench.py --evals-total 64 --steps 10 --no-cpu-baseline --no-secondary > $OUT/bench_slice64.json 2> $OUT/bench_slice64.err
+timeout -k 10 300 python3 bench.py --full --evals-total 64 --steps 10 --no-cpu-baseline --no-secondary > $OUT/bench_slice64.json 2> $OUT/bench_slice64.err
 python3 -c "
 import json
 r=json.loads(open('$OUT/bench_slice64.json').read().strip().splitlines()[-1])

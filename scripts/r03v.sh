@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 for v in default "$@" default "$@"; do
   if [ $v = default ]; then unset CCGP_LIB; else export CCGP_LIB=$R/build_ab/libccgp_$v.so; fi
-  timeout -k 10 300 python3 bench.py --steps 3 --no-cpu-baseline --no-secondary > $OUT/b512_$v.json 2> $OUT/b512_$v.err || { tail -5 $OUT/b512_$v.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --steps 3 --no-cpu-baseline --no-secondary > $OUT/b512_$v.json 2> $OUT/b512_$v.err || { tail -5 $OUT/b512_$v.err; exit 1; }
   python3 -c "
 import json
 r=json.loads(open('$OUT/b512_$v.json').read().strip().splitlines()[-1])

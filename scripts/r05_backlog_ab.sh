@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r05n
 one() { # label, env, args
   lab=$1; shift; envs=$1; shift
-  env $envs python bench.py --no-cpu-baseline --no-secondary --steps 8 --warmup 2 "$@" 2>/dev/null | python -c "
+  env $envs python bench.py --full --no-cpu-baseline --no-secondary --steps 8 --warmup 2 "$@" 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lab', round(d['ms_per_step'],2), d['config']['matches_cpu_potrf_digest'])"
 }
 for B in 64 128 256; do

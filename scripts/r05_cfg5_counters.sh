@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python3 $R/bench.py --workload cfg5 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+python3 $R/bench.py --full --workload cfg5 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats_cfg5 -o t --output-format csv -- python3 $R/bench.py --workload cfg5 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/stats_cfg5.log 2>&1
 i=0

@@ -1,13 +1,14 @@
 # same-box A/B: launch-per-phase sweep (sched 0) against the dataflow scheduler (1 = two workgroups per CU, 2 = one), 64-matrix
 # slice and full 512-point grid
-mkdir -p gpurun_out/r05b
+OUT=${1:-build_ab/r05b}
+mkdir -p $OUT
 run() {  # name, args...
   name=$1; shift
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary "$@" > gpurun_out/r05b/$name.json 2> gpurun_out/r05b/$name.err || { echo "$name FAILED"; tail -5 gpurun_out/r05b/$name.err; return 1; }
-  python - "$name" <<'PY'
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name FAILED"; tail -5 $OUT/$name.err; return 1; }
+  python - "$name" "$OUT" <<'PY'
 import sys, json
 name = sys.argv[1]
-d = json.loads(open("gpurun_out/r05b/%s.json" % name).read().strip().splitlines()[-1])
+d = json.loads(open("%s/%s.json" % (sys.argv[2], name)).read().strip().splitlines()[-1])
 print(name, "ms/step %.2f" % d["ms_per_step"], "notiming %.2f" % d["notiming_ms_per_step"], {k: round(v, 2) for k, v in d["kernel_ms_per_step"].items()},
       "frac %.3f" % d["roofline"]["frac"], d["config"]["matches_cpu_potrf_digest"], flush=True)
 PY

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Reference values for the benchmark's own workload (BASELINE config 4: n = 4096, d = 5, K = 3, 512 draws), so that
-bench.py can check what it just timed instead of only `isfinite`.
+`bench.py --full` can check what it just timed instead of only `isfinite`.
 
 Every draw: log-likelihood and beta by potrf + two forward solves on the CPU (the recipe of
 tests/test_gpu_parity.py::test_n4096_against_lapack_and_invariances).  All 512 go through the compiled CPU

@@ -29,7 +29,8 @@ def run_bench(*args):
 @pytest.mark.timeout(900)
 def test_two_ranks_started_by_bench_itself_prediction_tables_sharded_by_draw():
     one = run_bench("--gpus", "1", "--workload", "cfg5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
-    two = run_bench("--gpus", "2", "--workload", "cfg5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--backend", "gloo")
+    two = run_bench("--gpus", "2", "--workload", "cfg5", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--backend",
+                    "gloo")
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["config"]["draws_per_gpu"] == 500 and two["config"]["failed_draws"] == 0 and two["config"]["all_finite"]
     assert two["config"]["gathered_bytes"] == one["config"]["gathered_bytes"] == 2 * 2230 * 1000 * 8
@@ -38,6 +39,7 @@ def test_two_ranks_started_by_bench_itself_prediction_tables_sharded_by_draw():
 
 @pytest.mark.timeout(900)
 def test_three_ranks_grid_sharded_by_row_ragged():
-    r = run_bench("--gpus", "3", "--workload", "cfg3", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--backend", "gloo")
+    r = run_bench("--gpus", "3", "--workload", "cfg3", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--backend",
+                  "gloo")
     assert r["n_gpus"] == 3 and r["config"]["evals_total"] == 60 * 1728 and r["config"]["evals_per_gpu"] == 20 * 1728
     assert r["config"]["failed_evals"] == 0 and r["roofline"]["bound"] == "valu-issue"

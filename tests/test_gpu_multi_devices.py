@@ -35,7 +35,7 @@ def iso_row(p, t1, t2, d):
 def test_bench_two_ranks_over_rccl_cfg4_slice():
     from test_gpu_bench_ranks import run_bench
     r = run_bench("--gpus", "2", "--backend", "nccl", "--workload", "cfg4", "--evals-total", "16", "--steps", "1",
-                  "--warmup", "0", "--no-cpu-baseline", "--no-secondary")
+                  "--warmup", "0", "--full", "--no-cpu-baseline", "--no-secondary")
     # bench.py asserts the gathered vector against every rank's local slice ("all-gather mismatch") and the timed
     # log-likelihoods against the CPU potrf digest; reaching the JSON line means both held on both ranks
     assert r["n_gpus"] == 2 and r["config"]["evals_per_gpu"] == 8 and r["config"]["failed_evals"] == 0
@@ -47,7 +47,7 @@ def test_bench_two_ranks_over_rccl_prediction_tables():
     from test_gpu_bench_ranks import run_bench
     one = run_bench("--gpus", "1", "--workload", "cfg5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
     two = run_bench("--gpus", "2", "--backend", "nccl", "--workload", "cfg5", "--steps", "1", "--warmup", "0",
-                    "--no-cpu-baseline")
+                    "--full", "--no-cpu-baseline")
     assert two["n_gpus"] == 2 and two["config"]["draws_per_gpu"] == 500 and two["config"]["failed_draws"] == 0
     assert two["config"]["gathered_bytes"] == one["config"]["gathered_bytes"] and two["config"]["all_finite"]
 
@@ -56,7 +56,8 @@ def test_bench_two_ranks_over_rccl_prediction_tables():
 @pytest.mark.skipif(NDEV < 3, reason="needs three distinct GPUs")
 def test_bench_three_ranks_over_rccl_grid_by_row_ragged():
     from test_gpu_bench_ranks import run_bench
-    r = run_bench("--gpus", "3", "--backend", "nccl", "--workload", "cfg3", "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
+    r = run_bench("--gpus", "3", "--backend", "nccl", "--workload", "cfg3", "--steps", "1", "--warmup", "0", "--full",
+                  "--no-cpu-baseline")
     assert r["n_gpus"] == 3 and r["config"]["evals_per_gpu"] == 20 * 1728 and r["config"]["failed_evals"] == 0
 
 

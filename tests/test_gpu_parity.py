@@ -1188,11 +1188,20 @@ def test_kept_factor_prediction_has_the_bits_of_the_extra_row_scheme(handle, n, 
         assert st[S // 2] != 0          # the nearly constant correlation matrix is singular to working precision
     b = 0 if S // 2 else 1
     w, Th = orc.unpack_params(P[b], K, d)
-    R_inv = orc.solve_inverse(orc.mixed_corr_matrix_general(X, w, Th))
-    beta = orc.beta_mle(R_inv, y)
-    mf, v1, v2 = orc.factors(R_inv, beta, y)
+    # the cached terms (HX:454-458, HX:604-613) and predict.post (HX:667-670) in long double from the long-double inverse:
+    # the matrix at n = 100 has cond ~1e9, where an fp64 explicit inverse (dgesv) is itself ~1e-7 off the mean, and by how
+    # much depends on the host's BLAS and its thread count
+    LD = np.longdouble
+    R_inv = orc.solve_inverse_exact(orc.mixed_corr_matrix_general(X, w, Th), LD)
+    yl = np.asarray(y, dtype=LD)
+    v1 = R_inv.sum(axis=0)
+    v2 = v1.sum()
+    beta = (v1 @ yl) / v2
+    mf = R_inv @ (yl - beta)
     for t in (0, m - 1):
-        mean, var = orc.predict_post_from_factors(orc.mixed_corr_vec_general(Xt[t], X, w, Th), beta, mf, v1, v2, R_inv, 1.7)
+        r = np.ravel(orc.mixed_corr_vec_general(Xt[t], X, w, Th)).astype(LD)
+        mean = float(beta + mf @ r)
+        var = float(LD(1.7) * (1 - (r @ R_inv) @ r + (1 - v1 @ r) ** 2 / v2))
         assert res[1][0][b, t] == pytest.approx(mean, rel=1e-7, abs=1e-8)
         assert res[1][1][b, t] == pytest.approx(var, rel=1e-5, abs=1e-8)
 
