@@ -55,6 +55,7 @@ SIGNATURES = {
     "ccgp_grid_marginal": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, _dp, c_int, c_int,
                                    c_double, c_int, c_double, _dp, _ip, _dp]),
     "ccgp_mixed_logdet_designs": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, _dp, _ip]),
+    "ccgp_mixed_logdet_grad_designs": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, c_int, _dp, _dp, _ip]),
     "ccgp_halton_base2": (c_int, [c_int, _dp]),
     "ccgp_qigamma": (c_int, [_dp, c_int, c_double, c_double, _dp]),
     "ccgp_predict_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, c_int,
@@ -513,6 +514,20 @@ class Handle:
         st = np.zeros(B, dtype=np.int32)
         self._chk(lib().ccgp_mixed_logdet_designs(self._h, _p(Xs), n, d, B, K, _p(row), _p(out), _ipt(st)))
         return out, st
+
+    def mixed_logdet_grad_designs(self, designs, K, params_row, n_fixed=0):
+        """designs: [B, n, d] sharing one parameter row -> (logdet[B], grad[B, n - n_fixed, d], status[B]):
+        d log det R_mixed / d x of the rows >= n_fixed (NaN and status != 0 where the elimination failed)."""
+        designs = np.asarray(designs, dtype=np.float64)
+        B, n, d = designs.shape
+        nf = int(n_fixed)
+        Xs = np.ascontiguousarray(np.stack([np.asfortranarray(D).ravel(order="F") for D in designs]))
+        row = _f(params_row, (K + K * d,))
+        out = np.empty(B)
+        g = np.empty(B * max(n - nf, 0) * d)
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_mixed_logdet_grad_designs(self._h, _p(Xs), n, d, B, K, _p(row), nf, _p(out), _p(g), _ipt(st)))
+        return out, g.reshape(B, d, n - nf).transpose(0, 2, 1), st
 
     # -- a10 + a11 -------------------------------------------------------------------------
     def predict_batch(self, X, y, K, params, Xtest, sigma2):

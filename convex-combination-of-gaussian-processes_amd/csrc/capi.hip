@@ -1273,6 +1273,48 @@ int ccgp_mixed_logdet_designs(ccgp_handle* h, const double* Xs, int n, int d, in
   return count_bad(st.data(), B);
 } CCGP_GUARD_END(h)
 
+// d log det R_mixed / d X for B candidate designs (BSQ:856-948: the design search of Entropy.optim / Batch.Entropy.optim)
+int ccgp_mixed_logdet_grad_designs(ccgp_handle* h, const double* Xs, int n, int d, int B, int K,
+                                   const double* params, int n_fixed, double* out_logdet, double* out_grad,
+                                   int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || B < 1 || !Xs || !params || !out_logdet || !out_grad)
+    return fail(h, CCGP_EINVAL, "ccgp_mixed_logdet_grad_designs: bad argument");
+  if (n_fixed < 0 || n_fixed >= n)
+    return fail(h, CCGP_EINVAL, "ccgp_mixed_logdet_grad_designs: n_fixed must lie in [0, n)");
+  if (h->fam.id != 0)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_mixed_logdet_grad_designs: Gaussian family only (BSQ:856-948)");
+  if (!small_reg_design_grad_supported(n, d, K))
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_mixed_logdet_grad_designs: the design does not fit the register-resident "
+                                      "evaluator (n <= 128 and its LDS share: R^-1 and the design of one matrix)");
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  const size_t ng = (size_t)B * (n - n_fixed) * d;
+  size_t need = Carver::al(sizeof(double) * (size_t)B * n * d) + Carver::al(sizeof(double) * P) +
+                Carver::al(sizeof(double) * B) + Carver::al(sizeof(double) * ng) + Carver::al(sizeof(int) * (size_t)B);
+  int rc = ensure_stage(h, need);
+  if (rc) return rc;
+  Carver c(h->stage);
+  double* dXs = c.take<double>((size_t)B * n * d);
+  double* dp = c.take<double>(P);
+  double* dld = c.take<double>(B);
+  double* dg = c.take<double>(ng);
+  int* dst = c.take<int>(B);
+  if (int prc = push(h, {piece(dXs, Xs, (size_t)B * n * d), piece(dp, params, P)})) return prc;
+  DrawView dv{dp, 1, K, d};
+  dv.fam = h->fam;
+  if (int frc = check_family(h, dv.fam, d, K)) return frc;
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    launch_small_reg_logdet_grad_designs(h->stream, dXs, n, d, dv, B, n_fixed, dld, dg, dst);
+  }
+  CCGP_LAUNCH_CHECK();
+  std::vector<int> st(B);
+  if (int prc = pull(h, {piece(dld, out_logdet, B), piece(dg, out_grad, ng), piece(dst, st.data(), B)})) return prc;
+  if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)B);
+  return count_bad(st.data(), B);
+} CCGP_GUARD_END(h)
+
 // ---- a9: hyperprior grid ------------------------------------------------------------------------
 int ccgp_halton_base2(int N, double* out) {
   if (N < 0 || !out) return CCGP_EINVAL;

@@ -162,6 +162,11 @@ void launch_small_reg_inverse(hipStream_t s, const double* X, int n, int d, cons
                               double sigma2, double* Rinv, double* loglik, double* beta, int* status);
 void launch_small_reg_grad(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B,
                            double sigma2, double* loglik, double* beta, double* grad, int* status);
+// d log det R_mixed / d X of the rows >= n_fixed for B candidate designs (entropy criteria, BSQ:856-948); dgrad holds
+// per design (n - n_fixed) x d column-major
+bool small_reg_design_grad_supported(int n, int d, int K);
+void launch_small_reg_logdet_grad_designs(hipStream_t s, const double* Xs, int n, int d, DrawView dv, int B, int n_fixed,
+                                          double* logdet, double* dgrad, int* status);
 void launch_small_reg_loglik(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                              int B, double sigma2, int mean_mode, double tau2, double* loglik,
                              double* beta, int* status, bool grid16 = false);

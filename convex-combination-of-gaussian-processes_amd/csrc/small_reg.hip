@@ -62,6 +62,8 @@ struct RegArgs {
   int grid16;          // CCGP_OPT_SMALL_GRID16: 64 < n <= 104 on the 16 x 16 grid (measurements)
   double* fac;         // FAC instantiation: per draw a block of fac_stride doubles that keeps the factor for predict_sites_kernel
   size_t fac_stride;
+  double* dgrad;       // INV = 3: d log det R / d X of the free rows, per design (n - n_fixed) x d column-major
+  int n_fixed;         // INV = 3: rows below n_fixed are the fixed batch (D.old, BSQ:920-948): no gradient
 };
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
@@ -131,7 +133,8 @@ __device__ __forceinline__ void mat_sync() {
 #ifndef CCGP_SMALL_OCC_PRED
 #define CCGP_SMALL_OCC_PRED 3
 #endif
-// INV: 0 = none, 1 = explicit inverse (solve(R), HX:454), 2 = analytic gradient of the profile-beta log-likelihood
+// INV: 0 = none, 1 = explicit inverse (solve(R), HX:454), 2 = analytic gradient of the profile-beta log-likelihood,
+// 3 = gradient of log det R with respect to the design (per-design form, entropy criteria BSQ:856-948)
 template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
@@ -343,6 +346,9 @@ void small_reg_kernel(RegArgs a) {
       const double piv = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(piv_v)),
                                           __builtin_amdgcn_readfirstlane(__double2loint(piv_v)));
       if (!(piv > ptol)) { bad = k + 1; break; }   // uniform over the matrix's threads (pivot_tolerance: ccgp_internal.h)
+      if constexpr (INV == 3) {
+        if (__builtin_isinf(piv)) { bad = k + 1; break; }   // the design gradient's failure rule: pivot <= 0 or not finite
+      }
       // 1 / pivot by v_rcp_f64 + two Newton steps (full precision, ~6 instructions instead of ~30)
       double rinv = __builtin_amdgcn_rcp(piv);
       rinv = fma(fma(-piv, rinv, 1.0), rinv, rinv);
@@ -497,7 +503,7 @@ void small_reg_kernel(RegArgs a) {
           a.Rinv[i + (size_t)j * n] = acc;
           a.Rinv[j + (size_t)i * n] = acc;
         }
-    } else {
+    } else if constexpr (INV == 2) {
       // ---- gradient (build-defined extension; the reference differentiates numerically, HX:493) ------------------
       //   M = (alpha alpha' - Sigma^-1) / 2,  Sigma = cs R,  cs = sigma2 sum w^2,  alpha = Sigma^-1 (y - beta 1)
       //   d loglik / d w_q      =  2 sigma2 w_q   sum_ab M_ab R_q,ab
@@ -589,6 +595,63 @@ void small_reg_kernel(RegArgs a) {
       };
       if (d <= 8) contract(std::integral_constant<int, 3>{}, std::integral_constant<int, 8>{});
       else contract(std::integral_constant<int, 1>{}, std::integral_constant<int, 16>{});
+    } else {
+      // ---- design gradient (entropy criteria, BSQ:856-948; the reference's optim() differences numerically) --------
+      //   d log det R / d x_ik = -4 sum_{j != i} (R^-1)_ij (x_ik - x_jk) sum_q (w_q^2 / sw) theta_qk R_q,ij
+      // for the free rows i >= n_fixed.  Per row, not a handful of scalars as in INV = 2, so the reduction is a TWO-PASS
+      // split rather than LDS atomics: pass 1 forms every needed R^-1 entry once (the n-long dot product, the O(n^3)
+      // part) and parks it in the part of Z that row_dot never reads; pass 2 gives each thread one (row, 8 dimensions)
+      // and sums over j in a fixed order.  Atomic additions would make the bits depend on the order the waves arrive
+      // in, and a design's result must not depend on what else is in the batch (the optimiser's starts are independent).
+      //   where R^-1_ij (i > j) is parked: Z[i][j] for j <= i - 2 (row_dot reads row r from column 2 floor(r / 2) >= r - 1
+      //   on), Z[i][NP] for j = i - 1 (the row's padding columns NP, NP + 1 are never read either)
+      const int nf = a.n_fixed, nfree = n - nf;
+      if (!bad)
+        for (int idx = lt; idx < n * n; idx += TPM) {
+          const int i = idx % n, j = idx / n;
+          if (i <= j || i < nf) continue;   // (fixed, fixed) pairs feed no free row
+          const double r = row_dot(i, j);
+          zmat[i * ZS + (j + 1 == i ? NP : j)] = r;
+        }
+      mat_sync<G>();
+      constexpr int KC = 8;
+      const int nkc = (d + KC - 1) / KC;
+      const double rsw = 1.0 / sw;   // the normalisation of R (HX:412)
+      for (int item = lt; item < nfree * nkc; item += TPM) {
+        const int i = nf + item % nfree, k0 = (item / nfree) * KC;
+        double acc[KC];
+#pragma unroll
+        for (int k = 0; k < KC; ++k) acc[k] = 0.0;
+        if (!bad)
+          for (int j = 0; j < n; ++j) {
+            if (j == i) continue;
+            const int hi = i > j ? i : j, lo = i > j ? j : i;
+            const double rij = zmat[hi * ZS + (lo + 1 == hi ? NP : lo)];
+            double df[KC];
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+              const int kk = k0 + k < d ? k0 + k : d - 1;
+              df[k] = xs[kk * n + i] - xs[kk * n + j];
+            }
+            for (int q = 0; q < K; ++q) {
+              double sd = 0.0;
+              for (int k = 0; k < d; ++k) sd = fma(xs[k * n + hi] * th[q * d + k], xs[k * n + lo], sd);
+              const double dist = (us[q * NP + hi] + us[q * NP + lo]) + (-2.0 * sd);
+              const double v = rij * w2[q] * exp_small<true>(dist, etab);
+#pragma unroll
+              for (int k = 0; k < KC; ++k) {
+                const int kk = k0 + k < d ? k0 + k : d - 1;
+                acc[k] = fma(v * th[q * d + kk], df[k], acc[k]);
+              }
+            }
+          }
+        if (valid) {
+          double* g = a.dgrad + (size_t)b * nfree * d;
+#pragma unroll
+          for (int k = 0; k < KC; ++k)
+            if (k0 + k < d) g[(i - nf) + (size_t)(k0 + k) * nfree] = bad ? kNaN : -4.0 * rsw * acc[k];
+        }
+      }
     }
     return;
   }
@@ -992,18 +1055,28 @@ bool small_reg_inverse_supported(int n, int d, int K) {
          (size_t)kLdsBytes - 64;
 }
 
+// the design gradient (INV = 3) keeps its design in LDS behind the matrix: d n doubles more
+bool small_reg_design_grad_supported(int n, int d, int K) {
+  if (n > 128) return false;
+  const int NB = (n + 15) / 16;
+  return sizeof(double) * (kSmallExpTable + (size_t)2 * d * n + (size_t)kPerMat(16 * NB, 16, NB + 1, K, d, true)) <=
+         (size_t)kLdsBytes - 64;
+}
+
 template <int NB, int INV>
 static void launch_inv(hipStream_t s, const RegArgs& a) {
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
-    raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, INV>, INV == 1 ? "small_reg_kernel<inverse>" : "small_reg_kernel<gradient>");
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, INV>,
+                    INV == 1 ? "small_reg_kernel<inverse>" : INV == 2 ? "small_reg_kernel<gradient>" : "small_reg_kernel<design gradient>");
   });
+  const size_t lds = inv_lds_bytes<NB>(a.n, a.d, a.K) + (a.x_stride ? sizeof(double) * (size_t)a.d * a.n : 0);
   const int kMaxGrid = 1 << 20;
   RegArgs c = a;
   for (int b0 = 0; b0 < a.B; b0 += kMaxGrid) {
     c.draw0 = a.draw0 + b0;
     c.B = a.B - b0 < kMaxGrid ? a.B - b0 : kMaxGrid;
-    hipLaunchKernelGGL((small_reg_kernel<16, NB, NB + 1, false, INV>), dim3(c.B, 1), dim3(256), inv_lds_bytes<NB>(a.n, a.d, a.K), s, c);
+    hipLaunchKernelGGL((small_reg_kernel<16, NB, NB + 1, false, INV>), dim3(c.B, 1), dim3(256), lds, s, c);
   }
 }
 
@@ -1038,6 +1111,19 @@ void launch_small_reg_grad(hipStream_t s, const double* X, int n, int d, const d
   a.draw0 = 0; a.B = B; a.sigma2 = sigma2; a.mode = 0; a.tau2 = 0.0;
   a.loglik = loglik; a.beta = beta; a.status = status; a.grad = grad; a.Btot = B; a.m = 0; a.S = 1;
   dispatch_inv<2>(s, a);
+}
+
+// d log det R_mixed / d X for B candidate designs sharing one parameter row (ccgp_mixed_logdet_grad_designs, n <= 128):
+// one workgroup per design; log det as launch_small_reg_logdet_designs computes it, the gradient of rows >= n_fixed in dgrad
+void launch_small_reg_logdet_grad_designs(hipStream_t s, const double* Xs, int n, int d, DrawView dv, int B, int n_fixed,
+                                          double* logdet, double* dgrad, int* status) {
+  RegArgs a{};
+  a.X = Xs; a.y = Xs;   // the right-hand-side rows are not used; any n readable doubles will do
+  a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
+  a.draw0 = 0; a.B = B; a.sigma2 = 1.0; a.mode = 0; a.tau2 = 0.0;
+  a.status = status; a.x_stride = (size_t)n * d; a.shared_params = 1; a.logdet = logdet;
+  a.dgrad = dgrad; a.n_fixed = n_fixed; a.m = 0; a.S = 1;
+  dispatch_inv<3>(s, a);
 }
 
 bool small_reg_supported(int n, int d, int K, bool per_design, bool predict) {

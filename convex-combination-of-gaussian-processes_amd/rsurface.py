@@ -210,6 +210,63 @@ class CombinedGP:
             return float("nan")
         return -float(np.exp(ld_all[0] - ld_old[0]))
 
+    # ------------------------------------------------------------------ design search (BSQ)
+    @staticmethod
+    def _design_result(res, logdets):
+        """The reference's return value (BSQ:908-911: Design = the best start's design, log.entropy = -min.val, which is
+        a determinant, not a log) plus the search's own record."""
+        ok = np.isfinite(res["f"])
+        if not ok.any():
+            raise RuntimeError("Entropy_optim: no start could be evaluated")
+        best = int(np.argmin(np.where(ok, res["f"], np.inf)))
+        vals = np.where(ok, -np.exp(logdets), np.nan)   # the reference's criterion values, -det
+        return dict(Design=res["x"][best], log_entropy=float(np.exp(logdets[best])), logdet=float(logdets[best]),
+                    designs=res["x"], values=vals, logdets=logdets, converged=res["converged"],
+                    iterations=res["iterations"], best=best, device_calls=res["calls"])
+
+    def Entropy_optim(self, n, d, p, theta1, theta2, n_starts, starts=None, rng=None, **opts):
+        """Entropy.optim(n, d, p, theta1, theta2, n.starts), BSQ:886-912: the n-point maximum-entropy design from
+        n.starts starts, all of them searched side by side (design.minimize_starts; opts: m, maxit, factr, pgtol).
+        starts: [n_starts, n, d] or None for -1 + 2 LHS(n, d) from numpy's generator seeded with rng (the reference's
+        lhs::optimumLHS cannot be reproduced without R).  Returns dict(Design, log_entropy = det R of the best design, as
+        the reference returns it, logdet, designs, values = -det per start, logdets, converged, iterations, best,
+        device_calls)."""
+        from . import design
+        n, d = int(n), int(d)
+        S = design.make_starts(int(n_starts), n, d, rng) if starts is None else np.asarray(starts, dtype=np.float64)
+        row = pack_iso(p, theta1, theta2, d)
+
+        def evaluate(X):
+            ld, g, st = self.h.mixed_logdet_grad_designs(X, 2, row, 0)
+            return -ld, -g, st
+
+        res = design.minimize_starts(evaluate, S, **opts)
+        return self._design_result(res, -res["f"])
+
+    def Batch_Entropy_optim(self, D_old, n_new, d, p, theta1, theta2, n_starts, starts=None, rng=None, **opts):
+        """Batch.Entropy.optim(D.old, n.new, d, p, theta1, theta2, n.starts), BSQ:920-948: the n.new points to add to
+        D.old that maximise det(R.new - R.cross R.old^-1 R.cross') = det R(D.old U D.new) / det R(D.old) (Schur
+        complement; its log is what is searched).  Starts, options and the returned dict as in Entropy_optim; logdet,
+        logdets and log_entropy refer to the Schur determinant."""
+        from . import design
+        D_old = np.asarray(D_old, dtype=np.float64)
+        n_old, n_new, d = D_old.shape[0], int(n_new), int(d)
+        S = design.make_starts(int(n_starts), n_new, d, rng) if starts is None else np.asarray(starts, dtype=np.float64)
+        row = pack_iso(p, theta1, theta2, d)
+        ld_old, st_old = self.h.mixed_logdet_designs(D_old[None], 2, row)
+        if st_old[0]:
+            raise ValueError("Batch_Entropy_optim: R(D.old) cannot be factorised")
+
+        def evaluate(X):
+            full = np.concatenate([np.broadcast_to(D_old, (X.shape[0], n_old, d)), X], axis=1)
+            ld, g, st = self.h.mixed_logdet_grad_designs(full, 2, row, n_old)
+            return -(ld - ld_old[0]), -g, st
+
+        res = design.minimize_starts(evaluate, S, **opts)
+        out = self._design_result(res, -res["f"])
+        out["device_calls"] += 1   # log det R(D.old)
+        return out
+
     # ------------------------------------------------------------------ batched forms
     def draws_to_params(self, D_train, draws):
         """draws rows (p, theta1, theta2[, lambda]) -> C-ABI parameter matrix."""
@@ -340,7 +397,7 @@ class CombinedGP1D(CombinedGP):
     def likeli_hyperpars(self, *a, **k):
         raise NotImplementedError("the 1-D script has no hyperprior grid")
 
-    choose_hyperpars = Entropy = Entropy_batch = Augmented_Mixed_Entropy = likeli_hyperpars
+    choose_hyperpars = Entropy = Entropy_batch = Augmented_Mixed_Entropy = Entropy_optim = Batch_Entropy_optim = likeli_hyperpars
 
 
 class CombinedGP1DTwoFamilies(CombinedGP1D):

@@ -273,6 +273,20 @@ int ccgp_predict_post(ccgp_handle* h, const double* Xnew, int m, const double* X
  * design at a time. */
 int ccgp_mixed_logdet_designs(ccgp_handle* h, const double* Xs, int n, int d, int B, int K,
                               const double* params, double* out_logdet, int* status);
+/* The design search around those criteria (Entropy.optim / Batch.Entropy.optim, Batch Sequential ME Design.R:886-948;
+ * the criteria themselves :856-877): log det R.mixed(D) as ccgp_mixed_logdet_designs computes it AND its gradient with
+ * respect to the design,
+ *   d log det R / d x_ik = -4 sum_{j != i} (R^-1)_ij (x_ik - x_jk) sum_q (w_q^2 / sum_r w_r^2) theta_qk exp(-theta_q'(x_i - x_j)^2),
+ * for the rows i >= n_fixed.  Rows below n_fixed are the fixed batch D.old: they enter R and get no gradient, so with
+ * n_fixed = n.old the gradient is that of the Schur criterion log det R(D.old U D.new) - log det R(D.old) (:869-877) too.
+ * Xs, n, d, B, K and params as for ccgp_mixed_logdet_designs; out_logdet[B]; out_grad holds B blocks of (n - n_fixed) x d,
+ * column-major each (design b at out_grad + b*(n - n_fixed)*d).  A design whose elimination meets a pivot <= 0 or not
+ * finite (two coincident rows) gets status[b] != 0 and NaN log det and gradient; the others are unaffected.  One launch,
+ * one workgroup per design, n <= 128 (CCGP_EUNSUPPORTED where the design does not fit); Gaussian family only;
+ * CCGP_EINVAL for n_fixed outside [0, n).  Returns the number of failed designs. */
+int ccgp_mixed_logdet_grad_designs(ccgp_handle* h, const double* Xs, int n, int d, int B, int K,
+                                   const double* params, int n_fixed, double* out_logdet, double* out_grad,
+                                   int* status);
 
 /* ---- several GPUs behind ONE host process (csrc/multi.cpp) ------------------------------
  * The drop-in host is R: one single-threaded process.  A ccgp_multi owns one handle per device; the three

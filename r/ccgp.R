@@ -284,6 +284,50 @@ if (ccgp.script == "BSQ") {
   Augmented.Mixed.Entropy <- function(D.old, D.new, p, theta1, theta2, R.old.Inv = NULL)
     -exp(.ccgp.logdet(rbind(.ccgp.mat(D.old), .ccgp.mat(D.new)), p, theta1, theta2) -
          .ccgp.logdet(.ccgp.mat(D.old), p, theta1, theta2))
+
+  # The design search (BSQ:886-948): the script's loop, its optimumLHS starts, its objective -det and its return value,
+  # with the EXACT gradient -det * d log det / d D handed to optim() instead of its finite differences (2 n d criterion
+  # values per gradient).  The iterates can therefore differ from the script's (INTEGRATION.md).  fn and gr at the same
+  # point cost one .Call: the last (x -> log det, gradient) pair is kept.  A singular R (coincident points) is det = 0,
+  # as det() gives it: log det -Inf, gradient 0.
+  .ccgp.logdet.grad <- function(D.old, d, p, theta1, theta2) {
+    n.fixed <- if (is.null(D.old)) 0L else nrow(D.old)
+    last.x <- NULL
+    last <- NULL
+    function(x) {
+      if (is.null(last.x) || !identical(x, last.x)) {
+        D <- rbind(D.old, matrix(as.double(x), ncol = d))
+        r <- .Call("ccgp_R_mixed_logdet_grad_designs", matrix(as.double(D), ncol = 1), nrow(D), ncol(D), 2L,
+                   .ccgp.row(ncol(D), p, theta1, theta2), as.integer(n.fixed))
+        if (is.na(r$logdet)) r <- list(logdet = -Inf, grad = rep(0, length(x)))
+        last.x <<- x
+        last <<- r
+      }
+      last
+    }
+  }
+  .ccgp.design.search <- function(n, d, n.starts, at, shift) {
+    vals <- rep(0, n.starts)
+    designs <- list()
+    fn <- function(x) -exp(at(x)$logdet - shift)
+    gr <- function(x) { r <- at(x); -exp(r$logdet - shift) * as.vector(r$grad) }
+    for (k in 1:n.starts) {
+      start <- c(-1 + 2 * optimumLHS(n, d))
+      optimum <- optim(start, fn, gr, method = "L-BFGS-B", lower = rep(-1, n * d), upper = rep(1, n * d))
+      designs[[k]] <- matrix(optimum$par, ncol = d)
+      vals[k] <- optimum$value
+    }
+    min.val <- vals[which.min(vals)]
+    best.design <- designs[[which.min(vals)]]
+    list(Design = best.design, log.entropy = -min.val)
+  }
+  Entropy.optim <- function(n, d, p, theta1, theta2, n.starts)                           # BSQ:886-912
+    .ccgp.design.search(n, d, n.starts, .ccgp.logdet.grad(NULL, d, p, theta1, theta2), 0)
+  Batch.Entropy.optim <- function(D.old, n.new, d, p, theta1, theta2, n.starts) {        # BSQ:920-948
+    D.old <- .ccgp.mat(D.old)
+    .ccgp.design.search(n.new, d, n.starts, .ccgp.logdet.grad(D.old, d, p, theta1, theta2),
+                        .ccgp.logdet(D.old, p, theta1, theta2))
+  }
 }
 
 

@@ -27,6 +27,11 @@
 
 #include "ccgp.h"
 
+/* Entry points newer than the rest of the ABI are referenced WEAKLY: the shim still loads against a libccgp that predates
+ * them (or against a host-side stand-in of the device entry points), and only the routine that needs one stops with an R
+ * error naming it. */
+#pragma weak ccgp_mixed_logdet_grad_designs
+
 static ccgp_handle* g_handle = NULL; /* R is single-threaded: one handle per process */
 static ccgp_multi* g_multi = NULL;   /* CCGP_DEVICES=k (k > 1) or a comma list: the batched calls are sharded */
 static int g_multi_tried = 0;
@@ -612,6 +617,33 @@ SEXP ccgp_R_mixed_logdet_designs(SEXP Xs, SEXP n, SEXP d, SEXP K, SEXP params) {
   return out;
 }
 
+/* log det R.mixed AND its gradient with respect to the rows >= n_fixed for B candidate designs (Xs as above) ->
+ * list(logdet = B values, grad = (n - n_fixed) * d x B matrix, design b's column holding its (n - n_fixed) x d gradient
+ * column-major); NA for a design whose elimination failed -- the design search of Entropy.optim / Batch.Entropy.optim,
+ * Batch Sequential ME Design.R:886-948 */
+SEXP ccgp_R_mixed_logdet_grad_designs(SEXP Xs, SEXP n, SEXP d, SEXP K, SEXP params, SEXP n_fixed) {
+  if (!ccgp_mixed_logdet_grad_designs)
+    Rf_error("ccgp_R_mixed_logdet_grad_designs: the loaded libccgp has no ccgp_mixed_logdet_grad_designs (rebuild it)");
+  const int B = Rf_ncols(Xs), nn = Rf_asInteger(n), dd = Rf_asInteger(d), nf = Rf_asInteger(n_fixed);
+  const int rows = nn > nf && nf >= 0 ? (nn - nf) * dd : 0;
+  SEXP ld = PROTECT(Rf_allocVector(REALSXP, B));
+  SEXP g = PROTECT(Rf_allocMatrix(REALSXP, rows, B));
+  int rc = ccgp_mixed_logdet_grad_designs(handle(), REAL(Xs), nn, dd, B, Rf_asInteger(K), REAL(params), nf, REAL(ld),
+                                          REAL(g), NULL);
+  if (rc < 0) { warn_rc(rc); fill_na(REAL(ld), B); fill_na(REAL(g), (R_xlen_t)rows * B); }
+  for (int i = 0; i < B; ++i) if (ISNAN(REAL(ld)[i])) REAL(ld)[i] = NA_REAL;
+  for (R_xlen_t i = 0; i < (R_xlen_t)rows * B; ++i) if (ISNAN(REAL(g)[i])) REAL(g)[i] = NA_REAL;
+  SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+  SEXP names = PROTECT(Rf_allocVector(STRSXP, 2));
+  SET_STRING_ELT(names, 0, Rf_mkChar("logdet"));
+  SET_STRING_ELT(names, 1, Rf_mkChar("grad"));
+  SET_VECTOR_ELT(out, 0, ld);
+  SET_VECTOR_ELT(out, 1, g);
+  Rf_setAttrib(out, R_NamesSymbol, names);
+  UNPROTECT(4);
+  return out;
+}
+
 /* correlation family for the calls that follow: 0 = Gaussian, 1 = Matern(nu) of the 1-D script
  * (Matern.corr.func, 1D Combined GP Public.R:348-351), 2 = Matern(nu) + cubic spline of the two-family script
  * (1D Combined GP Two Families Public.R:346-357, 453-462) */
@@ -651,6 +683,7 @@ static const R_CallMethodDef call_methods[] = {
     {"ccgp_R_beta_mle", (DL_FUNC)&ccgp_R_beta_mle, 2},
     {"ccgp_R_sigma2_mle", (DL_FUNC)&ccgp_R_sigma2_mle, 3},
     {"ccgp_R_mixed_logdet_designs", (DL_FUNC)&ccgp_R_mixed_logdet_designs, 5},
+    {"ccgp_R_mixed_logdet_grad_designs", (DL_FUNC)&ccgp_R_mixed_logdet_grad_designs, 6},
     {"ccgp_R_set_kernel", (DL_FUNC)&ccgp_R_set_kernel, 2},
     {"ccgp_R_devices", (DL_FUNC)&ccgp_R_devices, 0},
     {NULL, NULL, 0}};
