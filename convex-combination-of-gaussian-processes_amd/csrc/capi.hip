@@ -9,11 +9,13 @@
 #include <exception>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "ccgp_internal.h"
 #include "special_math.h"
+#include "stage_layout.h"
 
 using namespace ccgp;
 
@@ -52,8 +54,11 @@ int fail_noexcept(ccgp_handle* h, int code, const char* msg) noexcept {
     }                                                                               \
   } while (0)
 
-// the Matern / spline families exist for the 1-D scripts only
-int check_family(ccgp_handle* h, const KernelFamily& fam, int d, int K) {
+// the B draws at `params` as the kernels see them, in kernel family `fam`; refuses what that family cannot do (the
+// Matern / spline families exist for the 1-D scripts only).  Callers run this BEFORE they push their inputs: a refused
+// call costs no PCIe traffic.
+int draw_view(ccgp_handle* h, const KernelFamily& fam, const double* params, int B, int K, int d, DrawView* dv) {
+  *dv = DrawView{params, B, K, d, fam};
   if (fam.id != 0 && d != 1)
     return fail(h, CCGP_EUNSUPPORTED, "the Matern / spline families are one-dimensional (D1:348-389): d must be 1");
   if (fam.id == 2 && K != 2)
@@ -114,35 +119,39 @@ int ensure_pin(ccgp_handle* h, size_t bytes) {
   return CCGP_OK;
 }
 
-// bump allocator over the staging buffer (256-byte aligned pieces)
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* p) : base(static_cast<char*>(p)) {}
-  static size_t al(size_t b) { return (b + 255) / 256 * 256; }
-  template <class T>
-  T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(base + off);
-    off += al(count * sizeof(T));
-    return p;
-  }
-};
+// the staging buffer of one call: `lay` declares its pieces (stage_layout.h) and runs twice, once to size the buffer and
+// once, over the buffer, to hand out the pointers
+template <class F>
+int stage(ccgp_handle* h, F&& lay) {
+  if (int rc = ensure_stage(h, layout_bytes(lay))) return rc;
+  Layout real(h->stage);
+  lay(real);
+  return CCGP_OK;
+}
 
 // ---- host <-> device traffic of the host-pointer entry points ------------------------------------------------
-// The pieces of a call lie back to back in the handle's staging buffer (Carver).  A hipMemcpyAsync from / to
+// The pieces of a call lie back to back in the handle's staging buffer (Layout).  A hipMemcpyAsync from / to
 // pageable memory is a staged, synchronous copy of its own (10 - 20 us each); what the reference's callers issue
 // are many SMALL calls (predict.post per draw and test site HX:688, beta.MLE / factors per draw HX:641), so up to
 // kPinMax the host image of the whole span is assembled in the handle's pinned buffer and crosses PCIe in ONE copy
-// each way; larger payloads are copied piece by piece as before.
+// each way; larger payloads are copied piece by piece as before.  pin_max lowers that bound for a call that has
+// measured a smaller one (ccgp_loglik_batch); 0 means piece by piece.
 struct Piece {
   void* dev;
   void* host;      // source for push, destination for pull; nullptr: skip
   size_t bytes;
 };
+struct Pieces {   // a braced list at the call site, or a vector
+  const Piece *b, *e;
+  Pieces(std::initializer_list<Piece> l) : b(l.begin()), e(l.end()) {}
+  Pieces(const std::vector<Piece>& v) : b(v.data()), e(v.data() + v.size()) {}
+  const Piece* begin() const { return b; }
+  const Piece* end() const { return e; }
+};
 constexpr size_t kPinMax = size_t(8) << 20;
 constexpr int kPullSlices = ccgp::kPullSlices;
 
-int push(ccgp_handle* h, std::initializer_list<Piece> ps) {
+int push(ccgp_handle* h, Pieces ps, size_t pin_max = kPinMax) {
   char *lo = nullptr, *hi = nullptr;
   for (const Piece& p : ps) {
     if (!p.host || !p.bytes) continue;
@@ -153,12 +162,12 @@ int push(ccgp_handle* h, std::initializer_list<Piece> ps) {
   h->pin_in = 0;
   if (!lo) return CCGP_OK;
   const size_t span = (size_t)(hi - lo);
-  if (span <= kPinMax && ensure_pin(h, span) == CCGP_OK) {
+  if (span <= pin_max && ensure_pin(h, span) == CCGP_OK) {
     char* pin = static_cast<char*>(h->pin);
     for (const Piece& p : ps)
       if (p.host && p.bytes) std::memcpy(pin + (static_cast<char*>(p.dev) - lo), p.host, p.bytes);
     CCGP_HIP(hipMemcpyAsync(lo, pin, span, hipMemcpyHostToDevice, h->stream));
-    h->pin_in = Carver::al(span);
+    h->pin_in = Layout::al(span);
     return CCGP_OK;
   }
   for (const Piece& p : ps)
@@ -167,7 +176,7 @@ int push(ccgp_handle* h, std::initializer_list<Piece> ps) {
 }
 
 // device -> host of the result pieces, then the stream is synchronised (the call's results are valid on return)
-int pull(ccgp_handle* h, std::initializer_list<Piece> ps) {
+int pull(ccgp_handle* h, Pieces ps, size_t pin_max = kPinMax) {
   char *lo = nullptr, *hi = nullptr;
   for (const Piece& p : ps) {
     if (!p.host || !p.bytes) continue;
@@ -180,7 +189,7 @@ int pull(ccgp_handle* h, std::initializer_list<Piece> ps) {
     return CCGP_OK;
   }
   const size_t span = (size_t)(hi - lo);
-  if (span <= kPinMax && ensure_pin(h, h->pin_in + span) == CCGP_OK) {
+  if (span <= pin_max && ensure_pin(h, h->pin_in + span) == CCGP_OK) {
     char* pin = static_cast<char*>(h->pin) + h->pin_in;
     // a large result (the S x m tables of ccgp_predict_batch: 2.4 MB per Ground-Vibrations set) comes back in four
     // slices, each followed by an event: the host copies slice c out of the pinned buffer while slice c + 1 is still
@@ -229,35 +238,48 @@ bool bad_shape(int n, int d, int K) {
   return n < 1 || d < 1 || d > kMaxD || K < 1 || K > kMaxK;
 }
 
-// blocked-path chunk size (matrices per pass) under the workspace limit
-int blocked_chunk(const ccgp_handle* h, int npad, int B, int ne = 0) {
-  size_t per = blocked_ws_bytes(npad, 1, ne);
-  // never plan beyond what the device can give right now (other handles / processes may share it):
-  // free memory plus what this handle would release by regrowing, less a margin
+// How many items (matrices of a blocked sweep, draws of a kept-factor prediction) one pass takes, and the workspace for
+// them: as many as `per_item` bytes each allow under the workspace limit and under what the device can give right now
+// (free memory plus what this handle would release by regrowing, less `margin`: other handles / processes may share
+// the device), at most 65535 (the chunk index is a grid y / z dimension in cov_kernel, rhs_rows_kernel, ...), at
+// least 1.  The workspace grows to total_bytes(chunk); when another handle / process took the memory in between, the
+// chunk is halved until it fits.
+constexpr size_t kSweepMargin = size_t(1) << 30;
+constexpr size_t kFactorsetMargin = size_t(256) << 20;   // the factor set itself holds most of the device
+
+template <class TotalBytes>
+int plan_chunk(ccgp_handle* h, size_t per_item, int count, size_t margin, TotalBytes total_bytes, int* chunk) {
   size_t limit = h->ws_limit, free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-    const size_t margin = size_t(1) << 30;
     const size_t avail = free_b + h->ws_bytes > margin ? free_b + h->ws_bytes - margin : 0;
     if (avail < limit) limit = avail;
   }
-  size_t nb = limit / per;
-  if (nb < 1) nb = 1;
-  if (nb > (size_t)B) nb = B;
-  if (nb > 65535) nb = 65535;   // the chunk index is a grid y / z dimension in cov_kernel, rhs_rows_kernel, ...
-  return (int)nb;
+  int nb = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)count, 65535), limit / per_item));
+  int rc = ensure_ws(h, total_bytes(nb));
+  while (rc == CCGP_ENOMEM && nb > 1) {
+    nb = (nb + 1) / 2;
+    rc = ensure_ws(h, total_bytes(nb));
+  }
+  *chunk = nb;
+  return rc;
 }
 
-int loglik_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy, int K,
-               const double* dparams, int B, double sigma2, int mean_mode, double tau2,
-               double* d_loglik, double* d_beta, int* d_status) {
-  if (bad_shape(n, d, K) || B < 0 || !dX || !dy || !dparams || !d_loglik || !d_status)
-    return fail(h, CCGP_EINVAL, "ccgp_loglik_batch: bad argument");
+// the blocked sweep's plan: matrices of npad rows with ne extra tile rows, `tail` bytes of scratch behind them
+int sweep_chunk(ccgp_handle* h, int npad, int ne, int count, size_t tail, int* chunk) {
+  return plan_chunk(h, blocked_ws_bytes(npad, 1, ne), count, kSweepMargin,
+                    [&](int nb) { return blocked_ws_bytes(npad, nb, ne) + tail; }, chunk);
+}
+
+int check_mean_mode(ccgp_handle* h, int mean_mode) {
   if (mean_mode != CCGP_MEAN_PROFILE_BETA && mean_mode != CCGP_MEAN_ZERO_PLUS_TAU2)
     return fail(h, CCGP_EINVAL, "ccgp_loglik_batch: unknown mean_mode");
-  if (B == 0) return CCGP_OK;
-  DrawView dv{dparams, B, K, d};
-  dv.fam = h->fam;
-  if (int frc = check_family(h, dv.fam, d, K)) return frc;
+  return CCGP_OK;
+}
+
+// the B >= 1 evaluations of dv on resident inputs; arguments are checked by the callers
+int loglik_run(ccgp_handle* h, const double* dX, int n, int d, const double* dy, const DrawView& dv, double sigma2,
+               int mean_mode, double tau2, double* d_loglik, double* d_beta, int* d_status) {
+  const int K = dv.K, B = dv.ldp;
   // the fused evaluators generate Gaussian correlations in registers; any other family goes through
   // the materialised-matrix (blocked) path, where only cov_kernel knows about families
   const bool gauss = dv.fam.id == 0;
@@ -275,13 +297,8 @@ int loglik_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy,
     return CCGP_OK;
   }
   const int npad = round_up(n, kTile);
-  int nbc = blocked_chunk(h, npad, B);
-  int rc = ensure_ws(h, blocked_ws_bytes(npad, nbc, 0));
-  while (rc == CCGP_ENOMEM && nbc > 1) {   // another handle / process took the memory in between: smaller chunks
-    nbc = (nbc + 1) / 2;
-    rc = ensure_ws(h, blocked_ws_bytes(npad, nbc, 0));
-  }
-  if (rc) return rc;
+  int nbc = 0;
+  if (int rc = sweep_chunk(h, npad, 0, B, 0, &nbc)) return rc;
   CCGP_HIP(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)B, h->stream));
   for (int b0 = 0; b0 < B; b0 += nbc) {
     const int nb = std::min(nbc, B - b0);
@@ -293,10 +310,95 @@ int loglik_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy,
   return CCGP_OK;
 }
 
-int count_bad(const int* status, int B) {
+int loglik_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy, int K,
+               const double* dparams, int B, double sigma2, int mean_mode, double tau2,
+               double* d_loglik, double* d_beta, int* d_status) {
+  if (bad_shape(n, d, K) || B < 0 || !dX || !dy || !dparams || !d_loglik || !d_status)
+    return fail(h, CCGP_EINVAL, "ccgp_loglik_batch: bad argument");
+  if (int rc = check_mean_mode(h, mean_mode)) return rc;
+  if (B == 0) return CCGP_OK;
+  DrawView dv;
+  if (int rc = draw_view(h, h->fam, dparams, B, K, d, &dv)) return rc;
+  return loglik_run(h, dX, n, d, dy, dv, sigma2, mean_mode, tau2, d_loglik, d_beta, d_status);
+}
+
+// the end of a batch call: the status words go to the caller if asked for, and the number of failed evaluations is the
+// C ABI's positive return value
+int report_status(const std::vector<int>& st, int* status) {
+  if (status) std::memcpy(status, st.data(), sizeof(int) * st.size());
   int c = 0;
-  for (int i = 0; i < B; ++i) c += status[i] != 0;
+  for (int v : st) c += v != 0;
   return c;
+}
+
+// pull the result pieces and the B status words at dst, then report_status.  whole_doubles: one word more when B is odd,
+// for a caller whose status words close a piece of doubles (ccgp_loglik_batch: the copy back stays a multiple of 8 bytes;
+// 140 instead of 144 bytes for 7 candidates measured 1.2 us more per call)
+int pull_status(ccgp_handle* h, std::initializer_list<Piece> ps, int* dst, int B, int* status, size_t pin_max = kPinMax,
+                bool whole_doubles = false) {
+  std::vector<int> st((size_t)B + (whole_doubles ? B & 1 : 0));
+  std::vector<Piece> all;
+  all.reserve(ps.size() + 1);
+  all.assign(ps);
+  all.push_back(piece(dst, st.data(), st.size()));
+  if (int rc = pull(h, all, pin_max)) return rc;
+  st.resize(B);
+  return report_status(st, status);
+}
+
+// ---- layouts that more than one function needs (ccgp_reserve sizes the buffers of the calls it reserves for) --------
+// staging of ccgp_loglik_batch: inputs X | y | params and results loglik | beta | status, each ONE piece, so that each
+// side crosses PCIe as one span
+struct LoglikStage {
+  double *X = nullptr, *y = nullptr, *params = nullptr, *loglik = nullptr, *beta = nullptr;
+  int* status = nullptr;
+  size_t payload = 0;   // bytes of the two pieces
+};
+LoglikStage loglik_stage(Layout& c, int n, int d, int P, int B) {
+  const size_t in_d = (size_t)n * d + n + (size_t)B * P, out_d = 2 * (size_t)B + ((size_t)B + 1) / 2;
+  double* in = c.take<double>(in_d);
+  double* out = c.take<double>(out_d);
+  LoglikStage s;
+  s.payload = sizeof(double) * (in_d + out_d);
+  if (!in) return s;   // planning pass
+  s.X = in;
+  s.y = in + (size_t)n * d;
+  s.params = s.y + n;
+  s.loglik = out;
+  s.beta = out + B;
+  s.status = reinterpret_cast<int*>(out + 2 * (size_t)B);
+  return s;
+}
+
+// staging of ccgp_predict_batch
+struct PredictStage {
+  double *X, *y, *params, *Xtest, *mean, *var, *beta;
+  int* status;
+};
+PredictStage predict_stage(Layout& c, int n, int d, int P, int S, int m) {
+  PredictStage s;
+  s.X = c.take<double>((size_t)n * d);
+  s.y = c.take<double>(n);
+  s.params = c.take<double>((size_t)S * P);
+  s.Xtest = c.take<double>((size_t)m * d);
+  s.mean = c.take<double>((size_t)S * m);
+  s.var = c.take<double>((size_t)S * m);
+  s.beta = c.take<double>(S);
+  s.status = c.take<int>(S);
+  return s;
+}
+
+// blocked prediction: scratch behind the matrices for the outputs the caller did not ask for
+struct PredictTail {
+  double *ll, *beta;
+  int* status;
+};
+PredictTail predict_tail(Layout& t, int S, double* d_beta, int* d_status) {
+  PredictTail p;
+  p.ll = t.take<double>(S);
+  p.beta = d_beta ? d_beta : t.take<double>(S);
+  p.status = d_status ? d_status : t.take<int>(S);
+  return p;
 }
 
 // ---- tiny kernels for the literal R.Inv-based helpers (a6, a7, a10, a11) -----------------
@@ -613,16 +715,15 @@ int ccgp_reserve(ccgp_handle* h, int n, int d, int K, int B, int m) try {
   if (!h || bad_shape(n, d, K) || B < 1 || m < 0) return fail(h, CCGP_EINVAL, "ccgp_reserve: bad argument");
   CCGP_HIP(hipSetDevice(h->device));
   if (n > kSmallMaxN || h->fam.id != 0) {
-    const int npad = round_up(n, kTile);
-    const int ne = (m + kTile - 1) / kTile;
-    int rc = ensure_ws(h, blocked_ws_bytes(npad, blocked_chunk(h, npad, B, ne), ne));
-    if (rc) return rc;
+    const int npad = round_up(n, kTile), ne = (m + kTile - 1) / kTile;
+    const size_t tail = m ? layout_bytes([&](Layout& t) { predict_tail(t, B, nullptr, nullptr); }) : 0;
+    int nbc = 0;
+    if (int rc = sweep_chunk(h, npad, ne, B, tail, &nbc)) return rc;
   }
   const int P = K + K * d;
-  size_t st = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * n) +
-              Carver::al(sizeof(double) * (size_t)B * P) + 3 * Carver::al(sizeof(double) * B) +
-              Carver::al(sizeof(double) * (size_t)m * d) + 2 * Carver::al(sizeof(double) * (size_t)B * m) + 4096;
-  return ensure_stage(h, st);
+  const size_t st_ll = layout_bytes([&](Layout& c) { loglik_stage(c, n, d, P, B); });
+  const size_t st_pr = m ? layout_bytes([&](Layout& c) { predict_stage(c, n, d, P, B, m); }) : 0;
+  return ensure_stage(h, std::max(st_ll, st_pr));
 } CCGP_GUARD_END(h)
 
 int ccgp_enable_timing(ccgp_handle* h, int on) try {
@@ -669,20 +770,18 @@ static int corr_common(ccgp_handle* h, const double* Xnew, int m, const double* 
     return fail(h, CCGP_EINVAL, "ccgp_corr_*: bad argument");
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
-  size_t need = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * (size_t)m * d) +
-                Carver::al(sizeof(double) * P) + Carver::al(sizeof(double) * (size_t)m * n);
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dX = c.take<double>((size_t)n * d);
-  double* dXn = c.take<double>((size_t)m * d);
-  double* dp = c.take<double>(P);
-  double* dout = c.take<double>((size_t)m * n);
+  double *dX, *dXn, *dp, *dout;
+  if (int rc = stage(h, [&](Layout& c) {
+        dX = c.take<double>((size_t)n * d);
+        dXn = c.take<double>((size_t)m * d);
+        dp = c.take<double>(P);
+        dout = c.take<double>((size_t)m * n);
+      }))
+    return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
   if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dXn, gram ? nullptr : Xnew, (size_t)m * d), piece(dp, params_row, P)}))
     return prc;
-  DrawView dv{dp, 1, K, d};
-  dv.fam = h->fam;
-  if (int frc = check_family(h, dv.fam, d, K)) return frc;
   {
     ScopedTimer t(h, CCGP_T_COV);
     launch_cov_dense(h->stream, gram ? dX : dXn, m, dX, n, d, dv, 0, dout, m);
@@ -724,15 +823,15 @@ static int rinv_terms(ccgp_handle* h, const double* R_inv, const double* y, int 
                       double* mean_factor, double* colsum, double scal[3]) {
   if (!h || n < 1 || !R_inv || !y) return fail(h, CCGP_EINVAL, "R.Inv helper: bad argument");
   CCGP_HIP(hipSetDevice(h->device));
-  size_t need = Carver::al(sizeof(double) * (size_t)n * n) + 3 * Carver::al(sizeof(double) * n) + 256;
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dR = c.take<double>((size_t)n * n);
-  double* dy = c.take<double>(n);
-  double* dmf = c.take<double>(n);
-  double* dcs = c.take<double>(n);
-  double* dsc = c.take<double>(4);
+  double *dR, *dy, *dmf, *dcs, *dsc;
+  if (int rc = stage(h, [&](Layout& c) {
+        dR = c.take<double>((size_t)n * n);
+        dy = c.take<double>(n);
+        dmf = c.take<double>(n);
+        dcs = c.take<double>(n);
+        dsc = c.take<double>(4);
+      }))
+    return rc;
   if (int prc = push(h, {piece(dR, R_inv, (size_t)n * n), piece(dy, y, n)})) return prc;
   hipLaunchKernelGGL(rinv_terms_kernel, dim3(1), dim3(256), 0, h->stream, dR, dy, n, beta, dmf, dcs, dsc);
   CCGP_LAUNCH_CHECK();
@@ -775,17 +874,16 @@ int ccgp_predict_from_factors(ccgp_handle* h, const double* r, int m, int n, dou
   if (!h || m < 1 || n < 1 || !r || !mean_factor || !var_factor1 || !R_inv || !out_mean || !out_var)
     return fail(h, CCGP_EINVAL, "ccgp_predict_from_factors: bad argument");
   CCGP_HIP(hipSetDevice(h->device));
-  size_t need = Carver::al(sizeof(double) * (size_t)n * n) + Carver::al(sizeof(double) * (size_t)m * n) +
-                2 * Carver::al(sizeof(double) * n) + 2 * Carver::al(sizeof(double) * m);
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dR = c.take<double>((size_t)n * n);
-  double* dr = c.take<double>((size_t)m * n);
-  double* dmf = c.take<double>(n);
-  double* dv1 = c.take<double>(n);
-  double* dmean = c.take<double>(m);
-  double* dvar = c.take<double>(m);
+  double *dR, *dr, *dmf, *dv1, *dmean, *dvar;
+  if (int rc = stage(h, [&](Layout& c) {
+        dR = c.take<double>((size_t)n * n);
+        dr = c.take<double>((size_t)m * n);
+        dmf = c.take<double>(n);
+        dv1 = c.take<double>(n);
+        dmean = c.take<double>(m);
+        dvar = c.take<double>(m);
+      }))
+    return rc;
   if (int prc = push(h, {piece(dR, R_inv, (size_t)n * n), piece(dr, r, (size_t)m * n), piece(dmf, mean_factor, n),
                          piece(dv1, var_factor1, n)}))
     return prc;
@@ -804,28 +902,24 @@ int ccgp_predict_post(ccgp_handle* h, const double* Xnew, int m, const double* X
     return fail(h, CCGP_EINVAL, "ccgp_predict_post: bad argument");
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
-  size_t need = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * (size_t)m * d) +
-                Carver::al(sizeof(double) * P) + 2 * Carver::al(sizeof(double) * n) +
-                Carver::al(sizeof(double) * (size_t)n * n) + Carver::al(sizeof(double) * (size_t)m * n) +
-                2 * Carver::al(sizeof(double) * m);
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dX = c.take<double>((size_t)n * d);
-  double* dXn = c.take<double>((size_t)m * d);
-  double* dp = c.take<double>(P);
-  double* dmf = c.take<double>(n);
-  double* dv1 = c.take<double>(n);
-  double* dR = c.take<double>((size_t)n * n);
-  double* dr = c.take<double>((size_t)m * n);
-  double* dmean = c.take<double>(m);
-  double* dvar = c.take<double>(m);
+  double *dX, *dXn, *dp, *dmf, *dv1, *dR, *dr, *dmean, *dvar;
+  if (int rc = stage(h, [&](Layout& c) {
+        dX = c.take<double>((size_t)n * d);
+        dXn = c.take<double>((size_t)m * d);
+        dp = c.take<double>(P);
+        dmf = c.take<double>(n);
+        dv1 = c.take<double>(n);
+        dR = c.take<double>((size_t)n * n);
+        dr = c.take<double>((size_t)m * n);
+        dmean = c.take<double>(m);
+        dvar = c.take<double>(m);
+      }))
+    return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
   if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dXn, Xnew, (size_t)m * d), piece(dp, params_row, P),
                          piece(dmf, mean_factor, n), piece(dv1, var_factor1, n), piece(dR, R_inv, (size_t)n * n)}))
     return prc;
-  DrawView dv{dp, 1, K, d};
-  dv.fam = h->fam;
-  if (int frc = check_family(h, dv.fam, d, K)) return frc;
   {
     ScopedTimer t(h, CCGP_T_COV);   // r = Mixed.corr.vec(x_t, D.train, ...) (HX:665), exactly ccgp_mixed_corr_cross's kernel
     launch_cov_dense(h->stream, dXn, m, dX, n, d, dv, 0, dr, m);
@@ -854,54 +948,21 @@ int ccgp_loglik_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
     return fail(h, CCGP_EINVAL, "ccgp_loglik_batch: bad argument");
   if (B == 0) return CCGP_OK;
   CCGP_HIP(hipSetDevice(h->device));
+  if (int rc = check_mean_mode(h, mean_mode)) return rc;
   const int P = K + K * d;
-  // inputs X | y | params and results loglik | beta | status, each contiguous on the device
-  const size_t in_d = (size_t)n * d + n + (size_t)B * P;
-  const size_t out_d = 2 * (size_t)B + ((size_t)B + 1) / 2;
-  int rc = ensure_stage(h, Carver::al(sizeof(double) * in_d) + Carver::al(sizeof(double) * out_d));
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* din = c.take<double>(in_d);
-  double* dout = c.take<double>(out_d);
-  double* dX = din;
-  double* dy = din + (size_t)n * d;
-  double* dp = dy + n;
-  double* dll = dout;
-  double* dbeta = dout + B;
-  int* dst = reinterpret_cast<int*>(dout + 2 * (size_t)B);
+  LoglikStage s;
+  if (int rc = stage(h, [&](Layout& c) { s = loglik_stage(c, n, d, P, B); })) return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, B, K, d, &dv)) return frc;
   // A small call (a speculative batch of Metropolis candidates, the points of a numerical derivative) is dominated by
   // the host side: through pageable memory every one of the three uploads and three downloads is a staged,
-  // synchronous copy of its own.  Up to 1 MiB the payload goes through the handle's pinned buffer: ONE copy each way.
-  const bool pinned = sizeof(double) * (in_d + out_d) <= (size_t(1) << 20) && ensure_pin(h, sizeof(double) * (in_d + out_d)) == CCGP_OK;
-  if (pinned) {
-    double* pin = static_cast<double*>(h->pin);
-    std::memcpy(pin, X, sizeof(double) * (size_t)n * d);
-    std::memcpy(pin + (size_t)n * d, y, sizeof(double) * n);
-    std::memcpy(pin + (size_t)n * d + n, params, sizeof(double) * (size_t)B * P);
-    CCGP_HIP(hipMemcpyAsync(din, pin, sizeof(double) * in_d, hipMemcpyHostToDevice, h->stream));
-  } else {
-    CCGP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream));
-    CCGP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    CCGP_HIP(hipMemcpyAsync(dp, params, sizeof(double) * (size_t)B * P, hipMemcpyHostToDevice, h->stream));
-  }
-  rc = loglik_dev(h, dX, n, d, dy, K, dp, B, sigma2, mean_mode, tau2, dll, dbeta, dst);
-  if (rc) return rc;
-  std::vector<int> st(B);
-  if (pinned) {
-    double* pout = static_cast<double*>(h->pin) + in_d;
-    CCGP_HIP(hipMemcpyAsync(pout, dout, sizeof(double) * out_d, hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipStreamSynchronize(h->stream));
-    std::memcpy(out_loglik, pout, sizeof(double) * B);
-    if (out_beta) std::memcpy(out_beta, pout + B, sizeof(double) * B);
-    std::memcpy(st.data(), pout + 2 * (size_t)B, sizeof(int) * (size_t)B);
-  } else {
-    CCGP_HIP(hipMemcpyAsync(out_loglik, dll, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-    if (out_beta) CCGP_HIP(hipMemcpyAsync(out_beta, dbeta, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipMemcpyAsync(st.data(), dst, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipStreamSynchronize(h->stream));
-  }
-  if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)B);
-  return count_bad(st.data(), B);
+  // synchronous copy of its own.  Up to 1 MiB (inputs + results) the payload goes through the handle's pinned buffer:
+  // ONE copy each way, the two spans of loglik_stage.
+  const size_t pin_max = s.payload <= (size_t(1) << 20) ? kPinMax : 0;
+  if (int prc = push(h, {piece(s.X, X, (size_t)n * d), piece(s.y, y, n), piece(s.params, params, (size_t)B * P)}, pin_max))
+    return prc;
+  if (int rc = loglik_run(h, s.X, n, d, s.y, dv, sigma2, mean_mode, tau2, s.loglik, s.beta, s.status)) return rc;
+  return pull_status(h, {piece(s.loglik, out_loglik, B), piece(s.beta, out_beta, B)}, s.status, B, status, pin_max, true);
 } CCGP_GUARD_END(h)
 
 int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
@@ -914,53 +975,48 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_loglik_grad_batch: analytic gradient is implemented for the Gaussian family only");
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
-  if (n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64) {
+  const bool blocked = n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64;
+  if (blocked && !blocked_grad_supported(d, K))
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_loglik_grad_batch: d + K too large for the contraction kernel's LDS");
+  const int nch = blocked ? 0 : small_grad_chunks(n, d);
+  double *dX, *dy, *dp, *dg, *dll, *dbeta, *dgp = nullptr;
+  int* dst;
+  if (int rc = stage(h, [&](Layout& c) {
+        dX = c.take<double>((size_t)n * d);
+        dy = c.take<double>(n);
+        dp = c.take<double>((size_t)B * P);
+        dg = c.take<double>((size_t)B * P);
+        dll = c.take<double>(B);
+        dbeta = c.take<double>(B);
+        dst = c.take<int>(B);
+        if (!blocked) dgp = c.take<double>((size_t)B * nch * P);   // partial sums of launch_small_grad
+      }))
+    return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dp, B, K, d, &dv)) return frc;
+  if (blocked) {
     // blocked path: identity rows ride along as extra tile rows, then the tiles of R^-1 are formed (rinv_tile_kernel), turned
     // into M and contracted with the kernel derivatives (grad_contract_kernel; blocked.hip)
-    if (!blocked_grad_supported(d, K))
-      return fail(h, CCGP_EUNSUPPORTED, "ccgp_loglik_grad_batch: d + K too large for the contraction kernel's LDS");
     const int npad = round_up(n, kTile), nt = npad / kTile, ne = nt;
     const size_t ntiles = blocked_grad_partials(npad);
-    const size_t per_extra = sizeof(double) * (ntiles * P + npad);
-    size_t per = blocked_ws_bytes(npad, 1, ne) + per_extra;
-    size_t glimit = h->ws_limit, gfree = 0, gtotal = 0;
-    if (hipMemGetInfo(&gfree, &gtotal) == hipSuccess) {
-      const size_t margin = size_t(1) << 30;
-      const size_t avail = gfree + h->ws_bytes > margin ? gfree + h->ws_bytes - margin : 0;
-      if (avail < glimit) glimit = avail;
-    }
-    int nbc = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)B, 65535), glimit / per));
-    size_t need_st = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * n) +
-                     2 * Carver::al(sizeof(double) * (size_t)B * P) + 2 * Carver::al(sizeof(double) * B) +
-                     Carver::al(sizeof(int) * (size_t)B);
-    int rc = ensure_stage(h, need_st);
-    if (rc) return rc;
-    rc = ensure_ws(h, blocked_ws_bytes(npad, nbc, ne) + (size_t)nbc * per_extra + 512);
-    while (rc == CCGP_ENOMEM && nbc > 1) {   // as in loglik_dev: halve the chunk until the workspace fits
-      nbc = (nbc + 1) / 2;
-      rc = ensure_ws(h, blocked_ws_bytes(npad, nbc, ne) + (size_t)nbc * per_extra + 512);
-    }
-    if (rc) return rc;
-    Carver c(h->stage);
-    double* dX = c.take<double>((size_t)n * d);
-    double* dy = c.take<double>(n);
-    double* dp = c.take<double>((size_t)B * P);
-    double* dg = c.take<double>((size_t)B * P);
-    double* dll = c.take<double>(B);
-    double* dbeta = c.take<double>(B);
-    int* dst = c.take<int>(B);
+    // the workspace: the chunk's matrices, then the contraction's partial sums and alpha for every matrix of the chunk
+    BlockedJob job{};
+    job.kind = kJobGrad; job.grad = dg; job.Btot = B;
+    auto ws_lay = [&](Layout& w, int nb) {
+      w.take<char>(blocked_ws_bytes(npad, nb, ne));
+      job.gpart = w.take<double>((size_t)nb * ntiles * P);
+      job.alpha = w.take<double>((size_t)nb * npad);
+    };
+    int nbc = 0;
+    if (int rc = plan_chunk(h, blocked_ws_bytes(npad, 1, ne) + sizeof(double) * (ntiles * P + npad), B, kSweepMargin,
+                            [&](int nb) { return layout_bytes([&](Layout& w) { ws_lay(w, nb); }); }, &nbc))
+      return rc;
+    Layout ws(h->ws);
+    ws_lay(ws, nbc);
     CCGP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream));
     CCGP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     CCGP_HIP(hipMemcpyAsync(dp, params, sizeof(double) * (size_t)B * P, hipMemcpyHostToDevice, h->stream));
     CCGP_HIP(hipMemsetAsync(dst, 0, sizeof(int) * (size_t)B, h->stream));
-    DrawView dv{dp, B, K, d};
-    dv.fam = h->fam;
-    if (int frc = check_family(h, dv.fam, d, K)) return frc;
-    Carver tail(static_cast<char*>(h->ws) + Carver::al(blocked_ws_bytes(npad, nbc, ne)));
-    BlockedJob job{};
-    job.kind = kJobGrad; job.grad = dg; job.Btot = B;
-    job.gpart = tail.take<double>((size_t)nbc * ntiles * P);
-    job.alpha = tail.take<double>((size_t)nbc * npad);
     for (int b0 = 0; b0 < B; b0 += nbc) {
       const int nb = std::min(nbc, B - b0);
       BlockedWs w = blocked_carve(h->ws, npad, nb, ne);
@@ -974,28 +1030,9 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
     CCGP_HIP(hipMemcpyAsync(out_grad, dg, sizeof(double) * (size_t)B * P, hipMemcpyDeviceToHost, h->stream));
     CCGP_HIP(hipMemcpyAsync(st.data(), dst, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, h->stream));
     CCGP_HIP(hipStreamSynchronize(h->stream));
-    if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)B);
-    return count_bad(st.data(), B);
+    return report_status(st, status);
   }
-  const int nch = small_grad_chunks(n, d);
-  size_t need = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * n) +
-                2 * Carver::al(sizeof(double) * (size_t)B * P) + 2 * Carver::al(sizeof(double) * B) +
-                Carver::al(sizeof(int) * (size_t)B) + Carver::al(sizeof(double) * (size_t)B * nch * P);
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dX = c.take<double>((size_t)n * d);
-  double* dy = c.take<double>(n);
-  double* dp = c.take<double>((size_t)B * P);
-  double* dg = c.take<double>((size_t)B * P);
-  double* dll = c.take<double>(B);
-  double* dbeta = c.take<double>(B);
-  int* dst = c.take<int>(B);
-  double* dgp = c.take<double>((size_t)B * nch * P);
   if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, (size_t)B * P)})) return prc;
-  DrawView dv{dp, B, K, d};
-  dv.fam = h->fam;
-  if (int frc = check_family(h, dv.fam, d, K)) return frc;
   {
     ScopedTimer t(h, CCGP_T_FUSED);
     if (small_reg_inverse_supported(n, d, K))
@@ -1004,12 +1041,8 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
       launch_small_grad(h->stream, dX, n, d, dy, dv, B, sigma2, dll, dbeta, dg, dst, dgp);
   }
   CCGP_LAUNCH_CHECK();
-  std::vector<int> st(B);
-  if (int prc = pull(h, {piece(dg, out_grad, (size_t)B * P), piece(dll, out_loglik, B), piece(dbeta, out_beta, B),
-                         piece(dst, st.data(), B)}))
-    return prc;
-  if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)B);
-  return count_bad(st.data(), B);
+  return pull_status(h, {piece(dg, out_grad, (size_t)B * P), piece(dll, out_loglik, B), piece(dbeta, out_beta, B)}, dst, B,
+                     status);
 } CCGP_GUARD_END(h)
 
 // ---- a8: logpost ------------------------------------------------------------------------------
@@ -1046,18 +1079,23 @@ static void logpost_terms(int prior_id, int d, const double* theta_t, int ldt, c
   *log_prior = lp;
 }
 
+// the argument checks ccgp_logpost and ccgp_logpost_batch share; `who` is the name the message carries
+static int logpost_args(ccgp_handle* h, const char* who, bool shapes_ok, int d, int prior_id, const double* prior_pars) {
+  auto bad = [&](const char* what) { return fail(h, CCGP_EINVAL, std::string(who) + what); };
+  if (!shapes_ok) return bad(": bad argument");
+  if (prior_id < CCGP_PRIOR_INVGAMMA || prior_id > CCGP_PRIOR_ANI) return bad(": unknown prior_id");
+  if (prior_id == CCGP_PRIOR_INVGAMMA && !prior_pars) return bad(": prior_pars required for CCGP_PRIOR_INVGAMMA");
+  if (prior_id == CCGP_PRIOR_ANI && d != 2) return bad(": the anisotropic script (ANI) is 2-D");
+  return CCGP_OK;
+}
+
 int ccgp_logpost_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, double sigma2, int prior_id,
                        const double* theta_t, int B, const double* prior_pars, double* out_val, double* out_beta,
                        double* out_loglik, int* status) try {
   if (!h) return CCGP_EINVAL;
-  if (n < 1 || d < 1 || d > kMaxD || B < 1 || !X || !y || !theta_t || !out_val)
-    return fail(h, CCGP_EINVAL, "ccgp_logpost_batch: bad argument");
-  if (prior_id < CCGP_PRIOR_INVGAMMA || prior_id > CCGP_PRIOR_ANI)
-    return fail(h, CCGP_EINVAL, "ccgp_logpost_batch: unknown prior_id");
-  if (prior_id == CCGP_PRIOR_INVGAMMA && !prior_pars)
-    return fail(h, CCGP_EINVAL, "ccgp_logpost_batch: prior_pars required for CCGP_PRIOR_INVGAMMA");
-  if (prior_id == CCGP_PRIOR_ANI && d != 2)
-    return fail(h, CCGP_EINVAL, "ccgp_logpost_batch: the anisotropic script (ANI) is 2-D");
+  if (int rc = logpost_args(h, "ccgp_logpost_batch", n >= 1 && d >= 1 && d <= kMaxD && B >= 1 && X && y && theta_t && out_val,
+                            d, prior_id, prior_pars))
+    return rc;
   const int K = 2, P = K + K * d;
   std::vector<double> rows((size_t)B * P), ljac(B), lpri(B), ll(B), beta(B);
   std::vector<int> st(B);
@@ -1083,14 +1121,9 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
                  int prior_id, const double* theta_t, const double* prior_pars, double* out_val,
                  double* out_beta, double* out_loglik, double* out_Rinv, int* status) try {
   if (!h) return CCGP_EINVAL;
-  if (n < 1 || d < 1 || d > kMaxD || !X || !y || !theta_t || !out_val)
-    return fail(h, CCGP_EINVAL, "ccgp_logpost: bad argument");
-  if (prior_id < CCGP_PRIOR_INVGAMMA || prior_id > CCGP_PRIOR_ANI)
-    return fail(h, CCGP_EINVAL, "ccgp_logpost: unknown prior_id");
-  if (prior_id == CCGP_PRIOR_INVGAMMA && !prior_pars)
-    return fail(h, CCGP_EINVAL, "ccgp_logpost: prior_pars required for CCGP_PRIOR_INVGAMMA");
-  if (prior_id == CCGP_PRIOR_ANI && d != 2)
-    return fail(h, CCGP_EINVAL, "ccgp_logpost: the anisotropic script (ANI) is 2-D");
+  if (int rc = logpost_args(h, "ccgp_logpost", n >= 1 && d >= 1 && d <= kMaxD && X && y && theta_t && out_val, d, prior_id,
+                            prior_pars))
+    return rc;
   const int K = 2, P = K + K * d;
   std::vector<double> row(P);
   double log_jacob = 0.0, log_prior = 0.0;
@@ -1110,27 +1143,25 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
     // The sequential caller's path (Metro evaluates ONE proposal per logpost call, HX:505-512): latency, not
     // throughput.  Inputs are packed into a pinned host buffer and cross PCIe in ONE copy, the results (log-lik,
     // beta, status[, R^-1]) come back in one: 300 -> ~100 us per call with R.Inv at n = 64, 113 -> ~60 us without (round 2).
-    int rc2 = ensure_stage(h, Carver::al(sizeof(double) * in_d) + Carver::al(sizeof(double) * out_d) + 256);
-    if (rc2) return rc2;
-    double* pin = static_cast<double*>(h->pin);
-    std::memcpy(pin, X, sizeof(double) * (size_t)n * d);
-    std::memcpy(pin + (size_t)n * d, y, sizeof(double) * n);
-    std::memcpy(pin + (size_t)n * d + n, row.data(), sizeof(double) * P);
-    Carver c(h->stage);
     // With R.Inv the kernel stores its results STRAIGHT into the pinned host buffer (device-visible like any hipHostMalloc
     // memory): no device-to-host copy of the n x n inverse behind the kernel -- 84 -> 72 us per call at n = 64, 125 -> 115 at
     // n = 90.  (Value only: three doubles, no difference; reading the INPUTS through PCIe from the kernel is slower.)
     const bool zo = out_Rinv != nullptr;
-    double* pout = pin + in_d;
-    double* din = c.take<double>(in_d);
-    double* dout = zo ? pout : c.take<double>(out_d);
+    double *din, *dout = nullptr;
+    if (int rc2 = stage(h, [&](Layout& c) {
+          din = c.take<double>(in_d);
+          if (!zo) dout = c.take<double>(out_d);
+        }))
+      return rc2;
+    double* pout = static_cast<double*>(h->pin) + in_d;
+    if (zo) dout = pout;
     double* dX = din;
     double* dy = din + (size_t)n * d;
     double* dp = dy + n;
     int* dst = reinterpret_cast<int*>(dout + 2);
-    CCGP_HIP(hipMemcpyAsync(din, pin, sizeof(double) * in_d, hipMemcpyHostToDevice, h->stream));
-    DrawView dv{dp, 1, K, d};
-    dv.fam = h->fam;
+    DrawView dv;
+    if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
+    if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, row.data(), P)})) return prc;
     {
       ScopedTimer t(h, CCGP_T_FUSED);
       if (out_Rinv)
@@ -1152,30 +1183,25 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
   } else {
     const bool blocked = h->fam.id != 0 || n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64;
     const int npad = round_up(n, kTile), nt = npad / kTile;
-    size_t need = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * n) +
-                  Carver::al(sizeof(double) * P) + Carver::al(sizeof(double) * (size_t)n * n) +
-                  3 * Carver::al(sizeof(double) * 2) + 256;
-    int rc2 = ensure_stage(h, need);
-    if (rc2) return rc2;
-    if (blocked) {
-      rc2 = ensure_ws(h, blocked_ws_bytes(npad, 1, nt));
-      if (rc2) return rc2;
-    }
-    Carver c(h->stage);
-    double* dX = c.take<double>((size_t)n * d);
-    double* dy = c.take<double>(n);
-    double* dp = c.take<double>(P);
-    double* dR = c.take<double>((size_t)n * n);
-    double* dll = c.take<double>(1);
-    double* dbt = c.take<double>(1);
-    int* dst = c.take<int>(1);
+    double *dX, *dy, *dp, *dR, *dll, *dbt;
+    int* dst;
+    if (int rc2 = stage(h, [&](Layout& c) {
+          dX = c.take<double>((size_t)n * d);
+          dy = c.take<double>(n);
+          dp = c.take<double>(P);
+          dR = c.take<double>((size_t)n * n);
+          dll = c.take<double>(1);
+          dbt = c.take<double>(1);
+          dst = c.take<int>(1);
+        }))
+      return rc2;
+    if (int rc2 = blocked ? ensure_ws(h, blocked_ws_bytes(npad, 1, nt)) : CCGP_OK) return rc2;
+    DrawView dv;
+    if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
     CCGP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream));
     CCGP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     CCGP_HIP(hipMemcpyAsync(dp, row.data(), sizeof(double) * P, hipMemcpyHostToDevice, h->stream));
     CCGP_HIP(hipMemsetAsync(dst, 0, sizeof(int), h->stream));
-    DrawView dv{dp, 1, K, d};
-    dv.fam = h->fam;
-    if (int frc = check_family(h, dv.fam, d, K)) return frc;
     if (blocked) {
       // identity as extra tile rows of the blocked sweep, then R^-1 = Z Z' tile by tile
       BlockedJob job{};
@@ -1210,31 +1236,30 @@ int ccgp_mixed_logdet_designs(ccgp_handle* h, const double* Xs, int n, int d, in
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_mixed_logdet_designs: Gaussian family only (BSQ:856-877)");
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
-  if (!small_reg_supported(n, d, K, true)) {
-    // more than 128 points (or too wide for the register-resident evaluator): the blocked sweep, one design at a time --
-    // its chunk shares ONE design among its matrices, and here every matrix has its own.  The reference's candidate
-    // sets are small (BSQ:856-877: a few dozen points); this branch exists so that the entry point has no size limit.
-    const int npad = round_up(n, kTile);
-    size_t need = Carver::al(sizeof(double) * (size_t)B * n * d) + Carver::al(sizeof(double) * n) + Carver::al(sizeof(double) * P) +
-                  3 * Carver::al(sizeof(double) * B) + Carver::al(sizeof(int) * (size_t)B);
-    int rc = ensure_stage(h, need);
-    if (rc) return rc;
-    rc = ensure_ws(h, blocked_ws_bytes(npad, 1, 0) + 512);
-    if (rc) return rc;
-    Carver c(h->stage);
-    double* dXs = c.take<double>((size_t)B * n * d);
-    double* dy = c.take<double>(n);
-    double* dp = c.take<double>(P);
-    double* dld = c.take<double>(B);
-    double* dll = c.take<double>(B);
-    double* dbeta = c.take<double>(B);
-    int* dst = c.take<int>(B);
-    if (int prc = push(h, {piece(dXs, Xs, (size_t)B * n * d), piece(dp, params, P)})) return prc;
+  // more than 128 points (or too wide for the register-resident evaluator): the blocked sweep, one design at a time --
+  // its chunk shares ONE design among its matrices, and here every matrix has its own.  The reference's candidate
+  // sets are small (BSQ:856-877: a few dozen points); this branch exists so that the entry point has no size limit.
+  const bool blocked = !small_reg_supported(n, d, K, true);
+  const int npad = round_up(n, kTile);
+  double *dXs, *dp, *dld, *dy = nullptr, *dll = nullptr, *dbeta = nullptr;
+  int* dst;
+  if (int rc = stage(h, [&](Layout& c) {
+        dXs = c.take<double>((size_t)B * n * d);
+        if (blocked) dy = c.take<double>(n);   // the sweep carries a right-hand side: zeros
+        dp = c.take<double>(P);
+        dld = c.take<double>(B);
+        if (blocked) dll = c.take<double>(B);
+        if (blocked) dbeta = c.take<double>(B);
+        dst = c.take<int>(B);
+      }))
+    return rc;
+  if (int rc = blocked ? ensure_ws(h, blocked_ws_bytes(npad, 1, 0) + 512) : CCGP_OK) return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
+  if (int prc = push(h, {piece(dXs, Xs, (size_t)B * n * d), piece(dp, params, P)})) return prc;
+  if (blocked) {
     CCGP_HIP(hipMemsetAsync(dy, 0, sizeof(double) * n, h->stream));
     CCGP_HIP(hipMemsetAsync(dst, 0, sizeof(int) * (size_t)B, h->stream));
-    DrawView dv{dp, 1, K, d};
-    dv.fam = h->fam;
-    if (int frc = check_family(h, dv.fam, d, K)) return frc;
     BlockedWs w = blocked_carve(h->ws, npad, 1, 0);
     for (int i = 0; i < B; ++i) {
       BlockedJob job{};
@@ -1243,34 +1268,12 @@ int ccgp_mixed_logdet_designs(ccgp_handle* h, const double* Xs, int n, int d, in
       blocked_loglik(h, dXs + (size_t)i * n * d, n, d, dy, dv, 0, 1, npad, 1.0, CCGP_MEAN_PROFILE_BETA, 0.0, w, dll + i,
                      dbeta + i, dst + i, &job);
     }
-    CCGP_LAUNCH_CHECK();
-    std::vector<int> st(B);
-    if (int prc = pull(h, {piece(dld, out_logdet, B), piece(dst, st.data(), B)})) return prc;
-    if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)B);
-    return count_bad(st.data(), B);
-  }
-  size_t need = Carver::al(sizeof(double) * (size_t)B * n * d) + Carver::al(sizeof(double) * P) +
-                Carver::al(sizeof(double) * B) + Carver::al(sizeof(int) * (size_t)B);
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dXs = c.take<double>((size_t)B * n * d);
-  double* dp = c.take<double>(P);
-  double* dld = c.take<double>(B);
-  int* dst = c.take<int>(B);
-  if (int prc = push(h, {piece(dXs, Xs, (size_t)B * n * d), piece(dp, params, P)})) return prc;
-  DrawView dv{dp, 1, K, d};
-  dv.fam = h->fam;
-  if (int frc = check_family(h, dv.fam, d, K)) return frc;
-  {
+  } else {
     ScopedTimer t(h, CCGP_T_FUSED);
     launch_small_reg_logdet_designs(h->stream, dXs, n, d, dv, B, dld, dst);
   }
   CCGP_LAUNCH_CHECK();
-  std::vector<int> st(B);
-  if (int prc = pull(h, {piece(dld, out_logdet, B), piece(dst, st.data(), B)})) return prc;
-  if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)B);
-  return count_bad(st.data(), B);
+  return pull_status(h, {piece(dld, out_logdet, B)}, dst, B, status);
 } CCGP_GUARD_END(h)
 
 // d log det R_mixed / d X for B candidate designs (BSQ:856-948: the design search of Entropy.optim / Batch.Entropy.optim)
@@ -1290,29 +1293,25 @@ int ccgp_mixed_logdet_grad_designs(ccgp_handle* h, const double* Xs, int n, int 
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
   const size_t ng = (size_t)B * (n - n_fixed) * d;
-  size_t need = Carver::al(sizeof(double) * (size_t)B * n * d) + Carver::al(sizeof(double) * P) +
-                Carver::al(sizeof(double) * B) + Carver::al(sizeof(double) * ng) + Carver::al(sizeof(int) * (size_t)B);
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dXs = c.take<double>((size_t)B * n * d);
-  double* dp = c.take<double>(P);
-  double* dld = c.take<double>(B);
-  double* dg = c.take<double>(ng);
-  int* dst = c.take<int>(B);
+  double *dXs, *dp, *dld, *dg;
+  int* dst;
+  if (int rc = stage(h, [&](Layout& c) {
+        dXs = c.take<double>((size_t)B * n * d);
+        dp = c.take<double>(P);
+        dld = c.take<double>(B);
+        dg = c.take<double>(ng);
+        dst = c.take<int>(B);
+      }))
+    return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
   if (int prc = push(h, {piece(dXs, Xs, (size_t)B * n * d), piece(dp, params, P)})) return prc;
-  DrawView dv{dp, 1, K, d};
-  dv.fam = h->fam;
-  if (int frc = check_family(h, dv.fam, d, K)) return frc;
   {
     ScopedTimer t(h, CCGP_T_FUSED);
     launch_small_reg_logdet_grad_designs(h->stream, dXs, n, d, dv, B, n_fixed, dld, dg, dst);
   }
   CCGP_LAUNCH_CHECK();
-  std::vector<int> st(B);
-  if (int prc = pull(h, {piece(dld, out_logdet, B), piece(dg, out_grad, ng), piece(dst, st.data(), B)})) return prc;
-  if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)B);
-  return count_bad(st.data(), B);
+  return pull_status(h, {piece(dld, out_logdet, B), piece(dg, out_grad, ng)}, dst, B, status);
 } CCGP_GUARD_END(h)
 
 // ---- a9: hyperprior grid ------------------------------------------------------------------------
@@ -1365,26 +1364,23 @@ int ccgp_grid_marginal(ccgp_handle* h, const double* X, int n, int d, const doub
     }
   }
   const size_t ns = shapes.size();
-  size_t need = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * n) +
-                Carver::al(sizeof(double) * 4 * G) + Carver::al(sizeof(double) * ns) +
-                Carver::al(sizeof(int) * 2 * G) + Carver::al(sizeof(double) * ns * N) +
-                Carver::al(sizeof(double) * B * P) + 2 * Carver::al(sizeof(double) * B) +
-                Carver::al(sizeof(int) * B) + Carver::al(sizeof(double) * G) + Carver::al(sizeof(int));
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dX = c.take<double>((size_t)n * d);
-  double* dy = c.take<double>(n);
-  double* dhy = c.take<double>((size_t)4 * G);
-  double* dsh = c.take<double>(ns);
-  int* dsi = c.take<int>((size_t)2 * G);
-  double* dq = c.take<double>(ns * N);
-  double* dp = c.take<double>(B * P);
-  double* dll = c.take<double>(B);
-  double* dbeta = c.take<double>(B);
-  int* dst = c.take<int>(B);
-  double* dout = c.take<double>(G);
-  int* dbad = c.take<int>(1);
+  double *dX, *dy, *dhy, *dsh, *dq, *dp, *dll, *dbeta, *dout;
+  int *dsi, *dst, *dbad;
+  if (int rc = stage(h, [&](Layout& c) {
+        dX = c.take<double>((size_t)n * d);
+        dy = c.take<double>(n);
+        dhy = c.take<double>((size_t)4 * G);
+        dsh = c.take<double>(ns);
+        dsi = c.take<int>((size_t)2 * G);
+        dq = c.take<double>(ns * N);
+        dp = c.take<double>(B * P);
+        dll = c.take<double>(B);
+        dbeta = c.take<double>(B);
+        dst = c.take<int>(B);
+        dout = c.take<double>(G);
+        dbad = c.take<int>(1);
+      }))
+    return rc;
   CCGP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream));
   CCGP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
   CCGP_HIP(hipMemcpyAsync(dhy, hyper, sizeof(double) * 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
@@ -1401,9 +1397,8 @@ int ccgp_grid_marginal(ccgp_handle* h, const double* X, int n, int d, const doub
     hipLaunchKernelGGL(grid_expand_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, dhy, dsi, dq, G, N,
                        d, aniso ? 1 : 0, aniso_lambda, dp);
   }
-  rc = loglik_dev(h, dX, n, d, dy, K, dp, (int)B, sigma2, CCGP_MEAN_ZERO_PLUS_TAU2, tau * tau, dll,
-                  dbeta, dst);
-  if (rc) return rc;
+  if (int rc = loglik_dev(h, dX, n, d, dy, K, dp, (int)B, sigma2, CCGP_MEAN_ZERO_PLUS_TAU2, tau * tau, dll, dbeta, dst))
+    return rc;
   hipLaunchKernelGGL(row_logmeanexp_kernel, dim3(G), dim3(256), 0, h->stream, dll, N, take_log, dout);
   hipLaunchKernelGGL(count_bad_kernel, dim3((unsigned)((B + 1023) / 1024)), dim3(256), 0, h->stream, dst, (int)B, dbad);
   CCGP_LAUNCH_CHECK();
@@ -1423,41 +1418,29 @@ int ccgp_grid_marginal(ccgp_handle* h, const double* X, int n, int d, const doub
 } CCGP_GUARD_END(h)
 
 // ---- a10/a11: prediction -------------------------------------------------------------------------
-int ccgp_predict_batch_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy, int K,
-                           const double* dparams, int S, const double* dXtest, int m,
-                           double sigma2, double* d_mean, double* d_var, double* d_beta,
-                           int* d_status) try {
-  if (!h) return CCGP_EINVAL;
-  if (bad_shape(n, d, K) || S < 1 || m < 1 || !dX || !dy || !dparams || !dXtest || !d_mean || !d_var)
-    return fail(h, CCGP_EINVAL, "ccgp_predict_batch: bad argument");
-  CCGP_HIP(hipSetDevice(h->device));
-  DrawView dv{dparams, S, K, d};
-  dv.fam = h->fam;
-  if (int frc = check_family(h, dv.fam, d, K)) return frc;
+// the prediction of the S draws of dv (kernel family included) at m test sites, on resident inputs; arguments are
+// checked by the callers
+static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const double* dy, const DrawView& dv,
+                       const double* dXtest, int m, double sigma2, double* d_mean, double* d_var, double* d_beta,
+                       int* d_status) {
+  const int K = dv.K, S = dv.ldp;
   if (dv.fam.id != 0 || n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64) {
     // blocked path: the m cross-correlation rows ride along as extra tile rows of the sweep
     const int npad = round_up(n, kTile), ne = (m + kTile - 1) / kTile;
-    int nbc = blocked_chunk(h, npad, S, ne);
-    size_t extra = Carver::al(sizeof(double) * (size_t)S) * 2 + Carver::al(sizeof(int) * (size_t)S);
-    int rc = ensure_ws(h, blocked_ws_bytes(npad, nbc, ne) + extra);
-    while (rc == CCGP_ENOMEM && nbc > 1) {   // another handle / process took the memory in between: smaller chunks
-      nbc = (nbc + 1) / 2;
-      rc = ensure_ws(h, blocked_ws_bytes(npad, nbc, ne) + extra);
-    }
-    if (rc) return rc;
     // scratch for outputs the caller did not ask for lives behind the matrices
-    Carver tail(static_cast<char*>(h->ws) + blocked_ws_bytes(npad, nbc, ne));
-    double* ll = tail.take<double>(S);
-    double* bt = d_beta ? d_beta : tail.take<double>(S);
-    int* st = d_status ? d_status : tail.take<int>(S);
-    CCGP_HIP(hipMemsetAsync(st, 0, sizeof(int) * (size_t)S, h->stream));
+    auto tail_lay = [&](Layout& t) { return predict_tail(t, S, d_beta, d_status); };
+    int nbc = 0;
+    if (int rc = sweep_chunk(h, npad, ne, S, layout_bytes(tail_lay), &nbc)) return rc;
+    Layout tail(static_cast<char*>(h->ws) + blocked_ws_bytes(npad, nbc, ne));
+    const PredictTail sc = tail_lay(tail);
+    CCGP_HIP(hipMemsetAsync(sc.status, 0, sizeof(int) * (size_t)S, h->stream));
     BlockedJob pr{};
     pr.kind = kJobPredict; pr.Xtest = dXtest; pr.m = m; pr.S = S; pr.mean = d_mean; pr.var = d_var;
     for (int b0 = 0; b0 < S; b0 += nbc) {
       const int nb = std::min(nbc, S - b0);
       BlockedWs w = blocked_carve(h->ws, npad, nb, ne);
-      blocked_loglik(h, dX, n, d, dy, dv, b0, nb, npad, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, w, ll, bt, st,
-                     &pr);
+      blocked_loglik(h, dX, n, d, dy, dv, b0, nb, npad, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, w, sc.ll, sc.beta,
+                     sc.status, &pr);
     }
     CCGP_LAUNCH_CHECK();
     return CCGP_OK;
@@ -1490,6 +1473,19 @@ int ccgp_predict_batch_dev(ccgp_handle* h, const double* dX, int n, int d, const
   }
   CCGP_LAUNCH_CHECK();
   return CCGP_OK;
+}
+
+int ccgp_predict_batch_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy, int K,
+                           const double* dparams, int S, const double* dXtest, int m,
+                           double sigma2, double* d_mean, double* d_var, double* d_beta,
+                           int* d_status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || S < 1 || m < 1 || !dX || !dy || !dparams || !dXtest || !d_mean || !d_var)
+    return fail(h, CCGP_EINVAL, "ccgp_predict_batch: bad argument");
+  CCGP_HIP(hipSetDevice(h->device));
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dparams, S, K, d, &dv)) return frc;
+  return predict_run(h, dX, n, d, dy, dv, dXtest, m, sigma2, d_mean, d_var, d_beta, d_status);
 } CCGP_GUARD_END(h)
 
 int ccgp_predict_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
@@ -1500,32 +1496,16 @@ int ccgp_predict_batch(ccgp_handle* h, const double* X, int n, int d, const doub
     return fail(h, CCGP_EINVAL, "ccgp_predict_batch: bad argument");
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
-  size_t need = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * n) +
-                Carver::al(sizeof(double) * (size_t)S * P) + Carver::al(sizeof(double) * (size_t)m * d) +
-                2 * Carver::al(sizeof(double) * (size_t)S * m) + Carver::al(sizeof(double) * S) +
-                Carver::al(sizeof(int) * (size_t)S);
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dX = c.take<double>((size_t)n * d);
-  double* dy = c.take<double>(n);
-  double* dp = c.take<double>((size_t)S * P);
-  double* dXt = c.take<double>((size_t)m * d);
-  double* dmean = c.take<double>((size_t)S * m);
-  double* dvar = c.take<double>((size_t)S * m);
-  double* dbeta = c.take<double>(S);
-  int* dst = c.take<int>(S);
-  if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, (size_t)S * P),
-                         piece(dXt, Xtest, (size_t)m * d)}))
+  PredictStage s;
+  if (int rc = stage(h, [&](Layout& c) { s = predict_stage(c, n, d, P, S, m); })) return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, S, K, d, &dv)) return frc;
+  if (int prc = push(h, {piece(s.X, X, (size_t)n * d), piece(s.y, y, n), piece(s.params, params, (size_t)S * P),
+                         piece(s.Xtest, Xtest, (size_t)m * d)}))
     return prc;
-  rc = ccgp_predict_batch_dev(h, dX, n, d, dy, K, dp, S, dXt, m, sigma2, dmean, dvar, dbeta, dst);
-  if (rc) return rc;
-  std::vector<int> st(S);
-  if (int prc = pull(h, {piece(dmean, out_mean, (size_t)S * m), piece(dvar, out_var, (size_t)S * m),
-                         piece(dbeta, out_beta, S), piece(dst, st.data(), S)}))
-    return prc;
-  if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)S);
-  return count_bad(st.data(), S);
+  if (int rc = predict_run(h, s.X, n, d, s.y, dv, s.Xtest, m, sigma2, s.mean, s.var, s.beta, s.status)) return rc;
+  return pull_status(h, {piece(s.mean, out_mean, (size_t)S * m), piece(s.var, out_var, (size_t)S * m),
+                         piece(s.beta, out_beta, S)}, s.status, S, status);
 } CCGP_GUARD_END(h)
 
 // ---- 8(f)-2: device-resident factor set --------------------------------------------------------------
@@ -1546,6 +1526,14 @@ struct ccgp_factorset {
   ccgp::BlockedWs w{};
 };
 
+// owner of a factor set and of its device memory
+struct FactorsetFree {
+  void operator()(ccgp_factorset* fs) const {
+    if (fs->mem) (void)hipFree(fs->mem);
+    delete fs;
+  }
+};
+
 int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
                       const double* params, int S, double sigma2, ccgp_factorset** out,
                       double* out_loglik, double* out_beta, int* status) try {
@@ -1553,60 +1541,54 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
   if (bad_shape(n, d, K) || S < 1 || !X || !y || !params || !out)
     return fail(h, CCGP_EINVAL, "ccgp_factor_batch: bad argument");
   *out = nullptr;
-  if (int frc = check_family(h, h->fam, d, K)) return frc;
+  DrawView dv;   // its params follow once the set has its memory
+  if (int frc = draw_view(h, h->fam, nullptr, S, K, d, &dv)) return frc;
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
   const bool fused = h->fam.id == 0 && n <= kSmallMaxN && small_lds_bytes(n, d, 1) <= (size_t)kLdsBytes - 64;
   const int npad = round_up(n, kTile);
   if (!fused && S > 65535)   // the draw index is a grid y / z dimension in cov_kernel, rhs_rows_kernel, ...
     return fail(h, CCGP_EINVAL, "ccgp_factor_batch: at most 65535 factors per set on the blocked path (n > 128)");
-  size_t head = Carver::al(sizeof(double) * (size_t)n * d) + Carver::al(sizeof(double) * n) +
-                Carver::al(sizeof(double) * (size_t)S * P) + 2 * Carver::al(sizeof(double) * S) +
-                Carver::al(sizeof(int) * (size_t)S);
-  size_t bytes = head + (fused ? 0 : blocked_ws_bytes(npad, S, 0) + 256);
-  ccgp_factorset* fs = new ccgp_factorset();
+  std::unique_ptr<ccgp_factorset, FactorsetFree> fs(new ccgp_factorset());
+  char* factors = nullptr;
+  auto lay = [&](Layout& c) {
+    fs->X = c.take<double>((size_t)n * d);
+    fs->y = c.take<double>(n);
+    fs->params = c.take<double>((size_t)S * P);
+    fs->ll = c.take<double>(S);
+    fs->beta = c.take<double>(S);
+    fs->status = c.take<int>(S);
+    if (!fused) factors = c.take<char>(blocked_ws_bytes(npad, S, 0));
+  };
+  const size_t bytes = layout_bytes(lay);
   if (hipMalloc(&fs->mem, bytes) != hipSuccess) {
-    delete fs;
+    fs->mem = nullptr;
     return fail(h, CCGP_ENOMEM, "ccgp_factor_batch: " + std::to_string(bytes) + " B for " + std::to_string(S) +
                                     " factors do not fit on the device");
   }
   fs->bytes = bytes; fs->device = h->device; fs->n = n; fs->d = d; fs->K = K; fs->S = S; fs->npad = npad;
   fs->sigma2 = sigma2; fs->fam = h->fam; fs->fused = fused;
-  Carver c(fs->mem);
-  fs->X = c.take<double>((size_t)n * d);
-  fs->y = c.take<double>(n);
-  fs->params = c.take<double>((size_t)S * P);
-  fs->ll = c.take<double>(S);
-  fs->beta = c.take<double>(S);
-  fs->status = c.take<int>(S);
-  auto bail = [&](int code) {
-    (void)hipFree(fs->mem);
-    delete fs;
-    return code;
-  };
+  Layout c(fs->mem);
+  lay(c);
+  dv.params = fs->params;
   if (hipMemcpyAsync(fs->X, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(fs->y, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(fs->params, params, sizeof(double) * (size_t)S * P, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemsetAsync(fs->status, 0, sizeof(int) * (size_t)S, h->stream) != hipSuccess)
-    return bail(fail(h, CCGP_EHIP, "ccgp_factor_batch: upload failed"));
-  DrawView dv{fs->params, S, K, d};
-  dv.fam = h->fam;
+    return fail(h, CCGP_EHIP, "ccgp_factor_batch: upload failed");
   if (fused) {
     // n <= 128: the factor of a draw lives and dies in registers / LDS inside the fused evaluator (10 us);
     // storing it would cost more HBM traffic than regenerating it.  The set keeps the draws; likelihood
     // and beta are evaluated once here, prediction re-runs the fused predictor on the resident inputs.
-    int rc = loglik_dev(h, fs->X, n, d, fs->y, K, fs->params, S, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, fs->ll,
-                        fs->beta, fs->status);
-    if (rc) return bail(rc);
+    if (int rc = loglik_run(h, fs->X, n, d, fs->y, dv, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, fs->ll, fs->beta, fs->status))
+      return rc;
   } else {
-    fs->w = blocked_carve(c.take<char>(blocked_ws_bytes(npad, S, 0)), npad, S, 0);
+    fs->w = blocked_carve(factors, npad, S, 0);
     blocked_loglik(h, fs->X, n, d, fs->y, dv, 0, S, npad, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, fs->w, fs->ll,
                    fs->beta, fs->status);
-    if (hipGetLastError() != hipSuccess) return bail(fail(h, CCGP_EHIP, "ccgp_factor_batch: launch failed"));
-    {
-      const std::string ae = ccgp::attr_error(h->device);
-      if (!ae.empty()) return bail(fail(h, CCGP_EHIP, ae));
-    }
+    if (hipGetLastError() != hipSuccess) return fail(h, CCGP_EHIP, "ccgp_factor_batch: launch failed");
+    const std::string ae = ccgp::attr_error(h->device);
+    if (!ae.empty()) return fail(h, CCGP_EHIP, ae);
   }
   std::vector<int> st(S);
   hipError_t e = hipSuccess;
@@ -1615,10 +1597,9 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
     e = hipMemcpyAsync(out_beta, fs->beta, sizeof(double) * S, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(st.data(), fs->status, sizeof(int) * (size_t)S, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return bail(fail(h, CCGP_EHIP, std::string("ccgp_factor_batch: ") + hipGetErrorString(e)));
-  if (status) std::memcpy(status, st.data(), sizeof(int) * (size_t)S);
-  *out = fs;
-  return count_bad(st.data(), S);
+  if (e != hipSuccess) return fail(h, CCGP_EHIP, std::string("ccgp_factor_batch: ") + hipGetErrorString(e));
+  *out = fs.release();
+  return report_status(st, status);
 } CCGP_GUARD_END(h)
 
 int ccgp_predict_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const double* Xtest, int m,
@@ -1630,47 +1611,29 @@ int ccgp_predict_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const 
     return fail(h, CCGP_EINVAL, "ccgp_predict_from_factorset: the factor set lives on another device");
   CCGP_HIP(hipSetDevice(h->device));
   const int n = fs->n, d = fs->d, S = fs->S;
-  size_t need = Carver::al(sizeof(double) * (size_t)m * d) + 2 * Carver::al(sizeof(double) * (size_t)S * m);
-  int rc = ensure_stage(h, need);
-  if (rc) return rc;
-  Carver c(h->stage);
-  double* dXt = c.take<double>((size_t)m * d);
-  double* dmean = c.take<double>((size_t)S * m);
-  double* dvar = c.take<double>((size_t)S * m);
+  double *dXt, *dmean, *dvar;
+  if (int rc = stage(h, [&](Layout& c) {
+        dXt = c.take<double>((size_t)m * d);
+        dmean = c.take<double>((size_t)S * m);
+        dvar = c.take<double>((size_t)S * m);
+      }))
+    return rc;
+  DrawView dv;   // the set's kernel family, whatever the handle has been set to since
+  if (int frc = draw_view(h, fs->fam, fs->params, S, fs->K, d, &dv)) return frc;
   CCGP_HIP(hipMemcpyAsync(dXt, Xtest, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, h->stream));
   if (fs->fused) {
-    const ccgp::KernelFamily keep = h->fam;
-    h->fam = fs->fam;
-    rc = ccgp_predict_batch_dev(h, fs->X, n, d, fs->y, fs->K, fs->params, S, dXt, m, fs->sigma2, dmean, dvar,
-                                nullptr, nullptr);
-    h->fam = keep;
-    if (rc) return rc;
+    if (int rc = predict_run(h, fs->X, n, d, fs->y, dv, dXt, m, fs->sigma2, dmean, dvar, nullptr, nullptr)) return rc;
   } else {
     const int ne = (m + kTile - 1) / kTile, lde = ne * kTile;
     const size_t e_stride = (size_t)lde * fs->npad;
-    // the m cross-correlation rows of every draw need lde x npad doubles of scratch: chunks of draws under the
-    // workspace limit and under what the device can give right now (the factor set itself holds most of it)
-    size_t limit = h->ws_limit, free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const size_t margin = size_t(256) << 20;
-      const size_t avail = free_b + h->ws_bytes > margin ? free_b + h->ws_bytes - margin : 0;
-      if (avail < limit) limit = avail;
-    }
-    size_t sc = limit / (sizeof(double) * e_stride);
-    if (sc < 1) sc = 1;
-    if (sc > (size_t)S) sc = S;
-    if (sc > 65535) sc = 65535;   // the draw index is a grid dimension
-    rc = ensure_ws(h, sizeof(double) * e_stride * sc);
-    while (rc == CCGP_ENOMEM && sc > 1) {
-      sc = (sc + 1) / 2;
-      rc = ensure_ws(h, sizeof(double) * e_stride * sc);
-    }
-    if (rc) return rc;
+    // the m cross-correlation rows of every draw need lde x npad doubles of scratch: chunks of draws
+    int sc = 0;
+    if (int rc = plan_chunk(h, sizeof(double) * e_stride, S, kFactorsetMargin,
+                            [&](int ns) { return sizeof(double) * e_stride * (size_t)ns; }, &sc))
+      return rc;
     double* E = static_cast<double*>(h->ws);
-    DrawView dv{fs->params, S, fs->K, d};
-    dv.fam = fs->fam;
-    for (int s0 = 0; s0 < S; s0 += (int)sc) {
-      const int ns = std::min((int)sc, S - s0);
+    for (int s0 = 0; s0 < S; s0 += sc) {
+      const int ns = std::min(sc, S - s0);
       CCGP_HIP(hipMemsetAsync(E, 0, sizeof(double) * e_stride * ns, h->stream));
       {
         ScopedTimer t(h, CCGP_T_COV);   // rows t = r(x_t)' (Mixed.corr.vec, HX:425-431)
@@ -1694,8 +1657,7 @@ int ccgp_factorset_free(ccgp_handle* h, ccgp_factorset* fs) try {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
   }
-  if (fs->mem) (void)hipFree(fs->mem);
-  delete fs;
+  FactorsetFree()(fs);
   return CCGP_OK;
 } CCGP_GUARD_END(h)
 
