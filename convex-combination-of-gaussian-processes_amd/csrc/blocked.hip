@@ -16,18 +16,22 @@
 // At 128-wide tiles that is 16 flop per HBM byte against a machine balance of ~10: MFMA-bound, with HBM at a
 // third of its peak.
 //
-// Two generations of k-loop live here.  Round 3 (tile_accumulate_il for whole update tiles, diag_rhs_accumulate<W> for
-// the diagonal workgroup): ds_read_b128 fragments on row-interleaved sub-tiles, buffer_load ... lds stage requests,
-// one request per MFMA -- 75 TFLOP/s for the bare loop against 67 - 71 (tests/hip/update_loop_probe.hip).  Round 2
-// (gemm_accumulate, strip_accumulate_ring): the panel solve, the strips, R^-1 tiles, and the fallback of the new
-// loops when a panel spans 4 GiB or more.  Every loop sums a tile element's k four at a time in ascending order,
-// so they are interchangeable bit for bit.
+// Two generations of k-loop live here.  Round 3 (tile_accumulate_il for whole update tiles and R^-1 tiles,
+// diag_rhs_accumulate<W> for the diagonal workgroup): ds_read_b128 fragments on row-interleaved sub-tiles,
+// buffer_load ... lds stage requests, one request per MFMA -- 75 TFLOP/s for the bare loop against 67 - 71
+// (tests/hip/update_loop_probe.hip).  Round 2, on 64-bit pointers: gemm_accumulate<S, THIN, TRI> (the panel solve,
+// the S = 2 rows-only sweeps, and the fallback of tile_accumulate_il when a panel spans 4 GiB or more),
+// diag_rhs_accumulate_wide (the same fallback for the diagonal workgroup) and ONE ring family,
+// strip_accumulate_ring<S> (four stages, counted waits) for the half- (S = 2) and quarter-width (S = 4) tail strips.
+// Every loop sums a tile element's k four at a time in ascending order, so they are interchangeable bit for bit.
+// Which element of a whole tile an accumulator register holds is stated in AccMap; the swizzled source offset of a
+// stage request in swz_src.
 //
 // Schedule of an update launch (profiles/r02_update_schedule.md): a launch of W workgroups takes ceil(W / 256)
 // steps -- one workgroup per CU (one wave per SIMD) already keeps the four MFMA pipes busy (84 % in round 2, 97 % of
 // the bare-MFMA rate now), the second resident workgroup only fills bubbles.  The diagonal workgroups (one per matrix: lower triangle + right-hand sides, then the
-// block factorisation) are dispatched first; whole tiles follow; the <= 128 tiles of a partial last step run as two
-// ring-pipelined half-width strips each.
+// block factorisation) are dispatched first; whole tiles follow; the tiles of a partial last step run as ring-pipelined
+// strips, two half-width or four quarter-width ones each, whichever fills that step (update_tail()).
 //
 // MFMA: v_mfma_f64_16x16x4_f64.  Operand lane map (one f64 per lane):
 //   A[i = lane&15][k = lane>>4],  B[k = lane>>4][j = lane&15],
@@ -55,6 +59,10 @@ __device__ __forceinline__ int tid_now() {
   return t;
 }
 
+// Source side of the XOR swizzle (see TileGeom): a stage request copies one k-row of an operand, 16 bytes per lane, to a
+// lane-linear LDS row in which the 16-element block index is XORed with the row's parity.  Lane l of the row therefore
+// FETCHES elements swz_src(l, parity) and the next one.
+__device__ __forceinline__ constexpr int swz_src(int l, int parity) { return (((l >> 3) ^ parity) << 4) + ((l & 7) << 1); }
 
 struct GemmArgs {
   double* A;
@@ -89,9 +97,10 @@ struct GemmArgs {
 
 // One output tile strip, C = C - P Q' (MODE 0, update) or C = P Q' (MODE 1, trsm): 128 rows x
 // (128 / S) columns per workgroup, K-loop over 16-deep double-buffered LDS stages.
-//   S = 1: 2 x 2 waves of 64 x 64      S = 2: 2 x 2 waves of 64 x 32
-// S = 2 re-reads the P panel twice through L2; it serves the rows-only sweeps of a kept factor (few, long rows)
-// and, in its ring-pipelined form (strip_accumulate_ring), the partial last step of an update launch.
+//   S = 1: 2 x 2 waves of 64 x 64      S = 2: 2 x 2 waves of 64 x 32      S = 4: 4 x 1 waves of 32 x 32
+// S = 2 re-reads the P panel twice through L2; it serves the rows-only sweeps of a kept factor (few, long rows).
+// S = 2 and S = 4 in their ring-pipelined form (strip_accumulate_ring<S>) serve the partial last step of an update
+// launch; S = 4 exists in that form only.
 // THIN = trsm's right-hand-side tile row: only its first 16 rows carry data, so the waves split
 // the strip's columns between them (16 rows x 32 columns per wave at S = 1).
 //
@@ -115,7 +124,7 @@ struct TileGeom {
 };
 
 // acc[x][y] += (Q strip)(P tile)' over Kdim: accumulator register r of sub-tile (x, y) is element
-// (row0 + 16y + lane&15, col0 + 16x + (lane>>4) + 4r) of the 128 x CW output.
+// (row0 + 16y + lane&15, 16 col_block(x) + (lane>>4) + 4r) of the 128 x CW output (for a whole tile: AccMap<false>).
 // TRI (trsm only, S = 1): Q = W_j is LOWER triangular (W[c][k] = 0 for k > c), so the 16-column
 // sub-tile cb contributes nothing once the stage index kt exceeds cb; those MFMAs are skipped,
 // and the sub-tiles are dealt to the two wave columns interleaved (cb = wn + 2x) so that both
@@ -125,6 +134,30 @@ __device__ __forceinline__ int col_block(int wave, int x) {
   if constexpr (TRI && !THIN) return (wave & 1) + 2 * x;
   else return (TileGeom<S, THIN>::col0(wave) >> 4) + x;
 }
+
+// Which element of a whole 128 x 128 tile (2 x 2 waves of 64 x 64) this lane's accumulator register acc[x][y][r] holds:
+//   classic     (gemm_accumulate<1, false>):  row0 + 16 y + l15,   col0 + 16 x + l4 + 4 r
+//   interleaved (tile_accumulate_il):         row0 + 4 l15 + y,    col0 + 16 r + 4 l4 + x
+// Interleaved, a lane's four y are four CONTIGUOUS rows of one column: an epilogue moves them as one 32-byte d4 at
+// lane_base(), and the columns of its registers lie dcol(x, r) -- the same for every lane -- beyond that base's.
+// Built from tid_now(), like everything else a tile routine derives from the thread index.  (gemm_tile's own epilogue
+// states the classic map once more in its general form: strips, the thin row and trsm's dealt-out column blocks go
+// through col_block.)
+template <bool IL>
+struct AccMap {
+  int row0, col0, l15, l4;
+  __device__ __forceinline__ AccMap() {
+    const int lane = tid_now() & 63, wave = tid_now() >> 6;
+    row0 = TileGeom<1, false>::row0(wave); col0 = TileGeom<1, false>::col0(wave); l15 = lane & 15; l4 = lane >> 4;
+  }
+  __device__ __forceinline__ int row(int y) const { return IL ? row0 + 4 * l15 + y : row0 + 16 * y + l15; }
+  __device__ __forceinline__ int col(int x, int r) const { return IL ? col0 + 16 * r + 4 * l4 + x : col0 + 16 * x + l4 + 4 * r; }
+  static constexpr __device__ __forceinline__ int dcol(int x, int r) { return IL ? 16 * r + x : 16 * x + 4 * r; }   // col(x, r) - col(0, 0)
+  // element (row(0), col(0, 0)) of the column-major tile C: one 64-bit address per lane, dcol(x, r) * ld beyond it the rest
+  __device__ __forceinline__ double* lane_base(double* C, int ld) const {
+    return IL ? C + row0 + 4 * l15 + (size_t)(col0 + 4 * l4) * ld : C + row0 + l15 + (size_t)(col0 + l4) * ld;
+  }
+};
 
 template <int S, bool THIN, bool TRI = false>
 __device__ __forceinline__ void gemm_accumulate(double* smem, const double* P, int ldP, const double* Q,
@@ -150,15 +183,13 @@ __device__ __forceinline__ void gemm_accumulate(double* smem, const double* P, i
     for (int y = 0; y < NY; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
 
   // per-lane source rows.  P: wave w issues columns k = w + 4q (parity = w & 1, fixed per wave).
-  const int psrc = ((((lane >> 3) ^ (wave & 1)) << 4) + ((lane & 7) << 1));
-  const double* pP = P + psrc + (size_t)wave * ldP;
+  const double* pP = P + swz_src(lane, wave & 1) + (size_t)wave * ldP;
   const size_t stepP = (size_t)4 * ldP;
   // Q: instruction u = w + 4q covers columns CPI*u .. CPI*u + CPI-1; lane -> column CPI*u + lane / (64/CPI)
   constexpr int LPC = 64 / CPI;                        // lanes per Q column
   const int qcol_in = lane / LPC, ql = lane % LPC;
   const int qpar = CPI == 1 ? (wave & 1) : (qcol_in & 1);
-  const int qsrc = ((((ql >> 3) ^ qpar) << 4) + ((ql & 7) << 1));
-  const double* pQ = Q + qsrc + (size_t)(CPI * wave + qcol_in) * ldQ;
+  const double* pQ = Q + swz_src(ql, qpar) + (size_t)(CPI * wave + qcol_in) * ldQ;
   const size_t stepQ = (size_t)(4 * CPI) * ldQ;
 
   auto issue = [&](int stage) {
@@ -263,7 +294,7 @@ __device__ __forceinline__ bool fits_buffer_offsets(int Kdim, int ld) {
 // Every output element still accumulates its k-sum four at a time in ascending order: the bits are those of
 // gemm_accumulate, whatever the sub-tile a row or column lands in (ring strips, trsm and the diagonal workgroup
 // keep the older loop).
-//   acc[x][y] register r  =  element (row0 + 4 l15 + y,  col0 + 4 (l4 + 4 r) + x)  of the 128 x 128 tile.
+// Which element acc[x][y] register r then is: AccMap<true>.
 __device__ __forceinline__ void tile_accumulate_il(double* smem, const double* P, int ldP, const double* Q,
                                                    int ldQ, int Kdim, d4 (&acc)[4][4]) {
   constexpr int BKs = 16, STAGE = 2 * BKs * kTile;     // doubles per stage: P image [16][128], then Q image [16][128]
@@ -360,55 +391,69 @@ __device__ __forceinline__ void update_tile_il(double* smem, const double* P, in
                                                int Kdim, double* C, int ld) {
   d4 acc[4][4];
   tile_accumulate_il(smem, P, ldP, Q, ldQ, Kdim, acc);
-  const int lane = tid_now() & 63, wave = tid_now() >> 6;
-  const int row0 = (wave >> 1) * 64, col0 = (wave & 1) * 64;
-  const int l15 = lane & 15, l4 = lane >> 4;
-  double* Cl = C + row0 + 4 * l15 + (size_t)(col0 + 4 * l4) * ld;
+  const AccMap<true> map;
+  double* Cl = map.lane_base(C, ld);   // the lane's four contiguous rows, first of its columns
 #pragma unroll
   for (int x = 0; x < 4; ++x) {
     d4 cv[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) cv[r] = *(const d4*)(Cl + (size_t)(16 * r + x) * ld);
+    for (int r = 0; r < 4; ++r) cv[r] = *(const d4*)(Cl + (size_t)map.dcol(x, r) * ld);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       d4 o;
 #pragma unroll
       for (int y = 0; y < 4; ++y) o[y] = cv[r][y] - acc[x][y][r];
-      *(d4*)(Cl + (size_t)(16 * r + x) * ld) = o;
+      *(d4*)(Cl + (size_t)map.dcol(x, r) * ld) = o;
     }
   }
 }
 
-// ---- half-width strip with a four-stage ring (tail of an update launch) ---------------------------
-// Same strip geometry, fragments and per-accumulator MFMA order as gemm_accumulate<2, false> (so the same
-// bits), but the LDS holds FOUR stages of 8 k-columns and a stage is requested THREE stages ahead, with counted
-// waits (s_waitcnt vmcnt(6 | 3 | 0): three DMA instructions per wave and stage) instead of a drain.  A strip does
-// half the MFMAs of a full tile per stage, so ALONE on a CU -- which is where the tail strips run -- the
-// one-stage-ahead loop is bound by the latency of its own requests (13.7 us per 128-deep block against 16.3 for
-// a whole tile, profiles/r02_update_schedule.md section 3); for full tiles the same ring was measured and
-// rejected (section 7: they are MFMA-bound even alone).
-__device__ __forceinline__ void strip_accumulate_ring(double* smem, const double* P, int ldP, const double* Q,
-                                                      int ldQ, int Kdim, d4 (&acc)[2][4]) {
-  constexpr int BKd = 8, NST = 4, CW = kTile / 2;
-  constexpr int STAGE = BKd * kTile + BKd * CW;   // doubles: P image [8][128], then Q image [8][64]
+// ---- half- and quarter-width strips with a four-stage ring (tail of an update launch) ---------------------
+// strip_accumulate_ring<S>: 128 rows x 128 / S columns per workgroup in TileGeom<S, false>'s layout, with the fragments,
+// swizzle and per-accumulator MFMA order of gemm_accumulate<S, false> (so the same bits), but the LDS holds FOUR stages
+// of 8 k-columns and a stage is requested THREE stages ahead, with counted waits (s_waitcnt vmcnt(6 | 3 | 0): three
+// DMA instructions per wave and stage) instead of a drain.  A strip does a half or a quarter of the MFMAs of a full
+// tile per stage, so ALONE on a CU -- which is where the tail strips run -- the one-stage-ahead loop is bound by the
+// latency of its own requests (13.7 us per 128-deep block against 16.3 for a whole tile,
+// profiles/r02_update_schedule.md section 3); for full tiles the same ring was measured and rejected (section 7: they
+// are MFMA-bound even alone).
+//   S = 2: 2 x 2 waves of 64 x 32 (2 x 4 sub-tiles, eight MFMAs per k-step): the partial last step of an update launch
+//          whose tail fits half a step of tiles.
+//   S = 4 (round 4): wave w owns rows 32 w .. 32 w + 31 of all 32 columns (2 x 2 sub-tiles, four MFMAs per k-step): a tail
+//          of a QUARTER of a step (64 tiles on 256 CUs: 256 quarter strips fill the chip where 128 half strips filled
+//          half of it) or of half a step (512 quarter strips, two per CU).
+template <int S>
+__device__ __forceinline__ void strip_accumulate_ring(double* smem, const double* P, int ldP, const double* Q, int ldQ,
+                                                      int Kdim,
+                                                      d4 (&acc)[TileGeom<S, false>::NX][TileGeom<S, false>::NY]) {
+  static_assert(S == 2 || S == 4, "the ring exists for half- and quarter-width strips");
+  constexpr int BKd = 8, NST = 4;
+  constexpr int CW = TileGeom<S, false>::CW, NX = TileGeom<S, false>::NX, NY = TileGeom<S, false>::NY;
+  static_assert(NX == 2, "the stage loop below splits a k-step's MFMAs at x = 1");
+  constexpr int STAGE = BKd * kTile + BKd * CW;   // doubles: P image [8][128], then Q image [8][CW]
   const int tid = tid_now(), lane = tid & 63, wave = tid >> 6;
-  const int row0 = (wave >> 1) * 64, col0 = (wave & 1) * 32;
+  const int row0 = TileGeom<S, false>::row0(wave), col0 = TileGeom<S, false>::col0(wave);
   const int l15 = lane & 15, l4 = lane >> 4;
 #pragma unroll
-  for (int x = 0; x < 2; ++x)
+  for (int x = 0; x < NX; ++x)
 #pragma unroll
-    for (int y = 0; y < 4; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
+    for (int y = 0; y < NY; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
 
-  // P: wave w stages columns k = w and w + 4 (parity w & 1).  Q: one instruction per wave covers columns
-  // 2w (lanes 0-31) and 2w + 1 (lanes 32-63): parity = lane >> 5
-  const int psrc = ((((lane >> 3) ^ (wave & 1)) << 4) + ((lane & 7) << 1));
-  const double* pP = P + psrc + (size_t)wave * ldP;
-  const int ql = lane & 31, qc = lane >> 5;
-  const int qsrc = ((((ql >> 3) ^ qc) << 4) + ((ql & 7) << 1));
-  const double* pQ = Q + qsrc + (size_t)(2 * wave + qc) * ldQ;
+  // P: wave w stages columns k = w and w + 4 (parity w & 1).
+  const double* pP = P + swz_src(lane, wave & 1) + (size_t)wave * ldP;
+  // Q: ONE request per wave and stage -- the only thing the two widths do differently.  A k-row of the Q image is CW / 2
+  // lanes of 16 bytes, so a wave-instruction covers S rows; lane -> row qrow (parity qrow & 1), 16-byte piece ql.
+  //   S = 2: wave w covers k-rows 2 w (lanes 0 - 31) and 2 w + 1 (lanes 32 - 63).
+  //   S = 4: the stage's 8 k-rows of 256 bytes are two wave-instructions, k-rows 4 (w & 1) + (lane >> 4); waves 2 and 3
+  //          request the same rows again (same bytes to the same place) so that every wave counts three requests per
+  //          stage and the counted waits stay wave-uniform.
+  constexpr int LPR = CW / 2;                     // lanes per Q k-row
+  const int ql = lane & (LPR - 1), qrow = lane / LPR;
+  const int qw = S == 2 ? wave : (wave & 1);      // which S rows of the stage this wave requests
+  const double* pQ = Q + swz_src(ql, qrow & 1) + (size_t)(S * qw + qrow) * ldQ;
   auto issue = [&](int slot) {
     double* Ps_ = smem + slot * STAGE + wave * kTile;
-    double* Qs_ = smem + slot * STAGE + BKd * kTile + wave * 2 * CW;
+    double* Qs_ = smem + slot * STAGE + BKd * kTile + qw * S * CW;
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pP,
                                      (__attribute__((address_space(3))) void*)Ps_, 16, 0, 0);
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pP + (size_t)4 * ldP),
@@ -429,23 +474,23 @@ __device__ __forceinline__ void strip_accumulate_ring(double* smem, const double
 
   const int sw = l4 & 1;
   const int offP = l4 * kTile + l15, offQ = BKd * kTile + l4 * CW + l15;
-  int rbo[4], cbo[2];
+  int rbo[NY], cbo[NX];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) rbo[t] = (((row0 >> 4) + t) ^ sw) << 4;
+  for (int t = 0; t < NY; ++t) rbo[t] = (((row0 >> 4) + t) ^ sw) << 4;
 #pragma unroll
-  for (int t = 0; t < 2; ++t) cbo[t] = (((col0 >> 4) + t) ^ sw) << 4;
-  double pfA[4], qfA[2], pfB[4], qfB[2];
+  for (int t = 0; t < NX; ++t) cbo[t] = (((col0 >> 4) + t) ^ sw) << 4;
+  double pfA[NY], qfA[NX], pfB[NY], qfB[NX];
 #define CCGP_RLOADF(PF, QF, SLOT, KK)                                                            \
   do {                                                                                          \
     const double* St_ = smem + (SLOT) * STAGE;                                                  \
-    _Pragma("unroll") for (int y = 0; y < 4; ++y) PF[y] = St_[(KK) * 4 * kTile + offP + rbo[y]]; \
-    _Pragma("unroll") for (int x = 0; x < 2; ++x) QF[x] = St_[(KK) * 4 * CW + offQ + cbo[x]];   \
+    _Pragma("unroll") for (int y = 0; y < NY; ++y) PF[y] = St_[(KK) * 4 * kTile + offP + rbo[y]]; \
+    _Pragma("unroll") for (int x = 0; x < NX; ++x) QF[x] = St_[(KK) * 4 * CW + offQ + cbo[x]];  \
     __builtin_amdgcn_sched_barrier(0);                                                          \
   } while (0)
 #define CCGP_RMFMAS(PF, QF, X0, X1)                                                              \
   do {                                                                                          \
     _Pragma("unroll") for (int x = (X0); x < (X1); ++x)                                         \
-      _Pragma("unroll") for (int y = 0; y < 4; ++y)                                             \
+      _Pragma("unroll") for (int y = 0; y < NY; ++y)                                            \
           acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(QF[x], PF[y], acc[x][y], 0, 0, 0);   \
     __builtin_amdgcn_sched_barrier(0);                                                          \
   } while (0)
@@ -476,96 +521,6 @@ __device__ __forceinline__ void strip_accumulate_ring(double* smem, const double
 #undef CCGP_RMFMAS
 }
 
-// ---- quarter-width strip on the same ring (round 4) ------------------------------------------------------
-// 128 rows x 32 columns per workgroup in TileGeom<4>'s layout (wave w: rows 32 w .. 32 w + 31, all 32 columns: 2 x 2 sub-tiles,
-// four MFMAs per k-step), for the partial last step of an update launch whose tail is a QUARTER of a step (64 tiles on 256
-// CUs: 256 quarter strips fill the chip where 128 half strips filled half of it) or half a step (512 quarter strips, two per
-// CU).  Fragments, swizzle and per-accumulator MFMA order are gemm_accumulate<4, false>'s: same bits.  The Q image of a stage
-// is 8 k-rows of 256 bytes: two wave-instructions; waves 2 and 3 request the same rows again (same bytes to the same place)
-// so that every wave counts three requests per stage and the counted waits stay wave-uniform.
-__device__ __forceinline__ void strip_accumulate_ring4(double* smem, const double* P, int ldP, const double* Q,
-                                                       int ldQ, int Kdim, d4 (&acc)[2][2]) {
-  constexpr int BKd = 8, NST = 4, CW = kTile / 4;
-  constexpr int STAGE = BKd * kTile + BKd * CW;   // doubles: P image [8][128], then Q image [8][32]
-  const int tid = tid_now(), lane = tid & 63, wave = tid >> 6;
-  const int row0 = wave * 32;
-  const int l15 = lane & 15, l4 = lane >> 4;
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
-  const int psrc = ((((lane >> 3) ^ (wave & 1)) << 4) + ((lane & 7) << 1));
-  const double* pP = P + psrc + (size_t)wave * ldP;
-  // Q: one wave-instruction = k-rows 4 (w & 1) + (lane >> 4), 16 lanes x 16 bytes each; parity of the row = (lane >> 4) & 1
-  const int qrk = lane >> 4, ql = lane & 15;
-  const int qsrc = ((((ql >> 3) ^ (qrk & 1)) << 4) + ((ql & 7) << 1));
-  const double* pQ = Q + qsrc + (size_t)(4 * (wave & 1) + qrk) * ldQ;
-  auto issue = [&](int slot) {
-    double* Ps_ = smem + slot * STAGE + wave * kTile;
-    double* Qs_ = smem + slot * STAGE + BKd * kTile + (wave & 1) * 4 * CW;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pP,
-                                     (__attribute__((address_space(3))) void*)Ps_, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pP + (size_t)4 * ldP),
-                                     (__attribute__((address_space(3))) void*)(Ps_ + 4 * kTile), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pQ,
-                                     (__attribute__((address_space(3))) void*)Qs_, 16, 0, 0);
-    pP += (size_t)BKd * ldP;
-    pQ += (size_t)BKd * ldQ;
-  };
-  auto wait_and_meet = [&](int later_stages) {   // as in strip_accumulate_ring: three requests per wave and stage
-    if (later_stages >= 3) __builtin_amdgcn_s_waitcnt(0x0079);
-    else if (later_stages == 2) __builtin_amdgcn_s_waitcnt(0x0076);
-    else if (later_stages == 1) __builtin_amdgcn_s_waitcnt(0x0073);
-    else __builtin_amdgcn_s_waitcnt(0x0070);
-    __builtin_amdgcn_s_barrier();
-  };
-  const int sw = l4 & 1;
-  const int offP = l4 * kTile + l15, offQ = BKd * kTile + l4 * CW + l15;
-  int rbo[2], cbo[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    rbo[t] = (((row0 >> 4) + t) ^ sw) << 4;
-    cbo[t] = (t ^ sw) << 4;
-  }
-  double pfA[2], qfA[2], pfB[2], qfB[2];
-#define CCGP_QLOADF(PF, QF, SLOT, KK)                                                            \
-  do {                                                                                          \
-    const double* St_ = smem + (SLOT) * STAGE;                                                  \
-    _Pragma("unroll") for (int y = 0; y < 2; ++y) PF[y] = St_[(KK) * 4 * kTile + offP + rbo[y]]; \
-    _Pragma("unroll") for (int x = 0; x < 2; ++x) QF[x] = St_[(KK) * 4 * CW + offQ + cbo[x]];   \
-    __builtin_amdgcn_sched_barrier(0);                                                          \
-  } while (0)
-#define CCGP_QMFMAS(PF, QF, X0, X1)                                                              \
-  do {                                                                                          \
-    _Pragma("unroll") for (int x = (X0); x < (X1); ++x)                                         \
-      _Pragma("unroll") for (int y = 0; y < 2; ++y)                                             \
-          acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(QF[x], PF[y], acc[x][y], 0, 0, 0);   \
-    __builtin_amdgcn_sched_barrier(0);                                                          \
-  } while (0)
-  const int nk = Kdim / BKd;
-  const int pre = nk < NST ? nk : NST;
-  for (int t = 0; t < pre; ++t) issue(t);
-  __builtin_amdgcn_sched_barrier(0);
-  wait_and_meet(pre - 1);
-  CCGP_QLOADF(pfA, qfA, 0, 0);
-  for (int kt = 0; kt < nk; ++kt) {
-    const int slot = kt & (NST - 1);
-    CCGP_QLOADF(pfB, qfB, slot, 1);
-    CCGP_QMFMAS(pfA, qfA, 0, 2);
-    if (kt + 1 < nk) {
-      const int last_issued = kt + NST - 1 < nk - 1 ? kt + NST - 1 : nk - 1;
-      wait_and_meet(last_issued - (kt + 1));
-      if (kt + NST < nk) issue(slot);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    CCGP_QMFMAS(pfB, qfB, 0, 1);
-    if (kt + 1 < nk) CCGP_QLOADF(pfA, qfA, (kt + 1) & (NST - 1), 0);
-    CCGP_QMFMAS(pfB, qfB, 1, 2);
-  }
-#undef CCGP_QLOADF
-#undef CCGP_QMFMAS
-}
-
 // C = C - acc (mode 0) or C = acc (mode 1) for one strip.
 template <int S, bool THIN, bool TRI = false, bool RING = false>
 __device__ __forceinline__ void gemm_tile(double* smem, const double* P, int ldP, const double* Q,
@@ -575,8 +530,7 @@ __device__ __forceinline__ void gemm_tile(double* smem, const double* P, int ldP
   d4 acc[NX][NY];
   if constexpr (RING) {
     static_assert((S == 2 || S == 4) && !THIN && !TRI, "the four-stage ring exists for half- and quarter-width update strips");
-    if constexpr (S == 2) strip_accumulate_ring(smem, P, ldP, Q, ldQ, Kdim, acc);
-    else strip_accumulate_ring4(smem, P, ldP, Q, ldQ, Kdim, acc);
+    strip_accumulate_ring<S>(smem, P, ldP, Q, ldQ, Kdim, acc);
   } else {
     gemm_accumulate<S, THIN, TRI>(smem, P, ldP, Q, ldQ, Kdim, acc);
   }
@@ -634,7 +588,7 @@ __device__ __forceinline__ void diag_rhs_accumulate(double* smem, const double* 
   const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc((void*)Qp, 0, -1, 0x00020000);
   const __amdgpu_buffer_rsrc_t rT = __builtin_amdgcn_make_buffer_rsrc((void*)Tp, 0, -1, 0x00020000);
   // panel rows k = W + 4 q, swizzled source (the 16-row block index of row k is XORed with k & 1 = W & 1)
-  const unsigned lane_q = (unsigned)(((((lane >> 3) ^ (W & 1)) << 4) + ((lane & 7) << 1)) * 8);
+  const unsigned lane_q = (unsigned)(swz_src(lane, W & 1) * 8);
   const unsigned lane_t = (unsigned)((((lane & 7) << 1) + (size_t)(lane >> 3) * ld) * 8);   // 8 columns x 16 rows
   const unsigned stepQ = (unsigned)ld * 32;
   unsigned oQ = (unsigned)W * (unsigned)ld * 8, oT = (unsigned)(8 * W) * (unsigned)ld * 8;
@@ -709,53 +663,16 @@ __device__ __forceinline__ void diag_rhs_accumulate(double* smem, const double* 
 #undef CCGP_SB
 }
 
-// ---- diagonal tile of the update, fused with the right-hand-side rows ---------------------------
-// The diagonal tile T_jj = A_jj - L_j L_j' (L_j = the finished panel, rows j of block columns < j)
-// needs only its lower triangle: 36 of its 64 16 x 16 sub-tiles, and both GEMM operands are the SAME
-// panel.  The right-hand-side rows (y', 1' and 14 zero rows below the matrix) need  b_j' - Z L_j'  against
-// that same panel: 8 more sub-tiles.  One workgroup does both: it stages the panel ONCE per k-stage
-// (16 KB + 2 KB for the 16 right-hand-side rows instead of 32 KB) and each wave accumulates 11 sub-tiles
-// (block rows w and 7 - w of the triangle: 9 sub-tiles whatever w; plus right-hand-side columns 2w, 2w+1)
-// against 16 for a full tile.  Before round 2 the diagonal tile ran as a full tile and the right-hand
-// sides as a separate "thin" workgroup that occupied a full slot for a whole tile time: at the late
-// block columns (few tile rows per matrix) half of the resident workgroups did almost no arithmetic.
-__device__ __forceinline__ void diag_rhs_tile(double* smem, const double* Qp, const double* Tp, int ld,
-                                              int Kdim, double* C, double* Ct, int wide) {
-  constexpr int BKs = 16;
-  constexpr int TR = 16;                                // right-hand-side rows staged
-  [[maybe_unused]] constexpr int STAGE = BKs * kTile + BKs * TR;         // doubles per stage
-  constexpr int NS = 11;                                // sub-tiles per wave: 9 of the triangle + 2 right-hand-side
-  const int tid = tid_now(), lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+// The round-2 k-loop of the diagonal workgroup on 64-bit pointers: diag_rhs_tile's fallback for panels that
+// buffer offsets cannot address, and nothing else.  One body for all waves: slot s multiplies column block cbs[s]
+// by block row rA (s <= wave), block row rB (s <= 8) or the right-hand-side rows, picked per slot at run time.
+__device__ __forceinline__ void diag_rhs_accumulate_wide(double* smem, const double* Qp, const double* Tp, int ld,
+                                                         int Kdim, int lane, int wave, const int (&cbs)[11],
+                                                         d4 (&acc)[11]) {
+  constexpr int BKs = 16, TR = 16, STAGE = BKs * kTile + BKs * TR, NS = 11;
   const int l15 = lane & 15, l4 = lane >> 4;
   const int rA = wave, rB = 7 - wave;
-
-  d4 acc[NS];
-#pragma unroll
-  for (int s = 0; s < NS; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
-
-  // slot -> column block: slots 0..wave belong to block row rA (cb = s), the rest of 0..8 to block row
-  // rB (cb = s - wave - 1); slots 9, 10 are the right-hand-side rows against column blocks 2w, 2w + 1
-  int cbs[NS];
-#pragma unroll
-  for (int s = 0; s < 9; ++s) cbs[s] = s <= wave ? s : s - wave - 1;
-  cbs[9] = 2 * wave;
-  cbs[10] = 2 * wave + 1;
-
-  // the specialised loop addresses its panel through 32-bit buffer offsets: matrices whose panel spans 4 GiB or
-  // more (n >= ~16 000 with the identity rows of an inverse below them) keep the 64-bit-pointer loop -- same bits.
-  // That older loop (the `else` branch) is kept for exactly this case and nothing else; CCGP_OPT_WIDE_OFFSETS forces it
-  // so that the tests can hold one loop against the other at sizes that fit a test (the OPT_WIDE_OFFSETS test of tests/test_gpu_parity.py).
-  if (!wide && fits_buffer_offsets(Kdim, ld)) {
-    switch (wave) {
-      case 0: diag_rhs_accumulate<0>(smem, Qp, Tp, ld, Kdim, acc); break;
-      case 1: diag_rhs_accumulate<1>(smem, Qp, Tp, ld, Kdim, acc); break;
-      case 2: diag_rhs_accumulate<2>(smem, Qp, Tp, ld, Kdim, acc); break;
-      default: diag_rhs_accumulate<3>(smem, Qp, Tp, ld, Kdim, acc); break;
-    }
-  } else {
-  const int psrc = ((((lane >> 3) ^ (wave & 1)) << 4) + ((lane & 7) << 1));
-  const double* pQ = Qp + psrc + (size_t)wave * ld;                       // wave w stages columns k = w + 4q
+  const double* pQ = Qp + swz_src(lane, wave & 1) + (size_t)wave * ld;    // wave w stages columns k = w + 4q
   const double* pT = Tp + ((lane & 7) << 1) + (size_t)(8 * wave + (lane >> 3)) * ld;   // waves 0, 1: 8 columns each
   const size_t stepQ = (size_t)4 * ld;
 
@@ -829,6 +746,51 @@ __device__ __forceinline__ void diag_rhs_tile(double* smem, const double* Qp, co
   }
 #undef CCGP_DLOADF
 #undef CCGP_DMFMAS
+}
+
+// ---- diagonal tile of the update, fused with the right-hand-side rows ---------------------------
+// The diagonal tile T_jj = A_jj - L_j L_j' (L_j = the finished panel, rows j of block columns < j)
+// needs only its lower triangle: 36 of its 64 16 x 16 sub-tiles, and both GEMM operands are the SAME
+// panel.  The right-hand-side rows (y', 1' and 14 zero rows below the matrix) need  b_j' - Z L_j'  against
+// that same panel: 8 more sub-tiles.  One workgroup does both: it stages the panel ONCE per k-stage
+// (16 KB + 2 KB for the 16 right-hand-side rows instead of 32 KB) and each wave accumulates 11 sub-tiles
+// (block rows w and 7 - w of the triangle: 9 sub-tiles whatever w; plus right-hand-side columns 2w, 2w+1)
+// against 16 for a full tile.  Before round 2 the diagonal tile ran as a full tile and the right-hand
+// sides as a separate "thin" workgroup that occupied a full slot for a whole tile time: at the late
+// block columns (few tile rows per matrix) half of the resident workgroups did almost no arithmetic.
+__device__ __forceinline__ void diag_rhs_tile(double* smem, const double* Qp, const double* Tp, int ld,
+                                              int Kdim, double* C, double* Ct, int wide) {
+  constexpr int NS = 11;                                // sub-tiles per wave: 9 of the triangle + 2 right-hand-side
+  const int tid = tid_now(), lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int rA = wave, rB = 7 - wave;
+
+  d4 acc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+
+  // slot -> column block: slots 0..wave belong to block row rA (cb = s), the rest of 0..8 to block row
+  // rB (cb = s - wave - 1); slots 9, 10 are the right-hand-side rows against column blocks 2w, 2w + 1
+  int cbs[NS];
+#pragma unroll
+  for (int s = 0; s < 9; ++s) cbs[s] = s <= wave ? s : s - wave - 1;
+  cbs[9] = 2 * wave;
+  cbs[10] = 2 * wave + 1;
+
+  // the specialised loop addresses its panel through 32-bit buffer offsets: matrices whose panel spans 4 GiB or
+  // more (n >= ~16 000 with the identity rows of an inverse below them) keep the 64-bit-pointer loop -- same bits.
+  // CCGP_OPT_WIDE_OFFSETS forces that loop so that the tests can hold one against the other at sizes that fit a
+  // test (the OPT_WIDE_OFFSETS test of tests/test_gpu_parity.py).
+  if (!wide && fits_buffer_offsets(Kdim, ld)) {
+    switch (wave) {
+      case 0: diag_rhs_accumulate<0>(smem, Qp, Tp, ld, Kdim, acc); break;
+      case 1: diag_rhs_accumulate<1>(smem, Qp, Tp, ld, Kdim, acc); break;
+      case 2: diag_rhs_accumulate<2>(smem, Qp, Tp, ld, Kdim, acc); break;
+      default: diag_rhs_accumulate<3>(smem, Qp, Tp, ld, Kdim, acc); break;
+    }
+  } else {
+    diag_rhs_accumulate_wide(smem, Qp, Tp, ld, Kdim, lane, wave, cbs, acc);
   }
 
   // C -= acc: all loads of a group before its stores (see gemm_tile)
@@ -875,6 +837,11 @@ struct DiagArgs {
   int ld;
   double ptol;          // pivot_tolerance(mean_mode, n), ccgp_internal.h
 };
+
+// The diagonal block's share of a sweep's GemmArgs, for block column j
+__host__ __device__ inline DiagArgs diag_args(const GemmArgs& g, int j) {
+  return DiagArgs{g.A, g.a_stride, g.npad, g.invd, g.invd_stride, g.logdet_part, g.status, j, g.nt, g.nb, g.n, g.ld, g.ptol};
+}
 
 // Register-resident: the 256 threads form a 16 x 16 grid (ty = row class, tx = column class)
 // and own the block 2-D cyclically -- thread (ty, tx) holds entries (ty + 16a, tx + 16b).  The
@@ -985,9 +952,9 @@ __global__ __launch_bounds__(256) void diag_kernel(DiagArgs g) {
 // update (MODE 0): first ONE workgroup per matrix for the diagonal tile + right-hand sides (diag_rhs_tile; it goes
 // on to factorise the block, so it is dispatched first), then the tile rows below the diagonal and the extra tile
 // rows (prediction: r(x_t)'; inverse / gradient: identity), matrices in groups of eight, each tile as S column
-// strips.  In the S = 1 kernel the LAST `tail` tiles (in that order) may run as two half-width ring-pipelined
-// strips each: the last, partial step of 256 workgroups then consists of strips only and takes about half a
-// tile time (update_tail()).
+// strips.  In the S = 1 kernel the LAST `tail` tiles (in that order) may run as tail_s ring-pipelined strips each
+// (two half-width or four quarter-width): the last, partial step of 256 workgroups then consists of strips only and
+// takes about half a tile time (update_tail()).
 // trsm (MODE 1): per matrix tile rows j+1 .. nt-1, the thin right-hand-side tile row nt, then the extra rows.
 // rows_only (kept factor): the extra rows alone.
 // Block index % 8 = matrix % 8 everywhere: blocks are dealt round-robin over the 8 XCDs, so all tiles of one matrix
@@ -1069,8 +1036,7 @@ __device__ __forceinline__ void diag_unit(const GemmArgs& g, double* smem, int j
     // thread layout.  All waves of a workgroup share that L1, so workgroup scope is enough: __syncthreads is
     // release(workgroup) + s_barrier + acquire(workgroup) -- no L2 write-back, no cache invalidate
     __syncthreads();
-    DiagArgs dg{g.A, g.a_stride, g.npad, g.invd, g.invd_stride, g.logdet_part, g.status, j, g.nt, g.nb, g.n, g.ld, g.ptol};
-    diag_factor(dg, b, smem);   // the staging LDS is free: the K loop ended on a barrier
+    diag_factor(diag_args(g, j), b, smem);   // the staging LDS is free: the K loop ended on a barrier
   }
 }
 
@@ -1423,21 +1389,10 @@ struct RinvArgs {
 // (512 VGPRs: one workgroup per CU, the round-2 loop alone on its CU -- 30 TFLOP/s), and every attempt to contract without
 // that second set under 256 registers ended in kilobytes of scratch (14.6 -> 25.6 ms per 16 draws at n = 4096).  A round
 // trip of M through HBM costs 2 x 67 MB per draw -- 0.03 ms at 5 TB/s -- and leaves each kernel with one job.
-template <bool IL>
-struct RinvMap {
-  int row0, col0, l15, l4;
-  __device__ RinvMap() {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    row0 = (wave >> 1) * 64; col0 = (wave & 1) * 64; l15 = lane & 15; l4 = lane >> 4;
-  }
-  __device__ __forceinline__ int row(int y) const { return IL ? row0 + 4 * l15 + y : row0 + 16 * y + l15; }
-  __device__ __forceinline__ int col(int x, int r) const { return IL ? col0 + 16 * r + 4 * l4 + x : col0 + 16 * x + l4 + 4 * r; }
-};
-
 template <bool GRAD, bool IL>
 __device__ __forceinline__ void rinv_tile_finish(const RinvArgs& g, d4 (&acc)[4][4], int b, int ta, int tb) {
   // acc[x][y][r] = Rinv[row = ta*128 + map.row(y)][col = tb*128 + map.col(x, r)]
-  const RinvMap<IL> map;
+  const AccMap<IL> map;
   const int n = g.n;
   if constexpr (!GRAD) {
     double* out = g.Rinv + (size_t)b * n * n;
@@ -1725,7 +1680,6 @@ struct GroupRun {
   int* status;
   const BlockedJob* job;
   GemmArgs g{};
-  DiagArgs dg{};
   void begin() {
     const BlockedJob* pr = job && job->kind == kJobPredict ? job : nullptr;
     nt = npad / kTile;
@@ -1742,10 +1696,7 @@ struct GroupRun {
     g.invd_stride = (size_t)nt * kTile * kTile; g.nt = nt; g.nb = nb; g.ld = w.ld; g.ne = w.ne;
     g.extra_lower = job && job->kind >= kJobInverse ? 1 : 0;
     g.fuse_diag = h->opt_fuse_diag; g.tail_strips = h->opt_tail_strips; g.wide = h->opt_wide_offsets; g.logdet_part = w.z; g.status = status + b0; g.n = n;
-    dg.A = w.A; dg.a_stride = w.a_stride; dg.npad = npad; dg.invd = w.invd;
-    dg.invd_stride = g.invd_stride; dg.logdet_part = w.z; dg.status = status + b0; dg.nt = nt;
-    dg.nb = nb; dg.n = n; dg.ld = w.ld;
-    dg.ptol = g.ptol = pivot_tolerance(mean_mode, n);
+    g.ptol = pivot_tolerance(mean_mode, n);
   }
 
   // T_ij = A_ij - sum_{k<j} L_ik L_jk' for every tile row of block column j (nothing to do at j = 0)
@@ -1761,8 +1712,7 @@ struct GroupRun {
   void panel(int j) {
     if (j == 0 || !g.fuse_diag) {   // block column 0 has no update launch; from column 1 on the update's diagonal workgroup does it
       ScopedTimer t(h, CCGP_T_DIAG, s);
-      dg.j = j;
-      hipLaunchKernelGGL(diag_kernel, dim3(nb), dim3(256), 0, s, dg);
+      hipLaunchKernelGGL(diag_kernel, dim3(nb), dim3(256), 0, s, diag_args(g, j));
     }
     {
       ScopedTimer t(h, CCGP_T_TRSM, s);
@@ -1883,9 +1833,8 @@ bool blocked_grad_supported(int d, int K) { return grad_contract_lds(d, K) <= (s
 // partial sums of the gradient contraction per matrix: one per lower 64 x 64 tile
 size_t blocked_grad_partials(int npad) { const size_t nt64 = (size_t)npad / 64; return nt64 * (nt64 + 1) / 2; }
 
-void blocked_loglik(ccgp_handle* h, const double* X, int n, int d, const double* y, DrawView dv,
-                    int b0, int nb, int npad, double sigma2, int mean_mode, double tau2,
-                    BlockedWs w, double* loglik, double* beta, int* status, const BlockedJob* job) {
+// every kernel of this file that asks for dynamic LDS, once per device
+static void raise_blocked_lds_limits() {
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
     raise_lds_limit((const void*)chol_update_kernel, "chol_update_kernel");
@@ -1899,6 +1848,12 @@ void blocked_loglik(ccgp_handle* h, const double* X, int n, int d, const double*
     raise_lds_limit((const void*)grad_contract_kernel<8>, "grad_contract_kernel<8>");
     raise_lds_limit((const void*)grad_contract_kernel<0>, "grad_contract_kernel<0>");
   });
+}
+
+void blocked_loglik(ccgp_handle* h, const double* X, int n, int d, const double* y, DrawView dv,
+                    int b0, int nb, int npad, double sigma2, int mean_mode, double tau2,
+                    BlockedWs w, double* loglik, double* beta, int* status, const BlockedJob* job) {
+  raise_blocked_lds_limits();
   GroupRun r{};
   r.h = h; r.s = h->stream; r.X = X; r.n = n; r.d = d; r.y = y; r.dv = dv; r.b0 = b0; r.nb = nb;
   r.npad = npad; r.sigma2 = sigma2; r.mean_mode = mean_mode; r.tau2 = tau2; r.w = w;
@@ -1922,12 +1877,7 @@ void blocked_loglik(ccgp_handle* h, const double* X, int n, int d, const double*
 void blocked_predict_from_factors(ccgp_handle* h, const BlockedWs& w, int n, int npad, int S, int s0, int ns, double* E,
                                   size_t e_stride, int lde, int m, const int* status, double sigma2,
                                   double* mean, double* var) {
-  static unsigned long long attr_mask = 0;
-  once_per_device(attr_mask, [] {
-    raise_lds_limit((const void*)chol_update_kernel, "chol_update_kernel");
-    raise_lds_limit((const void*)chol_update_s2_kernel, "chol_update_s2_kernel");
-    raise_lds_limit((const void*)chol_trsm_kernel, "chol_trsm_kernel");
-  });
+  raise_blocked_lds_limits();
   const int nt = npad / kTile, ne = lde / kTile;
   hipStream_t s = h->stream;
   GemmArgs g{};

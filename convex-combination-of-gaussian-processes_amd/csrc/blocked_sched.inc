@@ -174,8 +174,7 @@ __device__ __forceinline__ void sched_run(const GemmArgs& g, double* smem, unsig
   const int kind = sched::task_kind(w), j = sched::task_j(w), i = sched::task_i(w), b = sched::task_b(w);
   if (kind == sched::kD) {
     if (j == 0) {
-      DiagArgs dg{g.A, g.a_stride, g.npad, g.invd, g.invd_stride, g.logdet_part, g.status, 0, g.nt, g.nb, g.n, g.ld, g.ptol};
-      diag_factor(dg, b, smem);
+      diag_factor(diag_args(g, 0), b, smem);
     } else {
       diag_unit(g, smem, j, b);
     }
