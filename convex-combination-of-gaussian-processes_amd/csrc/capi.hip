@@ -283,16 +283,10 @@ int loglik_run(ccgp_handle* h, const double* dX, int n, int d, const double* dy,
   // the fused evaluators generate Gaussian correlations in registers; any other family goes through
   // the materialised-matrix (blocked) path, where only cov_kernel knows about families
   const bool gauss = dv.fam.id == 0;
-  const bool reg_ok = gauss && small_reg_supported(n, d, K);
-  const bool lds_ok = gauss && n <= kSmallMaxN && small_lds_bytes(n, d, 0) <= (size_t)kLdsBytes - 64;
-  if (reg_ok || lds_ok) {   // otherwise (n > 128, or d too large for LDS) the blocked path takes it
+  if (gauss && small_reg_supported(n, d, K)) {   // otherwise (n > 128, or d too large for LDS) the blocked path takes it
     ScopedTimer t(h, CCGP_T_FUSED);
-    if (reg_ok)
-      launch_small_reg_loglik(h->stream, dX, n, d, dy, dv, B, sigma2, mean_mode, tau2, d_loglik, d_beta,
-                              d_status, h->opt_small_grid16 != 0);
-    else
-      launch_small_loglik(h->stream, dX, n, d, dy, dv, B, sigma2, mean_mode, tau2, d_loglik, d_beta,
-                          d_status);
+    launch_small_reg_loglik(h->stream, dX, n, d, dy, dv, B, sigma2, mean_mode, tau2, d_loglik, d_beta,
+                            d_status, h->opt_small_grid16 != 0);
     CCGP_LAUNCH_CHECK();
     return CCGP_OK;
   }
@@ -1424,7 +1418,8 @@ static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const dou
                        const double* dXtest, int m, double sigma2, double* d_mean, double* d_var, double* d_beta,
                        int* d_status) {
   const int K = dv.K, S = dv.ldp;
-  if (dv.fam.id != 0 || n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64) {
+  if (dv.fam.id != 0 || n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64 ||
+      !small_reg_supported(n, d, K, false, true)) {
     // blocked path: the m cross-correlation rows ride along as extra tile rows of the sweep
     const int npad = round_up(n, kTile), ne = (m + kTile - 1) / kTile;
     // scratch for outputs the caller did not ask for lives behind the matrices
@@ -1447,29 +1442,25 @@ static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const dou
   }
   {
     ScopedTimer t(h, CCGP_T_FUSED);
-    if (small_reg_supported(n, d, K, false, true)) {
-      // kept-factor scheme where it applies (n <= 104, K <= 3) and its scratch fits the workspace: the factor block and the
-      // correlation vectors of as many draws at a time as the limit allows (at least 64)
-      void* scratch = nullptr;
-      size_t sbytes = 0;
-      if (h->opt_predict_factor && small_reg_sites_supported(n, d, K)) {
-        const size_t per = small_reg_sites_scratch(n, d, K, m);
-        const size_t want = per * (size_t)S, cap = std::max<size_t>(h->ws_limit / 2, per * 64);
-        if (ensure_ws(h, std::min(want, cap / per * per)) == CCGP_OK) { scratch = h->ws; sbytes = h->ws_bytes; }
-        if (scratch && !h->aux_stream) {
-          if (hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking) != hipSuccess) h->aux_stream = nullptr;
-          if (h->aux_stream && (hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming) != hipSuccess ||
-                                hipEventCreateWithFlags(&h->aux_join, hipEventDisableTiming) != hipSuccess)) {
-            (void)hipStreamDestroy(h->aux_stream);
-            h->aux_stream = nullptr;
-          }
+    // kept-factor scheme where it applies (n <= 104, K <= 3) and its scratch fits the workspace: the factor block and the
+    // correlation vectors of as many draws at a time as the limit allows (at least 64)
+    void* scratch = nullptr;
+    size_t sbytes = 0;
+    if (h->opt_predict_factor && small_reg_sites_supported(n, d, K)) {
+      const size_t per = small_reg_sites_scratch(n, d, K, m);
+      const size_t want = per * (size_t)S, cap = std::max<size_t>(h->ws_limit / 2, per * 64);
+      if (ensure_ws(h, std::min(want, cap / per * per)) == CCGP_OK) { scratch = h->ws; sbytes = h->ws_bytes; }
+      if (scratch && !h->aux_stream) {
+        if (hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking) != hipSuccess) h->aux_stream = nullptr;
+        if (h->aux_stream && (hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming) != hipSuccess ||
+                              hipEventCreateWithFlags(&h->aux_join, hipEventDisableTiming) != hipSuccess)) {
+          (void)hipStreamDestroy(h->aux_stream);
+          h->aux_stream = nullptr;
         }
       }
-      launch_small_reg_predict(h->stream, dX, n, d, dy, dv, S, dXtest, m, sigma2, d_mean, d_var, d_beta,
-                               d_status, scratch, sbytes, h->aux_stream, h->aux_fork, h->aux_join);
-    } else
-      launch_small_predict(h->stream, dX, n, d, dy, dv, S, dXtest, m, sigma2, d_mean, d_var, d_beta,
-                           d_status);
+    }
+    launch_small_reg_predict(h->stream, dX, n, d, dy, dv, S, dXtest, m, sigma2, d_mean, d_var, d_beta,
+                             d_status, scratch, sbytes, h->aux_stream, h->aux_fork, h->aux_join);
   }
   CCGP_LAUNCH_CHECK();
   return CCGP_OK;

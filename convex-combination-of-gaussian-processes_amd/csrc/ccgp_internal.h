@@ -12,14 +12,11 @@
 
 #include "../../include/ccgp.h"
 #include "exp_table.h"
+#include "small_layout.h"   // kSmallMaxN, kMaxD, kMaxK, kLdsBytes, kExpTableDoubles; the small-n carves and route predicates
 
 namespace ccgp {
 
 constexpr int kTile = 128;       // block size of the blocked Cholesky (rows/cols per tile)
-constexpr int kSmallMaxN = 128;  // n <= this goes to the fused in-LDS evaluator
-constexpr int kMaxD = 64;        // input dimensions supported by the covariance kernels
-constexpr int kMaxK = 8;         // component GPs per draw
-constexpr int kLdsBytes = 160 * 1024;
 
 // When does a factorisation "fail" (status != 0, NaN -- the reference's NA)?
 //   mean mode 1 (cond.like, HX:561-572): the reference only runs mnormt::dmnorm, whose chol() stops at a
@@ -127,16 +124,8 @@ void launch_cov_cross_batched(hipStream_t s, const double* Xtest, int m, const d
                               DrawView dv, int b0, int nb, double* Abase, size_t batch_stride, int ldo);
 
 // ---- small.hip -----------------------------------------------------------------------
-// Fused evaluator: one workgroup per draw (and per test-point chunk when m > 0).
-size_t small_lds_bytes(int n, int d, int mtile);
-int small_pick_mtile(int n, int d, int m);
-void launch_small_loglik(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
-                         int B, double sigma2, int mean_mode, double tau2, double* loglik,
-                         double* beta, int* status);
-void launch_small_predict(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
-                          int S, const double* Xtest, int m, double sigma2, double* mean,
-                          double* var, double* beta, int* status);
-// Explicit inverse (solve(R), HX:454) and gradient for small n.
+// In-LDS evaluator, one workgroup per (draw, chunk of unit rows): explicit inverse (solve(R), HX:454) and gradient for the
+// n <= 128 shapes whose register-resident inverse instance does not fit (small_lds_bytes, small_pick_mtile: small_layout.h)
 void launch_small_inverse(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int draw,
                           double sigma2, double* Rinv, double* loglik, double* beta, int* status);
 int small_grad_chunks(int n, int d);
@@ -145,26 +134,21 @@ void launch_small_grad(hipStream_t s, const double* X, int n, int d, const doubl
                        int B, double sigma2, double* loglik, double* beta, double* grad,
                        int* status, double* gpart);
 
-// ---- small_reg.hip: register-resident evaluator for the plain likelihood (n <= 128) ---------
-bool small_reg_supported(int n, int d, int K, bool per_design = false, bool predict = false);
+// ---- small_reg.hip: register-resident evaluator (n <= 128); the small_reg_*_supported predicates: small_layout.h ---------
 void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                               int S, const double* Xtest, int m, double sigma2, double* mean, double* var,
                               double* beta, int* status, void* scratch = nullptr, size_t scratch_bytes = 0,
                               hipStream_t aux = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr);
-bool small_reg_sites_supported(int n, int d, int K);          // kept-factor prediction (round 5): n <= 104, K <= 3
-size_t small_reg_sites_scratch(int n, int d, int K, int m);   // bytes of scratch per draw it needs
 void launch_small_reg_logdet_designs(hipStream_t s, const double* Xs, int n, int d, DrawView dv, int B,
                                      double* logdet, int* status);
 // solve(R) of ONE draw (logpost with R.Inv, HX:454) on the register-resident scheme; likelihood and beta of the same
 // factorisation come with it
-bool small_reg_inverse_supported(int n, int d, int K);
 void launch_small_reg_inverse(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int draw,
                               double sigma2, double* Rinv, double* loglik, double* beta, int* status);
 void launch_small_reg_grad(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B,
                            double sigma2, double* loglik, double* beta, double* grad, int* status);
 // d log det R_mixed / d X of the rows >= n_fixed for B candidate designs (entropy criteria, BSQ:856-948); dgrad holds
 // per design (n - n_fixed) x d column-major
-bool small_reg_design_grad_supported(int n, int d, int K);
 void launch_small_reg_logdet_grad_designs(hipStream_t s, const double* Xs, int n, int d, DrawView dv, int B, int n_fixed,
                                           double* logdet, double* dgrad, int* status);
 void launch_small_reg_loglik(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
@@ -261,8 +245,7 @@ inline void once_per_device(unsigned long long& mask, F set_attributes) {
 // exp (exact-FMA emulation; the library routine: < 1 ulp); tests hold 1e-13 on entries.
 // The argument is clamped at -1000 for the index computation only (the magic-number trick needs |n| < 2^31); r is
 // formed from the ORIGINAL x, so a NaN distance stays NaN, and v_ldexp_f64 underflows gradually to 0.
-static __device__ const unsigned long long kExpTableBits[256] = CCGP_EXP_TABLE_BITS;
-constexpr int kExpTableDoubles = 256;
+static __device__ const unsigned long long kExpTableBits[kExpTableDoubles] = CCGP_EXP_TABLE_BITS;
 
 // cooperative copy of the table into LDS (call before a barrier that precedes the first exp_cov)
 __device__ __forceinline__ void exp_table_load(double* tab, int tid, int nthreads) {
@@ -369,10 +352,7 @@ __device__ __forceinline__ double exp_cov_poly(double dist) {
 #endif
 }
 
-// which exp the small-n evaluators (small_reg.hip, small.hip) use: 0 = polynomial, 1 = table (A/B: -DCCGP_SMALL_EXP_TABLE=1)
-#ifndef CCGP_SMALL_EXP_TABLE
-#define CCGP_SMALL_EXP_TABLE 0
-#endif
+// the exp of the small-n evaluators (small_reg.hip, small.hip): CCGP_SMALL_EXP_TABLE (small_layout.h) 0 = polynomial, 1 = table
 template <bool SC = false>
 __device__ __forceinline__ double exp_small(double dist, const double* tab) {
 #if CCGP_SMALL_EXP_TABLE

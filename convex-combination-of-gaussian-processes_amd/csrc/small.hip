@@ -1,21 +1,22 @@
-// Fused in-LDS evaluator for n <= 128 (BASELINE configs 2, 3, 5).
+// In-LDS evaluator for n <= 128: the explicit inverse (solve(R) of ccgp_logpost) and the gradient of the shapes whose
+// register-resident instance (small_reg.hip, which serves everything else at n <= 128) does not fit in LDS -- many
+// dimensions with many components.
 //
-// One workgroup per (draw [, chunk of right-hand sides]).  The mixed covariance is
+// One workgroup per (draw, chunk of unit rows).  The mixed covariance is
 // built straight into LDS from X (never touching HBM), then factorised in place as
 // A = L' D L'^T with the right-hand sides appended as EXTRA ROWS of the lower
 // triangle:
 //
 //      rows 0..n-1   : the covariance (lower triangle)
 //      row  n        : y'          row n+1 : 1'
-//      rows n+2..    : chunk-specific rows (cross-correlations r(x_t)' for prediction,
-//                      unit vectors e_t' for the explicit inverse / gradient)
+//      rows n+2..    : the chunk's unit vectors e_t'
 //
 // Eliminating column k updates those rows exactly like matrix rows, so when the
 // factorisation ends each extra row holds z' = L'^-1 b (forward substitution for free)
 // and every quantity the reference needs is a D-weighted dot product of rows:
 //   logdet = sum log d_k,  b' A^-1 c = sum_k z'_b[k] z'_c[k] / d_k.
 // Replaces, per draw: Mixed.corr.matrix (HX:408-415), solve(R) (HX:454), beta.MLE
-// (HX:458), dmnorm (HX:460 / HX:570), factors (HX:604-613), predict.post (HX:655-673).
+// (HX:458), dmnorm (HX:460).
 //
 // Bound: neither HBM nor MFMA -- an n-step dependent chain (one barrier per column) over
 // LDS-resident data; algorithmic HBM traffic is the parameter row in and a few doubles out.
@@ -24,8 +25,6 @@
 namespace ccgp {
 
 namespace {
-
-enum { kRowsLoglik = 0, kRowsPredict = 1, kRowsUnit = 2 };
 
 struct SmallArgs {
   const double* X;
@@ -37,19 +36,14 @@ struct SmallArgs {
   double sigma2;
   int mode;
   double tau2;
-  // chunked extra rows
-  int kind;          // kRows*
-  const double* Xt;  // m x d test sites (kRowsPredict)
-  int m;             // total extra rows wanted (test points, or n for unit vectors)
+  // chunked unit rows
+  int m;             // total extra rows wanted (n)
   int mtile;         // extra rows per workgroup
-  int S;             // number of draws (leading dimension of mean/var)
   // outputs
   double* loglik;
   double* beta;
   int* status;
-  double* mean;
-  double* var;
-  double* Rinv;      // n x n (kRowsUnit, inverse)
+  double* Rinv;      // n x n (inverse)
   double* gpart;     // gradient partials [draw][chunk][P]
   int want_grad;
 };
@@ -59,7 +53,7 @@ __device__ inline double wave_sum(double v) {
   return __shfl(v, 0, 64);
 }
 
-// LDS carve (doubles):  A[ld*n] | xs[d*n] | us[K*n] | xt[d*mtile] | ut[K*mtile] | th[K*d] | w2[K] | red[16] | etab[256]
+// LDS carve: SmallCarve (small_layout.h)
 __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int n = a.n, d = a.d, K = a.K;
@@ -67,19 +61,13 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
   const int b = a.draw0 + blockIdx.x;
   const int chunk = blockIdx.y;
   const int t0 = chunk * a.mtile;
-  const int mt = a.kind == kRowsLoglik ? 0 : min(a.mtile, a.m - t0);
+  const int mt = min(a.mtile, a.m - t0);
   const int Rt = n + 2 + mt;
   const int ld = n + 2 + a.mtile;
 
-  double* A = smem;
-  double* xs = A + (size_t)ld * n;
-  double* us = xs + d * n;
-  double* xt = us + K * n;
-  double* ut = xt + d * a.mtile;
-  double* th = ut + K * a.mtile;
-  double* w2 = th + K * d;
-  double* red = w2 + K;
-  double* etab = red + 16;   // 2^(j/256) for exp_cov
+  const SmallCarve cv(n, d, K, a.mtile);
+  double *A = smem + cv.A, *xs = smem + cv.xs, *us = smem + cv.us, *th = smem + cv.th, *w2 = smem + cv.w2, *red = smem + cv.red;
+  double* etab = smem + cv.etab;   // 2^(j/256) for exp_cov
 
   if (CCGP_SMALL_EXP_TABLE) exp_table_load(etab, tid, 256);
   for (int e = tid; e < K * d; e += 256) th[e] = a.params[b + (size_t)(K + e) * a.ldp];
@@ -88,11 +76,6 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
     w2[tid] = w * w;
   }
   for (int e = tid; e < n * d; e += 256) xs[e] = a.X[e];  // xs[k*n + i]
-  if (a.kind == kRowsPredict)
-    for (int e = tid; e < mt * d; e += 256) {
-      int k = e / mt, t = e % mt;
-      xt[k * a.mtile + t] = a.Xt[(t0 + t) + (size_t)k * a.m];
-    }
   __syncthreads();
   for (int e = tid; e < K * n; e += 256) {
     int c = e / n, i = e % n;
@@ -100,13 +83,6 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
     for (int k = 0; k < d; ++k) { double v = xs[k * n + i]; s += v * v * th[c * d + k]; }
     us[e] = s;
   }
-  if (a.kind == kRowsPredict)
-    for (int e = tid; e < K * mt; e += 256) {
-      int c = e / mt, t = e % mt;
-      double s = 0.0;
-      for (int k = 0; k < d; ++k) { double v = xt[k * a.mtile + t]; s += v * v * th[c * d + k]; }
-      ut[c * a.mtile + t] = s;
-    }
   __syncthreads();
 
   double sw = 0.0;
@@ -132,17 +108,6 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
         v = a.y[j];
       } else if (i == n + 1) {
         v = 1.0;
-      } else if (a.kind == kRowsPredict) {
-        const int t = i - n - 2;
-        double acc = 0.0;
-        for (int c = 0; c < K; ++c) {
-          double s = 0.0;
-          for (int k = 0; k < d; ++k) s = fma(xs[k * n + j] * th[c * d + k], xt[k * a.mtile + t], s);
-          // corr.vec order: (theta'x^2 - 2 X Theta x) + u_i   (HX:373)
-          double dist = (ut[c * a.mtile + t] - 2.0 * s) + us[c * n + j];
-          acc += w2[c] * exp_small(dist, etab);
-        }
-        v = acc / sw;
       } else {
         v = (i - n - 2 + t0 == j) ? 1.0 : 0.0;
       }
@@ -210,33 +175,9 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
     }
   }
   __syncthreads();
-  if (a.kind == kRowsLoglik) return;
 
-  const double beta = red[0], s11 = red[1];
-  if (a.kind == kRowsPredict) {
-    // mean = beta + (z_y - beta z_1).w ; var = sigma2 (1 - w.w + (1 - z_1.w)^2 / (z_1.z_1))
-    for (int t = tid; t < mt; t += 256) {
-      double ww = 0.0, z1w = 0.0, zyw = 0.0;
-      if (!bad)
-        for (int k = 0; k < n; ++k) {
-          const double* col = A + (size_t)k * ld;
-          double rd = 1.0 / col[k];
-          double w = col[n + 2 + t];
-          ww = fma(w * rd, w, ww);
-          z1w = fma(col[n + 1] * rd, w, z1w);
-          zyw = fma(col[n] * rd, w, zyw);
-        }
-      double mean = beta + (zyw - beta * z1w);
-      double u = 1.0 - z1w;
-      double var = a.sigma2 * (1.0 - ww + u * u / s11);
-      if (bad) { mean = kNaN; var = kNaN; }
-      a.mean[b + (size_t)(t0 + t) * a.S] = mean;
-      a.var[b + (size_t)(t0 + t) * a.S] = var;
-    }
-    return;
-  }
-
-  // ---- kRowsUnit: back-substitute rows y, 1 and the unit rows: x = L'^-T D^-1 z' ---------
+  const double beta = red[0];
+  // ---- back-substitute rows y, 1 and the unit rows: x = L'^-T D^-1 z' ---------
   // thread r owns extra row n+r (r = 0: y, 1: ones, 2..: e_{t0+r-2}); in place, k downward.
   {
     const int nrows = 2 + mt;
@@ -304,57 +245,13 @@ __global__ void grad_reduce_kernel(const double* gpart, int nchunks, int P, int 
 
 }  // namespace
 
-size_t small_lds_bytes(int n, int d, int mtile) {
-  size_t dbl = (size_t)(n + 2 + mtile) * n + (size_t)d * n + (size_t)kMaxK * n +
-               (size_t)d * mtile + (size_t)kMaxK * mtile + (size_t)kMaxK * d + kMaxK + 16 + kExpTableDoubles;
-  return dbl * sizeof(double);
-}
-
-int small_pick_mtile(int n, int d, int m) {
-  const size_t budget = 150 * 1024;
-  int mt = m < 1 ? 1 : m;
-  if (mt > 256) mt = 256;
-  while (mt > 1 && small_lds_bytes(n, d, mt) > budget) --mt;
-  return mt;
-}
-
 static void small_launch(hipStream_t s, const SmallArgs& a, int ndraws, int nchunks) {
-  size_t lds = small_lds_bytes(a.n, a.d, a.kind == kRowsLoglik ? 0 : a.mtile);
+  size_t lds = small_lds_bytes(a.n, a.d, a.mtile);
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
     raise_lds_limit((const void*)small_kernel, "small_kernel");
   });
   hipLaunchKernelGGL(small_kernel, dim3(ndraws, nchunks), dim3(256), lds, s, a);
-}
-
-void launch_small_loglik(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
-                         int B, double sigma2, int mean_mode, double tau2, double* loglik,
-                         double* beta, int* status) {
-  SmallArgs a{};
-  a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.sigma2 = sigma2; a.mode = mean_mode; a.tau2 = tau2; a.kind = kRowsLoglik; a.mtile = 0;
-  a.loglik = loglik; a.beta = beta; a.status = status;
-  const int kMaxGrid = 1 << 20;
-  for (int b0 = 0; b0 < B; b0 += kMaxGrid) {
-    a.draw0 = b0;
-    small_launch(s, a, min(kMaxGrid, B - b0), 1);
-  }
-}
-
-void launch_small_predict(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
-                          int S, const double* Xtest, int m, double sigma2, double* mean,
-                          double* var, double* beta, int* status) {
-  SmallArgs a{};
-  a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.sigma2 = sigma2; a.mode = 0; a.kind = kRowsPredict; a.Xt = Xtest; a.m = m;
-  a.mtile = small_pick_mtile(n, d, m); a.S = S;
-  a.mean = mean; a.var = var; a.beta = beta; a.status = status;
-  const int nchunks = (m + a.mtile - 1) / a.mtile;
-  const int kMaxGrid = 1 << 20;
-  for (int b0 = 0; b0 < S; b0 += kMaxGrid) {
-    a.draw0 = b0;
-    small_launch(s, a, min(kMaxGrid, S - b0), nchunks);
-  }
 }
 
 void launch_small_inverse(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int draw,
@@ -363,7 +260,7 @@ void launch_small_inverse(hipStream_t s, const double* X, int n, int d, const do
   // the same elimination that yields R^-1 carries the rows y', 1': likelihood and beta of logpost
   // (HX:454-460) come out of this ONE factorisation (chunk 0 writes them)
   a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.sigma2 = sigma2; a.mode = 0; a.kind = kRowsUnit; a.m = n; a.mtile = small_pick_mtile(n, d, n);
+  a.sigma2 = sigma2; a.mode = 0; a.m = n; a.mtile = small_pick_mtile(n, d, n);
   a.draw0 = draw; a.Rinv = Rinv; a.status = status; a.loglik = loglik; a.beta = beta;
   small_launch(s, a, 1, (n + a.mtile - 1) / a.mtile);
 }
@@ -379,7 +276,7 @@ void launch_small_grad(hipStream_t s, const double* X, int n, int d, const doubl
                        int* status, double* gpart) {
   SmallArgs a{};
   a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.sigma2 = sigma2; a.mode = 0; a.kind = kRowsUnit; a.m = n; a.mtile = small_pick_mtile(n, d, n);
+  a.sigma2 = sigma2; a.mode = 0; a.m = n; a.mtile = small_pick_mtile(n, d, n);
   a.loglik = loglik; a.beta = beta; a.status = status; a.gpart = gpart; a.want_grad = 1;
   const int nchunks = (n + a.mtile - 1) / a.mtile;
   a.draw0 = 0;

@@ -1,0 +1,180 @@
+// LDS carves of the small-n evaluators (small_reg.hip, small.hip), each declared ONCE: the kernel takes its pointers from the
+// carve's offsets, the launcher its dynamic LDS size from the carve's `total`, and the routing predicates of capi.hip ask
+// whether `total` fits.  Plain C++ (no HIP include) so that a CPU test (tests/host_small/) runs the same declarations over
+// every shape the entry points accept.  All offsets (from the start of LDS) and totals are in doubles.
+#pragma once
+
+#include <cstddef>
+
+#if defined(__HIPCC__)
+#define CCGP_HD __host__ __device__
+#else
+#define CCGP_HD
+#endif
+
+// which exp the small-n evaluators use: 0 = polynomial, 1 = table in LDS (A/B: -DCCGP_SMALL_EXP_TABLE=1)
+#ifndef CCGP_SMALL_EXP_TABLE
+#define CCGP_SMALL_EXP_TABLE 0
+#endif
+
+namespace ccgp {
+
+constexpr int kSmallMaxN = 128;  // n <= this goes to the small-n tier: the register-resident evaluator, small.hip for two leftovers
+constexpr int kMaxD = 64;        // input dimensions supported by the covariance kernels
+constexpr int kMaxK = 8;         // component GPs per draw
+constexpr int kLdsBytes = 160 * 1024;
+constexpr int kExpTableDoubles = 256;
+constexpr int kSmallExpTable = CCGP_SMALL_EXP_TABLE ? kExpTableDoubles : 0;
+
+// does a carve fit the dynamic-LDS ceiling (raise_lds_limit) of per_cu workgroups on a CU?
+CCGP_HD constexpr bool lds_fits(size_t total, int per_cu = 1) { return sizeof(double) * total <= (size_t)kLdsBytes / per_cu - 64; }
+
+// ---- the factor a prediction keeps, in HBM (small_reg.hip) -------------------------------------------------------------
+//   hdr[8]: beta, s11, bad, sw | rd[NPF] | zy[NPF] | z1[NPF] | L'
+// L' in HBM: column-major packed (column k = rows k + 1 .. n - 1, contiguous: the elimination writes a column per step,
+// coalesced); site_solve_kernel re-lays it in LDS by row blocks of eight (lrect / ltri below).
+CCGP_HD constexpr int fac_npf(int n) { return (n + 7) / 8 * 8; }
+CCGP_HD constexpr int fac_col(int n, int k) { return k * (n - 1) - k * (k - 1) / 2; }   // first entry (row k + 1) of column k
+struct FacLayout {
+  int npf, rd, zy, z1, L, head, total;
+  CCGP_HD FacLayout(int n) {
+    npf = fac_npf(n);
+    rd = 8; zy = rd + npf; z1 = zy + npf; L = z1 + npf; head = L; total = (L + n * (n - 1) / 2 + 7) / 8 * 8;
+  }
+};
+// LDS image of L' for the blocked forward substitution: row block I (rows 8 I .. 8 I + 7) holds first its rectangle -- columns
+// k < 8 I, each column as the block's 8 row entries side by side (one FMA per row and column, eight independent chains, the
+// operands of a column in four ds_read_b128) -- then its 8 x 8 triangle row by row (row j: its j entries).
+// (block I starts at sum_{J<I} (64 J + 32) = 32 I^2 words)
+CCGP_HD constexpr int lrect(int I, int k, int j) { return 32 * I * I + k * 8 + j; }
+CCGP_HD constexpr int ltri(int I, int j, int c) { return 32 * I * I + 64 * I + j * (j - 1) / 2 + c; }
+
+// ---- small_reg_kernel<G, NB, NE, ., INV> -----------------------------------------------------------------------------
+//   etab | xs[d][n] | 256 / G^2 matrices of per_mat words | xt[d][G NE] (NE > 1) | one xs[d][n] per matrix (per-design)
+// (the inverse / gradient instances run one matrix per workgroup, so zmat's bump depends on nothing but the shape)
+// one matrix:  us[K][NP] | th[K][d] | w2[K] | colbuf[2][NP + G NE] | dvec[NP] | zb[2][NP] | slack[8] | tail
+//   tail, prediction (NE > 1): ut[K][G NE] | psum[3][G NE][G]
+//   tail, inverse / gradients: zmat[NP][NP + 2] behind a one-word bump to 16 bytes | part[4][kGradSlots]
+// Sized from the ACTUAL number of components and dimensions (round 3: sized for kMaxK / kMaxD before -- 4 KB of th[] per
+// matrix for a 2 x 4 table -- which left the prediction instances one workgroup per CU short).
+constexpr int kGradSlots = 28;   // accumulators of one pass of the gradient contraction: QG (1 + KG) <= 27
+struct RegCarve {
+  int etab, xs, mat0, per_mat, xt, xs_own;                          // from the start of LDS; mat0, xs_own: matrix 0's
+  int us, th, w2, colbuf, dvec, zb, slack, ut, psum, zmat, part;   // from the start of a matrix's block, mat0 + sub per_mat
+  size_t total;
+  CCGP_HD RegCarve(int G, int NB, int NE, bool inv, bool per_design, int n, int d, int K) {
+    const int NP = G * NB, XR = G * NE, MPW = 256 / (G * G);
+    etab = 0;                          // 2^(j/256) for exp_cov, shared by the workgroup
+    xs = kSmallExpTable;               // d x n, shared by the matrices of this workgroup
+    mat0 = xs + d * n;
+    us = 0;
+    th = us + K * NP;
+    w2 = th + K * d;
+    colbuf = w2 + K;                   // [2][NP + XR]
+    dvec = colbuf + 2 * (NP + XR);
+    zb = dvec + NP;                    // [2][NP]
+    slack = zb + 2 * NP;               // [8]: beta, 1'R^-1 1 for the epilogues
+    const int tail = slack + 8;
+    ut = tail;                         // [K][XR]    (prediction)
+    psum = ut + K * XR;                // [3][XR][G] (prediction)
+    // [NP][NP + 2] (inv): row t = L'^-1 e_t, columns scaled by d_c^-1/2; read two doubles at a time (ds_read_b128), and one
+    // matrix per workgroup there, so the block starts at mat0
+    zmat = tail + ((mat0 + tail) & 1);
+    part = zmat + NP * (NP + 2);       // [4][kGradSlots] wave partial sums of the gradient
+    per_mat = tail + (inv ? NP * (NP + 2) + 1 + 4 * kGradSlots : (NE > 1 ? K * XR + 3 * XR * G : 0));
+    xt = mat0 + MPW * per_mat;         // [d][XR], shared by the workgroup (prediction)
+    xs_own = xt + (NE > 1 && !inv ? d * XR : 0);   // per-design: matrix sub keeps its own copy at xs_own + sub d n
+    total = (size_t)xs_own + (per_design ? (size_t)MPW * d * n : 0);
+  }
+};
+inline size_t reg_lds_doubles(int G, int NB, int NE, bool inv, bool per_design, int n, int d, int K) {
+  return RegCarve(G, NB, NE, inv, per_design, n, d, K).total;
+}
+constexpr int kPredictNE = 4;   // extra row-blocks of the prediction instances: 30 (G = 8) / 62 (G = 16) sites per chunk
+// the 8 x 8 grid with up to 13 x 13 blocks per thread, four matrices per workgroup (64 < n <= 104, the likelihood)
+inline bool small_reg_fits8(int n, int d, int K, bool per_design) {
+  return lds_fits(reg_lds_doubles(8, (n + 7) / 8, 1, false, per_design, n, d, K));
+}
+
+// ---- site_corr_kernel<K>, `waves` batches of 64 test sites:  th[K][d] up to 8 | w2[8] | us[K][npf] | xs[K][d][npf] | xw[waves][d][64]
+struct SiteCorrCarve {
+  int th, w2, us, xs, xw;
+  size_t total;
+  CCGP_HD SiteCorrCarve(int npf /* fac_npf(n) */, int d, int K, int waves) {
+    th = 0;
+    w2 = th + (K * d + 7) / 8 * 8;
+    us = w2 + 8;
+    xs = us + K * npf;
+    xw = xs + K * d * npf;                     // wave w's test sites: xw + w d 64, [k][lane]
+    total = (size_t)xw + (size_t)waves * d * 64;
+  }
+};
+// ---- site_solve_kernel<fac_npf(n)>:  F: the factor block's head as it is in HBM | L' in row blocks of 8 (lrect / ltri) | slack[8]
+struct SiteSolveCarve {
+  int F, L;
+  size_t total;
+  CCGP_HD SiteSolveCarve(int n) {
+    const int nbl = fac_npf(n) / 8;
+    F = 0;
+    L = FacLayout(n).head;
+    total = (size_t)L + 32 * nbl * nbl + 8;
+  }
+};
+
+// ---- small_kernel, mtile unit rows per workgroup:
+//   A[n + 2 + mtile][n] | xs[d][n] | us[K][n] | reserved[(d + K) mtile] | th[K][d] | w2[K] | red[16] | etab[256]
+// The reserved words held the test sites of the in-LDS prediction, which the register scheme replaced; they stay in the
+// size because mtile is picked from it and the chunking of the gradient (hence its bits) and the routes follow from mtile.
+// The host sizes for K = kMaxK; the kernel carves with its own K, which ends no later.
+struct SmallCarve {
+  int A, xs, us, reserved, th, w2, red, etab;
+  size_t total;
+  CCGP_HD SmallCarve(int n, int d, int K, int mtile) {
+    A = 0;
+    xs = A + (n + 2 + mtile) * n;
+    us = xs + d * n;
+    reserved = us + K * n;
+    th = reserved + d * mtile + K * mtile;
+    w2 = th + K * d;
+    red = w2 + K;
+    etab = red + 16;                           // 2^(j/256) for exp_cov
+    total = (size_t)etab + kExpTableDoubles;
+  }
+};
+inline size_t small_lds_bytes(int n, int d, int mtile) { return sizeof(double) * SmallCarve(n, d, kMaxK, mtile).total; }
+inline int small_pick_mtile(int n, int d, int m) {
+  const size_t budget = 150 * 1024;
+  int mt = m < 1 ? 1 : m;
+  if (mt > 256) mt = 256;
+  while (mt > 1 && small_lds_bytes(n, d, mt) > budget) --mt;
+  return mt;
+}
+
+// ---- routing predicates (capi.hip) -------------------------------------------------------------------------------------
+// the register-resident evaluator: likelihood, log det of per-design matrices, prediction by the extra-row scheme
+inline bool small_reg_supported(int n, int d, int K, bool per_design = false, bool predict = false) {
+  if (n > 128) return false;
+  const int G = n <= 64 ? 8 : 16;
+  return lds_fits(reg_lds_doubles(G, (n + G - 1) / G, predict ? kPredictNE : 1, false, per_design, n, d, K));
+}
+// kept-factor prediction (round 5; else the extra-row scheme of rounds 2 - 4): the factorising instance on the 8 x 8 grid
+// and two workgroups per CU of each site kernel
+inline bool small_reg_sites_supported(int n, int d, int K) {
+  if (n > 104 || K > 3) return false;
+  return small_reg_fits8(n, d, K, false) && lds_fits(SiteSolveCarve(n).total, 2) &&
+         lds_fits(SiteCorrCarve(fac_npf(n), d, K, 4).total, 2);
+}
+// scratch per draw (bytes): the factor block + the correlation vectors of its ceil(m / 64) site batches
+inline size_t small_reg_sites_scratch(int n, int d, int K, int m) {
+  (void)d; (void)K;
+  return sizeof(double) * ((size_t)FacLayout(n).total + (size_t)((m + 63) / 64) * fac_npf(n) * 64);
+}
+// solve(R) of one draw and the analytic gradient (INV = 1, 2); the design gradient (INV = 3) keeps its design behind the matrix
+inline bool small_reg_inverse_supported(int n, int d, int K, bool per_design = false) {
+  if (n > 128) return false;
+  const int NB = (n + 15) / 16;
+  return lds_fits(reg_lds_doubles(16, NB, NB + 1, true, per_design, n, d, K));
+}
+inline bool small_reg_design_grad_supported(int n, int d, int K) { return small_reg_inverse_supported(n, d, K, true); }
+
+}  // namespace ccgp

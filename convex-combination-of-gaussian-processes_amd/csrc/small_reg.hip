@@ -75,29 +75,7 @@ struct RegArgs {
 // r(x_t) with lane = test site; site_solve_kernel then does the forward substitution w' = L'^-1 r and predict.post's arithmetic,
 // again lane = site, every matrix operand a broadcast LDS read.  Same operations in the same order per (draw, site) as the
 // extra-row scheme, hence the same bits.
-//   hdr[8]: beta, s11, bad, sw | rd[NPF] | zy[NPF] | z1[NPF] | L'
-// L' in HBM: column-major packed (column k = rows k + 1 .. n - 1, contiguous: the elimination writes a column per step,
-// coalesced); predict_sites_kernel re-lays it in LDS by row blocks of eight (lrect / ltri below).
-__host__ __device__ constexpr int fac_npf(int n) { return (n + 7) / 8 * 8; }
-__host__ __device__ constexpr int fac_col(int n, int k) { return k * (n - 1) - k * (k - 1) / 2; }   // first entry (row k + 1) of column k
-struct FacLayout {
-  int npf, rd, zy, z1, L, head, total;
-  __host__ __device__ FacLayout(int n) {
-    npf = fac_npf(n);
-    rd = 8; zy = rd + npf; z1 = zy + npf; L = z1 + npf; head = L; total = (L + n * (n - 1) / 2 + 7) / 8 * 8;
-  }
-};
-
-// doubles of LDS per matrix, from the ACTUAL number of components and dimensions (round 3: sized for kMaxK / kMaxD
-// before -- 4 KB of th[] per matrix for a 2 x 4 table -- which left the prediction instances one workgroup per CU short)
-constexpr int kGradSlots = 28;   // accumulators of one pass of the gradient contraction: QG (1 + KG) <= 27
-__host__ __device__ constexpr int kPerMat(int NP, int G, int NE, int K, int d, bool inv = false) {
-  return K * NP /*us*/ + K * d /*th*/ + K /*w2*/ + 2 * (NP + G * NE) /*colbuf*/ + NP /*dvec*/ +
-         2 * NP /*zb*/ + 8 +
-         (inv ? NP * (NP + 2) + 1 /*Z, row stride NP + 2, 16-byte aligned*/ + 4 * kGradSlots /*wave partial sums of the gradient*/
-              : (NE > 1 ? K * G * NE /*ut*/ + 3 * G * G * NE /*partial sums*/ : 0));
-}
-constexpr int kSmallExpTable = CCGP_SMALL_EXP_TABLE ? kExpTableDoubles : 0;
+// (FacLayout, fac_col, lrect / ltri: small_layout.h, with the LDS carve of every kernel here)
 
 template <int G>
 __device__ __forceinline__ void mat_sync() {
@@ -150,28 +128,28 @@ void small_reg_kernel(RegArgs a) {
   // correlation kernel's waves issuing beside it on the same SIMDs: it goes first
   if constexpr (FAC) __builtin_amdgcn_s_setprio(3);
   const int n = a.n, d = a.d, K = a.K;
-  const int PM = kPerMat(NP, G, NE, K, d, INV != 0);
   const int tid = threadIdx.x, sub = tid / TPM, lt = tid % TPM;
   const int ty = lt % G, tx = lt / G;
   int b = a.draw0 + blockIdx.x * MPW + sub;
   const bool valid = b < a.draw0 + a.B;
   if (!valid) b = a.draw0 + a.B - 1;   // keep the wave alive (shared loads, barriers); results discarded
 
-  double* etab = smem;                        // 2^(j/256) for exp_cov, shared by the workgroup
-  double* xs = etab + kSmallExpTable;         // d x n, shared by the matrices of this workgroup
-  double* mine = xs + d * n + (size_t)sub * PM;
-  double* us = mine;
-  double* th = us + K * NP;
-  double* w2 = th + K * d;
-  double* colbuf = w2 + K;                    // [2][NP + XR]
-  double* dvec = colbuf + 2 * (NP + XR);
-  double* zb = dvec + NP;                     // [2][NP]
-  double* ut = zb + 2 * NP + 8;               // [K][XR]   (NE > 1, prediction)
-  double* psum = ut + K * XR;                 // [3][XR][G] (NE > 1, prediction)
-  double* zmat = zb + 2 * NP + 8;             // [NP][NP + 2] (INV): row t = L'^-1 e_t, columns scaled by d_c^-1/2
-  zmat += (zmat - smem) & 1;                  // its rows are read two doubles at a time (ds_read_b128)
+  const RegCarve cv(G, NB, NE, INV != 0, false, n, d, K);
+  double* etab = smem + cv.etab;              // 2^(j/256) for exp_cov, shared by the workgroup
+  double* xs = smem + cv.xs;                  // d x n, shared by the matrices of this workgroup
+  double* mine = smem + cv.mat0 + (size_t)sub * cv.per_mat;
+  double* us = mine + cv.us;
+  double* th = mine + cv.th;
+  double* w2 = mine + cv.w2;
+  double* colbuf = mine + cv.colbuf;          // [2][NP + XR]
+  double* dvec = mine + cv.dvec;
+  double* zb = mine + cv.zb;                  // [2][NP]
+  double* slack = mine + cv.slack;            // beta, 1'R^-1 1 for the epilogues
+  double* ut = mine + cv.ut;                  // [K][XR]   (NE > 1, prediction)
+  double* psum = mine + cv.psum;              // [3][XR][G] (NE > 1, prediction)
+  double* zmat = mine + cv.zmat;              // [NP][NP + 2] (INV): row t = L'^-1 e_t, columns scaled by d_c^-1/2
+  double* xt = smem + cv.xt;                  // [d][XR], shared by the workgroup (NE > 1)
   const int t0 = blockIdx.y * MT;             // first test site of this chunk
-  double* xt = xs + (size_t)d * n + (size_t)MPW * PM;     // [d][XR], shared by the workgroup (NE > 1)
 
   const int pb = a.shared_params ? 0 : b;
   if (CCGP_SMALL_EXP_TABLE) exp_table_load(etab, tid, 256);
@@ -179,7 +157,7 @@ void small_reg_kernel(RegArgs a) {
     for (int e = tid; e < n * d; e += 256) xs[e] = a.X[e];
   } else {
     // per-evaluation designs: each matrix keeps its own copy right behind the shared slot
-    xs = xs + (size_t)d * n + (size_t)MPW * PM + (size_t)sub * d * n;     // (never combined with NE > 1)
+    xs = smem + cv.xs_own + (size_t)sub * d * n;
     for (int e = lt; e < n * d; e += TPM) xs[e] = a.X[(size_t)b * a.x_stride + e];
   }
   for (int e = lt; e < K * d; e += TPM) th[e] = a.params[pb + (size_t)(K + e) * a.ldp];
@@ -437,8 +415,8 @@ void small_reg_kernel(RegArgs a) {
     }
     if (bad) { ll = kNaN; beta = kNaN; }
     if (lt == 0) {
-      zb[2 * NP] = beta;      // for the prediction epilogue (slack words behind zb)
-      zb[2 * NP + 1] = s11;
+      slack[0] = beta;      // for the epilogues
+      slack[1] = s11;
     }
     if constexpr (FAC) {
       if (valid) {
@@ -514,8 +492,8 @@ void small_reg_kernel(RegArgs a) {
       // over the pairs, and a pass carries QG components x KG dimensions of accumulators -- K = 2, d = 4 (Heat Exchanger)
       // or K = 3, d = 5 is ONE pass; round 3 walked the pairs K ceil(d / 16) times, recomputing R^-1 every time.
       double* alpha = colbuf;                                  // [NP]   (the column buffers are free now)
-      double* part = zmat + NP * ZS;                           // [4][kGradSlots] wave partial sums
-      const double beta = zb[2 * NP];
+      double* part = mine + cv.part;                           // [4][kGradSlots] wave partial sums
+      const double beta = slack[0];
       double* resid = zb;                                      // (z_y - beta z_1)_c d_c^-1/2 in place of z_y
       for (int c = lt; c < NP; c += TPM) resid[c] = c < n ? (zb[c] - beta * zb[NP + c]) * dvec[c] : 0.0;
       mat_sync<G>();
@@ -685,7 +663,7 @@ void small_reg_kernel(RegArgs a) {
       psum[(2 * XR + ridx) * G + tx] = zyw;
     }
     mat_sync<G>();
-    const double beta = zb[2 * NP], s11 = zb[2 * NP + 1];
+    const double beta = slack[0], s11 = slack[1];
     for (int ridx = 2 + lt; ridx < XR; ridx += TPM) {
       const int t = t0 + ridx - 2;
       if (t >= a.m || !valid) continue;
@@ -706,44 +684,48 @@ void small_reg_kernel(RegArgs a) {
   }
 }
 
-template <int G, int NB, int NE>
-size_t reg_lds_bytes(const RegArgs& a) {
-  constexpr int MPW = 256 / (G * G);
-  return sizeof(double) * (kSmallExpTable + (size_t)a.d * a.n + (size_t)MPW * kPerMat(G * NB, G, NE, a.K, a.d) +
-                           (a.x_stride ? (size_t)MPW * a.d * a.n : 0) + (NE > 1 ? (size_t)a.d * G * NE : 0));
+// calls f(std::integral_constant<int, I>{}) for the I in [Lo, Hi] nearest to v: a run-time block count picks the instance
+template <int Lo, int Hi, class F>
+void pick(int v, F&& f) {
+  if constexpr (Lo == Hi) f(std::integral_constant<int, Lo>{});
+  else if (v <= Lo) f(std::integral_constant<int, Lo>{});
+  else pick<Lo + 1, Hi>(v, f);
+}
+
+// the arguments every launcher shares: one design, profile-beta likelihood of draw 0 unless the launcher says otherwise
+RegArgs reg_args(const double* X, int n, int d, const double* y, DrawView dv) {
+  RegArgs a{};
+  a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
+  a.draw0 = 0; a.B = 1; a.sigma2 = 1.0; a.mode = 0; a.tau2 = 0.0;
+  return a;
 }
 
 template <int G, int NB, int NE = 1>
 void launch_one(hipStream_t s, const RegArgs& a) {
   constexpr int MPW = 256 / (G * G);
-  const size_t lds = reg_lds_bytes<G, NB, NE>(a);
+  const size_t lds = sizeof(double) * reg_lds_doubles(G, NB, NE, false, a.x_stride != 0, a.n, a.d, a.K);
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
     raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false>, "small_reg_kernel");
     if constexpr (NE == 1) raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, true>, "small_reg_kernel<full>");
   });
-  const bool full = NE == 1 && a.n == G * NB && a.x_stride == 0 && !a.fac;
+  void (*kernel)(RegArgs) = small_reg_kernel<G, NB, NE, false>;
+  if constexpr (NE == 1) {
+    if (a.fac) {   // the likelihood instantiation that keeps its factor for site_solve_kernel
+      static unsigned long long fac_mask = 0;
+      once_per_device(fac_mask, [] { raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false, 0, true>, "small_reg_kernel<fac>"); });
+      kernel = small_reg_kernel<G, NB, NE, false, 0, true>;
+    } else if (a.n == G * NB && a.x_stride == 0) {
+      kernel = small_reg_kernel<G, NB, NE, true>;
+    }
+  }
   const int chunks = NE > 1 ? (a.m + (G * NE - 2) - 1) / (G * NE - 2) : 1;
   const int kMaxGrid = 1 << 20;
   RegArgs c = a;
   for (int b0 = 0; b0 < a.B; b0 += kMaxGrid * MPW) {
     c.draw0 = a.draw0 + b0;
     c.B = a.B - b0 < kMaxGrid * MPW ? a.B - b0 : kMaxGrid * MPW;
-    if constexpr (NE == 1) {
-      if (a.fac) {   // the likelihood instantiation that keeps its factor for predict_sites_kernel
-        static unsigned long long fac_mask = 0;
-        once_per_device(fac_mask, [] { raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false, 0, true>, "small_reg_kernel<fac>"); });
-        hipLaunchKernelGGL((small_reg_kernel<G, NB, NE, false, 0, true>), dim3((c.B + MPW - 1) / MPW, 1), dim3(256), lds, s, c);
-        continue;
-      }
-    }
-    if constexpr (NE == 1) {
-      if (full) {
-        hipLaunchKernelGGL((small_reg_kernel<G, NB, NE, true>), dim3((c.B + MPW - 1) / MPW, chunks), dim3(256), lds, s, c);
-        continue;
-      }
-    }
-    hipLaunchKernelGGL((small_reg_kernel<G, NB, NE, false>), dim3((c.B + MPW - 1) / MPW, chunks), dim3(256), lds, s, c);
+    hipLaunchKernelGGL(kernel, dim3((c.B + MPW - 1) / MPW, chunks), dim3(256), lds, s, c);
   }
 }
 
@@ -779,11 +761,9 @@ __global__ __launch_bounds__(256, 4) void site_corr_kernel(SiteArgs a) {
   const int b = blockIdx.y, nbatch = a.nbatch, npf = a.npf;
   const int batch = blockIdx.x * (nthr >> 6) + wave;
   const int n = a.n, d = a.d, m = a.m, gb = a.draw0 + b;
-  double* th = smem;                                 // [KC][d]
-  double* w2 = th + (KC * d + 7) / 8 * 8;            // [8]
-  double* us = w2 + 8;                               // [KC][npf]
-  double* xs = us + KC * npf;                        // [KC][d][npf]
-  double* xw = xs + (size_t)KC * d * npf + (size_t)wave * d * 64;   // this wave's test sites, [k][lane]
+  const SiteCorrCarve cv(npf, d, KC, nthr >> 6);
+  double *th = smem + cv.th, *w2 = smem + cv.w2, *us = smem + cv.us, *xs = smem + cv.xs;
+  double* xw = smem + cv.xw + (size_t)wave * d * 64; // this wave's test sites, [k][lane]
   for (int e = tid; e < KC * d; e += nthr) th[e] = a.params[gb + (size_t)(KC + e) * a.ldp];
   if (tid < KC) { const double w = a.params[gb + (size_t)tid * a.ldp]; w2[tid] = w * w; }
   const int t = batch * 64 + lane;
@@ -848,19 +828,6 @@ __global__ __launch_bounds__(256, 4) void site_corr_kernel(SiteArgs a) {
     }
   }
 }
-size_t site_corr_lds_bytes(int n, int d, int K, int waves) {
-  const int npf = fac_npf(n);
-  return sizeof(double) * ((size_t)(K * d + 7) / 8 * 8 + 8 + (size_t)K * npf + (size_t)K * d * npf + (size_t)waves * d * 64);
-}
-
-// LDS image of L' for the blocked forward substitution: row block I (rows 8 I .. 8 I + 7) holds first its rectangle -- columns
-// k < 8 I, each column as the block's 8 row entries side by side (one FMA per row and column, eight independent chains, the
-// operands of a column in four ds_read_b128) -- then its 8 x 8 triangle row by row (row j: its j entries).
-// (block I starts at sum_{J<I} (64 J + 32) = 32 I^2 words)
-__host__ __device__ constexpr int lrect(int I, int k, int j) { return 32 * I * I + k * 8 + j; }
-__host__ __device__ constexpr int ltri(int I, int j, int c) { return 32 * I * I + 64 * I + j * (j - 1) / 2 + c; }
-template <int NPF>
-constexpr size_t site_solve_lds_doubles(int n) { return (size_t)FacLayout(n).head + 32 * (NPF / 8) * (NPF / 8) + 8; }
 
 // One workgroup per (draw, group of up to four batches of 64 test sites), one wave per batch.  The draw's factor block comes
 // into LDS once per workgroup (one linear coalesced stream; L' re-laid by row blocks) and every factor operand is then a
@@ -884,8 +851,8 @@ __global__ __launch_bounds__(256, NPF <= 48 ? 3 : 2) void site_solve_kernel(Site
   const int n = a.n, m = a.m;
   const FacLayout fl(n);
   const double* __restrict__ Fg = a.fac + (size_t)b * a.fac_stride;
-  double* F = smem;                                  // the block's head as it is in HBM ...
-  double* L = smem + fl.head;                        // ... and L' in row blocks of 8 (lrect / ltri)
+  const SiteSolveCarve cv(n);
+  double *F = smem + cv.F, *L = smem + cv.L;                     // the block's head as it is in HBM, and L' in row blocks of 8
   for (int e = tid; e < fl.head; e += nthr) F[e] = Fg[e];
   {
     // L' arrives as one linear, coalesced stream (four loads in flight per thread); a thread finds the column of its
@@ -1004,7 +971,7 @@ static dim3 site_grid(int nbatch, int ns, int* wpb) {
 static void launch_site_corr(hipStream_t s, const SiteArgs& a, int ns) {
   int wpb;
   const dim3 grid = site_grid(a.nbatch, ns, &wpb), block(64 * wpb);
-  const size_t lds = site_corr_lds_bytes(a.n, a.d, a.K, wpb);
+  const size_t lds = sizeof(double) * SiteCorrCarve(a.npf, a.d, a.K, wpb).total;
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
     raise_lds_limit((const void*)site_corr_kernel<1>, "site_corr_kernel");
@@ -1015,54 +982,18 @@ static void launch_site_corr(hipStream_t s, const SiteArgs& a, int ns) {
   else if (a.K == 2) hipLaunchKernelGGL(site_corr_kernel<2>, grid, block, lds, s, a);
   else hipLaunchKernelGGL(site_corr_kernel<3>, grid, block, lds, s, a);
 }
-template <int NPF>
 static void launch_site_solve(hipStream_t s, const SiteArgs& a, int ns) {
   int wpb;
   const dim3 grid = site_grid(a.nbatch, ns, &wpb), block(64 * wpb);
-  static unsigned long long attr_mask = 0;
-  once_per_device(attr_mask, [] { raise_lds_limit((const void*)site_solve_kernel<NPF>, "site_solve_kernel"); });
-  hipLaunchKernelGGL(site_solve_kernel<NPF>, grid, block, sizeof(double) * site_solve_lds_doubles<NPF>(a.n), s, a);
+  pick<1, 13>(a.npf / 8, [&](auto nbl) {
+    constexpr int NPF = 8 * decltype(nbl)::value;
+    static unsigned long long attr_mask = 0;
+    once_per_device(attr_mask, [] { raise_lds_limit((const void*)site_solve_kernel<NPF>, "site_solve_kernel"); });
+    hipLaunchKernelGGL(site_solve_kernel<NPF>, grid, block, sizeof(double) * SiteSolveCarve(a.n).total, s, a);
+  });
 }
 
-}  // namespace
-
-// Can predict.post tables of this shape go through the kept-factor scheme (else: the extra-row scheme of rounds 2 - 4)?
-bool small_reg_sites_supported(int n, int d, int K) {
-  if (n > 104 || K > 3) return false;
-  const int nb8 = (n + 7) / 8, npf = fac_npf(n);
-  return sizeof(double) * (kSmallExpTable + (size_t)d * n + (size_t)4 * kPerMat(8 * nb8, 8, 1, K, d)) <= (size_t)kLdsBytes - 64 &&
-         sizeof(double) * ((size_t)FacLayout(n).head + 32 * (npf / 8) * (npf / 8) + 8) <= (size_t)kLdsBytes / 2 - 64 &&   // two per CU
-         site_corr_lds_bytes(n, d, K, 4) <= (size_t)kLdsBytes / 2 - 64;
-}
-// scratch per draw (bytes): the factor block + the correlation vectors of its ceil(m / 64) site batches
-size_t small_reg_sites_scratch(int n, int d, int K, int m) {
-  (void)d; (void)K;
-  return sizeof(double) * ((size_t)FacLayout(n).total + (size_t)((m + 63) / 64) * fac_npf(n) * 64);
-}
-
-constexpr int kPredictNE = 4;   // extra row-blocks of the prediction instances: 30 (G = 8) / 62 (G = 16) sites per chunk
-
-// ---- explicit inverse of ONE draw's matrix (solve(R), HX:454) on the register-resident scheme ------------------
-template <int NB>
-static size_t inv_lds_bytes(int n, int d, int K) {
-  return sizeof(double) * (kSmallExpTable + (size_t)d * n + (size_t)kPerMat(16 * NB, 16, NB + 1, K, d, true));
-}
-
-bool small_reg_inverse_supported(int n, int d, int K) {
-  if (n > 128) return false;
-  const int NB = (n + 15) / 16;
-  return sizeof(double) * (kSmallExpTable + (size_t)d * n + (size_t)kPerMat(16 * NB, 16, NB + 1, K, d, true)) <=
-         (size_t)kLdsBytes - 64;
-}
-
-// the design gradient (INV = 3) keeps its design in LDS behind the matrix: d n doubles more
-bool small_reg_design_grad_supported(int n, int d, int K) {
-  if (n > 128) return false;
-  const int NB = (n + 15) / 16;
-  return sizeof(double) * (kSmallExpTable + (size_t)2 * d * n + (size_t)kPerMat(16 * NB, 16, NB + 1, K, d, true)) <=
-         (size_t)kLdsBytes - 64;
-}
-
+// ---- explicit inverse of ONE draw's matrix (solve(R), HX:454), gradient, design gradient: one workgroup per matrix ------
 template <int NB, int INV>
 static void launch_inv(hipStream_t s, const RegArgs& a) {
   static unsigned long long attr_mask = 0;
@@ -1070,7 +1001,7 @@ static void launch_inv(hipStream_t s, const RegArgs& a) {
     raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, INV>,
                     INV == 1 ? "small_reg_kernel<inverse>" : INV == 2 ? "small_reg_kernel<gradient>" : "small_reg_kernel<design gradient>");
   });
-  const size_t lds = inv_lds_bytes<NB>(a.n, a.d, a.K) + (a.x_stride ? sizeof(double) * (size_t)a.d * a.n : 0);
+  const size_t lds = sizeof(double) * reg_lds_doubles(16, NB, NB + 1, true, a.x_stride != 0, a.n, a.d, a.K);
   const int kMaxGrid = 1 << 20;
   RegArgs c = a;
   for (int b0 = 0; b0 < a.B; b0 += kMaxGrid) {
@@ -1079,88 +1010,84 @@ static void launch_inv(hipStream_t s, const RegArgs& a) {
     hipLaunchKernelGGL((small_reg_kernel<16, NB, NB + 1, false, INV>), dim3(c.B, 1), dim3(256), lds, s, c);
   }
 }
-
 template <int INV>
 static void dispatch_inv(hipStream_t s, const RegArgs& a) {
-  switch ((a.n + 15) / 16) {
-    case 1: launch_inv<1, INV>(s, a); break;
-    case 2: launch_inv<2, INV>(s, a); break;
-    case 3: launch_inv<3, INV>(s, a); break;
-    case 4: launch_inv<4, INV>(s, a); break;
-    case 5: launch_inv<5, INV>(s, a); break;
-    case 6: launch_inv<6, INV>(s, a); break;
-    case 7: launch_inv<7, INV>(s, a); break;
-    default: launch_inv<8, INV>(s, a); break;
-  }
+  pick<1, 8>((a.n + 15) / 16, [&](auto nb) { launch_inv<decltype(nb)::value, INV>(s, a); });
 }
+
+template <int NE = 1>
+static void dispatch(hipStream_t s, const RegArgs& a) {
+  const int n = a.n;
+  // A handful of evaluations (Metro's one proposal per logpost call, a speculative batch of a few candidates) is a
+  // LATENCY problem: one wave per matrix leaves the chip empty and runs the whole elimination on 64 lanes; the
+  // 16 x 16 grid puts four waves on each matrix (n = 64, one evaluation: 41 -> 25 us of kernel time).
+  // (with the factor kept -- prediction -- the four-wave form up to 2048 draws: its one factorisation per draw is the critical
+  // path of the call and a wave per SIMD is all that 1000 draws fill anyway)
+  const bool wide = NE == 1 && a.x_stride == 0 && a.B <= (a.fac ? CCGP_FAC_WIDE_MAX : 64);
+  if constexpr (NE == 1) {
+    // 64 < n <= 104 (BASELINE config 3: maximin-100): still ONE WAVE per matrix on the 8 x 8 grid, with up to 13 x 13
+    // blocks per thread (two waves per SIMD: up to 256 VGPRs) -- at n = 100 1.68 x the minimal FMAs instead of the
+    // 2.75 x of the 16 x 16 grid at NB = 7, no s_barrier, and the per-column overhead (pivot, reciprocal, column
+    // broadcast) is paid by one wave instead of four: 25.7 k -> ~10 k VALU instructions per evaluation, 6.06 -> 5.07 ms
+    // per 103 680 evaluations on the same box, same bits (profiles/r04).  CCGP_OPT_SMALL_GRID16: the 16 x 16 grid (A/B).
+    if (n > 64 && n <= 104 && !wide && small_reg_fits8(n, a.d, a.K, a.x_stride != 0) && !a.grid16) {
+      pick<9, 13>((n + 7) / 8, [&](auto nb) { launch_one<8, decltype(nb)::value, NE>(s, a); });
+      return;
+    }
+  }
+  if (n <= 64 && !wide) pick<1, 8>((n + 7) / 8, [&](auto nb) { launch_one<8, decltype(nb)::value, NE>(s, a); });
+  // (the prediction instances only come here with n > 64)
+  else pick<(NE == 1 ? 1 : 5), 8>((n + 15) / 16, [&](auto nb) { launch_one<16, decltype(nb)::value, NE>(s, a); });
+}
+
+}  // namespace
 
 void launch_small_reg_inverse(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int draw,
                               double sigma2, double* Rinv, double* loglik, double* beta, int* status) {
-  RegArgs a{};
-  a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.draw0 = draw; a.B = 1; a.sigma2 = sigma2; a.mode = 0; a.tau2 = 0.0;
-  a.loglik = loglik; a.beta = beta; a.status = status; a.Rinv = Rinv; a.m = 0; a.S = 1;
+  RegArgs a = reg_args(X, n, d, y, dv);
+  a.draw0 = draw; a.sigma2 = sigma2;
+  a.loglik = loglik; a.beta = beta; a.status = status; a.Rinv = Rinv;
   dispatch_inv<1>(s, a);
 }
 
 // d loglik / d params for B draws (ccgp_loglik_grad_batch, n <= 128): one workgroup per draw on the same scheme
 void launch_small_reg_grad(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B,
                            double sigma2, double* loglik, double* beta, double* grad, int* status) {
-  RegArgs a{};
-  a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.draw0 = 0; a.B = B; a.sigma2 = sigma2; a.mode = 0; a.tau2 = 0.0;
-  a.loglik = loglik; a.beta = beta; a.status = status; a.grad = grad; a.Btot = B; a.m = 0; a.S = 1;
+  RegArgs a = reg_args(X, n, d, y, dv);
+  a.B = B; a.sigma2 = sigma2;
+  a.loglik = loglik; a.beta = beta; a.status = status; a.grad = grad; a.Btot = B;
   dispatch_inv<2>(s, a);
+}
+
+// log det R_mixed for B candidate designs (Xs = B blocks of n x d, column-major each) under ONE parameter row
+static RegArgs design_args(const double* Xs, int n, int d, DrawView dv, int B, double* logdet, int* status) {
+  RegArgs a = reg_args(Xs, n, d, Xs, dv);   // the right-hand-side rows are not used; any n readable doubles will do
+  a.B = B; a.status = status; a.x_stride = (size_t)n * d; a.shared_params = 1; a.logdet = logdet;
+  return a;
 }
 
 // d log det R_mixed / d X for B candidate designs sharing one parameter row (ccgp_mixed_logdet_grad_designs, n <= 128):
 // one workgroup per design; log det as launch_small_reg_logdet_designs computes it, the gradient of rows >= n_fixed in dgrad
 void launch_small_reg_logdet_grad_designs(hipStream_t s, const double* Xs, int n, int d, DrawView dv, int B, int n_fixed,
                                           double* logdet, double* dgrad, int* status) {
-  RegArgs a{};
-  a.X = Xs; a.y = Xs;   // the right-hand-side rows are not used; any n readable doubles will do
-  a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.draw0 = 0; a.B = B; a.sigma2 = 1.0; a.mode = 0; a.tau2 = 0.0;
-  a.status = status; a.x_stride = (size_t)n * d; a.shared_params = 1; a.logdet = logdet;
-  a.dgrad = dgrad; a.n_fixed = n_fixed; a.m = 0; a.S = 1;
+  RegArgs a = design_args(Xs, n, d, dv, B, logdet, status);
+  a.dgrad = dgrad; a.n_fixed = n_fixed;
   dispatch_inv<3>(s, a);
 }
-
-bool small_reg_supported(int n, int d, int K, bool per_design, bool predict) {
-  if (n > 128) return false;
-  const int G = n <= 64 ? 8 : 16;
-  const int NB = (n + G - 1) / G;
-  const int MPW = 256 / (G * G);
-  const int NE = predict ? kPredictNE : 1;
-  return sizeof(double) * (kSmallExpTable + (size_t)d * n + (size_t)MPW * kPerMat(G * NB, G, NE, K, d) +
-                           (per_design ? (size_t)MPW * d * n : 0) + (predict ? (size_t)d * G * NE : 0)) <=
-         (size_t)kLdsBytes - 64;
-}
-
-template <int NE = 1>
-static void dispatch(hipStream_t s, const RegArgs& a);
 
 void launch_small_reg_loglik(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                              int B, double sigma2, int mean_mode, double tau2, double* loglik,
                              double* beta, int* status, bool grid16) {
-  RegArgs a{};
-  a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.draw0 = 0; a.B = B; a.sigma2 = sigma2; a.mode = mean_mode; a.tau2 = tau2;
+  RegArgs a = reg_args(X, n, d, y, dv);
+  a.B = B; a.sigma2 = sigma2; a.mode = mean_mode; a.tau2 = tau2;
   a.loglik = loglik; a.beta = beta; a.status = status; a.grid16 = grid16;
   dispatch(s, a);
 }
 
-// log det R_mixed for B candidate designs (Xs = B blocks of n x d, column-major each) under ONE
-// parameter row: Entropy = -det(R) (BSQ:856-861), Augmented.Mixed.Entropy = -det(R_all)/det(R_old)
-// (BSQ:869-877, Schur complement).
+// Entropy = -det(R) (BSQ:856-861), Augmented.Mixed.Entropy = -det(R_all)/det(R_old) (BSQ:869-877, Schur complement)
 void launch_small_reg_logdet_designs(hipStream_t s, const double* Xs, int n, int d, DrawView dv, int B,
                                      double* logdet, int* status) {
-  RegArgs a{};
-  a.X = Xs; a.y = Xs;   // the right-hand-side row is not used; any n readable doubles will do
-  a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.draw0 = 0; a.B = B; a.sigma2 = 1.0; a.mode = 0; a.tau2 = 0.0;
-  a.status = status; a.x_stride = (size_t)n * d; a.shared_params = 1; a.logdet = logdet;
-  dispatch(s, a);
+  dispatch(s, design_args(Xs, n, d, dv, B, logdet, status));
 }
 
 // predict.post for S draws x m test sites (mean / var are S x m column-major).  scratch (scratch_bytes, may be null): with at
@@ -1170,9 +1097,8 @@ void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, cons
                               int S, const double* Xtest, int m, double sigma2, double* mean, double* var,
                               double* beta, int* status, void* scratch, size_t scratch_bytes, hipStream_t aux,
                               hipEvent_t ev_fork, hipEvent_t ev_join) {
-  RegArgs a{};
-  a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
-  a.draw0 = 0; a.B = S; a.sigma2 = sigma2; a.mode = 0; a.tau2 = 0.0;
+  RegArgs a = reg_args(X, n, d, y, dv);
+  a.B = S; a.sigma2 = sigma2;
   a.beta = beta; a.status = status; a.Xt = Xtest; a.m = m; a.S = S; a.mean = mean; a.var = var;
   const size_t per = small_reg_sites_scratch(n, d, dv.K, m);
   if (scratch && small_reg_sites_supported(n, d, dv.K) && scratch_bytes >= per) {
@@ -1201,79 +1127,11 @@ void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, cons
       f.fac_stride = (size_t)fl.total;
       dispatch<1>(s, f);
       if (aux && ev_fork && ev_join) (void)hipStreamWaitEvent(s, ev_join, 0);
-      switch (fl.npf / 8) {
-        case 1: launch_site_solve<8>(s, sa, ns); break;
-        case 2: launch_site_solve<16>(s, sa, ns); break;
-        case 3: launch_site_solve<24>(s, sa, ns); break;
-        case 4: launch_site_solve<32>(s, sa, ns); break;
-        case 5: launch_site_solve<40>(s, sa, ns); break;
-        case 6: launch_site_solve<48>(s, sa, ns); break;
-        case 7: launch_site_solve<56>(s, sa, ns); break;
-        case 8: launch_site_solve<64>(s, sa, ns); break;
-        case 9: launch_site_solve<72>(s, sa, ns); break;
-        case 10: launch_site_solve<80>(s, sa, ns); break;
-        case 11: launch_site_solve<88>(s, sa, ns); break;
-        case 12: launch_site_solve<96>(s, sa, ns); break;
-        default: launch_site_solve<104>(s, sa, ns); break;
-      }
+      launch_site_solve(s, sa, ns);
     }
     return;
   }
   dispatch<kPredictNE>(s, a);
-}
-
-template <int NE>
-static void dispatch(hipStream_t s, const RegArgs& a) {
-  const int n = a.n;
-  // A handful of evaluations (Metro's one proposal per logpost call, a speculative batch of a few candidates) is a
-  // LATENCY problem: one wave per matrix leaves the chip empty and runs the whole elimination on 64 lanes; the
-  // 16 x 16 grid puts four waves on each matrix (n = 64, one evaluation: 41 -> 25 us of kernel time).
-  // (with the factor kept -- prediction -- the four-wave form up to 2048 draws: its one factorisation per draw is the critical
-  // path of the call and a wave per SIMD is all that 1000 draws fill anyway)
-  const bool wide = NE == 1 && a.x_stride == 0 && a.B <= (a.fac ? CCGP_FAC_WIDE_MAX : 64);
-  if constexpr (NE == 1) {
-    // 64 < n <= 104 (BASELINE config 3: maximin-100): still ONE WAVE per matrix on the 8 x 8 grid, with up to 13 x 13
-    // blocks per thread (two waves per SIMD: up to 256 VGPRs) -- at n = 100 1.68 x the minimal FMAs instead of the
-    // 2.75 x of the 16 x 16 grid at NB = 7, no s_barrier, and the per-column overhead (pivot, reciprocal, column
-    // broadcast) is paid by one wave instead of four: 25.7 k -> ~10 k VALU instructions per evaluation, 6.06 -> 5.07 ms
-    // per 103 680 evaluations on the same box, same bits (profiles/r04).  CCGP_OPT_SMALL_GRID16: the 16 x 16 grid (A/B).
-    const int nb8 = (n + 7) / 8;
-    const bool fits8 = sizeof(double) * (kSmallExpTable + (size_t)a.d * n + (size_t)4 * kPerMat(8 * nb8, 8, 1, a.K, a.d) +
-                                         (a.x_stride ? (size_t)4 * a.d * n : 0)) <= (size_t)kLdsBytes - 64;   // four matrices per workgroup
-    if (n > 64 && n <= 104 && !wide && fits8 && !a.grid16) {
-      switch ((n + 7) / 8) {
-        case 9: launch_one<8, 9, NE>(s, a); break;
-        case 10: launch_one<8, 10, NE>(s, a); break;
-        case 11: launch_one<8, 11, NE>(s, a); break;
-        case 12: launch_one<8, 12, NE>(s, a); break;
-        default: launch_one<8, 13, NE>(s, a); break;
-      }
-      return;
-    }
-  }
-  if (n <= 64 && !wide) {
-    switch ((n + 7) / 8) {
-      case 1: launch_one<8, 1, NE>(s, a); break;
-      case 2: launch_one<8, 2, NE>(s, a); break;
-      case 3: launch_one<8, 3, NE>(s, a); break;
-      case 4: launch_one<8, 4, NE>(s, a); break;
-      case 5: launch_one<8, 5, NE>(s, a); break;
-      case 6: launch_one<8, 6, NE>(s, a); break;
-      case 7: launch_one<8, 7, NE>(s, a); break;
-      default: launch_one<8, 8, NE>(s, a); break;
-    }
-  } else {
-    switch ((n + 15) / 16) {
-      case 1: if constexpr (NE == 1) { launch_one<16, 1, NE>(s, a); break; }
-      case 2: if constexpr (NE == 1) { launch_one<16, 2, NE>(s, a); break; }
-      case 3: if constexpr (NE == 1) { launch_one<16, 3, NE>(s, a); break; }
-      case 4: if constexpr (NE == 1) { launch_one<16, 4, NE>(s, a); break; }
-      case 5: launch_one<16, 5, NE>(s, a); break;
-      case 6: launch_one<16, 6, NE>(s, a); break;
-      case 7: launch_one<16, 7, NE>(s, a); break;
-      default: launch_one<16, 8, NE>(s, a); break;
-    }
-  }
 }
 
 }  // namespace ccgp

@@ -209,8 +209,9 @@ int ccgp_qigamma(const double* p, int N, double alpha, double beta, double* out)
 /* ---- a10/a11: factors HX:604-613, predict.post HX:655-673 / ANI:604-623 --------------
  * ccgp_predict_batch recomputes, per draw, what Metro caches (R.Inv, beta; HX:515-525)
  * and returns the S x m tables mean[s + t*S], var[s + t*S] that prediction() averages
- * (HX:688-693).  out_beta (S) and status (S) may be NULL.  Any n: n <= 128 runs the fused
- * in-LDS evaluator, larger n appends the m cross-correlation rows to the blocked sweep. */
+ * (HX:688-693).  out_beta (S) and status (S) may be NULL.  Any n: n <= 128 runs the
+ * register-resident evaluator, larger n (or a shape its LDS carve cannot hold) appends the
+ * m cross-correlation rows to the blocked sweep. */
 int ccgp_predict_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
                        const double* params, int S, const double* Xtest, int m, double sigma2,
                        double* out_mean, double* out_var, double* out_beta, int* status);
@@ -325,7 +326,7 @@ enum {
   CCGP_T_DIAG = 2,     /* diagonal-block factor + inverse   */
   CCGP_T_TRSM = 3,     /* panel triangular solve (MFMA)     */
   CCGP_T_SOLVE = 4,    /* forward solves + reductions       */
-  CCGP_T_FUSED = 5,    /* small-n fused in-LDS evaluator    */
+  CCGP_T_FUSED = 5,    /* small-n fused evaluators (n <= 128) */
   CCGP_T_SWEEP = 6,    /* blocked Cholesky sweep as one scheduled launch (update + diag + trsm tiles) */
   CCGP_T_COUNT = 7
 };

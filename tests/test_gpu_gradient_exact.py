@@ -307,6 +307,32 @@ def test_explicit_inverse_componentwise(handle, n):
 
 
 @pytest.mark.gpu
+def test_explicit_inverse_componentwise_lds_evaluator(handle):
+    """The same check on the LDS evaluator of small.hip (launch_small_inverse), which ccgp_logpost reaches at n <= 128 when
+    the register instance with INV = 1 does not fit: n = 121 with d = 22 and the two components of the GV prior (cond1 of
+    this R is 4e4 in long double)."""
+    from ccgp_amd import api
+    n, d = 121, 22
+    assert route(n, d, 2) == "lds" and not small_reg_inverse_supported(n, d, 2)
+    X, y = _design(n, d, seed=6000 + n)
+    rough = 2.0 * n ** (2.0 / d) / d
+    p, t1, t2 = 0.7, 0.3 * rough, 1.5 * rough
+    R = (p ** 2 * orc.component_corr(X, [t1] * d) + (1 - p) ** 2 * orc.component_corr(X, [t2] * d)) / (p ** 2 + (1 - p) ** 2)
+    Rinv_ref = np.asarray(orc.solve_inverse_exact(R), dtype=np.float64)
+    kappa = orc.cond1(R, Rinv_ref)
+    assert kappa <= KAPPA_MAX
+    theta_t = [math.log(t1), math.log(t2), math.log(p / (1 - p))]
+    (r, tm) = _timed(handle, lambda: handle.logpost(X, y, 1.3, api.PRIOR_GV, theta_t))
+    assert r["status"] == 0
+    assert tm["fused"][1] > 0 and tm["solve"][1] == 0
+    A = np.abs(Rinv_ref)
+    bound = n * EPS * (A @ np.abs(R) @ A)
+    ratio = np.abs(r["R_inv"] - Rinv_ref) / bound
+    MAX_RATIO["inverse-lds"] = max(MAX_RATIO.get("inverse-lds", 0.0), float(ratio.max()))
+    assert ratio.max() <= INV_C, (n, ratio.max(), kappa)
+
+
+@pytest.mark.gpu
 def test_zz_report_headroom():
     """Largest observed |dev - ref| / (eps cond1 (1 + rho) scale) per route (for the inverse: / (n eps |R^-1||R||R^-1|))."""
     for k in sorted(MAX_RATIO):
