@@ -63,6 +63,11 @@ SIGNATURES = {
     "ccgp_predict_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                                        c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
+    "ccgp_predict_summary": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, c_int, c_double,
+                                     _dp, c_int, _dp, _dp, _dp, _ip]),
+    "ccgp_predict_summary_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                         c_int, c_double, _dp, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ccgp_summary_from_factorset": (c_int, [c_void_p, c_void_p, _dp, c_int, _dp, c_int, _dp, _dp]),
     "ccgp_factor_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, c_double, POINTER(c_void_p),
                                   _dp, _dp, _ip]),
     "ccgp_predict_from_factorset": (c_int, [c_void_p, c_void_p, _dp, c_int, _dp, _dp]),
@@ -143,6 +148,19 @@ def qigamma(p, alpha, beta):
     return out
 
 
+SUMMARY_MAX_PROBS = 8
+
+
+def _probs(probs):
+    return np.ascontiguousarray(np.ravel(np.asarray(probs, dtype=np.float64)))
+
+
+def _summary_dict(out, n_failed, beta=None, status=None):
+    """The m x (4 + n_probs) block of ccgp_predict_summary as named arrays."""
+    return dict(y_hat=out[:, 0], pred_var=out[:, 1], quant=out[:, 2], cdf_at=out[:, 3], quantiles=out[:, 4:],
+                beta=beta, status=status, n_failed=n_failed)
+
+
 class FactorSet:
     """S Cholesky factors kept in HBM (ccgp_factor_batch); predict(Xtest) -> (mean[S, m], var[S, m])."""
 
@@ -161,6 +179,18 @@ class FactorSet:
         var = np.empty((self.S, m), dtype=np.float64, order="F")
         self._handle._chk(lib().ccgp_predict_from_factorset(self._handle._h, self._fs, _p(Xtest), m, _p(mean), _p(var)))
         return mean, var
+
+    def summary(self, Xtest, probs, y_at=None):
+        """prediction()'s per-site summaries (HX:686-703) from the kept factors: the dict of Handle.predict_summary
+        (beta / status are the set's own)."""
+        Xtest = _f(np.atleast_2d(Xtest))
+        m = Xtest.shape[0]
+        probs = _probs(probs)
+        y_at = _f(np.ravel(y_at), (m,)) if y_at is not None else None
+        out = np.empty((m, 4 + probs.size), dtype=np.float64, order="F")
+        bad = self._handle._chk(lib().ccgp_summary_from_factorset(self._handle._h, self._fs, _p(Xtest), m, _p(probs),
+                                                                  probs.size, _p(y_at), _p(out)))
+        return _summary_dict(out, bad, self.beta, self.status)
 
     def free(self):
         if self._fs:
@@ -546,6 +576,27 @@ class Handle:
                                            float(sigma2), _p(mean), _p(var), _p(beta), _ipt(st)))
         return mean, var, beta, st
 
+    def predict_summary(self, X, y, K, params, Xtest, sigma2, probs, y_at=None):
+        """prediction()'s per-site summaries (HX:686-703) of the S draws, computed on the device from the exact
+        posterior predictive (the equal-weight mixture of the draws' normals); only m x (4 + n_probs) doubles come
+        back.  Returns a dict: y_hat[m], pred_var[m], quant[m], cdf_at[m] (NaN without y_at), quantiles[m, n_probs],
+        beta[S], status[S], n_failed."""
+        X, y = _f(X), _f(np.ravel(y))
+        n, d = X.shape
+        params = _f(np.atleast_2d(params))
+        S = params.shape[0]
+        Xtest = _f(np.atleast_2d(Xtest))
+        m = Xtest.shape[0]
+        probs = _probs(probs)
+        y_at = _f(np.ravel(y_at), (m,)) if y_at is not None else None
+        out = np.empty((m, 4 + probs.size), dtype=np.float64, order="F")
+        beta = np.empty(S)
+        st = np.zeros(S, dtype=np.int32)
+        bad = self._chk(lib().ccgp_predict_summary(self._h, _p(X), n, d, _p(y), K, _p(params), S, _p(Xtest), m,
+                                                   float(sigma2), _p(probs), probs.size, _p(y_at), _p(out), _p(beta),
+                                                   _ipt(st)))
+        return _summary_dict(out, bad, beta, st)
+
     # -- 8(f)-2: device-resident factor set -------------------------------------------------
     def factor_batch(self, X, y, K, params, sigma2):
         """Factorise the S draws once and keep the factors on the device -> FactorSet (use as a context manager or
@@ -585,3 +636,13 @@ class Handle:
                                                self._dptr(dparams), S, self._dptr(dXtest), m,
                                                float(sigma2), self._dptr(d_mean), self._dptr(d_var),
                                                self._dptr(d_beta), self._dptr(d_status)))
+
+    def predict_summary_dev(self, dX, n, d, dy, K, dparams, S, dXtest, m, sigma2, probs, d_y_at, d_out, d_beta=None,
+                            d_status=None):
+        """ccgp_predict_summary on device buffers, asynchronous: d_out is m x (4 + n_probs) column-major (float64),
+        d_y_at / d_beta / d_status may be None; probs is a host sequence."""
+        probs = _probs(probs)
+        self._chk(lib().ccgp_predict_summary_dev(self._h, self._dptr(dX), n, d, self._dptr(dy), K, self._dptr(dparams),
+                                                 S, self._dptr(dXtest), m, float(sigma2), _p(probs), probs.size,
+                                                 self._dptr(d_y_at), self._dptr(d_out), self._dptr(d_beta),
+                                                 self._dptr(d_status)))

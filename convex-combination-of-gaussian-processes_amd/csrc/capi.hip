@@ -382,6 +382,49 @@ PredictStage predict_stage(Layout& c, int n, int d, int P, int S, int m) {
   return s;
 }
 
+// staging of the prediction summaries (summary.hip).  The S x m tables never leave the device: they lie BETWEEN the
+// inputs (one span up) and the results (one span down), next to the scratch of the summary kernel.
+struct SummaryTables {
+  double *mean, *var;
+  int *idx, *count;
+};
+SummaryTables summary_tables(Layout& c, int S, int m) {
+  SummaryTables t;
+  t.mean = c.take<double>((size_t)S * m);
+  t.var = c.take<double>((size_t)S * m);
+  t.idx = c.take<int>(S);
+  t.count = c.take<int>(1);
+  return t;
+}
+struct SummaryStage {
+  double *X, *y, *params, *Xtest, *y_at;
+  SummaryTables t;
+  double *out, *beta;
+  int* status;
+};
+SummaryStage summary_stage(Layout& c, int n, int d, int P, int S, int m, int n_probs) {
+  SummaryStage s;
+  s.X = c.take<double>((size_t)n * d);
+  s.y = c.take<double>(n);
+  s.params = c.take<double>((size_t)S * P);
+  s.Xtest = c.take<double>((size_t)m * d);
+  s.y_at = c.take<double>(m);
+  s.t = summary_tables(c, S, m);
+  s.out = c.take<double>((size_t)m * (4 + n_probs));
+  s.beta = c.take<double>(S);
+  s.status = c.take<int>(S);
+  return s;
+}
+
+int check_summary_args(ccgp_handle* h, int m, const double* probs, int n_probs) {
+  if (m < 1 || n_probs < 0 || n_probs > CCGP_SUMMARY_MAX_PROBS || (n_probs > 0 && !probs))
+    return fail(h, CCGP_EINVAL, "ccgp_predict_summary: m >= 1 and 0 <= n_probs <= 8 (with probs) are required");
+  for (int j = 0; j < n_probs; ++j)
+    if (!(probs[j] > 0.0 && probs[j] < 1.0))
+      return fail(h, CCGP_EINVAL, "ccgp_predict_summary: every level of probs must lie strictly inside (0, 1)");
+  return CCGP_OK;
+}
+
 // blocked prediction: scratch behind the matrices for the outputs the caller did not ask for
 struct PredictTail {
   double *ll, *beta;
@@ -1499,6 +1542,55 @@ int ccgp_predict_batch(ccgp_handle* h, const double* X, int n, int d, const doub
                          piece(s.beta, out_beta, S)}, s.status, S, status);
 } CCGP_GUARD_END(h)
 
+// ---- prediction(): per-site summaries of the tables, HX:686-703 / GV:620-638 -------------------------------------
+int ccgp_predict_summary_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy, int K,
+                             const double* dparams, int S, const double* dXtest, int m, double sigma2,
+                             const double* probs, int n_probs, const double* d_y_at, double* d_out,
+                             double* d_beta, int* d_status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || S < 1 || !dX || !dy || !dparams || !dXtest || !d_out)
+    return fail(h, CCGP_EINVAL, "ccgp_predict_summary: bad argument");
+  if (int rc = check_summary_args(h, m, probs, n_probs)) return rc;
+  CCGP_HIP(hipSetDevice(h->device));
+  SummaryTables t;
+  int* st = d_status;
+  if (int rc = stage(h, [&](Layout& c) {
+        t = summary_tables(c, S, m);
+        if (!d_status) st = c.take<int>(S);
+      }))
+    return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dparams, S, K, d, &dv)) return frc;
+  if (int rc = predict_run(h, dX, n, d, dy, dv, dXtest, m, sigma2, t.mean, t.var, d_beta, st)) return rc;
+  launch_predict_summary(h->stream, t.mean, t.var, st, S, m, probs, n_probs, d_y_at, t.idx, t.count, d_out);
+  CCGP_LAUNCH_CHECK();
+  return CCGP_OK;
+} CCGP_GUARD_END(h)
+
+int ccgp_predict_summary(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                         const double* params, int S, const double* Xtest, int m, double sigma2,
+                         const double* probs, int n_probs, const double* y_at, double* out,
+                         double* out_beta, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || S < 1 || !X || !y || !params || !Xtest || !out)
+    return fail(h, CCGP_EINVAL, "ccgp_predict_summary: bad argument");
+  if (int rc = check_summary_args(h, m, probs, n_probs)) return rc;
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  SummaryStage s;
+  if (int rc = stage(h, [&](Layout& c) { s = summary_stage(c, n, d, P, S, m, n_probs); })) return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, S, K, d, &dv)) return frc;
+  if (int prc = push(h, {piece(s.X, X, (size_t)n * d), piece(s.y, y, n), piece(s.params, params, (size_t)S * P),
+                         piece(s.Xtest, Xtest, (size_t)m * d), piece(s.y_at, y_at, m)}))
+    return prc;
+  if (int rc = predict_run(h, s.X, n, d, s.y, dv, s.Xtest, m, sigma2, s.t.mean, s.t.var, s.beta, s.status)) return rc;
+  launch_predict_summary(h->stream, s.t.mean, s.t.var, s.status, S, m, probs, n_probs, y_at ? s.y_at : nullptr, s.t.idx,
+                         s.t.count, s.out);
+  CCGP_LAUNCH_CHECK();
+  return pull_status(h, {piece(s.out, out, (size_t)m * (4 + n_probs)), piece(s.beta, out_beta, S)}, s.status, S, status);
+} CCGP_GUARD_END(h)
+
 // ---- 8(f)-2: device-resident factor set --------------------------------------------------------------
 struct ccgp_factorset {
   int device = 0;
@@ -1593,6 +1685,34 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
   return report_status(st, status);
 } CCGP_GUARD_END(h)
 
+// the S x m tables of a factor set at the m resident test sites dXt; arguments are checked by the callers
+static int factorset_predict_run(ccgp_handle* h, const ccgp_factorset* fs, const double* dXt, int m, double* dmean,
+                                 double* dvar) {
+  const int n = fs->n, d = fs->d, S = fs->S;
+  DrawView dv;   // the set's kernel family, whatever the handle has been set to since
+  if (int frc = draw_view(h, fs->fam, fs->params, S, fs->K, d, &dv)) return frc;
+  if (fs->fused) return predict_run(h, fs->X, n, d, fs->y, dv, dXt, m, fs->sigma2, dmean, dvar, nullptr, nullptr);
+  const int ne = (m + kTile - 1) / kTile, lde = ne * kTile;
+  const size_t e_stride = (size_t)lde * fs->npad;
+  // the m cross-correlation rows of every draw need lde x npad doubles of scratch: chunks of draws
+  int sc = 0;
+  if (int rc = plan_chunk(h, sizeof(double) * e_stride, S, kFactorsetMargin,
+                          [&](int ns) { return sizeof(double) * e_stride * (size_t)ns; }, &sc))
+    return rc;
+  double* E = static_cast<double*>(h->ws);
+  for (int s0 = 0; s0 < S; s0 += sc) {
+    const int ns = std::min(sc, S - s0);
+    CCGP_HIP(hipMemsetAsync(E, 0, sizeof(double) * e_stride * ns, h->stream));
+    {
+      ScopedTimer t(h, CCGP_T_COV);   // rows t = r(x_t)' (Mixed.corr.vec, HX:425-431)
+      launch_cov_cross_batched(h->stream, dXt, m, fs->X, n, d, dv, s0, ns, E, e_stride, lde);
+    }
+    blocked_predict_from_factors(h, fs->w, n, fs->npad, S, s0, ns, E, e_stride, lde, m, fs->status, fs->sigma2, dmean, dvar);
+  }
+  CCGP_LAUNCH_CHECK();
+  return CCGP_OK;
+}
+
 int ccgp_predict_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const double* Xtest, int m,
                                 double* out_mean, double* out_var) try {
   if (!h) return CCGP_EINVAL;
@@ -1601,7 +1721,7 @@ int ccgp_predict_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const 
   if (fs->device != h->device)
     return fail(h, CCGP_EINVAL, "ccgp_predict_from_factorset: the factor set lives on another device");
   CCGP_HIP(hipSetDevice(h->device));
-  const int n = fs->n, d = fs->d, S = fs->S;
+  const int d = fs->d, S = fs->S;
   double *dXt, *dmean, *dvar;
   if (int rc = stage(h, [&](Layout& c) {
         dXt = c.take<double>((size_t)m * d);
@@ -1609,35 +1729,40 @@ int ccgp_predict_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const 
         dvar = c.take<double>((size_t)S * m);
       }))
     return rc;
-  DrawView dv;   // the set's kernel family, whatever the handle has been set to since
-  if (int frc = draw_view(h, fs->fam, fs->params, S, fs->K, d, &dv)) return frc;
   CCGP_HIP(hipMemcpyAsync(dXt, Xtest, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, h->stream));
-  if (fs->fused) {
-    if (int rc = predict_run(h, fs->X, n, d, fs->y, dv, dXt, m, fs->sigma2, dmean, dvar, nullptr, nullptr)) return rc;
-  } else {
-    const int ne = (m + kTile - 1) / kTile, lde = ne * kTile;
-    const size_t e_stride = (size_t)lde * fs->npad;
-    // the m cross-correlation rows of every draw need lde x npad doubles of scratch: chunks of draws
-    int sc = 0;
-    if (int rc = plan_chunk(h, sizeof(double) * e_stride, S, kFactorsetMargin,
-                            [&](int ns) { return sizeof(double) * e_stride * (size_t)ns; }, &sc))
-      return rc;
-    double* E = static_cast<double*>(h->ws);
-    for (int s0 = 0; s0 < S; s0 += sc) {
-      const int ns = std::min(sc, S - s0);
-      CCGP_HIP(hipMemsetAsync(E, 0, sizeof(double) * e_stride * ns, h->stream));
-      {
-        ScopedTimer t(h, CCGP_T_COV);   // rows t = r(x_t)' (Mixed.corr.vec, HX:425-431)
-        launch_cov_cross_batched(h->stream, dXt, m, fs->X, n, d, dv, s0, ns, E, e_stride, lde);
-      }
-      blocked_predict_from_factors(h, fs->w, n, fs->npad, S, s0, ns, E, e_stride, lde, m, fs->status, fs->sigma2, dmean, dvar);
-    }
-    CCGP_LAUNCH_CHECK();
-  }
+  if (int rc = factorset_predict_run(h, fs, dXt, m, dmean, dvar)) return rc;
   CCGP_HIP(hipMemcpyAsync(out_mean, dmean, sizeof(double) * (size_t)S * m, hipMemcpyDeviceToHost, h->stream));
   CCGP_HIP(hipMemcpyAsync(out_var, dvar, sizeof(double) * (size_t)S * m, hipMemcpyDeviceToHost, h->stream));
   CCGP_HIP(hipStreamSynchronize(h->stream));
   return CCGP_OK;
+} CCGP_GUARD_END(h)
+
+int ccgp_summary_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const double* Xtest, int m,
+                                const double* probs, int n_probs, const double* y_at, double* out) try {
+  if (!h) return CCGP_EINVAL;
+  if (!fs || !Xtest || !out) return fail(h, CCGP_EINVAL, "ccgp_summary_from_factorset: bad argument");
+  if (int rc = check_summary_args(h, m, probs, n_probs)) return rc;
+  if (fs->device != h->device)
+    return fail(h, CCGP_EINVAL, "ccgp_summary_from_factorset: the factor set lives on another device");
+  CCGP_HIP(hipSetDevice(h->device));
+  const int d = fs->d, S = fs->S;
+  double *dXt, *dy_at, *dout;
+  SummaryTables t;
+  if (int rc = stage(h, [&](Layout& c) {
+        dXt = c.take<double>((size_t)m * d);
+        dy_at = c.take<double>(m);
+        t = summary_tables(c, S, m);
+        dout = c.take<double>((size_t)m * (4 + n_probs));
+      }))
+    return rc;
+  if (int prc = push(h, {piece(dXt, Xtest, (size_t)m * d), piece(dy_at, y_at, m)})) return prc;
+  if (int rc = factorset_predict_run(h, fs, dXt, m, t.mean, t.var)) return rc;
+  launch_predict_summary(h->stream, t.mean, t.var, fs->status, S, m, probs, n_probs, y_at ? dy_at : nullptr, t.idx,
+                         t.count, dout);
+  CCGP_LAUNCH_CHECK();
+  int valid = 0;   // t.count closes the tables, dout follows it: one span down
+  if (int rc = pull(h, {piece(t.count, &valid, 1), piece(dout, out, (size_t)m * (4 + n_probs))})) return rc;
+  return S - valid;
 } CCGP_GUARD_END(h)
 
 size_t ccgp_factorset_bytes(const ccgp_factorset* fs) { return fs ? fs->bytes : 0; }

@@ -123,6 +123,18 @@ void launch_cov_tiles(hipStream_t s, const double* X, int n, int d, DrawView dv,
 void launch_cov_cross_batched(hipStream_t s, const double* Xtest, int m, const double* X, int n, int d,
                               DrawView dv, int b0, int nb, double* Abase, size_t batch_stride, int ldo);
 
+// ---- summary.hip ---------------------------------------------------------------------
+// predict_summary_kernel stages a site's (mu, 1 / sigma) pairs in LDS up to this many draws and streams them from the
+// (L2-resident) tables beyond: 2 x 8 B x 2048 = 32 KiB of static LDS, which holds the reference's S = 1000 with room and
+// still lets four workgroups share a CU's 160 KiB.
+constexpr int kSummaryLdsDraws = 2048;
+// prediction()'s per-site summaries (HX:686-703) of the S x m tables d_mean / d_var over the draws with d_status == 0:
+// d_out is m x (4 + n_probs) column-major (ccgp_predict_summary); probs is a HOST array; d_idx (S ints) and d_count
+// (1 int) are scratch.  Two launches on s.
+void launch_predict_summary(hipStream_t s, const double* d_mean, const double* d_var, const int* d_status, int S, int m,
+                            const double* probs, int n_probs, const double* d_y_at, int* d_idx, int* d_count,
+                            double* d_out);
+
 // ---- small.hip -----------------------------------------------------------------------
 // In-LDS evaluator, one workgroup per (draw, chunk of unit rows): explicit inverse (solve(R), HX:454) and gradient for the
 // n <= 128 shapes whose register-resident inverse instance does not fit (small_lds_bytes, small_pick_mtile: small_layout.h)

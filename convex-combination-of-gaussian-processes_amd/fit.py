@@ -285,9 +285,15 @@ def factors_frame(gp, start, N, samp_size, batch_size, alpha_geweke, D_train, si
 
 
 # ----------------------------------------------------------------------------- prediction / compare.GP
-def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=None):
+def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=None, exact=False):
     """HX:713-725 + prediction HX:686-703 (GV:620-646 adds Quant.Combined): one row per test point
-    (y.hat.Combined, Quant.Combined, LL.Combined, UL.Combined, y.true)."""
+    (y.hat.Combined, Quant.Combined, LL.Combined, UL.Combined, y.true).  exact=True takes Quant and the interval from
+    the exact posterior predictive on the device (gp.prediction) instead of sampling one variate per draw: rng is
+    ignored, the tables stay on the device, and the keys are the same without mean / var."""
+    if exact:
+        r = gp.prediction(D_test, alpha, draws, D_train, sigma2, y_train)
+        return dict(y_hat=r["y_hat"], quant=r["Quant"], LL=r["LL"], UL=r["UL"],
+                    y_true=np.asarray(y_test, dtype=np.float64))
     rng = np.random.default_rng(rng)
     t = gp.prediction_table(D_test, draws, D_train, sigma2, y_train)
     mean, var = t["mean"], t["var"]                      # [S, m]

@@ -276,7 +276,8 @@ class CombinedGP:
     def prediction_table(self, D_test, draws, D_train, sigma2, y_train, as_written=False):
         """The deterministic part of prediction()/compare.GP (HX:686-693, HX:713-725): the
         (draw x test point) mean and variance tables and y.hat = colMeans(mean).  The
-        rnorm/quantile interval step (HX:696-699) needs R's RNG and is out of scope.
+        interval step (HX:696-699) draws one rnorm per table entry in the reference; `prediction` returns the
+        interval of the exact posterior predictive instead, and fit.compare_GP samples it from these tables.
 
         script "ADV": the reference trains with R2 = corr.matrix.ISO(D, lambda) (ADV:417, ADV:456) but its
         predict.post builds r with theta1 * (1 + lambda) (ADV:672) -- two different second components.  The
@@ -296,6 +297,17 @@ class CombinedGP:
         params = self.draws_to_params(D_train, draws)
         mean, var, beta, status = self.h.predict_batch(D_train, y_train, 2, params, D_test, sigma2)
         return dict(mean=mean, var=var, beta=beta, status=status, y_hat=mean.mean(axis=0))
+
+    def prediction(self, D_test, alpha, draws, D_train, sigma2, y_train, y_test=None):
+        """prediction() (HX:686-703, GV:620-638) from the exact posterior predictive -- per test site the equal-weight
+        mixture of the draws' normals -- computed on the device (ccgp_predict_summary): y_hat, Quant = P(y.hat <=
+        predictive), and the interval LL / UL = its alpha/2 and 1 - alpha/2 quantiles.  No random numbers: the
+        reference's interval is a one-variate-per-draw Monte-Carlo estimate of these.  y_test adds cdf_at, the
+        predictive CDF at the held-out responses."""
+        params = self.draws_to_params(D_train, draws)
+        r = self.h.predict_summary(D_train, y_train, 2, params, D_test, sigma2, (alpha / 2.0, 1.0 - alpha / 2.0), y_test)
+        return dict(y_hat=r["y_hat"], Quant=r["quant"], LL=r["quantiles"][:, 0], UL=r["quantiles"][:, 1],
+                    pred_var=r["pred_var"], cdf_at=r["cdf_at"], beta=r["beta"], status=r["status"])
 
     def factors_frame_from_draws(self, draws, D_train, sigma2, y_train):
         """Materialise the data frame factors.frame() returns (HX:625-644) for drop-in
@@ -389,6 +401,9 @@ class CombinedGP1D(CombinedGP):
 
     def prediction_table(self, D_test, draws, D_train, sigma2, y_train):
         return super().prediction_table(self._col(D_test), draws, self._col(D_train), sigma2, y_train)
+
+    def prediction(self, D_test, alpha, draws, D_train, sigma2, y_train, y_test=None):
+        return super().prediction(self._col(D_test), alpha, draws, self._col(D_train), sigma2, y_train, y_test)
 
     def factors_frame_from_draws(self, draws, D_train, sigma2, y_train):
         return super().factors_frame_from_draws(draws, self._col(D_train), sigma2, y_train)

@@ -219,6 +219,34 @@ int ccgp_predict_batch_dev(ccgp_handle* h, const double* dX, int n, int d, const
                            const double* dparams, int S, const double* dXtest, int m,
                            double sigma2, double* d_mean, double* d_var, double* d_beta,
                            int* d_status);
+
+/* ---- prediction(): the per-site summaries of those tables (HX:686-703 / GV:620-638) -------------
+ * Every script ends in compare.GP -> prediction(): per test site the mean of the S per-draw means, a
+ * prediction interval and Quant.Combined, which the reference estimates from ONE normal variate per draw.
+ * The posterior predictive at a site is known exactly -- the equal-weight mixture of the S' normals
+ * N(mean_s, var_s) of the draws with status 0 -- so the summaries are computed from it, on the device,
+ * where the tables already are, and only m x (4 + n_probs) doubles come back:
+ *   sigma_s  = sqrt(max(var_s, 0));  F(q) = 1/S' sum_s Phi((q - mean_s) / sigma_s)  (sigma_s = 0: a step at mean_s)
+ *   column 0   y_hat    = 1/S' sum mean_s
+ *   column 1   pred_var = 1/S' sum sigma_s^2 + 1/S' sum (mean_s - y_hat)^2
+ *   column 2   quant    = 1 - F(y_hat)      (the expectation of mean(y.hat <= posterior.predictive))
+ *   column 3   cdf_at   = F(y_at[t])        (NaN when y_at is NULL)
+ *   column 4+j q_j      = inf{q : F(q) >= probs[j]},  j < n_probs <= CCGP_SUMMARY_MAX_PROBS
+ * out is m x (4 + n_probs) column-major.  Every probs[j] lies strictly inside (0, 1), else CCGP_EINVAL.  A site
+ * with S' = 0 is NaN throughout.  Failed draws are left out and reported through status as ccgp_predict_batch
+ * reports them; the return value is their count.  y_at (m), out_beta (S) and status (S) may be NULL.  A site's row
+ * depends on its own column of the tables only: not on m, the other sites, or the entry point. */
+enum { CCGP_SUMMARY_MAX_PROBS = 8 };
+int ccgp_predict_summary(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                         const double* params, int S, const double* Xtest, int m, double sigma2,
+                         const double* probs, int n_probs, const double* y_at, double* out,
+                         double* out_beta, int* status);
+/* the same on device pointers (HX:686-703), asynchronous on the handle's stream like ccgp_predict_batch_dev (returns
+ * CCGP_OK; the failed draws are in d_status).  probs stays a HOST array: its values travel as kernel arguments. */
+int ccgp_predict_summary_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy, int K,
+                             const double* dparams, int S, const double* dXtest, int m, double sigma2,
+                             const double* probs, int n_probs, const double* d_y_at, double* d_out,
+                             double* d_beta, int* d_status);
 /* ---- device-resident factor set ------------------------------------------------
  * Metro caches R.Inv and beta of every accepted draw (HX:515-525), factors.frame flattens them into a
  * (5 + 2n + n^2)-column data-frame row (HX:625-644) and predict.post re-parses that row for every test
@@ -238,6 +266,10 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
 /* out_mean / out_var: S x m column-major, as ccgp_predict_batch */
 int ccgp_predict_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const double* Xtest, int m,
                                 double* out_mean, double* out_var);
+/* the summaries of ccgp_predict_summary (HX:686-703 / GV:620-638) from kept factors: same kernel, same bits; returns
+ * the number of draws of the set that failed to factorise */
+int ccgp_summary_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const double* Xtest, int m,
+                                const double* probs, int n_probs, const double* y_at, double* out);
 size_t ccgp_factorset_bytes(const ccgp_factorset* fs);
 int ccgp_factorset_free(ccgp_handle* h, ccgp_factorset* fs);
 
