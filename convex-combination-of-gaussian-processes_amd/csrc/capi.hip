@@ -264,11 +264,49 @@ int plan_chunk(ccgp_handle* h, size_t per_item, int count, size_t margin, TotalB
   return rc;
 }
 
-// the blocked sweep's plan: matrices of npad rows with ne extra tile rows, `tail` bytes of scratch behind them
-int sweep_chunk(ccgp_handle* h, int npad, int ne, int count, size_t tail, int* chunk) {
-  return plan_chunk(h, blocked_ws_bytes(npad, 1, ne), count, kSweepMargin,
-                    [&](int nb) { return blocked_ws_bytes(npad, nb, ne) + tail; }, chunk);
+// The blocked sweep's workspace: a chunk of nb matrices of npad rows with ne extra tile rows, and behind them what
+// `scratch(Layout&, nb)` declares -- once per candidate chunk size to measure, and once over the workspace, where it hands
+// out its pointers.  scratch_per_item: what a matrix's share of the scratch adds to the plan's bytes per item.
+template <class Scratch>
+int sweep_plan(ccgp_handle* h, int npad, int ne, int count, size_t scratch_per_item, Scratch&& scratch, int* chunk) {
+  auto lay = [&](Layout& w, int nb) {
+    w.off += blocked_ws_bytes(npad, nb, ne);
+    scratch(w, nb);
+  };
+  if (int rc = plan_chunk(h, blocked_ws_bytes(npad, 1, ne) + scratch_per_item, count, kSweepMargin,
+                          [&](int nb) { return layout_bytes([&](Layout& w) { lay(w, nb); }); }, chunk))
+    return rc;
+  Layout ws(h->ws);
+  lay(ws, *chunk);
+  return CCGP_OK;
 }
+
+// where a sweep leaves the likelihood, beta and status of its matrices, each indexed by draw
+struct SweepOut {
+  double *loglik, *beta;
+  int* status;
+};
+
+// One blocked sweep over the `count` draws of dv on resident inputs: plan the chunk, zero the status words, factorise
+// chunk by chunk with `job` riding along, check the launches.  `out` and `job` are read AFTER the plan, so `scratch` may
+// point them into the workspace.
+template <class Scratch>
+int run_sweep(ccgp_handle* h, const double* dX, int n, int d, const double* dy, const DrawView& dv, int count, int ne,
+              double sigma2, int mean_mode, double tau2, const SweepOut& out, const BlockedJob* job,
+              size_t scratch_per_item, Scratch&& scratch) {
+  const int npad = round_up(n, kTile);
+  int nbc = 0;
+  if (int rc = sweep_plan(h, npad, ne, count, scratch_per_item, scratch, &nbc)) return rc;
+  CCGP_HIP(hipMemsetAsync(out.status, 0, sizeof(int) * (size_t)count, h->stream));
+  for (int b0 = 0; b0 < count; b0 += nbc) {
+    const int nb = std::min(nbc, count - b0);
+    blocked_loglik(h, dX, n, d, dy, dv, b0, nb, npad, sigma2, mean_mode, tau2, blocked_carve(h->ws, npad, nb, ne),
+                   out.loglik, out.beta, out.status, job);
+  }
+  CCGP_LAUNCH_CHECK();
+  return CCGP_OK;
+}
+const auto no_scratch = [](Layout&, int) {};
 
 int check_mean_mode(ccgp_handle* h, int mean_mode) {
   if (mean_mode != CCGP_MEAN_PROFILE_BETA && mean_mode != CCGP_MEAN_ZERO_PLUS_TAU2)
@@ -280,26 +318,11 @@ int check_mean_mode(ccgp_handle* h, int mean_mode) {
 int loglik_run(ccgp_handle* h, const double* dX, int n, int d, const double* dy, const DrawView& dv, double sigma2,
                int mean_mode, double tau2, double* d_loglik, double* d_beta, int* d_status) {
   const int K = dv.K, B = dv.ldp;
-  // the fused evaluators generate Gaussian correlations in registers; any other family goes through
-  // the materialised-matrix (blocked) path, where only cov_kernel knows about families
-  const bool gauss = dv.fam.id == 0;
-  if (gauss && small_reg_supported(n, d, K)) {   // otherwise (n > 128, or d too large for LDS) the blocked path takes it
-    ScopedTimer t(h, CCGP_T_FUSED);
-    launch_small_reg_loglik(h->stream, dX, n, d, dy, dv, B, sigma2, mean_mode, tau2, d_loglik, d_beta,
-                            d_status, h->opt_small_grid16 != 0);
-    CCGP_LAUNCH_CHECK();
-    return CCGP_OK;
-  }
-  const int npad = round_up(n, kTile);
-  int nbc = 0;
-  if (int rc = sweep_chunk(h, npad, 0, B, 0, &nbc)) return rc;
-  CCGP_HIP(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)B, h->stream));
-  for (int b0 = 0; b0 < B; b0 += nbc) {
-    const int nb = std::min(nbc, B - b0);
-    BlockedWs w = blocked_carve(h->ws, npad, nb, 0);
-    blocked_loglik(h, dX, n, d, dy, dv, b0, nb, npad, sigma2, mean_mode, tau2, w, d_loglik, d_beta,
-                   d_status);
-  }
+  if (small_route(Op::Loglik, dv.fam.id == 0, n, d, K) == Route::Blocked)
+    return run_sweep(h, dX, n, d, dy, dv, B, 0, sigma2, mean_mode, tau2, {d_loglik, d_beta, d_status}, nullptr, 0, no_scratch);
+  ScopedTimer t(h, CCGP_T_FUSED);
+  launch_small_reg_loglik(h->stream, dX, n, d, dy, dv, B, sigma2, mean_mode, tau2, d_loglik, d_beta,
+                          d_status, h->opt_small_grid16 != 0);
   CCGP_LAUNCH_CHECK();
   return CCGP_OK;
 }
@@ -426,13 +449,9 @@ int check_summary_args(ccgp_handle* h, int m, const double* probs, int n_probs) 
 }
 
 // blocked prediction: scratch behind the matrices for the outputs the caller did not ask for
-struct PredictTail {
-  double *ll, *beta;
-  int* status;
-};
-PredictTail predict_tail(Layout& t, int S, double* d_beta, int* d_status) {
-  PredictTail p;
-  p.ll = t.take<double>(S);
+SweepOut predict_tail(Layout& t, int S, double* d_beta, int* d_status) {
+  SweepOut p;
+  p.loglik = t.take<double>(S);
   p.beta = d_beta ? d_beta : t.take<double>(S);
   p.status = d_status ? d_status : t.take<int>(S);
   return p;
@@ -751,11 +770,15 @@ int ccgp_synchronize(ccgp_handle* h) try {
 int ccgp_reserve(ccgp_handle* h, int n, int d, int K, int B, int m) try {
   if (!h || bad_shape(n, d, K) || B < 1 || m < 0) return fail(h, CCGP_EINVAL, "ccgp_reserve: bad argument");
   CCGP_HIP(hipSetDevice(h->device));
-  if (n > kSmallMaxN || h->fam.id != 0) {
-    const int npad = round_up(n, kTile), ne = (m + kTile - 1) / kTile;
-    const size_t tail = m ? layout_bytes([&](Layout& t) { predict_tail(t, B, nullptr, nullptr); }) : 0;
+  // the sweep's workspace where the likelihood or, with test sites, the prediction of this shape takes the sweep (a
+  // prediction on the register-resident evaluator implies the likelihood there: its instance is the larger one)
+  const bool gauss = h->fam.id == 0;
+  const bool sweep_predict = m > 0 && small_route(Op::Predict, gauss, n, d, K) == Route::Blocked;
+  if (sweep_predict || small_route(Op::Loglik, gauss, n, d, K) == Route::Blocked) {
     int nbc = 0;
-    if (int rc = sweep_chunk(h, npad, ne, B, tail, &nbc)) return rc;
+    if (int rc = sweep_plan(h, round_up(n, kTile), sweep_predict ? (m + kTile - 1) / kTile : 0, B, 0,
+                            [&](Layout& t, int) { if (sweep_predict) predict_tail(t, B, nullptr, nullptr); }, &nbc))
+      return rc;
   }
   const int P = K + K * d;
   const size_t st_ll = layout_bytes([&](Layout& c) { loglik_stage(c, n, d, P, B); });
@@ -1012,10 +1035,10 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_loglik_grad_batch: analytic gradient is implemented for the Gaussian family only");
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
-  const bool blocked = n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64;
-  if (blocked && !blocked_grad_supported(d, K))
+  const Route route = small_route(Op::Grad, true, n, d, K);
+  if (route == Route::Blocked && !blocked_grad_supported(d, K))
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_loglik_grad_batch: d + K too large for the contraction kernel's LDS");
-  const int nch = blocked ? 0 : small_grad_chunks(n, d);
+  const int nch = route == Route::Blocked ? 0 : small_grad_chunks(n, d);
   double *dX, *dy, *dp, *dg, *dll, *dbeta, *dgp = nullptr;
   int* dst;
   if (int rc = stage(h, [&](Layout& c) {
@@ -1026,58 +1049,35 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
         dll = c.take<double>(B);
         dbeta = c.take<double>(B);
         dst = c.take<int>(B);
-        if (!blocked) dgp = c.take<double>((size_t)B * nch * P);   // partial sums of launch_small_grad
+        if (route != Route::Blocked) dgp = c.take<double>((size_t)B * nch * P);   // partial sums of launch_small_grad
       }))
     return rc;
   DrawView dv;
   if (int frc = draw_view(h, h->fam, dp, B, K, d, &dv)) return frc;
-  if (blocked) {
-    // blocked path: identity rows ride along as extra tile rows, then the tiles of R^-1 are formed (rinv_tile_kernel), turned
-    // into M and contracted with the kernel derivatives (grad_contract_kernel; blocked.hip)
-    const int npad = round_up(n, kTile), nt = npad / kTile, ne = nt;
+  if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, (size_t)B * P)})) return prc;
+  if (route == Route::Blocked) {
+    // identity rows ride along as extra tile rows, then the tiles of R^-1 are formed (rinv_tile_kernel), turned into M and
+    // contracted with the kernel derivatives (grad_contract_kernel; blocked.hip).  Behind the chunk's matrices, from the
+    // next 256-byte line: the contraction's partial sums and alpha for every matrix of the chunk
+    const int npad = round_up(n, kTile);
     const size_t ntiles = blocked_grad_partials(npad);
-    // the workspace: the chunk's matrices, then the contraction's partial sums and alpha for every matrix of the chunk
     BlockedJob job{};
     job.kind = kJobGrad; job.grad = dg; job.Btot = B;
-    auto ws_lay = [&](Layout& w, int nb) {
-      w.take<char>(blocked_ws_bytes(npad, nb, ne));
-      job.gpart = w.take<double>((size_t)nb * ntiles * P);
-      job.alpha = w.take<double>((size_t)nb * npad);
-    };
-    int nbc = 0;
-    if (int rc = plan_chunk(h, blocked_ws_bytes(npad, 1, ne) + sizeof(double) * (ntiles * P + npad), B, kSweepMargin,
-                            [&](int nb) { return layout_bytes([&](Layout& w) { ws_lay(w, nb); }); }, &nbc))
+    if (int rc = run_sweep(h, dX, n, d, dy, dv, B, npad / kTile, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, {dll, dbeta, dst}, &job,
+                           sizeof(double) * (ntiles * P + npad), [&](Layout& w, int nb) {
+                             w.off = Layout::al(w.off);
+                             job.gpart = w.take<double>((size_t)nb * ntiles * P);
+                             job.alpha = w.take<double>((size_t)nb * npad);
+                           }))
       return rc;
-    Layout ws(h->ws);
-    ws_lay(ws, nbc);
-    CCGP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream));
-    CCGP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    CCGP_HIP(hipMemcpyAsync(dp, params, sizeof(double) * (size_t)B * P, hipMemcpyHostToDevice, h->stream));
-    CCGP_HIP(hipMemsetAsync(dst, 0, sizeof(int) * (size_t)B, h->stream));
-    for (int b0 = 0; b0 < B; b0 += nbc) {
-      const int nb = std::min(nbc, B - b0);
-      BlockedWs w = blocked_carve(h->ws, npad, nb, ne);
-      blocked_loglik(h, dX, n, d, dy, dv, b0, nb, npad, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, w, dll, dbeta,
-                     dst, &job);
-    }
-    CCGP_LAUNCH_CHECK();
-    std::vector<int> st(B);
-    if (out_loglik) CCGP_HIP(hipMemcpyAsync(out_loglik, dll, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-    if (out_beta) CCGP_HIP(hipMemcpyAsync(out_beta, dbeta, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipMemcpyAsync(out_grad, dg, sizeof(double) * (size_t)B * P, hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipMemcpyAsync(st.data(), dst, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipStreamSynchronize(h->stream));
-    return report_status(st, status);
-  }
-  if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, (size_t)B * P)})) return prc;
-  {
+  } else {
     ScopedTimer t(h, CCGP_T_FUSED);
-    if (small_reg_inverse_supported(n, d, K))
+    if (route == Route::Reg)
       launch_small_reg_grad(h->stream, dX, n, d, dy, dv, B, sigma2, dll, dbeta, dg, dst);
     else
       launch_small_grad(h->stream, dX, n, d, dy, dv, B, sigma2, dll, dbeta, dg, dst, dgp);
+    CCGP_LAUNCH_CHECK();
   }
-  CCGP_LAUNCH_CHECK();
   return pull_status(h, {piece(dg, out_grad, (size_t)B * P), piece(dll, out_loglik, B), piece(dbeta, out_beta, B)}, dst, B,
                      status);
 } CCGP_GUARD_END(h)
@@ -1172,11 +1172,10 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
   int st = 0;
   CCGP_HIP(hipSetDevice(h->device));
   const bool gauss = h->fam.id == 0;
-  const bool reg_val = gauss && small_reg_supported(n, d, K);
-  const bool reg_inv = gauss && small_reg_inverse_supported(n, d, K);
+  Route route = small_route(out_Rinv ? Op::Inverse : Op::Loglik, gauss, n, d, K);
   const size_t in_d = (size_t)n * d + n + P;                       // X | y | row
   const size_t out_d = 3 + (out_Rinv ? (size_t)n * n : 0);         // ll, beta, status (as one double slot) | R^-1
-  if ((out_Rinv ? reg_inv : reg_val) && ensure_pin(h, sizeof(double) * (in_d + out_d)) == CCGP_OK) {
+  if (route == Route::Reg && ensure_pin(h, sizeof(double) * (in_d + out_d)) == CCGP_OK) {
     // The sequential caller's path (Metro evaluates ONE proposal per logpost call, HX:505-512): latency, not
     // throughput.  Inputs are packed into a pinned host buffer and cross PCIe in ONE copy, the results (log-lik,
     // beta, status[, R^-1]) come back in one: 300 -> ~100 us per call with R.Inv at n = 64, 113 -> ~60 us without (round 2).
@@ -1218,8 +1217,7 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
                                &st);
     if (rc < 0) return rc;
   } else {
-    const bool blocked = h->fam.id != 0 || n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64;
-    const int npad = round_up(n, kTile), nt = npad / kTile;
+    if (route == Route::Reg) route = small_route_inverse_staged(gauss, n, d);   // no pinned buffer
     double *dX, *dy, *dp, *dR, *dll, *dbt;
     int* dst;
     if (int rc2 = stage(h, [&](Layout& c) {
@@ -1232,24 +1230,24 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
           dst = c.take<int>(1);
         }))
       return rc2;
-    if (int rc2 = blocked ? ensure_ws(h, blocked_ws_bytes(npad, 1, nt)) : CCGP_OK) return rc2;
     DrawView dv;
     if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
     CCGP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream));
     CCGP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     CCGP_HIP(hipMemcpyAsync(dp, row.data(), sizeof(double) * P, hipMemcpyHostToDevice, h->stream));
-    CCGP_HIP(hipMemsetAsync(dst, 0, sizeof(int), h->stream));
-    if (blocked) {
+    if (route == Route::Blocked) {
       // identity as extra tile rows of the blocked sweep, then R^-1 = Z Z' tile by tile
       BlockedJob job{};
       job.kind = kJobInverse; job.Rinv = dR;
-      BlockedWs w = blocked_carve(h->ws, npad, 1, nt);
-      blocked_loglik(h, dX, n, d, dy, dv, 0, 1, npad, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, w, dll, dbt, dst, &job);
+      if (int rc2 = run_sweep(h, dX, n, d, dy, dv, 1, round_up(n, kTile) / kTile, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0,
+                              {dll, dbt, dst}, &job, 0, no_scratch))
+        return rc2;
     } else {
+      CCGP_HIP(hipMemsetAsync(dst, 0, sizeof(int), h->stream));
       ScopedTimer t(h, CCGP_T_FUSED);
       launch_small_inverse(h->stream, dX, n, d, dy, dv, 0, sigma2, dR, dll, dbt, dst);
+      CCGP_LAUNCH_CHECK();
     }
-    CCGP_LAUNCH_CHECK();
     CCGP_HIP(hipMemcpyAsync(out_Rinv, dR, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, h->stream));
     CCGP_HIP(hipMemcpyAsync(&ll, dll, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     CCGP_HIP(hipMemcpyAsync(&beta, dbt, sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1276,7 +1274,7 @@ int ccgp_mixed_logdet_designs(ccgp_handle* h, const double* Xs, int n, int d, in
   // more than 128 points (or too wide for the register-resident evaluator): the blocked sweep, one design at a time --
   // its chunk shares ONE design among its matrices, and here every matrix has its own.  The reference's candidate
   // sets are small (BSQ:856-877: a few dozen points); this branch exists so that the entry point has no size limit.
-  const bool blocked = !small_reg_supported(n, d, K, true);
+  const bool blocked = small_route(Op::LogdetDesigns, true, n, d, K) == Route::Blocked;
   const int npad = round_up(n, kTile);
   double *dXs, *dp, *dld, *dy = nullptr, *dll = nullptr, *dbeta = nullptr;
   int* dst;
@@ -1324,7 +1322,7 @@ int ccgp_mixed_logdet_grad_designs(ccgp_handle* h, const double* Xs, int n, int 
     return fail(h, CCGP_EINVAL, "ccgp_mixed_logdet_grad_designs: n_fixed must lie in [0, n)");
   if (h->fam.id != 0)
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_mixed_logdet_grad_designs: Gaussian family only (BSQ:856-948)");
-  if (!small_reg_design_grad_supported(n, d, K))
+  if (small_route(Op::DesignGrad, true, n, d, K) == Route::Unsupported)
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_mixed_logdet_grad_designs: the design does not fit the register-resident "
                                       "evaluator (n <= 128 and its LDS share: R^-1 and the design of one matrix)");
   CCGP_HIP(hipSetDevice(h->device));
@@ -1461,27 +1459,14 @@ static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const dou
                        const double* dXtest, int m, double sigma2, double* d_mean, double* d_var, double* d_beta,
                        int* d_status) {
   const int K = dv.K, S = dv.ldp;
-  if (dv.fam.id != 0 || n > kSmallMaxN || small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64 ||
-      !small_reg_supported(n, d, K, false, true)) {
-    // blocked path: the m cross-correlation rows ride along as extra tile rows of the sweep
-    const int npad = round_up(n, kTile), ne = (m + kTile - 1) / kTile;
-    // scratch for outputs the caller did not ask for lives behind the matrices
-    auto tail_lay = [&](Layout& t) { return predict_tail(t, S, d_beta, d_status); };
-    int nbc = 0;
-    if (int rc = sweep_chunk(h, npad, ne, S, layout_bytes(tail_lay), &nbc)) return rc;
-    Layout tail(static_cast<char*>(h->ws) + blocked_ws_bytes(npad, nbc, ne));
-    const PredictTail sc = tail_lay(tail);
-    CCGP_HIP(hipMemsetAsync(sc.status, 0, sizeof(int) * (size_t)S, h->stream));
+  if (small_route(Op::Predict, dv.fam.id == 0, n, d, K) == Route::Blocked) {
+    // the m cross-correlation rows ride along as extra tile rows of the sweep; scratch for the outputs the caller did not
+    // ask for lives behind the matrices
+    SweepOut sc{};
     BlockedJob pr{};
     pr.kind = kJobPredict; pr.Xtest = dXtest; pr.m = m; pr.S = S; pr.mean = d_mean; pr.var = d_var;
-    for (int b0 = 0; b0 < S; b0 += nbc) {
-      const int nb = std::min(nbc, S - b0);
-      BlockedWs w = blocked_carve(h->ws, npad, nb, ne);
-      blocked_loglik(h, dX, n, d, dy, dv, b0, nb, npad, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, w, sc.ll, sc.beta,
-                     sc.status, &pr);
-    }
-    CCGP_LAUNCH_CHECK();
-    return CCGP_OK;
+    return run_sweep(h, dX, n, d, dy, dv, S, (m + kTile - 1) / kTile, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, sc, &pr, 0,
+                     [&](Layout& t, int) { sc = predict_tail(t, S, d_beta, d_status); });
   }
   {
     ScopedTimer t(h, CCGP_T_FUSED);
@@ -1628,7 +1613,7 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
   if (int frc = draw_view(h, h->fam, nullptr, S, K, d, &dv)) return frc;
   CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
-  const bool fused = h->fam.id == 0 && n <= kSmallMaxN && small_lds_bytes(n, d, 1) <= (size_t)kLdsBytes - 64;
+  const bool fused = small_route(Op::Predict, h->fam.id == 0, n, d, K) == Route::Reg;
   const int npad = round_up(n, kTile);
   if (!fused && S > 65535)   // the draw index is a grid y / z dimension in cov_kernel, rhs_rows_kernel, ...
     return fail(h, CCGP_EINVAL, "ccgp_factor_batch: at most 65535 factors per set on the blocked path (n > 128)");

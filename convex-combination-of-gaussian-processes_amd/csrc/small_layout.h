@@ -19,7 +19,7 @@
 
 namespace ccgp {
 
-constexpr int kSmallMaxN = 128;  // n <= this goes to the small-n tier: the register-resident evaluator, small.hip for two leftovers
+constexpr int kSmallMaxN = 128;  // the small-n evaluators take no more rows; which call they serve below it: small_route (foot of this file)
 constexpr int kMaxD = 64;        // input dimensions supported by the covariance kernels
 constexpr int kMaxK = 8;         // component GPs per draw
 constexpr int kLdsBytes = 160 * 1024;
@@ -150,7 +150,7 @@ inline int small_pick_mtile(int n, int d, int m) {
   return mt;
 }
 
-// ---- routing predicates (capi.hip) -------------------------------------------------------------------------------------
+// ---- does an instance fit: the building blocks of small_route below ---------------------------------------------------
 // the register-resident evaluator: likelihood, log det of per-design matrices, prediction by the extra-row scheme
 inline bool small_reg_supported(int n, int d, int K, bool per_design = false, bool predict = false) {
   if (n > 128) return false;
@@ -176,5 +176,47 @@ inline bool small_reg_inverse_supported(int n, int d, int K, bool per_design = f
   return lds_fits(reg_lds_doubles(16, NB, NB + 1, true, per_design, n, d, K));
 }
 inline bool small_reg_design_grad_supported(int n, int d, int K) { return small_reg_inverse_supported(n, d, K, true); }
+
+// ---- which tier serves which call: decided HERE, once per call (capi.hip branches on the result) ------------------------
+//   Reg      the register-resident evaluator (small_reg.hip)
+//   Lds      the in-LDS evaluator (small.hip): the gradient and solve(R) of shapes whose INV instance does not fit
+//   Blocked  the blocked sweep over materialised matrices (cov.hip + blocked.hip): any n, any kernel family
+// `gauss`: the Gaussian family; the others exist on the blocked sweep only.  Grad, LogdetDesigns and DesignGrad refuse them
+// before they ask, so their routes do not look at it.  For Grad the caller turns Blocked into a refusal when the
+// contraction kernel cannot take (d, K) (blocked_grad_supported, blocked.hip).
+// What is decided after the route, from more than the shape, stays with its owner: kept-factor or extra-row prediction
+// (capi.hip: option, small_reg_sites_supported, scratch), the grid of an instance (small_reg.hip: dispatch), the sweep's
+// schedule (blocked.hip).  tests/host_small/small_layout_check.cpp holds this function, shape by shape, to the expressions
+// it replaced and prints the table; tests/test_gpu_routes.py runs one shape of every cell.
+enum class Op { Loglik, Predict, Inverse, Grad, LogdetDesigns, DesignGrad };
+enum class Route { Reg, Lds, Blocked, Unsupported };
+// where small.hip's one-row carve fits: the Lds tier's domain
+inline bool small_lds_tier(int n, int d) { return n <= kSmallMaxN && lds_fits(SmallCarve(n, d, kMaxK, 1).total); }
+// Op::Inverse without its Reg route: what ccgp_logpost falls back to when that route's pinned host buffer cannot be had
+inline Route small_route_inverse_staged(bool gauss, int n, int d) {
+  return gauss && small_lds_tier(n, d) ? Route::Lds : Route::Blocked;
+}
+inline Route small_route(Op op, bool gauss, int n, int d, int K) {
+  const bool lds_tier = small_lds_tier(n, d);
+  switch (op) {
+    case Op::Loglik:
+      return gauss && small_reg_supported(n, d, K) ? Route::Reg : Route::Blocked;
+    case Op::Predict:
+      // lds_tier is a frozen legacy boundary (the in-LDS prediction that used to sit between the two is gone): every shape
+      // inside it has its register instance (the check program's `dead` line), and so have the 4216 shapes of n <= 128
+      // outside it (its `predict_outside_lds`), which the blocked sweep keeps serving until the boundary is moved
+      return gauss && lds_tier && small_reg_supported(n, d, K, false, true) ? Route::Reg : Route::Blocked;
+    case Op::Inverse:
+      return gauss && small_reg_inverse_supported(n, d, K) ? Route::Reg : small_route_inverse_staged(gauss, n, d);
+    case Op::Grad:
+      if (!lds_tier) return Route::Blocked;
+      return small_reg_inverse_supported(n, d, K) ? Route::Reg : Route::Lds;
+    case Op::LogdetDesigns:
+      return small_reg_supported(n, d, K, true) ? Route::Reg : Route::Blocked;
+    case Op::DesignGrad:
+      return small_reg_design_grad_supported(n, d, K) ? Route::Reg : Route::Unsupported;
+  }
+  return Route::Unsupported;
+}
 
 }  // namespace ccgp

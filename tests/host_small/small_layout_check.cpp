@@ -1,8 +1,10 @@
 // CPU check of csrc/small_layout.h over every shape the entry points accept (n 1..128, d 1..kMaxD, K 1..kMaxK) and every
 // (G, NB, NE, inv, per-design) instance the dispatchers of small_reg.hip can form.  The `old` namespace holds the hand-summed
 // formulas the header replaced, written out as they stood before it, so that sizes and routes are pinned to those values.
-// Prints counts and, with "table" as argument, one line per (n, d) for tests/test_small_layout.py to compare the Python
-// mirrors of tests/test_gpu_gradient_exact.py against.
+// small_route is held, over n 1..129, both families and all six ops, to the route expressions the entry points of capi.hip
+// carried before it (old::route).  Prints counts and, with "table" as argument, one line per (n, d) -- the gradient's route
+// letters from small_route itself -- for tests/test_small_layout.py to compare the Python mirrors of
+// tests/test_gpu_gradient_exact.py against; with "witness", one shape per reachable (op, route) cell (tests/route_witnesses.py).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -78,6 +80,39 @@ int small_pick_mtile(int n, int d, int m) {
   while (mt > 1 && small_lds_bytes(n, d, mt) > budget) --mt;
   return mt;
 }
+// The route decisions as the entry points of capi.hip wrote them out, each in its own words, before small_route: over the
+// header's predicates (which the loop in main holds to the formulas above).
+using ccgp::kLdsBytes;
+using ccgp::kSmallMaxN;
+bool loglik_reg(bool gauss, int n, int d, int K) { return gauss && ccgp::small_reg_supported(n, d, K); }   // loglik_run
+bool reserve_sweep(bool gauss, int n) { return n > kSmallMaxN || !gauss; }                                  // ccgp_reserve
+bool grad_blocked(int n, int d) { return n > kSmallMaxN || ccgp::small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64; }
+bool grad_reg(int n, int d, int K) { return ccgp::small_reg_inverse_supported(n, d, K); }                   // ccgp_loglik_grad_batch
+bool logpost_reg_val(bool gauss, int n, int d, int K) { return gauss && ccgp::small_reg_supported(n, d, K); }
+bool logpost_reg_inv(bool gauss, int n, int d, int K) { return gauss && ccgp::small_reg_inverse_supported(n, d, K); }
+bool logpost_blocked(bool gauss, int n, int d) {
+  return !gauss || n > kSmallMaxN || ccgp::small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64;
+}
+bool designs_blocked(int n, int d, int K) { return !ccgp::small_reg_supported(n, d, K, true); }          // ccgp_mixed_logdet_designs
+bool design_grad_ok(int n, int d, int K) { return ccgp::small_reg_design_grad_supported(n, d, K); }
+bool predict_blocked(bool gauss, int n, int d, int K) {                                                   // predict_run
+  return !gauss || n > kSmallMaxN || ccgp::small_lds_bytes(n, d, 1) > (size_t)kLdsBytes - 64 ||
+         !ccgp::small_reg_supported(n, d, K, false, true);
+}
+bool fused(bool gauss, int n, int d) {                                                                    // ccgp_factor_batch
+  return gauss && n <= kSmallMaxN && ccgp::small_lds_bytes(n, d, 1) <= (size_t)kLdsBytes - 64;
+}
+Route route(Op op, bool gauss, int n, int d, int K) {
+  switch (op) {
+    case Op::Loglik: return loglik_reg(gauss, n, d, K) ? Route::Reg : Route::Blocked;
+    case Op::Predict: return predict_blocked(gauss, n, d, K) ? Route::Blocked : Route::Reg;
+    case Op::Inverse: return logpost_reg_inv(gauss, n, d, K) ? Route::Reg : logpost_blocked(gauss, n, d) ? Route::Blocked : Route::Lds;
+    case Op::Grad: return grad_blocked(n, d) ? Route::Blocked : grad_reg(n, d, K) ? Route::Reg : Route::Lds;
+    case Op::LogdetDesigns: return designs_blocked(n, d, K) ? Route::Blocked : Route::Reg;
+    case Op::DesignGrad: return design_grad_ok(n, d, K) ? Route::Reg : Route::Unsupported;
+  }
+  return Route::Unsupported;
+}
 }  // namespace old
 
 static long failures = 0;
@@ -140,8 +175,54 @@ static void check_reg(int G, int NB, int NE, bool inv, bool per_design, int n, i
   check_order(r, count, (long)total, "RegCarve", n, d, K);
 }
 
+// small_route over n 1..129, every d and K, both families and all six ops against the expressions it replaced.  Prints
+// the counts of its last line; with `witness`, instead, the first shape (smallest n, then d, then K) of every reachable
+// (op, route) cell of the Gaussian family, and of the shapes where ccgp_reserve now reserves the sweep's workspace.
+static const char* const kOpNames[] = {"loglik", "predict", "inverse", "grad", "logdet_designs", "design_grad"};
+static const char kRouteLetters[] = "rlbu";
+static void check_routes(bool witness) {
+  long reserve_m0 = 0, reserve_m = 0, predict_outside_lds = 0;
+  bool seen[6][4] = {};
+  bool seen_reserve = false;
+  for (int n = 1; n <= kSmallMaxN + 1; ++n)
+    for (int d = 1; d <= kMaxD; ++d)
+      for (int K = 1; K <= kMaxK; ++K)
+        for (int gauss = 1; gauss >= 0; --gauss) {
+          for (int o = 0; o < 6; ++o) {
+            const Op op = (Op)o;
+            const Route r = small_route(op, gauss, n, d, K);
+            CHECK(r == old::route(op, gauss, n, d, K), "small_route %s gauss=%d n=%d d=%d K=%d", kOpNames[o], gauss, n, d, K);
+            if (witness && gauss && !seen[o][(int)r] && (op != Op::Inverse || K == 2)) {   // ccgp_logpost has two components
+              seen[o][(int)r] = true;
+              std::printf("%s %c %d %d %d\n", kOpNames[o], kRouteLetters[(int)r], n, d, K);
+            }
+          }
+          const Route ll = small_route(Op::Loglik, gauss, n, d, K), pr = small_route(Op::Predict, gauss, n, d, K);
+          CHECK((pr == Route::Reg) == old::fused(gauss, n, d), "predict route and ccgp_factor_batch's fused n=%d d=%d K=%d", n, d, K);
+          CHECK(small_route_inverse_staged(gauss, n, d) == (old::logpost_blocked(gauss, n, d) ? Route::Blocked : Route::Lds),
+                "staged inverse gauss=%d n=%d d=%d", gauss, n, d);
+          CHECK(pr != Route::Reg || ll == Route::Reg, "prediction on the register evaluator without the likelihood n=%d d=%d K=%d", n, d, K);
+          // ccgp_reserve: the sweep's workspace without test sites (m = 0) and with them
+          const bool was = old::reserve_sweep(gauss, n), now_m0 = ll == Route::Blocked, now_m = now_m0 || pr == Route::Blocked;
+          CHECK(!was || now_m0, "ccgp_reserve stopped reserving at gauss=%d n=%d d=%d K=%d", gauss, n, d, K);
+          reserve_m0 += now_m0 != was;
+          reserve_m += now_m != was;
+          if (witness && now_m != was && !seen_reserve) {
+            seen_reserve = true;
+            std::printf("reserve b %d %d %d\n", n, d, K);
+          }
+          // is Predict's small.hip clause redundant?  shapes whose prediction instance fits outside small.hip's domain
+          predict_outside_lds += gauss && n <= kSmallMaxN && small_reg_supported(n, d, K, false, true) && pr != Route::Reg;
+        }
+  if (!witness) std::printf("reserve %ld %ld predict_outside_lds %ld\n", reserve_m0, reserve_m, predict_outside_lds);
+}
+
 int main(int argc, char** argv) {
   const bool table = argc > 1 && !std::strcmp(argv[1], "table");
+  if (argc > 1 && !std::strcmp(argv[1], "witness")) {
+    check_routes(true);
+    return failures != 0;
+  }
   long dead_loglik = 0, dead_predict = 0, lds_grad = 0, lds_inverse_k2 = 0, old_lds_grad = 0, old_lds_inverse_k2 = 0;
   for (int n = 1; n <= kSmallMaxN; ++n) {
     const FacLayout fl(n);
@@ -200,13 +281,12 @@ int main(int argc, char** argv) {
         // routes: the in-LDS value and prediction routes are gone; the gradient and solve(R) still reach small.hip
         dead_loglik += small0 && !small_reg_supported(n, d, K);
         dead_predict += small1 && !small_reg_supported(n, d, K, false, true);
-        const bool lds = small1 && !small_reg_inverse_supported(n, d, K);
         const bool lds_old = old::small_lds_bytes(n, d, 1) <= old::kLds - 64 && !old::small_reg_inverse_supported(n, d, K);
-        lds_grad += lds;
+        lds_grad += small_route(Op::Grad, true, n, d, K) == Route::Lds;
         old_lds_grad += lds_old;
-        if (K == 2) { lds_inverse_k2 += lds; old_lds_inverse_k2 += lds_old; }
+        if (K == 2) { lds_inverse_k2 += small_route(Op::Inverse, true, n, d, K) == Route::Lds; old_lds_inverse_k2 += lds_old; }
         inv_bits[K - 1] = small_reg_inverse_supported(n, d, K) ? '1' : '0';
-        routes[K - 1] = !small1 ? 'b' : small_reg_inverse_supported(n, d, K) ? 'r' : 'l';
+        routes[K - 1] = kRouteLetters[(int)small_route(Op::Grad, true, n, d, K)];
       }
       if (table) std::printf("%d %d %zu %s %s\n", n, d, small_lds_bytes(n, d, 1), inv_bits, routes);
     }
@@ -216,6 +296,7 @@ int main(int argc, char** argv) {
         "limits");
   CHECK(dead_loglik == 0 && dead_predict == 0, "shapes that needed the removed routes: %ld likelihood, %ld prediction", dead_loglik, dead_predict);
   CHECK(lds_grad == old_lds_grad && lds_inverse_k2 == old_lds_inverse_k2 && lds_grad > 0 && lds_inverse_k2 > 0, "in-LDS routes");
+  check_routes(false);
   std::printf("dead %ld %ld lds_grad %ld lds_inverse_k2 %ld\n", dead_loglik, dead_predict, lds_grad, lds_inverse_k2);
   if (failures) { std::fprintf(stderr, "%ld checks failed\n", failures); return 1; }
   std::printf("ok\n");

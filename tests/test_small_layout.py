@@ -7,13 +7,20 @@ and predicate equals the hand-summed formula it replaced (written out in the che
 Routes.  No accepted shape has the in-LDS tier (csrc/small.hip) fit while the register-resident evaluator does not, for
 the likelihood or for prediction: those two in-LDS routes are gone.  small.hip is still reached by the gradient at 2711
 shapes (3227 with the exp table) and by solve(R) of ccgp_logpost, K = 2, at 235 (d, n) pairs (296): counted twice by the
-check program, once from the header and once from the replaced formulas, and pinned here."""
+check program, once from small_route and once from the replaced formulas, and pinned here.
+
+small_route (which tier serves which call) is held by the same program to the route expressions the entry points carried
+before it, over n 1..129, both kernel families and all six ops; prediction's route equals ccgp_factor_batch's former
+`fused` on every shape.  Pinned here: the shapes at which ccgp_reserve now reserves the sweep's workspace and did not
+before, and one witness shape per reachable (op, route) cell (tests/route_witnesses.py, which tests/test_gpu_routes.py
+runs on the device)."""
 import os
 import shutil
 import subprocess
 
 import pytest
 
+import route_witnesses
 import test_gpu_gradient_exact as grad_routes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,18 +32,20 @@ LDS_ROUTE_COUNTS = {0: (2711, 235), 1: (3227, 296)}      # exp table off / on: (
 _RUNS = {}
 
 
-def _run(table, tmp_path_factory):
-    """stdout lines of the check program built with CCGP_SMALL_EXP_TABLE = table (one build and run per setting)"""
+def _run(table, tmp_path_factory, mode="table"):
+    """stdout lines of the check program built with CCGP_SMALL_EXP_TABLE = table (one build per setting, one run per mode)"""
     if shutil.which("g++") is None:
         pytest.skip("no g++")
     if table not in _RUNS:
         exe = str(tmp_path_factory.mktemp("small_layout") / "small_layout_check")
         subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-DCCGP_SMALL_EXP_TABLE=%d" % table, "-I", CSRC, SRC,
                         "-o", exe], check=True)
-        r = subprocess.run([exe, "table"], capture_output=True, text=True, timeout=60)
+        _RUNS[table] = {"exe": exe}
+    if mode not in _RUNS[table]:
+        r = subprocess.run([_RUNS[table]["exe"], mode], capture_output=True, text=True, timeout=60)
         assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-        _RUNS[table] = r.stdout.splitlines()
-    return _RUNS[table]
+        _RUNS[table][mode] = r.stdout.splitlines()
+    return _RUNS[table][mode]
 
 
 @pytest.mark.parametrize("table", [0, 1], ids=["poly", "table"])
@@ -48,10 +57,22 @@ def test_carves_and_predicates(table, tmp_path_factory):
     assert (int(words[4]), int(words[6])) == LDS_ROUTE_COUNTS[table]
 
 
+@pytest.mark.parametrize("table", [0, 1], ids=["poly", "table"])
+def test_route_function_counts_and_witnesses(table, tmp_path_factory):
+    """The exhaustive equality of small_route with the replaced expressions is the program's exit status (_run); here the
+    counts of its `reserve` line and the witness list."""
+    words = _run(table, tmp_path_factory)[-3].split()
+    assert words[0] == "reserve" and words[3] == "predict_outside_lds"
+    assert (int(words[1]), int(words[2])) == route_witnesses.RESERVE_CHANGES[table]
+    assert int(words[4]) == route_witnesses.PREDICT_OUTSIDE_LDS[table]
+    got = [(w[0], w[1], int(w[2]), int(w[3]), int(w[4])) for w in (l.split() for l in _run(table, tmp_path_factory, "witness"))]
+    assert got == route_witnesses.WITNESSES[table]
+
+
 def test_python_mirrors_of_the_route_predicates(tmp_path_factory):
     """small_lds_bytes, small_reg_inverse_supported and route of tests/test_gpu_gradient_exact.py (which mirror the default
     build: no exp table) against the header, shape by shape."""
-    rows = _run(0, tmp_path_factory)[:-2]
+    rows = _run(0, tmp_path_factory)[:-3]
     assert len(rows) == 128 * 64
     name = {"b": "blocked", "r": "reg", "l": "lds"}
     for line in rows:
