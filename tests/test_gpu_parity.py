@@ -10,6 +10,7 @@ import math
 import numpy as np
 import pytest
 
+import exact_designs as ex
 from conftest import golden, load_gv, load_hyper, load_maximin, load_qian, synthetic_design
 from oracle import ccgp_oracle as orc
 from oracle import mp_check
@@ -679,6 +680,14 @@ def test_non_positive_definite_maps_to_na(handle):
     Pb = orc.params_from_iso(0.6, 2.0, 9.0, 3)[None]
     llb, _, stb = handle.loglik_batch(X, yy, 2, Pb, 1.0, 0, 0.0)
     assert stb[0] > 0 and math.isnan(llb[0])
+    # the same duplicates (row 41 on an earlier row, row 251 on an earlier row) on inputs whose outcome is exact in any
+    # arithmetic (tests/exact_designs.py): there the status is the pivot itself, and the first one where two are bad
+    for n, seps in ((64, (9, 41)), (300, (18, 251))):
+        E = ex.ExactDesign(n, seps)
+        rows, want = E.draws(2, [(1,), (0,), (1, 0), ()])
+        lle, be, ste = handle.loglik_batch(E.X, E.y, 2, rows, 10.0, 0, 0.0)
+        assert np.array_equal(ste, want) and list(want) == [seps[1], seps[0], seps[0], 0]
+        assert np.isnan(lle[:3]).all() and np.isnan(be[:3]).all() and np.isfinite(lle[3]) and np.isfinite(be[3])
 
 
 def test_chunked_batches_equal_one_pass(handle):
@@ -698,6 +707,10 @@ def test_chunked_batches_equal_one_pass(handle):
         Xd = X.copy()
         Xd[120] = Xd[7]                                     # exactly singular: pivot 121 is 0 up to rounding
         lld, _, std = handle.loglik_batch(Xd, y, 2, P, 1.0, 0, 0.0)
+        # the same duplicate where pivot 121 is 0 in any arithmetic (tests/exact_designs.py): every such draw must fail there
+        E = ex.ExactDesign(300, (121,))
+        rows_e, want_e = E.draws(2, [(), (0,), (), (0,), (0,), (), (0,)])
+        lle, _, ste = handle.loglik_batch(E.X, E.y, 2, rows_e, 1.0, 0, 0.0)
     finally:
         handle.set_workspace_limit(200 << 30)
     np.testing.assert_array_equal(ll0, ll1)
@@ -709,6 +722,8 @@ def test_chunked_batches_equal_one_pass(handle):
     # 1-based index, NaN value -- the reference's NA) or, for some draws, as a positive rounding residue
     assert set(std.tolist()) <= {0, 121} and np.count_nonzero(std) >= 4
     assert np.all(np.isnan(lld[std > 0]))
+    assert ste.tolist() == want_e.tolist() == [0, 121, 0, 121, 121, 0, 121]
+    assert np.isnan(lle[want_e > 0]).all() and np.isfinite(lle[want_e == 0]).all()
 
 
 def test_edge_shapes(handle):
