@@ -626,6 +626,13 @@ def _chol_inverse(A, dtype):
             raise np.linalg.LinAlgError("dpotri failed")
         inv = np.tril(inv) + np.tril(inv, -1).T
         return inv, 2.0 * float(np.log(np.diag(c)).sum())
+    L = _chol_lower(A, dtype)
+    Z = _lower_inverse(L, dtype)
+    return Z.T @ Z, dtype(2) * np.log(np.diag(L)).sum()
+
+
+def _chol_lower(A, dtype):
+    """The lower Cholesky factor of a symmetric positive definite A in long double: a column Cholesky."""
     require_extended_precision()
     A = np.asarray(A, dtype=dtype)
     n = A.shape[0]
@@ -636,11 +643,17 @@ def _chol_inverse(A, dtype):
             raise np.linalg.LinAlgError("not positive definite at pivot %d" % j)
         L[j, j] = np.sqrt(v[0])
         L[j + 1:, j] = v[1:] / L[j, j]
-    Z = np.zeros((n, n), dtype=dtype)           # Z = L^-1, lower triangular
+    return L
+
+
+def _lower_inverse(L, dtype):
+    """Z = L^-1 (lower triangular) by forward substitution on the identity, vectorised over rows."""
+    n = L.shape[0]
+    Z = np.zeros((n, n), dtype=dtype)
     for i in range(n):
         Z[i, :i] = -(L[i, :i] @ Z[:i, :i]) / L[i, i]
         Z[i, i] = dtype(1) / L[i, i]
-    return Z.T @ Z, dtype(2) * np.log(np.diag(L)).sum()
+    return Z
 
 
 def _sq_dist(X, k, dtype):
@@ -739,14 +752,16 @@ def solve_inverse_exact(R, dtype=np.longdouble):
     return inv
 
 
-def conditioned_row(X, K, d, rng, kappa_max=1e8):
+def conditioned_row(X, K, d, rng, kappa_max=1e8, w=None):
     """A random anisotropic draw (w_1..w_K, theta_c,k) for the gradient tests whose mixed matrix has cond1 <= kappa_max:
     length scales spread over a factor 20 around the design spacing (n^(-1/d)), the last component rough, then every theta
-    scaled up by 1.5 until the fp64 1-norm condition number is within bound.  Returns (row, cond1)."""
+    scaled up by 1.5 until the fp64 1-norm condition number is within bound.  w: the weights to use instead of random ones
+    (the random ones are still drawn, so the length scales do not depend on it).  Returns (row, cond1)."""
     X = np.asarray(X, dtype=np.float64)
     n = X.shape[0]
     rough = 2.0 * n ** (2.0 / d) / d
-    w = 0.2 + 0.6 * rng.random(K)
+    w_drawn = 0.2 + 0.6 * rng.random(K)
+    w = w_drawn if w is None else np.asarray(w, dtype=np.float64)
     Th = rough * np.exp(rng.uniform(np.log(0.05), 0.0, size=(K, d)))
     Th[-1] = rng.uniform(rough, 2.0 * rough, d)
     for _ in range(200):
@@ -755,3 +770,158 @@ def conditioned_row(X, K, d, rng, kappa_max=1e8):
             return np.concatenate([w, Th.ravel()]), kappa
         Th = Th * 1.5
     raise RuntimeError("no draw with cond1 <= %g" % kappa_max)
+
+
+# --------------------------------------------------------------------------- predict.post tables, extended precision
+# The tables of predict.post (HX:655-673) in the factor's metric, as every device route computes them:
+#   ww = r'R^-1 r,  z1w = 1'R^-1 r,  zyw = y'R^-1 r,  s11 = 1'R^-1 1,  beta = 1'R^-1 y / s11,
+#   mean = beta + (zyw - beta z1w),  var = sigma2 (1 - ww + (1 - z1w)^2 / s11),
+# from the pieces of the gradient reference above (direct squared differences, the hand-written Cholesky in long double).
+# The acceptance bands of tests/test_gpu_predict_exact.py are predict_bands(); why this C is in that module's docstring.
+PREDICT_TOL_C = 128.0
+
+
+def cross_corr(Xtest, X, theta_c, dtype=np.float64):
+    """m x n correlations exp(-sum_k theta_ck (x_tk - x_ak)^2) between test sites and the design, direct form, in dtype."""
+    X = np.asarray(X, dtype=np.float64)
+    Xtest = np.asarray(Xtest, dtype=np.float64)
+    acc = np.zeros((Xtest.shape[0], X.shape[0]), dtype=dtype)
+    for k in range(X.shape[1]):
+        acc += dtype(theta_c[k]) * (np.asarray(Xtest[:, k], dtype=dtype)[:, None] - np.asarray(X[:, k], dtype=dtype)[None, :]) ** 2
+    return np.exp(-acc)
+
+
+def predict_factor(X, y, row, K, d, dtype=np.longdouble):
+    """What a draw's tables share between test sites, in dtype: dict(R, L, Rinv, o = R^-1 1, s11 = 1'o, beta, g = R^-1 (y -
+    beta 1), Rinv_y) of the normalised mixed matrix R = sum_c w_c^2 R_c / sum_c w_c^2 (HX:408-415)."""
+    dtype = np.dtype(dtype).type
+    X = np.asarray(X, dtype=np.float64)
+    yv = np.asarray(y, dtype=dtype).reshape(-1)
+    n = yv.shape[0]
+    w, Th = unpack_params(row, K, d)
+    w2 = np.asarray(w, dtype=dtype) ** 2
+    R = np.zeros((n, n), dtype=dtype)
+    for c in range(K):
+        R += w2[c] * component_corr(X, Th[c], dtype)
+    R = R / w2.sum()
+    L = _chol_lower(R, dtype)
+    Z = _lower_inverse(L, dtype)
+    Rinv = Z.T @ Z
+    o = Rinv.sum(axis=0)
+    s11 = o.sum()
+    Rinv_y = Rinv @ yv
+    beta = (o @ yv) / s11
+    g = Rinv @ (yv - beta)
+    return dict(R=R, L=L, Rinv=Rinv, o=o, s11=s11, beta=beta, g=g, Rinv_y=Rinv_y, y=yv, w2=w2, Th=Th)
+
+
+def predict_parts(X, y, row, K, d, sigma2, Xtest, dtype=np.longdouble, factor=None):
+    """The tables of one draw at the rows of Xtest in dtype (default long double: no LAPACK, about 1e-19 relative):
+    dict(mean[m], var[m], beta, s11, r[m, n], a[m, n] = (R^-1 r)', g, o, ww[m], z1w[m], zyw[m], W = |L| |L|', rho, rho_t[m]).
+    factor: a predict_factor() of the same draw, to share it between site sets."""
+    dtype = np.dtype(dtype).type
+    f = factor if factor is not None else predict_factor(X, y, row, K, d, dtype)
+    Xtest = np.atleast_2d(np.asarray(Xtest, dtype=np.float64))
+    r = np.zeros((Xtest.shape[0], f["R"].shape[0]), dtype=dtype)
+    for c in range(K):
+        r += f["w2"][c] * cross_corr(Xtest, X, f["Th"][c], dtype)
+    r = r / f["w2"].sum()
+    a = r @ f["Rinv"]
+    ww = (a * r).sum(axis=1)
+    z1w = r @ f["o"]
+    zyw = r @ f["Rinv_y"]
+    u = dtype(1) - z1w
+    mean = f["beta"] + r @ f["g"]
+    var = dtype(sigma2) * (dtype(1) - ww + u * u / f["s11"])
+    aL = np.abs(np.asarray(f["L"], dtype=np.float64))
+    Th = np.asarray(f["Th"], dtype=np.float64)
+    return dict(mean=mean, var=var, beta=f["beta"], s11=f["s11"], r=r, a=a, g=f["g"], o=f["o"], ww=ww, z1w=z1w, zyw=zyw,
+                W=aL @ aL.T, y=f["y"], rho=expanded_form_magnitude(X, row, K, d),
+                rho_t=2.0 * ((Xtest ** 2) @ Th.T).max(axis=1))
+
+
+def predict_bands(parts, sigma2, c=PREDICT_TOL_C):
+    """First-order bands dict(mean[m], var[m], beta, s11) of a device table around predict_parts().  The device errs in the
+    entries of R and r -- a relative eps (1 + rho) each, rho the size of the expanded exponent's terms (for an entry of r the
+    larger of the design's and the site's own) -- and in the factorisation and the solves, a backward error |dR| <= eta W with
+    W = |L| |L|' >= |R|.  For a bilinear form p'R^-1 q both give
+        Q(p, q) = eta (|R^-1 p|' W |R^-1 q| + |R^-1 p|' |q| + |p|' |R^-1 q|),   eta = c eps (1 + rho),
+    and from there
+        var  : sigma2 (Q(r, r) + 2 |u| Q(1, r) / s11 + u^2 Q(1, 1) / s11^2 + eps (1 + ww + u^2 / s11)),  u = 1 - z1w
+        beta : (Q(1, y - beta 1) + 2 |beta| Q(1, 1)) / s11 + eps sum_i |o_i y_i| / s11
+        mean : Q(r, y - beta 1) + (1 + |z1w|) band_beta + eps (|beta| + |r|' |g|).
+    beta: the device divides 1'R^-1 y by 1'R^-1 1, two solves with their own roundings, so the error of the second does not
+    cancel against the first's: hence the |beta| Q(1, 1) beside the form in y - beta 1; the last term is the size of the sum
+    before cancellation (loglik_beta_scales).  No condition number and no floor anywhere: on a training point R^-1 r is a unit
+    vector and the variance band is a few eta sigma2."""
+    eps = float(np.finfo(np.float64).eps)
+    W, r, a, g, o, y, ww, z1w = (np.asarray(parts[k], dtype=np.float64) for k in ("W", "r", "a", "g", "o", "y", "ww", "z1w"))
+    beta, s11 = float(parts["beta"]), float(parts["s11"])
+    A, G, O, Rr = np.abs(a), np.abs(g), np.abs(o), np.abs(r)
+    eta0 = c * eps * (1.0 + parts["rho"])
+    eta = c * eps * (1.0 + np.maximum(parts["rho"], parts["rho_t"]))
+    yc = np.abs(y - beta)
+    one = np.ones_like(O)
+    AW = A @ W
+    q_ww = eta * ((AW * A).sum(axis=1) + 2.0 * (A * Rr).sum(axis=1))
+    q_z1w = eta * (AW @ O + A @ one + Rr @ O)
+    q_s11 = eta0 * (O @ W @ O + 2.0 * O.sum())
+    q_ry = eta * (AW @ G + A @ yc + Rr @ G)
+    q_1y = eta0 * (O @ W @ G + O @ yc + G.sum())
+    u = 1.0 - z1w
+    band_var = sigma2 * (q_ww + 2.0 * np.abs(u) * q_z1w / s11 + u * u * q_s11 / s11 ** 2 + eps * (1.0 + ww + u * u / s11))
+    band_beta = (q_1y + 2.0 * abs(beta) * q_s11) / s11 + eps * float(O @ np.abs(y)) / s11
+    band_mean = q_ry + (1.0 + np.abs(z1w)) * band_beta + eps * (abs(beta) + Rr @ G)
+    return dict(mean=band_mean, var=band_var, beta=band_beta, s11=q_s11)
+
+
+def _ldl_lower(A):
+    """fp64 L' D L'^T of a symmetric positive definite A: (unit lower L', D), column by column as the device eliminates."""
+    A = np.asarray(A, dtype=np.float64)
+    n = A.shape[0]
+    Lp = np.eye(n)
+    D = np.empty(n)
+    for j in range(n):
+        v = A[j:, j] - Lp[j:, :j] @ (D[:j] * Lp[j, :j])
+        if not v[0] > 0:
+            raise np.linalg.LinAlgError("not positive definite at pivot %d" % j)
+        D[j] = v[0]
+        Lp[j + 1:, j] = v[1:] * (1.0 / D[j])
+    return Lp, D
+
+
+def predict_device_restatement(X, y, row, K, d, Xtest):
+    """A plain fp64 restatement of the device's own formula, the yardstick PREDICT_TOL_C is measured against (and the subject
+    of the planted mistakes of tests/test_oracle.py): expanded-form exponents (corr_matrix / corr_vec), the L' D L'^T
+    factorisation, unit-lower forward substitutions of y, 1 and every r, then the D^-1-weighted dot products.  Returns
+    dict(w[m, n] = L'^-1 r, rd = 1 / D, zy, z1, s11, beta); predict_device_finish() makes the tables of them."""
+    X = np.asarray(X, dtype=np.float64)
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    Xtest = np.atleast_2d(np.asarray(Xtest, dtype=np.float64))
+    wts, Th = unpack_params(row, K, d)
+    Lp, D = _ldl_lower(mixed_corr_matrix_general(X, wts, Th))
+    n, m = yv.shape[0], Xtest.shape[0]
+    B = np.empty((n, 2 + m))
+    B[:, 0], B[:, 1] = yv, 1.0
+    for t in range(m):
+        B[:, 2 + t] = mixed_corr_vec_general(Xtest[t], X, wts, Th)
+    for i in range(1, n):
+        B[i] -= Lp[i, :i] @ B[:i]
+    rd = 1.0 / D
+    zy, z1 = B[:, 0].copy(), B[:, 1].copy()
+    s11 = float(np.sum(z1 * (z1 * rd)))
+    beta = float(np.sum(zy * (z1 * rd))) / s11
+    return dict(w=B[:, 2:].T.copy(), rd=rd, zy=zy, z1=z1, s11=s11, beta=beta)
+
+
+def predict_device_finish(dev, sigma2):
+    """(mean[m], var[m], ww, z1w, zyw) from predict_device_restatement(): the three dot products in the device's order (ww, z1w,
+    zyw over w D^-1), then mean = beta + (zyw - beta z1w), var = sigma2 (1 - ww + u u / s11)."""
+    wr = dev["w"] * dev["rd"][None, :]
+    ww = (dev["w"] * wr).sum(axis=1)
+    z1w = wr @ dev["z1"]
+    zyw = wr @ dev["zy"]
+    u = 1.0 - z1w
+    mean = dev["beta"] + (zyw - dev["beta"] * z1w)
+    var = sigma2 * (1.0 - ww + u * u / dev["s11"])
+    return mean, var, ww, z1w, zyw

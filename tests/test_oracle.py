@@ -349,3 +349,140 @@ def test_exact_inverse_against_lapack():
     assert np.abs(np.asarray(Rinv @ R.astype(np.longdouble) - np.eye(70), dtype=np.float64)).max() <= 70 * 70 * LD_EPS * kappa
     bound = np.abs(np.asarray(Rinv, np.float64)) @ np.abs(R) @ np.abs(np.asarray(Rinv, np.float64))
     assert np.all(np.abs(np.linalg.inv(R) - np.asarray(Rinv, np.float64)) <= 16 * 70 * F64_EPS * bound)
+
+
+# --------------------------------------------------------------------------- exact predict.post tables (host only)
+def _predict_sites(X, rng):
+    """a training point, that point + 1e-6 and + 1e-3 in one coordinate, two interior points, one far point"""
+    d = X.shape[1]
+    e = np.eye(d)[d - 1]
+    return np.vstack([X[3], X[3] + 1e-6 * e, X[3] + 1e-3 * e, rng.random((2, d)), np.full(d, 50.0)])
+
+
+def _mpf(v):
+    """a long double as an mpf, exactly: its fp64 rounding plus the remainder"""
+    hi = float(v)
+    return mp_check.mp.mpf(hi) + mp_check.mp.mpf(float(v - np.longdouble(hi)))
+
+
+def _predict_host_cases():
+    from conftest import synthetic_design
+    D = load_maximin(14)
+    y14 = np.array([orc.test_function_2d(a, b, 3) for a, b in D])
+    X33, y33 = synthetic_design(33, 3, seed=33)
+    return [(D, y14, 2, 2, 14), (X33, y33 + 0.3 * X33[:, 0], 2, 3, 33)]
+
+
+def test_predict_reference_against_50_digits():
+    """The long-double tables sit within band / 64 of mp_check.predict at 50 digits: at a training point (variance ~ 1e-17
+    sigma2), its 1e-6 and 1e-3 neighbours, two interior sites and the far site, on maximin-14 and n = 33, d = 3, K = 2."""
+    orc.require_extended_precision()
+    for X, y, K, d, seed in _predict_host_cases():
+        rng = np.random.default_rng(seed)
+        row, _ = orc.conditioned_row(X, K, d, rng, kappa_max=1e8)
+        Xt = _predict_sites(X, rng)
+        parts = orc.predict_parts(X, y, row, K, d, 0.8, Xt, np.longdouble)
+        band = orc.predict_bands(parts, 0.8)
+        w, Th = orc.unpack_params(row, K, d)
+        m_mp, v_mp, b_mp = mp_check.predict(X, y, w, Th, 0.8, Xt)
+        # the differences are formed at 50 digits: a variance of 1e-17 is not rounded to fp64 before it is compared
+        ev = np.array([abs(float(_mpf(v) - vm)) for v, vm in zip(parts["var"], v_mp)])
+        em = np.array([abs(float(_mpf(v) - vm)) for v, vm in zip(parts["mean"], m_mp)])
+        eb = abs(float(_mpf(parts["beta"]) - b_mp))
+        assert float(parts["var"][0]) < 1e-12 * 0.8 and (np.asarray(parts["r"][-1], np.float64) == 0).all()
+        assert (ev <= band["var"] / 64).all(), ev / band["var"]
+        assert (em <= band["mean"] / 64).all(), em / band["mean"]
+        assert eb <= band["beta"] / 64
+
+
+def _planted(dev, sigma2, plant, s11_other=None):
+    """oracle.predict_device_finish with one planted kernel mistake."""
+    w, rd, z1, zy, beta, s11 = dev["w"], dev["rd"].copy(), dev["z1"], dev["zy"], dev["beta"], dev["s11"]
+    n = rd.shape[0]
+    if plant == "reciprocal twice":
+        rd[n // 2] *= rd[n // 2]
+    if plant == "neighbour r":
+        w = np.roll(w, -1, axis=0)
+    wr = w * rd[None, :]
+    ww = (w[:, :n - 1] * wr[:, :n - 1]).sum(axis=1) if plant == "row n-1 out of ww" else (w * wr).sum(axis=1)
+    z1w, zyw = wr @ z1, wr @ zy
+    u = 1.0 - z1w
+    if plant == "neighbour s11":
+        s11 = s11_other
+    mean = beta + (zyw + beta * z1w if plant == "beta z1w sign" else zyw - beta * z1w)
+    var = sigma2 * (1.0 - ww + (0.0 if plant == "u u / s11 dropped" else u * u / s11))
+    return mean, var
+
+
+def test_predict_band_rejects_the_kernel_mistakes_it_is_meant_to_catch():
+    """Each planted mistake, applied to the fp64 restatement of the device's formula, leaves the band by a factor of at least
+    1e3 at some site; the restatement itself stays inside."""
+    orc.require_extended_precision()
+    for X, y, K, d, seed in _predict_host_cases():
+        rng = np.random.default_rng(seed)
+        rows = [orc.conditioned_row(X, K, d, rng, kappa_max=1e8)[0] for _ in range(2)]
+        Xt = np.vstack([_predict_sites(X, rng), X[-1]])
+        parts = orc.predict_parts(X, y, rows[0], K, d, 0.8, Xt, np.longdouble)
+        band = orc.predict_bands(parts, 0.8)
+        ref_mean, ref_var = np.asarray(parts["mean"], np.float64), np.asarray(parts["var"], np.float64)
+        dev = orc.predict_device_restatement(X, y, rows[0], K, d, Xt)
+        other = orc.predict_device_restatement(X, y, rows[1], K, d, Xt)["s11"]
+
+        def off(plant):
+            mean, var = _planted(dev, 0.8, plant, other)
+            return max((np.abs(var - ref_var) / band["var"]).max(), (np.abs(mean - ref_mean) / band["mean"]).max())
+        assert off(None) <= 1.0
+        for plant in ("row n-1 out of ww", "neighbour r", "u u / s11 dropped", "neighbour s11", "beta z1w sign", "reciprocal twice"):
+            assert off(plant) >= 1e3, (plant, off(plant))
+
+
+_PREDICT_CASE_STATS = {}
+
+
+def _predict_case_stats():
+    """Over every table case of tests/test_gpu_predict_exact.py and its three draws: the largest |fp64 restatement - long
+    double| / (band / C) for (var, mean, beta), and the largest band_var / sigma2 at a site on or within 1e-6 of a training
+    point, per case.  Computed once for the tests below."""
+    if not _PREDICT_CASE_STATS:
+        import test_gpu_predict_exact as tp
+        orc.require_extended_precision()
+        ratio = np.zeros(3)
+        caps = {}
+        for route, n, d, K, m, kind in tp.all_table_cases():
+            X, y, P, Xt = tp.make_case(n, d, K, m, kind)
+            near = tp.near_training(X, Xt)
+            assert near.any() == (kind == "full")
+            for s in range(tp.S):
+                parts, band, kappa = tp.reference(X, y, P[s], K, Xt, tp.SIGMA2)
+                assert kappa <= tp.KAPPA_MAX, (n, d, K, s, kappa)
+                mean, var, *_ = orc.predict_device_finish(orc.predict_device_restatement(X, y, P[s], K, d, Xt), tp.SIGMA2)
+                dev_beta = orc.predict_device_restatement(X, y, P[s], K, d, Xt[:1])["beta"]
+                ratio = np.maximum(ratio, [(np.abs(var - np.asarray(parts["var"], np.float64)) / band["var"]).max() * tp.C,
+                                           (np.abs(mean - np.asarray(parts["mean"], np.float64)) / band["mean"]).max() * tp.C,
+                                           abs(dev_beta - float(parts["beta"])) / band["beta"] * tp.C])
+                if near.any():
+                    key = (route, n, d, K, m)
+                    caps[key] = max(caps.get(key, 0.0), float(band["var"][near].max()) / tp.SIGMA2)
+                if kind == "plain" and d == 1:
+                    caps["rho"] = max(caps.get("rho", 0.0), parts["rho"])
+        _PREDICT_CASE_STATS.update(ratio=ratio, caps=caps)
+    return _PREDICT_CASE_STATS
+
+
+def test_predict_constant_has_its_margin_over_the_fp64_restatement():
+    """PREDICT_TOL_C is at least 8 times what a plain fp64 evaluation of the device's formula needs, over every case the
+    device is run at (the recorded figures: tests/test_gpu_predict_exact.py's docstring)."""
+    ratio = _predict_case_stats()["ratio"]
+    print("fp64 restatement, largest |fp64 - long double| / (band / C): var %.3g mean %.3g beta %.3g" % tuple(ratio))
+    assert orc.PREDICT_TOL_C >= 8.0 * ratio.max(), ratio
+
+
+def test_predict_variance_band_is_not_vacuous_where_the_variance_cancels():
+    """On a training point or within 1e-6 of one the variance band is at most 1e-9 sigma2 in every case with such sites (all
+    but the d = 63 witness and the d = 1 case, which has rho ~ 1e4 to exercise that term instead)."""
+    caps = dict(_predict_case_stats()["caps"])
+    assert caps.pop("rho") >= 3e3
+    assert len(caps) == 36                                        # 19 kept-factor, 8 extra-row and 9 blocked cases
+    worst = max(caps, key=caps.get)
+    print("largest band_var / sigma2 near a training point: %.3g at %s" % (caps[worst], worst))
+    assert caps[worst] <= 1e-9, (worst, caps[worst])
