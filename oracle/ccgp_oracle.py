@@ -616,6 +616,14 @@ def require_extended_precision():
                            "is unavailable (no fall-back to fp64)" % (eps, LONGDOUBLE_EPS_MAX))
 
 
+def _log_2pi(dtype):
+    """log(2 pi) in dtype: the fp64 constant is 1.4e-16 off, which n / 2 times over is a visible share of a rounding unit of
+    the log-likelihood at n in the hundreds."""
+    if dtype == np.float64:
+        return LOG_2PI
+    return np.log(dtype(8) * np.arctan(dtype(1)))
+
+
 def _chol_inverse(A, dtype):
     """(Sigma^-1, log det Sigma) of a symmetric positive definite A.  fp64: LAPACK (dpotrf / dpotri).  long double: a
     column Cholesky, then L^-1 by forward substitution on the identity and Sigma^-1 = L^-T L^-1, vectorised over rows."""
@@ -688,7 +696,7 @@ def loglik_grad_parts(X, y, row, K, d, sigma2, dtype=np.float64):
     beta = u @ yv
     alpha = Sinv @ (yv - beta)
     q = (yv - beta) @ alpha
-    ll = -(dtype(n) * dtype(LOG_2PI) + logdet + q) / dtype(2)
+    ll = -(dtype(n) * _log_2pi(dtype) + logdet + q) / dtype(2)
     M = (np.outer(alpha, alpha) - Sinv) / dtype(2)
     return dict(Sigma=Sigma, Sinv=Sinv, Rc=Rc, M=M, alpha=alpha, u=u, loglik=ll, beta=beta)
 
@@ -770,6 +778,85 @@ def conditioned_row(X, K, d, rng, kappa_max=1e8, w=None):
             return np.concatenate([w, Th.ravel()]), kappa
         Th = Th * 1.5
     raise RuntimeError("no draw with cond1 <= %g" % kappa_max)
+
+
+# --------------------------------------------------------------------------- marginal likelihood (mean mode 1), extended precision
+# cond.like (HX:561-572) factorises Sigma = Sigma0 + tau2 11', Sigma0 = sigma2 sum_c w_c^2 R_c, with mean 0.  With alpha =
+# Sigma^-1 y and M = (alpha alpha' - Sigma^-1) / 2, d loglik = tr(M dSigma): a relative perturbation delta of every entry of
+# Sigma moves the value by at most delta sum_ab |M_ab| |Sigma_ab|, and errors of the kernel values touch Sigma0 only.  The
+# acceptance band of tests/test_gpu_marginal_exact.py is therefore, with rho = expanded_form_magnitude(...),
+#   |ll_dev - ll_ref| <= MARGINAL_TOL_C * eps * (sum |M| |Sigma| + rho sum |M| |Sigma0|)        (marginal_unit)
+# -- no condition number in it (the gradient tests' eps cond1 scale is vacuous here: cond1 and |alpha|'|Sigma||alpha| both
+# grow with tau2 n).  First order only holds while eps cond1(Sigma) is small: every checked draw has cond1(Sigma) <=
+# MARGINAL_COND_MAX.  The constant: the fp64 LAPACK evaluation with the exponent in the scripts' expanded form (marginal_parts(
+# ..., np.float64, expanded=True)), a correct fp64 implementation, reaches at most MARGINAL_LAPACK_MAX units over the whole
+# case list of the device module (tests/test_oracle.py measures it on every run); C is 32 times that -- the device's own
+# summation orders, a 2-ulp exp, a Cholesky backward error growing like sqrt(n) up to n = 520 -- rounded up to a power of two
+# and capped at GRAD_TOL_C.  Nothing here was taken from a device run; measured afterwards on an MI355X, the device's largest
+# ratio over all routes is 0.085 units, 2 % of C (DESIGN.md has the per-route table).
+MARGINAL_COND_MAX = 4e9
+MARGINAL_LAPACK_MAX = 0.108        # measured: 0.1077 at n = 5, d = 4, K = 2, (sigma2, tau2) = (1, 25); 100 draws, n = 2 ... 520
+MARGINAL_TOL_C = 4.0               # 32 x 0.108 = 3.46, rounded up to a power of two
+# relative accuracy tests/test_special.py requires of the host inverse-gamma quantile; the device instance of the same source
+# gets the same allowance in the grid's node term
+GRID_NODE_Q = 2e-13
+
+
+def marginal_parts(X, y, row, K, d, sigma2, tau2, dtype=np.longdouble, expanded=False):
+    """The mode-1 counterpart of loglik_grad_parts in dtype (long double: the hand-written Cholesky of Sigma0 and the rank-one
+    term in closed form; fp64: LAPACK on Sigma):
+    dict(Sigma, Sigma0, Sinv, Rc (list), M, alpha, loglik, beta = 0).  Kernel values in the direct squared-difference form, or,
+    with expanded (fp64 only), in the scripts' expanded form u_a + u_b - 2 sum_k theta_k x_ak x_bk (corr_matrix).
+    grad_from_parts() works on the result as it stands (it reads M and Rc).  Raises LinAlgError when not positive definite."""
+    dtype = np.dtype(dtype).type
+    X = np.asarray(X, dtype=np.float64)
+    yv = np.asarray(y, dtype=dtype).reshape(-1)
+    n = yv.shape[0]
+    w, Th = unpack_params(row, K, d)
+    s2 = dtype(sigma2)
+    if expanded:
+        assert dtype == np.float64
+        Rc = [corr_matrix(X, Th[c]) for c in range(K)]
+    else:
+        Rc = [component_corr(X, Th[c], dtype) for c in range(K)]
+    Sigma0 = np.zeros((n, n), dtype=dtype)
+    for c in range(K):
+        Sigma0 += (s2 * dtype(w[c]) ** 2) * Rc[c]
+    Sigma = Sigma0 + dtype(tau2)
+    if dtype == np.float64:
+        Sinv, logdet = _chol_inverse(Sigma, dtype)          # what the scripts and the device do: factorise Sigma itself
+        alpha = Sinv @ yv
+    else:
+        # the rank-one term in closed form (Sherman-Morrison, matrix determinant lemma): only Sigma0 is factorised, so that
+        # the reference does not lose cond1(Sigma) / cond1(Sigma0) ~ tau2 n / sigma2 of its own precision
+        S0inv, logdet0 = _chol_inverse(Sigma0, dtype)
+        t2 = dtype(tau2)
+        u = S0inv.sum(axis=0)
+        den = dtype(1) + t2 * u.sum()
+        Sinv = S0inv - (t2 / den) * np.outer(u, u)
+        logdet = logdet0 + np.log1p(t2 * u.sum())
+        alpha = S0inv @ yv - (t2 * (u @ yv) / den) * u
+    ll = -(dtype(n) * _log_2pi(dtype) + logdet + yv @ alpha) / dtype(2)
+    M = (np.outer(alpha, alpha) - Sinv) / dtype(2)
+    return dict(Sigma=Sigma, Sigma0=Sigma0, Sinv=Sinv, Rc=Rc, M=M, alpha=alpha, loglik=ll, beta=dtype(0))
+
+
+def marginal_unit(parts, X, row, K, d):
+    """eps (sum_ab |M_ab| |Sigma_ab| + rho sum_ab |M_ab| |Sigma0_ab|): what one relative fp64 rounding of every entry of Sigma,
+    and rho roundings of every kernel value's exponent, move the mode-1 log-likelihood by (first order)."""
+    aM = np.abs(parts["M"])
+    rho = expanded_form_magnitude(X, row, K, d)
+    return float(np.finfo(np.float64).eps * ((aM * np.abs(parts["Sigma"])).sum() + rho * (aM * np.abs(parts["Sigma0"])).sum()))
+
+
+def logmeanexp_exact(logs, take_log=True):
+    """log(mean(exp(logs))) (likeli.hyperpars / choose.hyperpars, HX:574, HX:591) or, without take_log, the mean itself
+    (ADV:595), in long double (its exponent range holds exp(-11000))."""
+    require_extended_precision()
+    v = np.asarray(logs, dtype=np.longdouble).reshape(-1)
+    mx = v.max()
+    lme = mx + np.log(np.exp(v - mx).sum() / np.longdouble(v.shape[0]))
+    return lme if take_log else np.exp(lme)
 
 
 # --------------------------------------------------------------------------- predict.post tables, extended precision

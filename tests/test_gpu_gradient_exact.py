@@ -103,15 +103,23 @@ def check_draw(X, y, row, K, d, s2, got, tag, dtype=np.longdouble, c=orc.GRAD_TO
     assert kappa <= KAPPA_MAX, (tag, kappa)
     g_ref, scale = orc.grad_from_parts(parts, X, row, K, d, s2)
     g_ref, scale = g_ref.astype(np.float64), scale.astype(np.float64)
-    s_ll, s_beta = orc.loglik_beta_scales(parts, y)
     ll, beta, g = got
     unit = EPS * kappa * (1.0 + orc.expanded_form_magnitude(X, row, K, d))
     ratio = np.abs(g - g_ref) / (unit * scale)
     MAX_RATIO[tag] = max(MAX_RATIO.get(tag, 0.0), float(ratio.max()))
     bad = np.nonzero(~(ratio <= c))[0]
     assert bad.size == 0, "%s: components %s off by %s x eps cond1 scale (cond1 %.3g)" % (tag, bad[:8], ratio[bad[:8]], kappa)
-    assert abs(ll - float(parts["loglik"])) <= c * unit * s_ll, (tag, ll, float(parts["loglik"]), kappa)
-    assert abs(beta - float(parts["beta"])) <= c * unit * s_beta, (tag, beta, float(parts["beta"]), kappa)
+    s_ll, s_beta = orc.loglik_beta_scales(parts, y)
+    check_loglik_beta(float(parts["loglik"]), float(parts["beta"]), unit * s_ll, unit * s_beta, ll, beta, tag, c)
+
+
+def check_loglik_beta(ll_ref, beta_ref, unit_ll, unit_beta, ll, beta, tag, c=orc.GRAD_TOL_C):
+    """The log-likelihood and beta of one mode-0 draw: each within c of its unit = eps cond1 (1 + rho) times its
+    cancellation-free size (oracle.loglik_beta_scales).  Returns the two ratios |dev - ref| / unit."""
+    r_ll, r_beta = abs(ll - ll_ref) / unit_ll, abs(beta - beta_ref) / unit_beta
+    assert r_ll <= c, (tag, ll, ll_ref, r_ll)
+    assert r_beta <= c, (tag, beta, beta_ref, r_beta)
+    return r_ll, r_beta
 
 
 def _design(n, d, seed):

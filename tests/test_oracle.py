@@ -486,3 +486,158 @@ def test_predict_variance_band_is_not_vacuous_where_the_variance_cancels():
     worst = max(caps, key=caps.get)
     print("largest band_var / sigma2 near a training point: %.3g at %s" % (caps[worst], worst))
     assert caps[worst] <= 1e-9, (worst, caps[worst])
+
+
+# --------------------------------------------------------------------------- exact marginal likelihood, mode 1 (host only)
+def _marginal_host_cases():
+    from conftest import synthetic_design
+    D = load_maximin(14)
+    y14 = np.array([orc.test_function_2d(a, b, 3) for a, b in D])
+    X21, y21 = synthetic_design(21, 3, seed=21)
+    return [(D, y14, 2, 2, 14), (X21, y21 + 0.3 * X21[:, 0], 3, 3, 21)]
+
+
+@pytest.mark.parametrize("tau2", [0.0, 2500.0])
+def test_marginal_reference_against_50_digits(tau2):
+    """oracle.marginal_parts in long double against mp_check.loglik(..., 1, tau2): 1e-17 relative on maximin-14 (K = 2) and on
+    n = 21, d = 3, K = 3; the difference is formed at 50 digits."""
+    orc.require_extended_precision()
+    for X, y, K, d, seed in _marginal_host_cases():
+        row, _ = orc.conditioned_row(X, K, d, np.random.default_rng(seed), kappa_max=1e3)
+        parts = orc.marginal_parts(X, y, row, K, d, 0.8, tau2, np.longdouble)
+        w, Th = orc.unpack_params(row, K, d)
+        ll_mp, beta_mp = mp_check.loglik(X, y, w, Th, 0.8, 1, tau2)
+        assert beta_mp == 0 and parts["beta"] == 0
+        assert abs(float(_mpf(parts["loglik"]) - ll_mp)) <= 1e-17 * abs(float(ll_mp)), (seed, tau2)
+        # the two matrices differ by tau2 exactly, and M is the derivative the band is built on: central difference in tau2
+        assert np.array_equal(parts["Sigma"] - parts["Sigma0"], np.full_like(parts["Sigma"], np.longdouble(tau2)))
+        h = np.longdouble(1e-4) * max(tau2, 1.0)
+        up = orc.marginal_parts(X, y, row, K, d, 0.8, np.longdouble(tau2) + h, np.longdouble)["loglik"]
+        dn = orc.marginal_parts(X, y, row, K, d, 0.8, np.longdouble(tau2) - h, np.longdouble)["loglik"] if tau2 else None
+        if dn is not None:
+            assert float((up - dn) / (2 * h)) == pytest.approx(float(parts["M"].sum()), rel=1e-6)
+
+
+def test_logmeanexp_exact_known_answers():
+    orc.require_extended_precision()
+    assert float(orc.logmeanexp_exact([-3.5])) == -3.5 and float(orc.logmeanexp_exact([-3.5], False)) == pytest.approx(math.exp(-3.5), rel=1e-16)
+    assert float(orc.logmeanexp_exact([0.0, math.log(3.0)])) == pytest.approx(math.log(2.0), rel=1e-15)
+    assert float(orc.logmeanexp_exact([-1e5, -1e5 - 800.0, -1e5 - 2.0])) == pytest.approx(-1e5 + math.log((1 + math.exp(-2.0)) / 3), rel=1e-16)
+    v = orc.logmeanexp_exact([-11000.0, -11001.0], False)
+    assert 0 < v < np.finfo(np.float64).tiny and float(np.log(v)) == pytest.approx(-11000.0 + math.log((1 + math.exp(-1.0)) / 2), rel=1e-15)
+
+
+def test_marginal_case_lists_of_the_device_module():
+    """Host check of tests/test_gpu_marginal_exact.py's lists: the sizes, dimensions and component counts its docstring names,
+    and that no Gaussian likelihood shape below n = 129 takes the blocked sweep (the witness is n = 129)."""
+    import route_witnesses
+    import test_gpu_marginal_exact as tm
+    assert tm.WITNESS == (129, 1, 1) and route_witnesses.RESERVE_CHANGES[0][0] == 0
+    small = tm.REG8_CASES + tm.WAVE_CASES + tm.REG16_CASES
+    assert {d for _, d, _ in small} == set(range(1, 10)) and {K for _, _, K in small} == {1, 2, 3, 8}
+    assert [n for n, _, _ in small] == [2, 5, 8, 9, 63, 64, 65, 72, 104, 105, 127, 128]
+    assert [n for n, _, _ in tm.BLOCKED_CASES[1:]] == [129, 191, 192, 193, 255, 256, 257, 383, 385, 520]
+    assert {K for _, _, K in tm.BLOCKED_CASES} == {1, 2, 8}
+    assert all(tm._lds_fits(tm._reg_lds_doubles8(*c)) for c in tm.WAVE_CASES)
+    assert [n for n, _, _ in tm.PAIR_SHAPES] == [14, 100, 128, 257] and [n for n, _, _ in tm.TINY_SHAPES] == [64, 257]
+    assert 0.0 < tm.TINY_TAU2[1] < np.finfo(np.float64).tiny and tm.TINY_TAU2[0] == 1e-300
+
+
+def test_marginal_constant_comes_from_the_fp64_lapack_evaluation():
+    """The measurement that fixes MARGINAL_TOL_C: the fp64 LAPACK likelihood with the exponent in the expanded form, on every
+    mode-1 draw the device module checks, in units of oracle.marginal_unit; every draw within the condition cap.  C = 32 x the
+    largest ratio, rounded up to a power of two, capped at GRAD_TOL_C."""
+    import test_gpu_marginal_exact as tm
+    orc.require_extended_precision()
+    worst, worst_at, kappa_max = 0.0, None, 0.0
+    for case in tm.mode1_draws():
+        n, d, K, B, b, s2, tau2 = case
+        ll_ref, unit, kappa = tm.mode1_reference(*case)
+        assert kappa <= orc.MARGINAL_COND_MAX, (case, kappa)
+        X, y, rows = tm.make_case(n, d, K, B)
+        ll = float(orc.marginal_parts(X, y, rows[b], K, d, s2, tau2, np.float64, expanded=True)["loglik"])
+        assert abs(ll - orc.loglik_general(X, y, *orc.unpack_params(rows[b], K, d), s2, 1, tau2)[0]) <= unit   # the scripts' dmnorm
+        ratio = abs(ll - ll_ref) / unit
+        kappa_max = max(kappa_max, kappa)
+        if ratio > worst:
+            worst, worst_at = ratio, case
+    print("fp64 LAPACK, expanded exponent: largest |ll - ll_ref| / unit %.4g at %s; largest cond1(Sigma) %.3g" % (worst, worst_at, kappa_max))
+    want = min(orc.GRAD_TOL_C, 2.0 ** math.ceil(math.log2(32.0 * orc.MARGINAL_LAPACK_MAX)))
+    assert orc.MARGINAL_TOL_C == want, (orc.MARGINAL_TOL_C, want)
+    # the recorded maximum is this host's LAPACK; another build's must still leave the factor 32 under the same C
+    assert 32.0 * worst <= orc.MARGINAL_TOL_C, (worst, worst_at)
+
+
+def _marginal_ll(Sigma, y):
+    """The mode-1 value of a (possibly wrong) Sigma in long double; -inf where it is not positive definite (the device would
+    report a failed draw)."""
+    LD = np.longdouble
+    try:
+        Sinv, logdet = orc._chol_inverse(Sigma, LD)
+    except np.linalg.LinAlgError:
+        return -np.inf
+    yv = np.asarray(y, dtype=LD)
+    return -(LD(len(yv)) * orc._log_2pi(LD) + logdet + yv @ (Sinv @ yv)) / 2
+
+
+def _marginal_bugs(X, y, row, K, d, s2, tau2, parts):
+    """name -> the Sigma a modelled kernel bug would factorise, built from the long-double reference's pieces."""
+    LD = np.longdouble
+    n = len(y)
+    w, Th = orc.unpack_params(row, K, d)
+    sw = (np.asarray(w, dtype=LD) ** 2).sum()
+    S0, t2 = parts["Sigma0"], LD(tau2)
+    bugs = {}
+    if tau2 > 0:
+        bugs["tau2 added before the scaling"] = S0 + LD(s2) * sw * t2
+        bugs["tau instead of tau^2"] = S0 + np.sqrt(t2)
+    bugs["sigma2 without sum w^2"] = S0 / sw + t2
+    q = K - 1
+    bugs["last weight unsquared"] = S0 + LD(s2) * (LD(w[q]) - LD(w[q]) ** 2) * parts["Rc"][q] + t2
+    X0 = np.array(X, dtype=np.float64)
+    X0[n - 1] = 0.0
+    leak = S0.copy()
+    for c in range(K):
+        Rc0 = orc.component_corr(X0, Th[c], LD)
+        delta = LD(s2) * LD(w[c]) ** 2 * (Rc0[n - 1, :n - 1] - parts["Rc"][c][n - 1, :n - 1])
+        leak[n - 1, :n - 1] += delta
+        leak[:n - 1, n - 1] += delta
+    bugs["padded row leaking into row n - 1"] = leak + t2
+    if n > 64:
+        hi = min(n, 128)
+        if tau2 > 0:
+            S = parts["Sigma"].copy()
+            S[64:hi, :64] -= t2
+            S[:64, 64:hi] -= t2
+            bugs["tau2 missing on tile (1, 0)"] = S
+        for name, f in (("dropped", 0), ("doubled", 2)):
+            S = S0.copy()
+            S[64:hi, :64] *= f
+            S[:64, 64:hi] *= f
+            bugs["tile (1, 0) of Sigma0 %s" % name] = S + t2
+            S = S0.copy()
+            S[64:hi, 64:hi] *= f
+            bugs["tile (1, 1) of Sigma0 %s" % name] = S + t2
+    return bugs
+
+
+def test_marginal_band_rejects_the_kernel_bugs_it_is_meant_to_catch():
+    """Each modelled bug, applied to the long-double reference's Sigma, moves the value by at least 4 C units, at every shape
+    and pair of the device module's (sigma2, tau2) table (the tile bugs where there is a second 64-row tile: n = 100, 128,
+    257; the tau2 bugs where tau2 > 0).  The smallest figure per bug is printed."""
+    import test_gpu_marginal_exact as tm
+    orc.require_extended_precision()
+    least = {}
+    for n, d, K in tm.PAIR_SHAPES:
+        X, y, rows = tm.make_case(n, d, K)
+        for s2, tau2 in tm.PAIRS + [tm.S2_TAU2]:
+            parts = orc.marginal_parts(X, y, rows[0], K, d, s2, tau2, np.longdouble)
+            unit = orc.marginal_unit(parts, X, rows[0], K, d)
+            for name, S in _marginal_bugs(X, y, rows[0], K, d, s2, tau2, parts).items():
+                units = abs(float(_marginal_ll(S, y) - parts["loglik"])) / unit
+                assert units >= 4.0 * orc.MARGINAL_TOL_C, (name, n, s2, tau2, units)
+                if units <= least.get(name, (np.inf,))[0]:
+                    least[name] = (units, n, s2, tau2)
+    for name in sorted(least):
+        print("%-36s at least %.3g units (n = %d, sigma2 = %g, tau2 = %g)" % ((name,) + least[name]))
+    assert len(least) == 10
