@@ -93,6 +93,7 @@ SIGNATURES = {
     "ccgp_enable_timing": (c_int, [c_void_p, c_int]),
     "ccgp_get_timing": (c_int, [c_void_p, c_int, _dp, _ip]),
     "ccgp_last_sched_profile": (c_int, [c_void_p, c_void_p, c_int, _ip]),
+    "ccgp_workspace_bytes": (c_int, [c_void_p, POINTER(c_size_t), POINTER(c_size_t)]),
 }
 
 _bound = None
@@ -336,6 +337,11 @@ class Handle:
 
     # -- plumbing ----------------------------------------------------------------------
     def set_stream(self, hip_stream_ptr):
+        """Run the calls that follow on the caller's stream: pass `torch.cuda.Stream().cuda_stream`.  0 / None selects the
+        handle's OWN non-blocking stream, not the default stream -- and torch's default stream may report
+        `cuda_stream == 0`, so `torch.cuda.current_stream().cuda_stream` can silently mean the handle's own stream, which
+        does not order with the work torch enqueued.  The switch itself orders nothing: with work in flight on the previous
+        stream, order the two streams (an event, or synchronize()) first."""
         self._chk(lib().ccgp_set_stream(self._h, c_void_p(hip_stream_ptr or 0)))
 
     def set_kernel(self, family=0, nu=0.0):
@@ -351,7 +357,15 @@ class Handle:
         self._chk(lib().ccgp_set_option(self._h, int(option), int(value)))
 
     def reserve(self, n, d, K, B, m=0):
+        """Size every buffer the *_dev calls of this shape need (with m > 0 the prediction's too, kept-factor scratch and
+        second stream included): afterwards they only enqueue."""
         self._chk(lib().ccgp_reserve(self._h, n, d, K, B, m))
+
+    def workspace_bytes(self):
+        """(workspace, staging) bytes of device scratch the handle holds now; does not synchronise."""
+        ws, st = c_size_t(), c_size_t()
+        self._chk(lib().ccgp_workspace_bytes(self._h, ctypes.byref(ws), ctypes.byref(st)))
+        return ws.value, st.value
 
     def synchronize(self):
         self._chk(lib().ccgp_synchronize(self._h))

@@ -448,6 +448,40 @@ int check_summary_args(ccgp_handle* h, int m, const double* probs, int n_probs) 
   return CCGP_OK;
 }
 
+// staging of ccgp_predict_summary_dev: the tables and, where the caller keeps no status words, room for them
+struct SummaryDevStage {
+  SummaryTables t;
+  int* status;
+};
+SummaryDevStage summary_dev_stage(Layout& c, int S, int m, bool own_status) {
+  SummaryDevStage s;
+  s.t = summary_tables(c, S, m);
+  s.status = own_status ? c.take<int>(S) : nullptr;
+  return s;
+}
+
+// ---- kept-factor prediction: what predict_run needs beyond the launches, shared with ccgp_reserve ---------------------
+// the scratch for S draws at m test sites -- the factor block and the correlation vectors of as many draws at a time as
+// half the workspace limit allows (at least 64) --, or 0 where that scheme does not serve the shape (route, option, LDS)
+size_t kept_factor_ws_bytes(const ccgp_handle* h, bool gauss, int n, int d, int K, int S, int m) {
+  if (!h->opt_predict_factor || small_route(Op::Predict, gauss, n, d, K) != Route::Reg || !small_reg_sites_supported(n, d, K))
+    return 0;
+  const size_t per = small_reg_sites_scratch(n, d, K, m);
+  const size_t want = per * (size_t)S, cap = std::max<size_t>(h->ws_limit / 2, per * 64);
+  return std::min(want, cap / per * per);
+}
+// its second stream and the fork / join events, created once per handle; false: the scheme runs on one stream
+bool ensure_aux(ccgp_handle* h) {
+  if (h->aux_stream) return true;
+  if (hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking) != hipSuccess) h->aux_stream = nullptr;
+  if (h->aux_stream && (hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming) != hipSuccess ||
+                        hipEventCreateWithFlags(&h->aux_join, hipEventDisableTiming) != hipSuccess)) {
+    (void)hipStreamDestroy(h->aux_stream);
+    h->aux_stream = nullptr;
+  }
+  return h->aux_stream != nullptr;
+}
+
 // blocked prediction: scratch behind the matrices for the outputs the caller did not ask for
 SweepOut predict_tail(Layout& t, int S, double* d_beta, int* d_status) {
   SweepOut p;
@@ -780,10 +814,19 @@ int ccgp_reserve(ccgp_handle* h, int n, int d, int K, int B, int m) try {
                             [&](Layout& t, int) { if (sweep_predict) predict_tail(t, B, nullptr, nullptr); }, &nbc))
       return rc;
   }
+  // kept-factor prediction: its scratch (the size predict_run asks for) and its second stream with the two events
+  if (m > 0) {
+    if (const size_t want = kept_factor_ws_bytes(h, gauss, n, d, K, B, m)) {
+      if (int rc = ensure_ws(h, want)) return rc;
+      if (!ensure_aux(h)) return fail(h, CCGP_EHIP, "ccgp_reserve: the second stream of the kept-factor prediction could not be created");
+    }
+  }
+  // staging: the host-pointer likelihood and prediction, and the tables of ccgp_predict_summary_dev
   const int P = K + K * d;
   const size_t st_ll = layout_bytes([&](Layout& c) { loglik_stage(c, n, d, P, B); });
   const size_t st_pr = m ? layout_bytes([&](Layout& c) { predict_stage(c, n, d, P, B, m); }) : 0;
-  return ensure_stage(h, std::max(st_ll, st_pr));
+  const size_t st_sm = m ? layout_bytes([&](Layout& c) { summary_dev_stage(c, B, m, true); }) : 0;
+  return ensure_stage(h, std::max({st_ll, st_pr, st_sm}));
 } CCGP_GUARD_END(h)
 
 int ccgp_enable_timing(ccgp_handle* h, int on) try {
@@ -822,6 +865,13 @@ int ccgp_last_sched_profile(ccgp_handle* h, unsigned long long* out, int max_wor
     CCGP_HIP(hipMemcpy(out, h->sched_prof_dev, sizeof(unsigned long long) * 8 * (size_t)nw, hipMemcpyDeviceToHost));
   return CCGP_OK;
 } CCGP_GUARD_END(h)
+
+int ccgp_workspace_bytes(const ccgp_handle* h, size_t* ws_bytes, size_t* stage_bytes) {
+  if (!h) return CCGP_EINVAL;
+  if (ws_bytes) *ws_bytes = h->ws_bytes;
+  if (stage_bytes) *stage_bytes = h->stage_bytes;
+  return CCGP_OK;
+}
 
 // ---- a1-a5 ------------------------------------------------------------------------------
 static int corr_common(ccgp_handle* h, const double* Xnew, int m, const double* X, int n, int d,
@@ -1470,22 +1520,13 @@ static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const dou
   }
   {
     ScopedTimer t(h, CCGP_T_FUSED);
-    // kept-factor scheme where it applies (n <= 104, K <= 3) and its scratch fits the workspace: the factor block and the
-    // correlation vectors of as many draws at a time as the limit allows (at least 64)
+    // kept-factor scheme where it applies (n <= 104, K <= 3) and its scratch fits the workspace.  After ccgp_reserve of
+    // this shape both steps find what they need; a caller that never reserved pays for them here, once.
     void* scratch = nullptr;
     size_t sbytes = 0;
-    if (h->opt_predict_factor && small_reg_sites_supported(n, d, K)) {
-      const size_t per = small_reg_sites_scratch(n, d, K, m);
-      const size_t want = per * (size_t)S, cap = std::max<size_t>(h->ws_limit / 2, per * 64);
-      if (ensure_ws(h, std::min(want, cap / per * per)) == CCGP_OK) { scratch = h->ws; sbytes = h->ws_bytes; }
-      if (scratch && !h->aux_stream) {
-        if (hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking) != hipSuccess) h->aux_stream = nullptr;
-        if (h->aux_stream && (hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming) != hipSuccess ||
-                              hipEventCreateWithFlags(&h->aux_join, hipEventDisableTiming) != hipSuccess)) {
-          (void)hipStreamDestroy(h->aux_stream);
-          h->aux_stream = nullptr;
-        }
-      }
+    if (const size_t want = kept_factor_ws_bytes(h, dv.fam.id == 0, n, d, K, S, m)) {
+      if (ensure_ws(h, want) == CCGP_OK) { scratch = h->ws; sbytes = h->ws_bytes; }
+      if (scratch) (void)ensure_aux(h);
     }
     launch_small_reg_predict(h->stream, dX, n, d, dy, dv, S, dXtest, m, sigma2, d_mean, d_var, d_beta,
                              d_status, scratch, sbytes, h->aux_stream, h->aux_fork, h->aux_join);
@@ -1537,13 +1578,10 @@ int ccgp_predict_summary_dev(ccgp_handle* h, const double* dX, int n, int d, con
     return fail(h, CCGP_EINVAL, "ccgp_predict_summary: bad argument");
   if (int rc = check_summary_args(h, m, probs, n_probs)) return rc;
   CCGP_HIP(hipSetDevice(h->device));
-  SummaryTables t;
-  int* st = d_status;
-  if (int rc = stage(h, [&](Layout& c) {
-        t = summary_tables(c, S, m);
-        if (!d_status) st = c.take<int>(S);
-      }))
-    return rc;
+  SummaryDevStage sd;
+  if (int rc = stage(h, [&](Layout& c) { sd = summary_dev_stage(c, S, m, !d_status); })) return rc;
+  const SummaryTables& t = sd.t;
+  int* st = d_status ? d_status : sd.status;
   DrawView dv;
   if (int frc = draw_view(h, h->fam, dparams, S, K, d, &dv)) return frc;
   if (int rc = predict_run(h, dX, n, d, dy, dv, dXtest, m, sigma2, t.mean, t.var, d_beta, st)) return rc;

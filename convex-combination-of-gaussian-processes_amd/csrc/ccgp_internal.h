@@ -85,7 +85,7 @@ struct ccgp_handle {
   void* pin = nullptr;
   size_t pin_bytes = 0;
   size_t pin_in = 0;     // bytes of `pin` holding the inputs of the call in flight (results land behind them)
-  hipStream_t aux_stream = nullptr;     // second stream of the kept-factor prediction (created on first use)
+  hipStream_t aux_stream = nullptr;     // second stream of the kept-factor prediction (ccgp_reserve, or first use)
   hipEvent_t aux_fork = nullptr, aux_join = nullptr;
   hipEvent_t pull_ev[ccgp::kPullSlices] = {};   // one per slice of a large result on its way back (capi.hip: pull)
   std::string err;

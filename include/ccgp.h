@@ -32,6 +32,9 @@
  *   - "_dev" entry points take DEVICE pointers and only enqueue work on the
  *     handle's stream (no allocation, no synchronisation once the workspace has
  *     been sized by ccgp_reserve); the others take HOST pointers and block.
+ *     The kept-factor prediction also uses a second stream of the handle's, forked
+ *     from and joined back into the handle's stream inside the call: to the caller
+ *     the call is ordered on the handle's stream alone.
  */
 #ifndef CCGP_H
 #define CCGP_H
@@ -72,7 +75,11 @@ int ccgp_create(int device, ccgp_handle** out);
 int ccgp_destroy(ccgp_handle* h);
 const char* ccgp_last_error(const ccgp_handle* h);
 const char* ccgp_version(void);
-/* run on a caller-owned hipStream_t (pass NULL to go back to the handle's own stream) */
+/* run on a caller-owned hipStream_t.  NULL does NOT mean the legacy default stream: it selects the library's own stream,
+ * created non-blocking, which does not order with the legacy default stream (nor with any other); a caller whose default
+ * stream reports a null pointer passes a stream it created.  The call only switches: it neither waits for the work already
+ * enqueued on the previous stream nor makes the new stream wait for it.  A caller who changes streams with work in flight
+ * must order the two streams themself (an event, or ccgp_synchronize before the switch). */
 int ccgp_set_stream(ccgp_handle* h, void* hip_stream);
 /* correlation family of every component GP for the calls that follow (default Gaussian).
  * CCGP_KERNEL_GAUSS : R_c[i,j] = exp(-sum_k theta_ck (x_ik - x_jk)^2)     corr.matrix HX:328-337, ANI:351-360
@@ -126,7 +133,12 @@ int ccgp_set_workspace_limit(ccgp_handle* h, size_t bytes);
 enum { CCGP_OPT_FUSE_DIAG = 2, CCGP_OPT_TAIL_STRIPS = 3, CCGP_OPT_WIDE_OFFSETS = 4, CCGP_OPT_SMALL_GRID16 = 5,
        CCGP_OPT_SCHED = 7, CCGP_OPT_SCHED_POLICY = 8, CCGP_OPT_PREDICT_FACTOR = 9 };
 int ccgp_set_option(ccgp_handle* h, int option, int value);
-/* pre-size scratch so that later _dev calls of this shape never allocate */
+/* pre-size scratch so that later _dev calls of this shape (or of fewer draws B or test sites m), under the kernel family,
+ * options and workspace limit in force now, never allocate, synchronise or create a stream or an event.  Covers: the
+ * blocked sweep's workspace of ccgp_loglik_batch_dev; with m > 0 also that of a prediction on the sweep, the kept-factor
+ * prediction's scratch together with its second stream and fork / join events (CCGP_OPT_PREDICT_FACTOR), and the tables
+ * ccgp_predict_summary_dev keeps between its launches; the staging of the host-pointer likelihood and prediction.  Not
+ * covered: the events of ccgp_enable_timing (created on first use).  May itself allocate and synchronise. */
 int ccgp_reserve(ccgp_handle* h, int n, int d, int K, int B, int m);
 int ccgp_synchronize(ccgp_handle* h);
 
@@ -369,6 +381,9 @@ int ccgp_get_timing(ccgp_handle* h, int id, double* out_ms, int* out_launches);
  * waiting for a task, in diagonal / update / panel-solve tiles, applying arrivals; then tasks run, XCD served, 1 if second on
  * its CU).  Copies the account of the LAST scheduled sweep (synchronises the stream). */
 int ccgp_last_sched_profile(ccgp_handle* h, unsigned long long* out, int max_workgroups, int* out_workgroups);
+/* Bytes of device scratch the handle holds now: the workspace (sweep matrices, kept factors) and the staging buffer.
+ * Both grow only; a figure that changed across a call means the call allocated.  Does not synchronise.  Either may be NULL. */
+int ccgp_workspace_bytes(const ccgp_handle* h, size_t* ws_bytes, size_t* stage_bytes);
 
 #ifdef __cplusplus
 }
