@@ -376,8 +376,9 @@ __device__ __forceinline__ double exp_small(double dist, const double* tab) {
 }
 
 // ---- correlation families ---------------------------------------------------------------------------
-// Every kernel forms the weighted squared distance  dist = sum_k rate_k (x_ik - x_jk)^2  (in the
-// reference's expanded form) and then the correlation.  Gaussian (HX:328-356): rate = theta,
+// Every kernel forms the weighted squared distance  dist = sum_k rate_k (x_ik - x_jk)^2  and then the correlation:
+// the Gaussian family in the reference's expanded form, the 1-D families from the direct difference x_i - x_j, as
+// their scripts do (U <- abs(A - t(A)), D1:368-374).  Gaussian (HX:328-356): rate = theta,
 // corr = exp(-dist).  Matern (1-D scripts, D1:348-351): corr = z^nu K_nu(z) / (Gamma(nu) 2^(nu-1)) with
 // z = 2 sqrt(nu) |h| / theta, so rate = 4 nu / theta^2 and z = sqrt(dist); d = 1 only, as in the reference.
 // Two-family script (D1F:346-357, D1F:453-462): component 1 Matern as above, component 2 the non-negative
@@ -387,20 +388,31 @@ __device__ __forceinline__ double theta_to_rate(const KernelFamily& f, double th
   if (f.id == 2 && component == 1) return 1.0 / (theta * theta);
   return 4.0 * f.nu / (theta * theta);
 }
+// both take the squared scaled distance as the kernel forms it, rate (x_i - x_j)^2 from the direct difference: exactly 0
+// where the points coincide and NaN where a coordinate is (sqrt and every comparison below let a NaN through)
 __device__ __forceinline__ double spline_corr(double u2) {
-  const double u = sqrt(u2 > 0.0 ? u2 : 0.0);
+  const double u = sqrt(u2);
   if (u <= 0.5) return 1.0 - 6.0 * u * u + 6.0 * u * u * u;
   if (u <= 1.0) { const double v = 1.0 - u; return 2.0 * v * v * v; }
-  return 0.0;
+  return u > 1.0 ? 0.0 : u;   // NaN stays NaN (the reference's NA)
 }
 // z^nu K_nu(z) / (Gamma(nu) 2^(nu-1)) from  K_nu(z) = int_0^inf exp(-z cosh t) cosh(nu t) dt  by the
 // trapezoidal rule (the integrand is entire and decays double-exponentially, so the rule converges
-// geometrically): step 0.15 / max(1, sqrt z) gives <= 2e-14 relative error for 1 < nu <= 10 against a
-// 40-digit evaluation over z in [1e-6, 300] (tests/test_special.py holds the same rule in numpy); below
-// z = 1e-6 the two-term series 1 - z^2 / (4 (nu - 1)).  ~130 terms of three exp each: the Matern family
-// is for the reference's small 1-D designs (n = 8), not a throughput path.
+// geometrically) with step 0.15 / max(1, sqrt z): ~130 - 190 terms of three exp each -- the Matern family is for the
+// reference's small 1-D designs (n = 8), not a throughput path.  Three switches:
+//   z^2 <= 9e-20 (z <= 3e-10): exactly 1; 1 - f < 1.1e-18 there for every nu > 1 (at nu -> 1 it is z^2 |log z| / 2).
+//   z^2 <= 1e-10 and nu >= 1.5: 1 - z^2 / (4 (nu - 1)); what it drops is below z^3 / 3 = 3.3e-16 (largest at nu = 1.5,
+//     where f = (1 + z) exp(-z)).  NOT for nu < 1.5: the next term, of order (z / 2)^(2 nu) Gamma(-nu) / Gamma(nu),
+//     cancels the kept one into z^2 log z as nu -> 1 (2.5e-9 relative at nu = 1.0001, z = 1e-6).
+//   otherwise the rule.  Its rounding is that of the exponent nu log z - z and of the terms' exponents, ~eps times their
+//     size: below z = 1e-5 that size is nu |log z| <= 1.5 * 22, above it <= 10 * 11.5, and for large z it is z, the
+//     conditioning of exp(-z).
+// Held by tests/test_special.py (the same rule in libm arithmetic) and tests/test_gpu_family_corr_exact.py (this code)
+// to 5e-14 + 4 eps z relative against a 40-digit evaluation for nu from 1.0001 to 10 and z from 1e-9 to 740.  The last
+// product is grouped so that a subnormal exp() is multiplied once, by a factor below 1: within two quanta down to 0.
 __device__ inline double matern_corr(const KernelFamily& f, double z2) {
-  if (!(z2 > 1e-12)) return 1.0 - (z2 > 0.0 ? z2 : 0.0) / (4.0 * (f.nu - 1.0));
+  if (!(z2 > 9e-20)) return z2 == z2 ? 1.0 : z2;
+  if (z2 <= 1e-10 && f.nu >= 1.5) return 1.0 - z2 / (4.0 * (f.nu - 1.0));
   const double z = sqrt(z2);
   const double hs = 0.15 / fmax(1.0, sqrt(z));
   double s = 0.5;
@@ -414,7 +426,7 @@ __device__ inline double matern_corr(const KernelFamily& f, double z2) {
     s += g;
     if (g < 1e-17 * s && f.nu * t < z * c1) break;
   }
-  return exp(f.nu * log(z) - z) * hs * s * f.norm;
+  return exp(f.nu * log(z) - z) * (hs * s * f.norm);
 }
 __device__ __forceinline__ double corr_of_dist(const KernelFamily& f, double dist, const double* tab, int component = 0) {
   if (f.id == 0) return exp_cov(dist, tab);

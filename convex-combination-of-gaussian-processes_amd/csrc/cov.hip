@@ -4,7 +4,8 @@
 // corr.vec(.ISO) HX:367-375 / ANI:369-377, Mixed.corr.matrix HX:408-415 / ANI:399-406,
 // Mixed.corr.vec HX:425-431.  The reference's EXPANDED distance is kept:
 //   dist_c(i,j) = (u_ci + u_cj) - 2 sum_k (x_ik theta_ck) x_jk,   u_ci = sum_k theta_ck x_ik^2
-// (HX:352-355), so the diagonal is exp(-rounding) exactly as in R, not a forced 1.
+// (HX:352-355), so the diagonal is exp(-rounding) exactly as in R, not a forced 1.  The 1-D scripts' families (Matern,
+// cubic spline) take |x_i - x_j| directly (D1:368-374, D1F:366-462) and so does cov_kernel<1>.
 //
 // Roofline: the algorithmic traffic is the output write (8 n^2 B dense, 4 n^2 B lower tiles; X is read
 // once per tile into LDS and every output column is written as 512 B contiguous per wave, lane = row),
@@ -144,6 +145,19 @@ __global__ __launch_bounds__(256) void cov_kernel(CovArgs a) {
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const double* __restrict__ bcol = SCOL ? a.colpad + j0 + wave_u * JW : nullptr;
   for (int c = 0; c < K; ++c) {
+    if constexpr (FAM != 0) {
+      // the 1-D families (draw_view enforces d = 1) take the distance as their scripts do, from the direct difference
+      // (U <- abs(A - t(A)), D1:368-374): rate (x_i - x_j)^2 is exactly 0 where the points coincide -- a diagonal of
+      // exactly 1 -- its rounding is relative, whatever the design's offset, and a NaN coordinate stays NaN.  The
+      // expanded form's rounding is absolute in z^2, eps rate x^2: 6e-10 on the diagonal at theta = 0.01, x = 10.
+      const double xr = xa[lane], rate = th[c * d], wc = w2[c];
+#pragma unroll
+      for (int jj = 0; jj < JW; ++jj) {
+        const double h = xr - xb[jl0 + jj];
+        accs[jj] = fma(wc, corr_of_dist(a.fam, rate * (h * h), etab, c), accs[jj]);
+      }
+      continue;
+    }
     double sdot[JW];
 #pragma unroll
     for (int jj = 0; jj < JW; ++jj) sdot[jj] = 0.0;
@@ -165,14 +179,7 @@ __global__ __launch_bounds__(256) void cov_kernel(CovArgs a) {
     }
     const double ur = ua[c * kCovRows + lane], wc = w2[c];
 #pragma unroll
-    for (int jj = 0; jj < JW; ++jj) {
-      if constexpr (FAM == 0) {
-        accs[jj] = cov_mix_term(accs[jj], wc, ur, ub[c * kCovCols + jl0 + jj], sdot[jj], etab);
-      } else {
-        const double dist = (ur + ub[c * kCovCols + jl0 + jj]) + (-2.0 * sdot[jj]);
-        accs[jj] = fma(wc, corr_of_dist(a.fam, dist, etab, c), accs[jj]);
-      }
-    }
+    for (int jj = 0; jj < JW; ++jj) accs[jj] = cov_mix_term(accs[jj], wc, ur, ub[c * kCovCols + jl0 + jj], sdot[jj], etab);
   }
   if constexpr (SCOL) {
     // lower-tile launches (the blocked path's matrix build): the tile lies inside the npad x npad array (npad a multiple

@@ -678,15 +678,18 @@ def component_corr(X, theta_c, dtype=np.float64):
     return np.exp(-acc)
 
 
-def loglik_grad_parts(X, y, row, K, d, sigma2, dtype=np.float64):
+def loglik_grad_parts(X, y, row, K, d, sigma2, dtype=np.float64, Rc=None):
     """The pieces of the closed form in dtype: dict(Sigma, Sinv, Rc (list), M, alpha, u, loglik, beta).  u = Sigma^-1 1 /
-    1' Sigma^-1 1 are the weights with beta = u' y.  Raises LinAlgError on a matrix that is not positive definite."""
+    1' Sigma^-1 1 are the weights with beta = u' y.  Raises LinAlgError on a matrix that is not positive definite.
+    Rc: the K component matrices in dtype, for a family other than the Gaussian (the 1-D scripts' Matern and spline: the row
+    then supplies the weights only); default: component_corr of the row's theta."""
     X = np.asarray(X, dtype=np.float64)
     yv = np.asarray(y, dtype=dtype).reshape(-1)
     n = yv.shape[0]
     w, Th = unpack_params(row, K, d)
     s2 = dtype(sigma2)
-    Rc = [component_corr(X, Th[c], dtype) for c in range(K)]
+    if Rc is None:
+        Rc = [component_corr(X, Th[c], dtype) for c in range(K)]
     Sigma = np.zeros((n, n), dtype=dtype)
     for c in range(K):
         Sigma += (s2 * dtype(w[c]) ** 2) * Rc[c]
@@ -802,19 +805,22 @@ MARGINAL_TOL_C = 4.0               # 32 x 0.108 = 3.46, rounded up to a power of
 GRID_NODE_Q = 2e-13
 
 
-def marginal_parts(X, y, row, K, d, sigma2, tau2, dtype=np.longdouble, expanded=False):
+def marginal_parts(X, y, row, K, d, sigma2, tau2, dtype=np.longdouble, expanded=False, Rc=None):
     """The mode-1 counterpart of loglik_grad_parts in dtype (long double: the hand-written Cholesky of Sigma0 and the rank-one
     term in closed form; fp64: LAPACK on Sigma):
     dict(Sigma, Sigma0, Sinv, Rc (list), M, alpha, loglik, beta = 0).  Kernel values in the direct squared-difference form, or,
     with expanded (fp64 only), in the scripts' expanded form u_a + u_b - 2 sum_k theta_k x_ak x_bk (corr_matrix).
-    grad_from_parts() works on the result as it stands (it reads M and Rc).  Raises LinAlgError when not positive definite."""
+    grad_from_parts() works on the result as it stands (it reads M and Rc).  Raises LinAlgError when not positive definite.
+    Rc: the K component matrices in dtype, as in loglik_grad_parts."""
     dtype = np.dtype(dtype).type
     X = np.asarray(X, dtype=np.float64)
     yv = np.asarray(y, dtype=dtype).reshape(-1)
     n = yv.shape[0]
     w, Th = unpack_params(row, K, d)
     s2 = dtype(sigma2)
-    if expanded:
+    if Rc is not None:
+        assert not expanded
+    elif expanded:
         assert dtype == np.float64
         Rc = [corr_matrix(X, Th[c]) for c in range(K)]
     else:
@@ -841,11 +847,13 @@ def marginal_parts(X, y, row, K, d, sigma2, tau2, dtype=np.longdouble, expanded=
     return dict(Sigma=Sigma, Sigma0=Sigma0, Sinv=Sinv, Rc=Rc, M=M, alpha=alpha, loglik=ll, beta=dtype(0))
 
 
-def marginal_unit(parts, X, row, K, d):
+def marginal_unit(parts, X, row, K, d, rho=None):
     """eps (sum_ab |M_ab| |Sigma_ab| + rho sum_ab |M_ab| |Sigma0_ab|): what one relative fp64 rounding of every entry of Sigma,
-    and rho roundings of every kernel value's exponent, move the mode-1 log-likelihood by (first order)."""
+    and rho roundings of every kernel value's exponent, move the mode-1 log-likelihood by (first order).  rho: the relative
+    error of a kernel value in units of eps where it is not the expanded exponent's (another family); default: that."""
     aM = np.abs(parts["M"])
-    rho = expanded_form_magnitude(X, row, K, d)
+    if rho is None:
+        rho = expanded_form_magnitude(X, row, K, d)
     return float(np.finfo(np.float64).eps * ((aM * np.abs(parts["Sigma"])).sum() + rho * (aM * np.abs(parts["Sigma0"])).sum()))
 
 
@@ -878,9 +886,10 @@ def cross_corr(Xtest, X, theta_c, dtype=np.float64):
     return np.exp(-acc)
 
 
-def predict_factor(X, y, row, K, d, dtype=np.longdouble):
+def predict_factor(X, y, row, K, d, dtype=np.longdouble, Rc=None):
     """What a draw's tables share between test sites, in dtype: dict(R, L, Rinv, o = R^-1 1, s11 = 1'o, beta, g = R^-1 (y -
-    beta 1), Rinv_y) of the normalised mixed matrix R = sum_c w_c^2 R_c / sum_c w_c^2 (HX:408-415)."""
+    beta 1), Rinv_y) of the normalised mixed matrix R = sum_c w_c^2 R_c / sum_c w_c^2 (HX:408-415).  Rc: the K component
+    matrices in dtype, as in loglik_grad_parts."""
     dtype = np.dtype(dtype).type
     X = np.asarray(X, dtype=np.float64)
     yv = np.asarray(y, dtype=dtype).reshape(-1)
@@ -889,7 +898,7 @@ def predict_factor(X, y, row, K, d, dtype=np.longdouble):
     w2 = np.asarray(w, dtype=dtype) ** 2
     R = np.zeros((n, n), dtype=dtype)
     for c in range(K):
-        R += w2[c] * component_corr(X, Th[c], dtype)
+        R += w2[c] * (component_corr(X, Th[c], dtype) if Rc is None else Rc[c])
     R = R / w2.sum()
     L = _chol_lower(R, dtype)
     Z = _lower_inverse(L, dtype)
@@ -902,17 +911,21 @@ def predict_factor(X, y, row, K, d, dtype=np.longdouble):
     return dict(R=R, L=L, Rinv=Rinv, o=o, s11=s11, beta=beta, g=g, Rinv_y=Rinv_y, y=yv, w2=w2, Th=Th)
 
 
-def predict_parts(X, y, row, K, d, sigma2, Xtest, dtype=np.longdouble, factor=None):
+def predict_parts(X, y, row, K, d, sigma2, Xtest, dtype=np.longdouble, factor=None, rc=None, raw_r=False, rho=None, rho_t=None):
     """The tables of one draw at the rows of Xtest in dtype (default long double: no LAPACK, about 1e-19 relative):
     dict(mean[m], var[m], beta, s11, r[m, n], a[m, n] = (R^-1 r)', g, o, ww[m], z1w[m], zyw[m], W = |L| |L|', rho, rho_t[m]).
-    factor: a predict_factor() of the same draw, to share it between site sets."""
+    factor: a predict_factor() of the same draw, to share it between site sets.
+    Another family than the Gaussian passes rc, the K component cross blocks [m, n] in dtype (with its factor built on Rc),
+    raw_r = True where its scripts leave r un-normalised (D1F:470-480), and rho, rho_t[m]: the relative error of an entry of R
+    (against W = |L| |L|') and of r in units of eps, which predict_bands reads in place of the expanded exponent's size."""
     dtype = np.dtype(dtype).type
     f = factor if factor is not None else predict_factor(X, y, row, K, d, dtype)
     Xtest = np.atleast_2d(np.asarray(Xtest, dtype=np.float64))
     r = np.zeros((Xtest.shape[0], f["R"].shape[0]), dtype=dtype)
     for c in range(K):
-        r += f["w2"][c] * cross_corr(Xtest, X, f["Th"][c], dtype)
-    r = r / f["w2"].sum()
+        r += f["w2"][c] * (cross_corr(Xtest, X, f["Th"][c], dtype) if rc is None else rc[c])
+    if not raw_r:
+        r = r / f["w2"].sum()
     a = r @ f["Rinv"]
     ww = (a * r).sum(axis=1)
     z1w = r @ f["o"]
@@ -923,8 +936,8 @@ def predict_parts(X, y, row, K, d, sigma2, Xtest, dtype=np.longdouble, factor=No
     aL = np.abs(np.asarray(f["L"], dtype=np.float64))
     Th = np.asarray(f["Th"], dtype=np.float64)
     return dict(mean=mean, var=var, beta=f["beta"], s11=f["s11"], r=r, a=a, g=f["g"], o=f["o"], ww=ww, z1w=z1w, zyw=zyw,
-                W=aL @ aL.T, y=f["y"], rho=expanded_form_magnitude(X, row, K, d),
-                rho_t=2.0 * ((Xtest ** 2) @ Th.T).max(axis=1))
+                W=aL @ aL.T, y=f["y"], rho=expanded_form_magnitude(X, row, K, d) if rho is None else rho,
+                rho_t=2.0 * ((Xtest ** 2) @ Th.T).max(axis=1) if rho_t is None else rho_t)
 
 
 def predict_bands(parts, sigma2, c=PREDICT_TOL_C):

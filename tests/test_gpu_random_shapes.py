@@ -136,8 +136,9 @@ def test_kept_factors_and_design_logdets(handle, n, d, K, seed):
 @pytest.mark.parametrize("n,nu,seed", [(7, 1.25, 1), (33, 1.5, 2), (64, 2.5, 3), (90, 5.0, 4), (128, 1.5, 5), (129, 2.5, 6),
                                         (200, 7.5, 7), (300, 5.0, 8)])
 def test_matern_family_on_both_paths(handle, n, nu, seed):
-    """The 1-D scripts' Matern kernel (D1:348-351) through the batched likelihood and prediction, on the register-resident
-    evaluator (n <= 128) and on the blocked sweep; design points a jittered grid on [0, 1], length scales around the spacing
+    """The 1-D scripts' Matern kernel (D1:348-351) through the batched likelihood and prediction.  The family exists on the
+    blocked sweep only, whatever n (tests/test_gpu_routes.py test_matern_goes_blocked asserts the route): the sizes cover
+    one 128-row tile and less, and several tiles.  Design points a jittered grid on [0, 1], length scales around the spacing
     (smoother kernels on closer points are numerically singular at any precision)."""
     from ccgp_amd import api
     rng = np.random.default_rng(seed)
