@@ -49,6 +49,7 @@ SIGNATURES = {
                                       c_int, c_double, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "ccgp_loglik_grad_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, c_double,
                                        _dp, _dp, _dp, _ip]),
+    "ccgp_profile_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, _dp, _dp, _dp, _ip]),
     "ccgp_logpost": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, c_int, _dp, _dp, _dp, _dp,
                              _dp, _dp, _ip]),
     "ccgp_logpost_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, c_int, _dp, c_int, _dp, _dp, _dp, _dp, _ip]),
@@ -504,6 +505,23 @@ class Handle:
         self._chk(lib().ccgp_loglik_grad_batch(self._h, _p(X), n, d, _p(y), K, _p(params), B,
                                                float(sigma2), _p(ll), _p(beta), _p(grad), _ipt(st)))
         return ll, beta, grad, st
+
+    def profile_batch(self, X, y, K, params, grad=False):
+        """ccgp_profile_batch: the likelihood with sigma2 concentrated out (ordinary kriging), one factorisation per
+        draw.  params: [B, K + K*d].  Returns (loglik[B], sigma2[B], beta[B], grad[B, P] or None, status[B]); grad is
+        d loglik / d params at each draw's own (beta, sigma2) and needs the Gaussian family."""
+        X, y = _f(X), _f(np.ravel(y))
+        n, d = X.shape
+        params = _f(np.atleast_2d(params))
+        B, P = params.shape
+        if P != K + K * d:
+            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
+        ll, s2, beta = np.empty(B), np.empty(B), np.empty(B)
+        g = np.empty((B, P), dtype=np.float64, order="F") if grad else None
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_profile_batch(self._h, _p(X), n, d, _p(y), K, _p(params), B, _p(ll), _p(s2), _p(beta),
+                                           _p(g), _ipt(st)))
+        return ll, s2, beta, g, st
 
     def logpost(self, X, y, sigma2, prior_id, theta_t, prior_pars=None, want_Rinv=True):
         X, y = _f(X), _f(np.ravel(y))

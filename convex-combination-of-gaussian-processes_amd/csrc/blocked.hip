@@ -1199,6 +1199,7 @@ struct FinishArgs {
   double* s11_out;   // nb doubles (1' R^-1 1 in the factor's metric), for the prediction pass
   double* beta_out;  // nb doubles, chunk-local copy of beta
   double* logdet_out;   // log det of the factorised matrix (mode 0: the normalised R), indexed like loglik; or nullptr
+  double* s2hat;        // PROF: sigma2_hat = q / (n sum w^2) per matrix, indexed like loglik (b0 + b); `sigma2` is not read
 };
 
 __device__ inline double block_sum(double v, double* red, int tid) {
@@ -1209,6 +1210,9 @@ __device__ inline double block_sum(double v, double* red, int tid) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// PROF: sigma2 concentrated out (ccgp_profile_batch; sigma2.MLE D1:411-415): cs = q / n, formed here where q is, and left
+// per matrix for the gradient stages.  A template parameter so that the existing instantiation compiles from unchanged code.
+template <bool PROF = false>
 __global__ __launch_bounds__(256) void finish_kernel(FinishArgs g) {
   __shared__ double red[4];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -1241,7 +1245,13 @@ __global__ __launch_bounds__(256) void finish_kernel(FinishArgs g) {
       q = fma(v, v, q);
     }
     q = block_sum(q, red, tid);
-    ll = -0.5 * (g.n * kLog2Pi + g.n * log(cs) + logdet + q / cs);
+    if constexpr (PROF) {
+      const double csh = q / g.n;
+      ll = -0.5 * (g.n * kLog2Pi + g.n * log(csh) + logdet + g.n);
+      if (tid == 0) g.s2hat[gb] = (g.status && g.status[gb] != 0) ? __longlong_as_double(0x7ff8000000000000LL) : csh / sw;
+    } else {
+      ll = -0.5 * (g.n * kLog2Pi + g.n * log(cs) + logdet + q / cs);
+    }
   } else {
     ll = -0.5 * (g.n * kLog2Pi + logdet + syy);
   }
@@ -1376,6 +1386,7 @@ struct RinvArgs {
   double sigma2;
   const double* alpha;   // nb x npad
   double* gpart;         // nb x ntiles x P
+  const double* s2hat;   // PROF: sigma2 per matrix, indexed by draw0 + b, instead of the scalar
 };
 
 // One 128 x 128 tile (ta >= tb) of R^-1 = Z Z' (k from block ta on, where both row blocks are non-zero), kept in
@@ -1389,7 +1400,7 @@ struct RinvArgs {
 // (512 VGPRs: one workgroup per CU, the round-2 loop alone on its CU -- 30 TFLOP/s), and every attempt to contract without
 // that second set under 256 registers ended in kilobytes of scratch (14.6 -> 25.6 ms per 16 draws at n = 4096).  A round
 // trip of M through HBM costs 2 x 67 MB per draw -- 0.03 ms at 5 TB/s -- and leaves each kernel with one job.
-template <bool GRAD, bool IL>
+template <bool GRAD, bool IL, bool PROF = false>
 __device__ __forceinline__ void rinv_tile_finish(const RinvArgs& g, d4 (&acc)[4][4], int b, int ta, int tb) {
   // acc[x][y][r] = Rinv[row = ta*128 + map.row(y)][col = tb*128 + map.col(x, r)]
   const AccMap<IL> map;
@@ -1412,7 +1423,7 @@ __device__ __forceinline__ void rinv_tile_finish(const RinvArgs& g, d4 (&acc)[4]
     const int gdraw = g.draw0 + b;
     double sw = 0.0;
     for (int q = 0; q < g.K; ++q) { const double w = g.params[gdraw + (size_t)q * g.ldp]; sw += w * w; }
-    const double cs = g.sigma2 * sw;
+    const double cs = (PROF ? g.s2hat[gdraw] : g.sigma2) * sw;
     const double* al = g.alpha + (size_t)b * g.npad;
     double* Mt = const_cast<double*>(g.A) + (size_t)b * g.a_stride + (size_t)ta * kTile + (size_t)tb * kTile * g.ld;
     double ala[4];
@@ -1441,7 +1452,7 @@ __device__ __forceinline__ void rinv_tile_finish(const RinvArgs& g, d4 (&acc)[4]
   }
 }
 
-template <bool GRAD>
+template <bool GRAD, bool PROF = false>
 __global__ __launch_bounds__(256, 2) void rinv_tile_kernel(RinvArgs g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int ntiles = g.nt * (g.nt + 1) / 2;
@@ -1463,10 +1474,10 @@ __global__ __launch_bounds__(256, 2) void rinv_tile_kernel(RinvArgs g) {
   d4 acc[4][4];
   if (!g.wide && fits_buffer_offsets(Kdim, g.ld)) {   // uniform
     tile_accumulate_il(smem, P, g.ld, Q, g.ld, Kdim, acc);
-    rinv_tile_finish<GRAD, true>(g, acc, b, ta, tb);
+    rinv_tile_finish<GRAD, true, PROF>(g, acc, b, ta, tb);
   } else {                                            // 64-bit-pointer loop, same bits
     gemm_accumulate<1, false>(smem, P, g.ld, Q, g.ld, Kdim, acc);
-    rinv_tile_finish<GRAD, false>(g, acc, b, ta, tb);
+    rinv_tile_finish<GRAD, false, PROF>(g, acc, b, ta, tb);
   }
 }
 
@@ -1610,10 +1621,12 @@ struct GradReduceArgs {
   double sigma2;
   const int* status;
   double* grad;
+  const double* s2hat;   // PROF: sigma2 per matrix, indexed like grad's rows
 };
 
 // one workgroup per (matrix, parameter): 256 strided partial sums, then the block's fixed-order tree (round 4; before, ONE
 // thread walked a parameter's 528 -- now 2080 -- partials: 0.9 ms for 16 draws at n = 4096, as long as the contraction itself)
+template <bool PROF = false>
 __global__ __launch_bounds__(256) void blocked_grad_reduce_kernel(GradReduceArgs g) {
   __shared__ double red[4];
   const int b = blockIdx.x / g.P, q = blockIdx.x % g.P, gb = g.b0 + b, tid = threadIdx.x;
@@ -1623,8 +1636,10 @@ __global__ __launch_bounds__(256) void blocked_grad_reduce_kernel(GradReduceArgs
   if (tid) return;
   const int c = q < g.K ? q : (q - g.K) / g.d;
   const double wc = g.params[gb + (size_t)c * g.ldp];
-  double v = q < g.K ? 2.0 * g.sigma2 * wc * s : -g.sigma2 * wc * wc * s;
+  const double s2 = PROF ? g.s2hat[gb] : g.sigma2;
+  double v = q < g.K ? 2.0 * s2 * wc * s : -s2 * wc * wc * s;
   if (g.status && g.status[gb] != 0) v = __longlong_as_double(0x7ff8000000000000LL);
+  if (PROF && !(s2 > 0.0)) v = __longlong_as_double(0x7ff8000000000000LL);   // q = 0: the likelihood is +Inf and has no gradient
   g.grad[gb + (size_t)q * g.Btot] = v;
 }
 
@@ -1724,6 +1739,7 @@ struct GroupRun {
 
   void finish() {
     const BlockedJob* pr = job && job->kind == kJobPredict ? job : nullptr;
+    double* s2hat = job ? job->s2hat : nullptr;   // the profiled mode: every later stage reads sigma2 per matrix from here
     {
       ScopedTimer t(h, CCGP_T_SOLVE, s);
       FinishArgs fa{};
@@ -1732,7 +1748,9 @@ struct GroupRun {
       fa.mode = mean_mode; fa.loglik = loglik; fa.beta = beta; fa.status = status; fa.ld = w.ld;
       fa.s11_out = w.fin; fa.beta_out = w.fin + nb;
       fa.logdet_out = job && job->kind == kJobLogdet ? job->logdet : nullptr;
-      hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, s, fa);
+      fa.s2hat = s2hat;
+      if (s2hat) hipLaunchKernelGGL(finish_kernel<true>, dim3(nb), dim3(256), 0, s, fa);
+      else hipLaunchKernelGGL(finish_kernel<false>, dim3(nb), dim3(256), 0, s, fa);
       if (pr) {
         PredFinishArgs pa{w.A, w.a_stride, npad, w.ld, n, pr->m, nullptr, 0, 0, w.fin, w.fin + nb, status, b0, pr->S,
                           sigma2, pr->mean, pr->var};
@@ -1754,8 +1772,9 @@ struct GroupRun {
         AlphaArgs aa{w.A, w.a_stride, npad, w.ld, n, w.fin + nb, job->alpha};
         hipLaunchKernelGGL(alpha_kernel, dim3(npad / 64, nb), dim3(64 * kAlphaWaves), 0, s, aa);
         ra.X = X; ra.d = d; ra.K = dv.K; ra.params = dv.params; ra.ldp = dv.ldp; ra.draw0 = b0;
-        ra.sigma2 = sigma2; ra.alpha = job->alpha; ra.gpart = job->gpart;
-        hipLaunchKernelGGL(rinv_tile_kernel<true>, grid, block, gemm_lds_bytes<1>(), s, ra);
+        ra.sigma2 = sigma2; ra.alpha = job->alpha; ra.gpart = job->gpart; ra.s2hat = s2hat;
+        if (s2hat) hipLaunchKernelGGL((rinv_tile_kernel<true, true>), grid, block, gemm_lds_bytes<1>(), s, ra);
+        else hipLaunchKernelGGL(rinv_tile_kernel<true>, grid, block, gemm_lds_bytes<1>(), s, ra);
         const int nt64 = npad / 64, ntg = nt64 * (nt64 + 1) / 2;
         GradContractArgs ca{w.A, w.a_stride, w.ld, n, d, dv.K, X, dv.params, dv.ldp, b0, job->gpart, ntg};
         const dim3 cgrid(ntg, 1, nb);
@@ -1765,8 +1784,9 @@ struct GroupRun {
         else if (d <= 8) hipLaunchKernelGGL(grad_contract_kernel<8>, cgrid, block, clds, s, ca);
         else hipLaunchKernelGGL(grad_contract_kernel<0>, cgrid, block, clds, s, ca);
         GradReduceArgs ga{job->gpart, ntg, P, dv.K, d, nb, b0, job->Btot, dv.params, dv.ldp, sigma2,
-                          status, job->grad};
-        hipLaunchKernelGGL(blocked_grad_reduce_kernel, dim3(nb * P), dim3(256), 0, s, ga);
+                          status, job->grad, s2hat};
+        if (s2hat) hipLaunchKernelGGL(blocked_grad_reduce_kernel<true>, dim3(nb * P), dim3(256), 0, s, ga);
+        else hipLaunchKernelGGL(blocked_grad_reduce_kernel<false>, dim3(nb * P), dim3(256), 0, s, ga);
       }
     }
   }
@@ -1843,6 +1863,7 @@ static void raise_blocked_lds_limits() {
     raise_lds_limit((const void*)chol_sched_kernel, "chol_sched_kernel");
     raise_lds_limit((const void*)rinv_tile_kernel<false>, "rinv_tile_kernel<false>");
     raise_lds_limit((const void*)rinv_tile_kernel<true>, "rinv_tile_kernel<true>");
+    raise_lds_limit((const void*)rinv_tile_kernel<true, true>, "rinv_tile_kernel<true, profiled>");
     raise_lds_limit((const void*)grad_contract_kernel<4>, "grad_contract_kernel<4>");
     raise_lds_limit((const void*)grad_contract_kernel<6>, "grad_contract_kernel<6>");
     raise_lds_limit((const void*)grad_contract_kernel<8>, "grad_contract_kernel<8>");

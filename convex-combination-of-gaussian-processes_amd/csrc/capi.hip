@@ -1132,6 +1132,71 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
                      status);
 } CCGP_GUARD_END(h)
 
+// ---- ordinary-kriging MLE: the likelihood with sigma2 concentrated out (ccgp.h) -----------------------------------------
+int ccgp_profile_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                       const double* params, int B, double* out_loglik, double* out_sigma2,
+                       double* out_beta, double* out_grad, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || B < 0 || !X || !y || !params || !out_loglik || !out_sigma2)
+    return fail(h, CCGP_EINVAL, "ccgp_profile_batch: bad argument");
+  if (B == 0) return CCGP_OK;
+  const bool want_grad = out_grad != nullptr, gauss = h->fam.id == 0;
+  if (want_grad && !gauss)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch: analytic gradient is implemented for the Gaussian family only");
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  // no route of its own: the value is a likelihood call, the gradient a gradient call
+  const Route route = want_grad ? small_route(Op::Grad, true, n, d, K) : small_route(Op::Loglik, gauss, n, d, K);
+  if (want_grad && route == Route::Blocked && !blocked_grad_supported(d, K))
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch: d + K too large for the contraction kernel's LDS");
+  const int nch = route == Route::Lds ? small_grad_chunks(n, d) : 0;
+  double *dX, *dy, *dp, *dg = nullptr, *dll, *ds2, *dbeta, *dgp = nullptr;
+  int* dst;
+  if (int rc = stage(h, [&](Layout& c) {
+        dX = c.take<double>((size_t)n * d);
+        dy = c.take<double>(n);
+        dp = c.take<double>((size_t)B * P);
+        if (want_grad) dg = c.take<double>((size_t)B * P);
+        dll = c.take<double>(B);
+        ds2 = c.take<double>(B);
+        dbeta = c.take<double>(B);
+        dst = c.take<int>(B);
+        if (route == Route::Lds) dgp = c.take<double>((size_t)B * nch * P);   // partial sums of launch_small_grad
+      }))
+    return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dp, B, K, d, &dv)) return frc;
+  if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, (size_t)B * P)})) return prc;
+  if (route == Route::Blocked) {
+    // the sweep of ccgp_loglik_batch / ccgp_loglik_grad_batch; finish_kernel leaves sigma2_hat per matrix in ds2 (indexed by
+    // draw across the chunks, as loglik, beta and status are) and the gradient stages read it there
+    const int npad = round_up(n, kTile);
+    const size_t ntiles = blocked_grad_partials(npad);
+    BlockedJob job{};
+    job.kind = want_grad ? kJobGrad : kJobNone; job.grad = dg; job.Btot = B; job.s2hat = ds2;
+    int rc;
+    if (want_grad)
+      rc = run_sweep(h, dX, n, d, dy, dv, B, npad / kTile, 1.0, CCGP_MEAN_PROFILE_BETA, 0.0, {dll, dbeta, dst}, &job,
+                     sizeof(double) * (ntiles * P + npad), [&](Layout& w, int nb) {
+                       w.off = Layout::al(w.off);
+                       job.gpart = w.take<double>((size_t)nb * ntiles * P);
+                       job.alpha = w.take<double>((size_t)nb * npad);
+                     });
+    else
+      rc = run_sweep(h, dX, n, d, dy, dv, B, 0, 1.0, CCGP_MEAN_PROFILE_BETA, 0.0, {dll, dbeta, dst}, &job, 0, no_scratch);
+    if (rc) return rc;
+  } else {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    if (route == Route::Reg)
+      launch_small_reg_profile(h->stream, dX, n, d, dy, dv, B, dll, ds2, dbeta, dg, dst, h->opt_small_grid16 != 0);
+    else
+      launch_small_grad(h->stream, dX, n, d, dy, dv, B, 1.0, dll, dbeta, dg, dst, dgp, ds2);
+    CCGP_LAUNCH_CHECK();
+  }
+  return pull_status(h, {piece(dg, out_grad, want_grad ? (size_t)B * P : 0), piece(dll, out_loglik, B), piece(ds2, out_sigma2, B),
+                         piece(dbeta, out_beta, B)}, dst, B, status);
+} CCGP_GUARD_END(h)
+
 // ---- a8: logpost ------------------------------------------------------------------------------
 // One transformed parameter vector (psi1, psi2, phi[, zeta]) = (log theta1, log theta2, logit p[, log lambda]) -> the C-ABI
 // parameter row (w_1, w_2, theta_1k.., theta_2k..), the log-Jacobian and the script's log-prior (HX:446-463, GV:450, ISO:453,

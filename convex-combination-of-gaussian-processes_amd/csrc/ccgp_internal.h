@@ -141,10 +141,11 @@ void launch_predict_summary(hipStream_t s, const double* d_mean, const double* d
 void launch_small_inverse(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int draw,
                           double sigma2, double* Rinv, double* loglik, double* beta, int* status);
 int small_grad_chunks(int n, int d);
-// gpart: scratch of B * small_grad_chunks(n, d) * P doubles
+// gpart: scratch of B * small_grad_chunks(n, d) * P doubles.  s2hat != nullptr: the profiled mode (ccgp_profile_batch) --
+// sigma2 is not read, every draw is evaluated at its own sigma2_hat, which lands in s2hat[B]
 void launch_small_grad(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                        int B, double sigma2, double* loglik, double* beta, double* grad,
-                       int* status, double* gpart);
+                       int* status, double* gpart, double* s2hat = nullptr);
 
 // ---- small_reg.hip: register-resident evaluator (n <= 128); the small_reg_*_supported predicates: small_layout.h ---------
 void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
@@ -159,6 +160,9 @@ void launch_small_reg_inverse(hipStream_t s, const double* X, int n, int d, cons
                               double sigma2, double* Rinv, double* loglik, double* beta, int* status);
 void launch_small_reg_grad(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B,
                            double sigma2, double* loglik, double* beta, double* grad, int* status);
+// ccgp_profile_batch at n <= 128: sigma2 concentrated out; grad may be nullptr (value only: the likelihood instances)
+void launch_small_reg_profile(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B,
+                              double* loglik, double* s2hat, double* beta, double* grad, int* status, bool grid16 = false);
 // d log det R_mixed / d X of the rows >= n_fixed for B candidate designs (entropy criteria, BSQ:856-948); dgrad holds
 // per design (n - n_fixed) x d column-major
 void launch_small_reg_logdet_grad_designs(hipStream_t s, const double* Xs, int n, int d, DrawView dv, int B, int n_fixed,
@@ -181,7 +185,7 @@ struct BlockedWs {
   int ne;           // extra full tile rows (ceil(m / 128) for prediction, else 0)
 };
 // optional extra work riding on a blocked sweep (n > 128)
-enum { kJobLogdet = -1, kJobPredict = 1, kJobInverse = 2, kJobGrad = 3 };   // >= kJobInverse: identity rows ride along
+enum { kJobLogdet = -1, kJobNone = 0, kJobPredict = 1, kJobInverse = 2, kJobGrad = 3 };   // >= kJobInverse: identity rows ride along
 struct BlockedJob {
   int kind;
   // kJobPredict (a10 + a11): m cross-correlation rows ride along as extra tile rows
@@ -198,6 +202,9 @@ struct BlockedJob {
   double* alpha;        // scratch: nb x npad,  R^-1 (y - beta 1)
   // kJobLogdet: log det of the normalised mixed correlation matrix (entropy criteria, BSQ:856-877), indexed like loglik
   double* logdet;
+  // any kind (kJobNone: nothing else rides): the profiled mode of ccgp_profile_batch.  finish_kernel concentrates sigma2 out
+  // and leaves each matrix's sigma2_hat here, indexed like loglik; the gradient stages read it instead of the scalar
+  double* s2hat;
 };
 bool blocked_grad_supported(int d, int K);
 size_t blocked_grad_partials(int npad);   // partial sums per matrix and parameter (gpart = nb x this x P)

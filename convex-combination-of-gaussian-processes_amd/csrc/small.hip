@@ -46,6 +46,7 @@ struct SmallArgs {
   double* Rinv;      // n x n (inverse)
   double* gpart;     // gradient partials [draw][chunk][P]
   int want_grad;
+  double* s2hat;     // PROF: the draw's own sigma2 = q / (n sum w^2); `sigma2` is not read
 };
 
 __device__ inline double wave_sum(double v) {
@@ -54,6 +55,9 @@ __device__ inline double wave_sum(double v) {
 }
 
 // LDS carve: SmallCarve (small_layout.h)
+// PROF: sigma2 concentrated out (as small_reg_kernel's PROF): cs becomes this draw's q / n where the likelihood is finished, and
+// the gradient stage reads it from there.  Every chunk of a draw repeats the draw's factorisation, so each forms the same bits.
+template <bool PROF = false>
 __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int n = a.n, d = a.d, K = a.K;
@@ -159,7 +163,16 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
           q += r * r / dk;
         }
       quad = wave_sum(q);
-      ll = -0.5 * (n * kLog2Pi + n * log(cs) + logdet + quad / cs);
+      if constexpr (PROF) {
+        const double csh = quad / n;
+        ll = -0.5 * (n * kLog2Pi + n * log(csh) + logdet + n);
+        if (lane == 0) {
+          red[3] = csh;
+          if (chunk == 0) a.s2hat[b] = bad ? kNaN : csh / sw;
+        }
+      } else {
+        ll = -0.5 * (n * kLog2Pi + n * log(cs) + logdet + quad / cs);
+      }
     } else {
       quad = syy;
       ll = -0.5 * (n * kLog2Pi + logdet + quad);
@@ -205,6 +218,9 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
     // alpha = R^-1 (y - beta 1) / cs.  Partial sums over this chunk's columns t:
     //   G_c  = sum M R_c ,  H_ck = sum M D_k R_c      (R_c recomputed, never stored)
     const int P = K + K * d;
+    const double csg = PROF ? red[3] : cs;
+    const double s2g = PROF ? csg / sw : a.sigma2;
+    const bool nograd = bad || (PROF && !(csg > 0.0));   // q = 0: the likelihood is +Inf and has no gradient
     double* gp = a.gpart + ((size_t)blockIdx.x * gridDim.y + chunk) * P;
     for (int q = wave; q < P; q += 4) {
       const int c = q < K ? q : (q - K) / d;
@@ -214,9 +230,9 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
         for (int e = lane; e < mt * n; e += 64) {
           int t = e / n, i = e % n;
           int jt = t0 + t;
-          double ai = (A[n + (size_t)i * ld] - beta * A[n + 1 + (size_t)i * ld]) / cs;
-          double at = (A[n + (size_t)jt * ld] - beta * A[n + 1 + (size_t)jt * ld]) / cs;
-          double Mit = 0.5 * (ai * at - A[n + 2 + t + (size_t)i * ld] / cs);
+          double ai = (A[n + (size_t)i * ld] - beta * A[n + 1 + (size_t)i * ld]) / csg;
+          double at = (A[n + (size_t)jt * ld] - beta * A[n + 1 + (size_t)jt * ld]) / csg;
+          double Mit = 0.5 * (ai * at - A[n + 2 + t + (size_t)i * ld] / csg);
           double s = 0.0;
           for (int k = 0; k < d; ++k) s = fma(xs[k * n + i] * th[c * d + k], xs[k * n + jt], s);
           double dist = (us[c * n + i] + us[c * n + jt]) + (-2.0 * s);
@@ -227,8 +243,8 @@ __global__ __launch_bounds__(256) void small_kernel(SmallArgs a) {
       acc = wave_sum(acc);
       if (lane == 0) {
         double wc = a.params[b + (size_t)c * a.ldp];
-        double g = kk < 0 ? 2.0 * a.sigma2 * wc * acc : -a.sigma2 * wc * wc * acc;
-        gp[q] = bad ? kNaN : g;
+        double g = kk < 0 ? 2.0 * s2g * wc * acc : -s2g * wc * wc * acc;
+        gp[q] = nograd ? kNaN : g;
       }
     }
   }
@@ -249,9 +265,11 @@ static void small_launch(hipStream_t s, const SmallArgs& a, int ndraws, int nchu
   size_t lds = small_lds_bytes(a.n, a.d, a.mtile);
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
-    raise_lds_limit((const void*)small_kernel, "small_kernel");
+    raise_lds_limit((const void*)small_kernel<false>, "small_kernel");
+    raise_lds_limit((const void*)small_kernel<true>, "small_kernel<profiled>");
   });
-  hipLaunchKernelGGL(small_kernel, dim3(ndraws, nchunks), dim3(256), lds, s, a);
+  if (a.s2hat) hipLaunchKernelGGL(small_kernel<true>, dim3(ndraws, nchunks), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL(small_kernel<false>, dim3(ndraws, nchunks), dim3(256), lds, s, a);
 }
 
 void launch_small_inverse(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int draw,
@@ -273,8 +291,9 @@ int small_grad_chunks(int n, int d) {
 
 void launch_small_grad(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                        int B, double sigma2, double* loglik, double* beta, double* grad,
-                       int* status, double* gpart) {
+                       int* status, double* gpart, double* s2hat) {
   SmallArgs a{};
+  a.s2hat = s2hat;
   a.X = X; a.y = y; a.n = n; a.d = d; a.params = dv.params; a.ldp = dv.ldp; a.K = dv.K;
   a.sigma2 = sigma2; a.mode = 0; a.m = n; a.mtile = small_pick_mtile(n, d, n);
   a.loglik = loglik; a.beta = beta; a.status = status; a.gpart = gpart; a.want_grad = 1;

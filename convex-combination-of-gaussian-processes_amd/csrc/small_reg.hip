@@ -64,6 +64,7 @@ struct RegArgs {
   size_t fac_stride;
   double* dgrad;       // INV = 3: d log det R / d X of the free rows, per design (n - n_fixed) x d column-major
   int n_fixed;         // INV = 3: rows below n_fixed are the fixed batch (D.old, BSQ:920-948): no gradient
+  double* s2hat;       // PROF instantiations: the draw's own sigma2 = q / (n sum w^2) (sigma2.MLE, D1:411-415); `sigma2` is not read
 };
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
@@ -113,11 +114,17 @@ __device__ __forceinline__ void mat_sync() {
 #endif
 // INV: 0 = none, 1 = explicit inverse (solve(R), HX:454), 2 = analytic gradient of the profile-beta log-likelihood,
 // 3 = gradient of log det R with respect to the design (per-design form, entropy criteria BSQ:856-948)
-template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false>
+// PROF: sigma2 concentrated out (ordinary kriging, `ord$sig2` HX:759-760; log.likeli D1:424-444): where the likelihood is
+// finished the quadratic form q is at hand, so cs = sigma2 sum w^2 becomes the draw's own q / n, and the gradient epilogue
+// reads that value instead of the caller's -- by the envelope theorem the closed form at (beta_hat, sigma2_hat) IS the
+// gradient of the profiled likelihood.  A template parameter, not a branch: the n <= 64 instances sit at the edge of their
+// register budget (CCGP_SMALL_OCC_G8 above) and the existing instantiations compile from unchanged code.
+template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
   static_assert(!FAC || (NE == 1 && !FULL && !INV), "the factor is kept by the plain likelihood instantiation");
+  static_assert(!PROF || ((NE == 1 || INV == 2) && INV != 1 && INV != 3 && !FAC), "sigma2 is concentrated out of the likelihood and of its gradient only");
   constexpr int TPM = G * G;       // threads per matrix
   constexpr int MPW = 256 / TPM;   // matrices per workgroup
   constexpr int NP = G * NB;       // padded order
@@ -409,7 +416,15 @@ void small_reg_kernel(RegArgs a) {
           q += r * r / dvec[k];
         }
       for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-      ll = -0.5 * (n * kLog2Pi + n * log(cs) + logdet + q / cs);
+      if constexpr (PROF) {
+        // q / cs = n at cs = q / n: l_p = -(n log 2 pi + n log cs_hat + log det R + n) / 2; q = 0 (a constant y): +Inf
+        const double csh = q / n;
+        ll = -0.5 * (n * kLog2Pi + n * log(csh) + logdet + n);
+        if (lt == 0) slack[2] = csh;   // for the gradient epilogue
+        if (lt == 0 && valid && blockIdx.y == 0) a.s2hat[b] = bad ? kNaN : csh / sw;
+      } else {
+        ll = -0.5 * (n * kLog2Pi + n * log(cs) + logdet + q / cs);
+      }
     } else {
       ll = -0.5 * (n * kLog2Pi + logdet + syy);
     }
@@ -494,13 +509,17 @@ void small_reg_kernel(RegArgs a) {
       double* alpha = colbuf;                                  // [NP]   (the column buffers are free now)
       double* part = mine + cv.part;                           // [4][kGradSlots] wave partial sums
       const double beta = slack[0];
+      // the profiled mode differs here only: this draw's cs_hat = q / n and sigma2_hat = cs_hat / sum w^2 (what s2hat[b] holds)
+      const double csg = PROF ? slack[2] : cs;
+      const double s2g = PROF ? csg / sw : a.sigma2;
+      const bool nograd = bad || (PROF && !(csg > 0.0));   // q = 0: the likelihood is +Inf and has no gradient
       double* resid = zb;                                      // (z_y - beta z_1)_c d_c^-1/2 in place of z_y
       for (int c = lt; c < NP; c += TPM) resid[c] = c < n ? (zb[c] - beta * zb[NP + c]) * dvec[c] : 0.0;
       mat_sync<G>();
       for (int i = lt; i < n; i += TPM) {
         double s = 0.0;
         for (int c = i; c < n; ++c) s = fma(zmat[i * ZS + c], resid[c], s);
-        alpha[i] = s / cs;
+        alpha[i] = s / csg;
       }
       mat_sync<G>();
       const int lane64 = lt & 63, wv = lt >> 6;
@@ -520,7 +539,7 @@ void small_reg_kernel(RegArgs a) {
               for (int idx = lt; idx < n * n; idx += TPM) {
                 const int i = idx % n, j = idx / n;
                 if (i < j) continue;
-                const double m = (i == j ? 0.5 : 1.0) * (alpha[i] * alpha[j] - row_dot(i, j) / cs);
+                const double m = (i == j ? 0.5 : 1.0) * (alpha[i] * alpha[j] - row_dot(i, j) / csg);
                 double df2[KG];
 #pragma unroll
                 for (int k = 0; k < KG; ++k) {
@@ -561,9 +580,9 @@ void small_reg_kernel(RegArgs a) {
               if (q < K) {
                 const double wq = a.params[pb + (size_t)q * a.ldp];
                 if (slot == 0) {
-                  if (k0 == 0) a.grad[b + (size_t)q * a.Btot] = bad ? kNaN : 2.0 * a.sigma2 * wq * tot;
+                  if (k0 == 0) a.grad[b + (size_t)q * a.Btot] = nograd ? kNaN : 2.0 * s2g * wq * tot;
                 } else if (k0 + slot - 1 < d) {
-                  a.grad[b + (size_t)(K + q * d + k0 + slot - 1) * a.Btot] = bad ? kNaN : -a.sigma2 * wq * wq * tot;
+                  a.grad[b + (size_t)(K + q * d + k0 + slot - 1) * a.Btot] = nograd ? kNaN : -s2g * wq * wq * tot;
                 }
               }
             }
@@ -715,6 +734,14 @@ void launch_one(hipStream_t s, const RegArgs& a) {
       static unsigned long long fac_mask = 0;
       once_per_device(fac_mask, [] { raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false, 0, true>, "small_reg_kernel<fac>"); });
       kernel = small_reg_kernel<G, NB, NE, false, 0, true>;
+    } else if (a.s2hat) {   // sigma2 concentrated out: the same two instances (general, FULL) compiled with PROF
+      static unsigned long long prof_mask = 0;
+      once_per_device(prof_mask, [] {
+        raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false, 0, false, true>, "small_reg_kernel<profiled>");
+        raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, true, 0, false, true>, "small_reg_kernel<full, profiled>");
+      });
+      if (a.n == G * NB && a.x_stride == 0) kernel = small_reg_kernel<G, NB, NE, true, 0, false, true>;
+      else kernel = small_reg_kernel<G, NB, NE, false, 0, false, true>;
     } else if (a.n == G * NB && a.x_stride == 0) {
       kernel = small_reg_kernel<G, NB, NE, true>;
     }
@@ -994,11 +1021,11 @@ static void launch_site_solve(hipStream_t s, const SiteArgs& a, int ns) {
 }
 
 // ---- explicit inverse of ONE draw's matrix (solve(R), HX:454), gradient, design gradient: one workgroup per matrix ------
-template <int NB, int INV>
+template <int NB, int INV, bool PROF = false>
 static void launch_inv(hipStream_t s, const RegArgs& a) {
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
-    raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, INV>,
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF>,
                     INV == 1 ? "small_reg_kernel<inverse>" : INV == 2 ? "small_reg_kernel<gradient>" : "small_reg_kernel<design gradient>");
   });
   const size_t lds = sizeof(double) * reg_lds_doubles(16, NB, NB + 1, true, a.x_stride != 0, a.n, a.d, a.K);
@@ -1007,12 +1034,12 @@ static void launch_inv(hipStream_t s, const RegArgs& a) {
   for (int b0 = 0; b0 < a.B; b0 += kMaxGrid) {
     c.draw0 = a.draw0 + b0;
     c.B = a.B - b0 < kMaxGrid ? a.B - b0 : kMaxGrid;
-    hipLaunchKernelGGL((small_reg_kernel<16, NB, NB + 1, false, INV>), dim3(c.B, 1), dim3(256), lds, s, c);
+    hipLaunchKernelGGL((small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF>), dim3(c.B, 1), dim3(256), lds, s, c);
   }
 }
-template <int INV>
+template <int INV, bool PROF = false>
 static void dispatch_inv(hipStream_t s, const RegArgs& a) {
-  pick<1, 8>((a.n + 15) / 16, [&](auto nb) { launch_inv<decltype(nb)::value, INV>(s, a); });
+  pick<1, 8>((a.n + 15) / 16, [&](auto nb) { launch_inv<decltype(nb)::value, INV, PROF>(s, a); });
 }
 
 template <int NE = 1>
@@ -1057,6 +1084,21 @@ void launch_small_reg_grad(hipStream_t s, const double* X, int n, int d, const d
   a.B = B; a.sigma2 = sigma2;
   a.loglik = loglik; a.beta = beta; a.status = status; a.grad = grad; a.Btot = B;
   dispatch_inv<2>(s, a);
+}
+
+// ccgp_profile_batch at n <= 128: likelihood with sigma2 concentrated out, the draw's sigma2_hat, and (grad != nullptr) the
+// gradient at (beta_hat, sigma2_hat), all from the one factorisation per draw of the instances above
+void launch_small_reg_profile(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B,
+                              double* loglik, double* s2hat, double* beta, double* grad, int* status, bool grid16) {
+  RegArgs a = reg_args(X, n, d, y, dv);
+  a.B = B; a.loglik = loglik; a.beta = beta; a.status = status; a.s2hat = s2hat;
+  if (grad) {
+    a.grad = grad; a.Btot = B;
+    dispatch_inv<2, true>(s, a);
+  } else {
+    a.grid16 = grid16;
+    dispatch(s, a);
+  }
 }
 
 // log det R_mixed for B candidate designs (Xs = B blocks of n x d, column-major each) under ONE parameter row

@@ -407,6 +407,69 @@ def matern_MLEs(handle, D, y, nu, grid=96, lo=1e-3, hi=1e2):
     return dict(beta=float(beta[0]), sigma2=float(Q[0] / n), theta=float(theta))
 
 
+def kriging_starts(D_train, starts=8, rng=0, extra_starts=None):
+    """The start points of ordinary_kriging_sigma2 as rows of log theta -- the same generator drawn in the same order: start 0
+    is 1 / span^2, the others uniform(0.2, 5) / span^2 -- with `extra_starts` (rows of theta) appended."""
+    D = np.asarray(D_train, dtype=np.float64)
+    d = D.shape[1]
+    span = np.maximum(D.max(axis=0) - D.min(axis=0), 1e-12)
+    gen = np.random.default_rng(rng)
+    rows = [np.log((1.0 if s == 0 else gen.uniform(0.2, 5.0, size=d)) / span ** 2) * np.ones(d) for s in range(starts)]
+    if extra_starts is not None:
+        rows += [np.log(t) for t in np.atleast_2d(np.asarray(extra_starts, dtype=np.float64))]
+    return np.stack(rows)
+
+
+def ordinary_kriging_fit(handle, D_train, y_train, starts=8, rng=0, extra_starts=None):
+    """The ordinary-kriging MLE with one anisotropic Gaussian kernel (`mlegp(...)$sig2`, HX:759-760; the 1-D scripts' MLEs,
+    D1:455-471) with the whole objective on the device: ccgp_profile_batch returns the likelihood with sigma2 concentrated
+    out, sigma2 itself and the gradient from ONE factorisation per point, and design.minimize_starts drives all starts in
+    lockstep, so every evaluator call is one device call that carries every start still running.
+
+    Variables: log theta in [-12, 12]^d; objective -l_p, gradient -g_theta theta (chain rule to log theta; g_theta is the
+    mode-0 gradient at the point's own (beta, sigma2): envelope theorem).  Starts: kriging_starts -- those of
+    ordinary_kriging_sigma2, then `extra_starts` (rows of theta).  Returns dict(sigma2, theta[d], beta, loglik of the best
+    start -- sigma2, beta and loglik as a final value-only call at theta gives them -- f[S], x[S, d] (log theta) and converged[S]
+    per start, calls: the number of profile_batch calls, the final one included, and evaluations: the points they carried)."""
+    from .design import minimize_starts
+
+    D = np.asarray(D_train, dtype=np.float64)
+    y = np.asarray(y_train, dtype=np.float64).ravel()
+    x0 = kriging_starts(D, starts, rng, extra_starts)
+    count = dict(points=0)
+
+    def evaluate(logth):
+        theta = np.exp(logth)
+        rows = np.concatenate([np.ones((theta.shape[0], 1)), theta], axis=1)
+        ll, _, _, g, st = handle.profile_batch(D, y, 1, rows, grad=True)
+        count["points"] += theta.shape[0]
+        return -ll, -(g[:, 1:] * theta), st
+
+    res = minimize_starts(evaluate, x0, lower=-12.0, upper=12.0)
+    if not np.isfinite(res["f"]).any():
+        raise RuntimeError("ordinary_kriging_fit: the likelihood failed at every start")
+    best = int(np.argmin(np.where(np.isfinite(res["f"]), res["f"], np.inf)))
+    theta = np.exp(res["x"][best])
+    ll, s2, beta, _, _ = handle.profile_batch(D, y, 1, np.concatenate([[1.0], theta])[None], grad=False)
+    return dict(sigma2=float(s2[0]), theta=theta, beta=float(beta[0]), loglik=float(ll[0]), f=res["f"], x=res["x"],
+                converged=res["converged"], calls=res["calls"] + 1, evaluations=count["points"] + 1)
+
+
+def matern_profile(handle, D, y, nu, thetas):
+    """log.likeli of the 1-D scripts (D1:424-444) for an array of scale parameters in ONE value-only device call under the
+    Matern(nu) family: log det R(theta) + n log sigma2.MLE(theta), with beta.MLE and sigma2.MLE (D1:411-415) at each theta.
+    Returns dict(loglikeli, beta, sigma2, status), NaN where the factorisation failed."""
+    from .rsurface import _FamilyHandle
+
+    D = np.asarray(D, dtype=np.float64).reshape(-1, 1)
+    y = np.asarray(y, dtype=np.float64).ravel()
+    n = D.shape[0]
+    thetas = np.atleast_1d(np.asarray(thetas, dtype=np.float64))
+    h = _FamilyHandle(handle, api.KERNEL_MATERN, float(nu))
+    ll, s2, beta, _, st = h.profile_batch(D, y, 1, np.stack([np.ones_like(thetas), thetas], axis=1), grad=False)
+    return dict(loglikeli=-2.0 * ll - n * math.log(2.0 * math.pi) - n, beta=beta, sigma2=s2, status=st)
+
+
 def Combined_GP_fit(gp, D_train, y_train, D_new, start, N_max, samp_size, alpha_geweke, batch_size,
                     alpha=0.05, net_samp_size=None, y_new=None, sigma2=None, theta1_pars=None,
                     theta2_pars=None, rng=None, speculate=0):

@@ -184,6 +184,24 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
                            const double* params, int B, double sigma2, double* out_loglik,
                            double* out_beta, double* out_grad, int* status);
 
+/* ---- ordinary-kriging MLE: the likelihood with sigma2 concentrated out ------------------
+ * What the scripts take from an ordinary-kriging fit: sigma2.MLE (D1:411-415) inside log.like / log.likeli
+ * (D1:424-444), and `ord$sig2` of mlegp (HX:759-760).  For draw b with M = sum_c w_c^2 R_c(theta_c):
+ *   beta   = 1'M^-1 y / 1'M^-1 1,   Q = (y - beta 1)'M^-1 (y - beta 1),   sigma2 = Q / n,
+ *   loglik = -(n log 2 pi + n log sigma2 + log det M + n) / 2
+ * (the 1-D scripts' log.likeli is log det M + n log sigma2 = -2 loglik - n log 2 pi - n), from ONE factorisation per
+ * draw: sigma2 is formed on the device in the pass that forms Q.  out_grad (B x P column-major, may be NULL):
+ * d loglik / d params[b, j] -- the gradient of the mode-0 likelihood at (beta, sigma2) of the draw (envelope theorem).
+ * Host pointers; blocks.  Every family of ccgp_set_kernel without out_grad; with it the Gaussian family only
+ * (CCGP_EUNSUPPORTED otherwise, and for d + K beyond the blocked contraction's LDS, as ccgp_loglik_grad_batch).
+ * A failed factorisation: status[b] = 1-based pivot index, NaN in loglik, sigma2, beta and the gradient row; returns
+ * the number of failed draws.  Q == 0 (y exactly constant): sigma2 = 0, loglik = +Inf, gradient row NaN, status 0.
+ * out_beta / out_grad / status may be NULL. */
+int ccgp_profile_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                       const double* params, int B, double* out_loglik, double* out_sigma2,
+                       double* out_beta, double* out_grad /* B x P column-major, may be NULL */,
+                       int* status);
+
 /* ---- a8 (+a13): logpost(D.train, theta, y, sigma2[, pars]) -> list(val, beta, R.Inv) --
  * theta_t = (psi1, psi2, phi[, zeta]) on the transformed scale; prior_pars =
  * (a1,b1,a2,b2) for CCGP_PRIOR_INVGAMMA, ignored otherwise.  out_loglik (the bare
