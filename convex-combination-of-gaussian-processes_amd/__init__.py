@@ -9,15 +9,16 @@ Layout
   tables.py    reader/writer for the reference's text tables
   shard.py     one-process-per-GPU sharding of the independent evaluations
   fit.py       host-side counterpart of laplace / Metro / prediction / Combined.GP.fit (seeded RNG)
+  cgp.py       the CGP comparator of compare.GP (CGP / predict.CGP) on the device's batched state
 """
 from . import tables  # noqa: F401  (pure Python, usable without the library)
 from ._lib import LibraryMissing, library_path, load_library  # noqa: F401
 
-__all__ = ["tables", "api", "rsurface", "shard", "fit", "load_library", "library_path", "LibraryMissing"]
+__all__ = ["tables", "api", "rsurface", "shard", "fit", "cgp", "load_library", "library_path", "LibraryMissing"]
 
 
 def __getattr__(name):
-    if name in ("api", "rsurface", "shard", "fit"):
+    if name in ("api", "rsurface", "shard", "fit", "cgp"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -50,6 +50,8 @@ SIGNATURES = {
     "ccgp_loglik_grad_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, c_double,
                                        _dp, _dp, _dp, _ip]),
     "ccgp_profile_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, _dp, _dp, _dp, _ip]),
+    "ccgp_cgp_state_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, _ip, _dp, _dp, _dp, _dp, _ip]),
+    "ccgp_cgp_predict": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, _dp, c_int, _dp, _dp, _ip]),
     "ccgp_logpost": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, c_int, _dp, _dp, _dp, _dp,
                              _dp, _dp, _ip]),
     "ccgp_logpost_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, c_int, _dp, c_int, _dp, _dp, _dp, _dp, _ip]),
@@ -522,6 +524,48 @@ class Handle:
         self._chk(lib().ccgp_profile_batch(self._h, _p(X), n, d, _p(y), K, _p(params), B, _p(ll), _p(s2), _p(beta),
                                            _p(g), _ipt(st)))
         return ll, s2, beta, g, st
+
+    def cgp_state_batch(self, X, y, params, skip=None):
+        """ccgp_cgp_state_batch: the CGP state (var.MLE.DK, GV:102-133) at the B rows (lambda, theta[d], alpha[d], bw) of
+        params in one call; skip[B] (-1: none) holds a row out and predicts it (the jackknife, GV:168-197).  Returns
+        (val[B], beta[B], tau2[B], loo[B] or None without skip, status[B]); NaN where status != 0."""
+        X, y = _f(X), _f(np.ravel(y))
+        n, d = X.shape
+        params = _f(np.atleast_2d(params))
+        B, P = params.shape
+        if P != 2 * d + 2:
+            raise ValueError("params must have 2 d + 2 = %d columns" % (2 * d + 2))
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(np.ravel(skip), dtype=np.int32)
+            if sk.shape[0] != B:
+                raise ValueError("skip must have one entry per row of params")
+        val, beta, tau2 = np.empty(B), np.empty(B), np.empty(B)
+        loo = np.empty(B) if sk is not None else None
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_cgp_state_batch(self._h, _p(X), n, d, _p(y), _p(params), B, _ipt(sk), _p(val), _p(beta),
+                                             _p(tau2), _p(loo), _ipt(st)))
+        return val, beta, tau2, loo, st
+
+    def cgp_predict(self, X, y, row, Xtest):
+        """ccgp_cgp_predict: the final CGP state (GV:200-221) at ONE parameter row and predict.CGP(PI = TRUE) (GV:287-307)
+        at the m rows of Xtest (m may be 0).  Returns (out[m, 6]: Yp gp lp v Y_low Y_up, dict(s, res2, temp, sf, beta, tau2)
+        or None when the state failed, status)."""
+        X, y = _f(X), _f(np.ravel(y))
+        n, d = X.shape
+        row = _f(np.ravel(row), (2 * d + 2,))
+        Xt = _f(np.asarray(Xtest, dtype=np.float64).reshape(-1, d))
+        m = Xt.shape[0]
+        out = np.empty((m, 6), dtype=np.float64, order="F")
+        state = np.empty(3 * n + 3)
+        st = c_int()
+        self._chk(lib().ccgp_cgp_predict(self._h, _p(X), n, d, _p(y), _p(row), _p(Xt) if m else None, m,
+                                         _p(out) if m else None, _p(state), ctypes.byref(st)))
+        if st.value:
+            return out, None, st.value
+        keep = dict(s=state[:n].copy(), res2=state[n:2 * n].copy(), temp=state[2 * n:3 * n].copy(), sf=float(state[3 * n]),
+                    beta=float(state[3 * n + 1]), tau2=float(state[3 * n + 2]))
+        return out, keep, 0
 
     def logpost(self, X, y, sigma2, prior_id, theta_t, prior_pars=None, want_Rinv=True):
         X, y = _f(X), _f(np.ravel(y))

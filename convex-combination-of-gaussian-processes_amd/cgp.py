@@ -1,0 +1,167 @@
+"""The composite GP of Ba & Joseph as every script carries it: CGP (GV:58-236) and predict.CGP (GV:245-317), the third model of
+compare.GP's table (GV:654-660), with its objective on the device.
+
+The reference evaluates var.MLE.DK (GV:102-133) -- three correlation matrices, five solve(Q) -- at 505 Latin-hypercube
+candidates one after another, refines the num_starts best with optim(method = "L-BFGS-B") on finite differences, one
+evaluation per call, and then runs n more five-solve fits for the jackknife.  Here
+
+  * the 505 candidates are ONE call of ccgp_cgp_state_batch;
+  * the num_starts refinements run in lockstep through design.minimize_starts under the reference's per-variable bounds.  The
+    gradient is by central differences clipped at the bounds, so an evaluator call is one device call that carries, for every
+    start still running, its trial point and the 2 (p + 3) points around it;
+  * the jackknife is one call of n rows with skip = 0 .. n-1;
+  * the final state and every prediction come from ccgp_cgp_predict.
+
+Difference step.  R's optim differences with ndeps = 1e-3.  The objective is smooth in the box (five fixed reweighting
+passes, no data-dependent iteration), its values carry a rounding error of about n eps cond(Q) <= 1e-10, and a central
+difference with step h has truncation error h^2 f''' / 6 and rounding error 1e-10 / h: h = 1e-5 leaves both near 1e-5 of a
+gradient whose entries are of order 1 to 100, where 1e-3 leaves a truncation error of 1e-6 |f'''| that moved the optimum's
+predictions by 0.01 rms on the Ground-Vibrations set (0.001 with 1e-5).  `step` is an argument.
+
+The final optim run from `beststart` (GV:155-157) is not repeated: it starts where that start's refinement started, every
+evaluation depends on its own row only (not on the batch it travels in), so the lockstep run of that start IS that run.
+"""
+from __future__ import annotations
+
+import math
+import time
+
+import numpy as np
+
+from .design import minimize_starts
+
+N_CANDIDATE_BASE = 500      # n_candidate = 500 + num_starts (GV:136)
+NONFINITE = 1e6             # GV:130-131
+
+
+def _plain(handle):
+    return getattr(handle, "_handle", handle)
+
+
+def standardise(X):
+    """(Stand_DD, scales) of GV:68-70."""
+    X = np.asarray(X, dtype=np.float64)
+    lo = X.min(axis=0)
+    scales = X.max(axis=0) - lo
+    return (X - lo) / scales, scales
+
+
+def bounds(Xs, nugget_l=0.001, theta_l=None, alpha_l=None, kappa_u=None):
+    """(lower, upper) of (lambda, Stand_theta[p], kappa, bw), GV:77-89."""
+    n, p = Xs.shape
+    iu = np.triu_indices(n, 1)
+    d2 = ((Xs[:, None, :] - Xs[None, :, :]) ** 2).sum(-1)[iu]
+    inv = float(np.mean(1.0 / d2))
+    theta_l = 1e-4 if theta_l is None else float(theta_l)
+    alpha_l = math.log(10.0 ** 2) * inv if alpha_l is None else float(alpha_l)
+    kappa_u = math.log(10.0 ** 6) * inv if kappa_u is None else float(kappa_u)
+    if theta_l > alpha_l:
+        raise ValueError("CGP: the lower bound of theta exceeds its upper bound alpha_l")
+    lower = np.concatenate([[nugget_l], np.full(p, theta_l), [alpha_l], [0.0]])
+    upper = np.concatenate([[1.0], np.full(p, alpha_l), [kappa_u], [1.0]])
+    return lower, upper
+
+
+def rows_from_ww(ww):
+    """(lambda, Stand_theta, kappa, bw) -> the device's (lambda, theta, alpha = kappa + theta, bw), GV:103-107."""
+    ww = np.atleast_2d(np.asarray(ww, dtype=np.float64))
+    p = ww.shape[1] - 3
+    return np.concatenate([ww[:, :1 + p], ww[:, 1:1 + p] + ww[:, 1 + p:2 + p], ww[:, 2 + p:]], axis=1)
+
+
+def lhd(N, k, rng):
+    """LHD of GV:137-142 from a seeded numpy generator: a random permutation of the N cell midpoints per column."""
+    return (np.stack([rng.permutation(N) for _ in range(k)], axis=1) + 0.5) / N
+
+
+def CGP(handle, X, y, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, kappa_u=None, rng=0, step=1e-5):
+    """CGP(X, yobs, ...) of GV:58-236 -> dict with the reference's fields (lambda, theta, alpha, bandwidth, Sig_matrix: its
+    diagonal, sf, res2, temp_matrix, mu, tau2, beststart, objval, rmscv, Yp_jackknife, X, yobs), the fit's bounds, and
+    calls / evaluations: device calls and the parameter rows they carried (seconds: host clock around the three steps).  invQ
+    is not returned: predict_CGP solves with the factor the device keeps."""
+    h = _plain(handle)
+    DD = np.asarray(X, dtype=np.float64)
+    yobs = np.asarray(y, dtype=np.float64).ravel()
+    n, p = DD.shape
+    Xs, scales = standardise(DD)
+    lower, upper = bounds(Xs, nugget_l, theta_l, alpha_l, kappa_u)
+    n_par = p + 3
+    gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    count = dict(calls=0, rows=0)
+
+    def objective(ww):
+        """var.MLE.DK at the rows of ww in one device call -> (val with GV:130-131 applied, status)."""
+        val, _, _, _, st = h.cgp_state_batch(Xs, yobs, rows_from_ww(ww))
+        count["calls"] += 1
+        count["rows"] += ww.shape[0]
+        return np.where(np.isfinite(val), val, NONFINITE), st
+
+    starts = lower + lhd(N_CANDIDATE_BASE + num_starts, n_par, gen) * (upper - lower)       # GV:144-148
+    clock = [time.perf_counter()]
+    cand, _ = objective(starts)
+    clock.append(time.perf_counter())
+    order = np.argsort(cand, kind="stable")[:num_starts]                                   # GV:150-151
+    Starts = starts[np.sort(order)]
+
+    def evaluate(W):
+        k = W.shape[0]
+        hi = np.minimum(W + step, upper)
+        lo = np.maximum(W - step, lower)
+        pts = np.repeat(W[:, None, :], 1 + 2 * n_par, axis=1)
+        for j in range(n_par):
+            pts[:, 1 + 2 * j, j] = hi[:, j]
+            pts[:, 2 + 2 * j, j] = lo[:, j]
+        f, st = objective(pts.reshape(-1, n_par))
+        f = f.reshape(k, 1 + 2 * n_par)
+        g = (f[:, 1::2] - f[:, 2::2]) / (hi - lo)
+        return f[:, 0], g, st.reshape(k, -1)[:, 0]
+
+    res = minimize_starts(evaluate, Starts, lower=lower, upper=upper)                      # GV:152-154
+    clock.append(time.perf_counter())
+    if not np.isfinite(res["f"]).any():
+        raise RuntimeError("CGP: the objective failed at every start")
+    best = int(np.argmin(np.where(np.isfinite(res["f"]), res["f"], np.inf)))              # GV:155-157
+    par = res["x"][best]
+    lam, st_theta, kappa, bw = float(par[0]), par[1:1 + p], float(par[1 + p]), float(par[2 + p])
+    theta = st_theta / scales ** 2                                                         # GV:164-165
+    alpha = (kappa + st_theta) / scales ** 2
+    row = np.concatenate([[lam], theta, alpha, [bw]])
+
+    clock.append(time.perf_counter())
+    _, _, _, loo, st = h.cgp_state_batch(DD, yobs, np.repeat(row[None], n, axis=0), skip=np.arange(n))   # GV:166-198
+    clock.append(time.perf_counter())
+    count["calls"] += 1
+    count["rows"] += n
+    rmscv = float(np.sqrt(np.sum((yobs - loo) ** 2) / n))
+
+    _, keep, status = h.cgp_predict(DD, yobs, row, np.empty((0, p)))                        # GV:200-221
+    count["calls"] += 1
+    count["rows"] += 1
+    if status:
+        raise RuntimeError("CGP: the final state cannot be factorised (pivot %d)" % status)
+    return dict(X=DD, yobs=yobs, **{"lambda": lam}, theta=theta[None], alpha=alpha[None], bandwidth=bw,
+                Sig_matrix=keep["s"], sf=keep["sf"], res2=keep["res2"], temp_matrix=keep["temp"], mu=keep["beta"],
+                tau2=keep["tau2"], beststart=Starts[best], objval=float(res["f"][best]), rmscv=rmscv, Yp_jackknife=loo,
+                lower=lower, upper=upper, par=par, scales=scales, starts=Starts, f_starts=res["f"], x_starts=res["x"],
+                converged=res["converged"], jackknife_status=st, calls=count["calls"], evaluations=count["rows"],
+                refinement_calls=res["calls"],
+                seconds=dict(candidates=clock[1] - clock[0], refinement=clock[2] - clock[1], jackknife=clock[4] - clock[3]))
+
+
+def param_row(est):
+    """The device's parameter row of a fitted model."""
+    return np.concatenate([[est["lambda"]], np.ravel(est["theta"]), np.ravel(est["alpha"]), [est["bandwidth"]]])
+
+
+def predict_CGP(handle, est, newdata, PI=False):
+    """predict.CGP(object, newdata, PI) of GV:245-317 -> dict(Yp, gp, lp, v, Y_low, Y_up) as GV:314 returns it: without PI, lp
+    stays 0 and the interval is None.  The state is rebuilt on the device from the model's parameters (five factorisations)
+    rather than carried through the host."""
+    U = np.asarray(newdata, dtype=np.float64)
+    U = U.reshape(-1, est["X"].shape[1])
+    out, _, status = _plain(handle).cgp_predict(est["X"], est["yobs"], param_row(est), U)
+    if status:
+        raise RuntimeError("predict_CGP: the state cannot be factorised (pivot %d)" % status)
+    if not PI:
+        return dict(Yp=out[:, 0], gp=out[:, 1], lp=np.zeros(U.shape[0]), v=out[:, 3], Y_low=None, Y_up=None)
+    return dict(Yp=out[:, 0], gp=out[:, 1], lp=out[:, 2], v=out[:, 3], Y_low=out[:, 4], Y_up=out[:, 5])

@@ -1197,6 +1197,120 @@ int ccgp_profile_batch(ccgp_handle* h, const double* X, int n, int d, const doub
                          piece(dbeta, out_beta, B)}, dst, B, status);
 } CCGP_GUARD_END(h)
 
+// ---- the CGP comparator of compare.GP (ccgp.h; kernels: cgp.hip) ---------------------------------------------------------
+static int cgp_shape(ccgp_handle* h, const char* who, int n, int d) {
+  if (!cgp_supported(n, d))
+    return fail(h, CCGP_EUNSUPPORTED, std::string(who) + ": n must be <= 128 and the design must fit in LDS beside the "
+                                      "working matrix (n = 128: d <= 21)");
+  return CCGP_OK;
+}
+
+int ccgp_cgp_state_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, const double* params, int B,
+                         const int* skip, double* out_val, double* out_beta, double* out_tau2, double* out_loo,
+                         int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (n < 1 || d < 1 || B < 0 || !X || !y || !params || !out_val)
+    return fail(h, CCGP_EINVAL, "ccgp_cgp_state_batch: bad argument");
+  if (skip)
+    for (int b = 0; b < B; ++b)
+      if (skip[b] < -1 || skip[b] >= n || (skip[b] >= 0 && n < 2))
+        return fail(h, CCGP_EINVAL, "ccgp_cgp_state_batch: skip must be -1 or a row of a design of at least two points");
+  if (int rc = cgp_shape(h, "ccgp_cgp_state_batch", n, d)) return rc;   // before any launch
+  if (B == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = 2 * d + 2;
+  // A chunk is a call of its own: its parameter rows, its held-out rows and its results lie in the workspace, X and y in
+  // front of them.  The planner cuts B by the workspace limit and by the grid's 65535; an evaluation reads its own row only,
+  // so where the cuts fall changes no bit.
+  double *dX, *dy, *dp, *dval, *dbeta, *dtau2, *dloo;
+  int *dst, *dskip;
+  auto lay = [&](Layout& w, int nb) {
+    dX = w.take<double>((size_t)n * d);
+    dy = w.take<double>(n);
+    dp = w.take<double>((size_t)nb * P);
+    dval = w.take<double>(nb);
+    dbeta = w.take<double>(nb);
+    dtau2 = w.take<double>(nb);
+    dloo = w.take<double>(nb);
+    dst = w.take<int>(nb);
+    dskip = w.take<int>(nb);
+  };
+  int nbc = 0;
+  if (int rc = plan_chunk(h, sizeof(double) * (P + 4) + 2 * sizeof(int), B, kSweepMargin,
+                          [&](int nb) { return layout_bytes([&](Layout& w) { lay(w, nb); }); }, &nbc))
+    return rc;
+  Layout ws(h->ws);
+  lay(ws, nbc);
+  std::vector<double> rows;
+  int failed = 0;
+  for (int b0 = 0; b0 < B; b0 += nbc) {
+    const int nb = std::min(nbc, B - b0);
+    const double* hp = params;
+    if (nb != B) {   // the chunk's rows, column-major with leading dimension nb
+      rows.resize((size_t)nb * P);
+      for (int j = 0; j < P; ++j) std::memcpy(&rows[(size_t)j * nb], params + b0 + (size_t)j * B, sizeof(double) * nb);
+      hp = rows.data();
+    }
+    if (int prc = push(h, {piece(dX, b0 == 0 ? X : nullptr, (size_t)n * d), piece(dy, b0 == 0 ? y : nullptr, n),
+                           piece(dp, hp, (size_t)nb * P), piece(dskip, skip ? skip + b0 : nullptr, nb)}))
+      return prc;
+    {
+      ScopedTimer t(h, CCGP_T_FUSED);
+      launch_cgp_state(h->stream, dX, n, d, dy, dp, nb, nb, skip ? dskip : nullptr, dval, dbeta, dtau2,
+                       out_loo ? dloo : nullptr, dst, nullptr);
+    }
+    CCGP_LAUNCH_CHECK();
+    const int rc = pull_status(h, {piece(dval, out_val + b0, nb), piece(dbeta, out_beta ? out_beta + b0 : nullptr, nb),
+                                   piece(dtau2, out_tau2 ? out_tau2 + b0 : nullptr, nb),
+                                   piece(dloo, out_loo ? out_loo + b0 : nullptr, nb)},
+                               dst, nb, status ? status + b0 : nullptr);
+    if (rc < 0) return rc;
+    failed += rc;
+  }
+  return failed;
+} CCGP_GUARD_END(h)
+
+int ccgp_cgp_predict(ccgp_handle* h, const double* X, int n, int d, const double* y, const double* params,
+                     const double* Xtest, int m, double* out, double* out_state, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (n < 1 || d < 1 || m < 0 || !X || !y || !params || (m > 0 && (!Xtest || !out)))
+    return fail(h, CCGP_EINVAL, "ccgp_cgp_predict: bad argument");
+  if (int rc = cgp_shape(h, "ccgp_cgp_predict", n, d)) return rc;
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = 2 * d + 2;
+  const CgpKeep kp(n);
+  double *dX, *dy, *dp, *dXt, *dout, *dres, *dkeep;
+  int* dst;
+  auto lay = [&](Layout& w) {
+    dX = w.take<double>((size_t)n * d);
+    dy = w.take<double>(n);
+    dp = w.take<double>(P);
+    dXt = w.take<double>((size_t)m * d);
+    dout = w.take<double>((size_t)m * 6);
+    dres = w.take<double>(4);
+    dst = w.take<int>(2);
+    dkeep = w.take<double>(kp.total);
+  };
+  if (int rc = ensure_ws(h, layout_bytes(lay))) return rc;
+  Layout ws(h->ws);
+  lay(ws);
+  if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, P), piece(dXt, Xtest, (size_t)m * d)}))
+    return prc;
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    launch_cgp_state(h->stream, dX, n, d, dy, dp, 1, 1, nullptr, dres, dres + 1, dres + 2, nullptr, dst, dkeep);
+    if (m > 0) launch_cgp_predict(h->stream, dX, n, d, dp, dXt, m, dkeep, dst, dout);
+  }
+  CCGP_LAUNCH_CHECK();
+  int st = 0;
+  const int rc = pull_status(h, {piece(dout, out, (size_t)m * 6), piece(dkeep + kp.s, out_state, (size_t)3 * n + 3)}, dst, 1, &st);
+  if (rc < 0) return rc;
+  if (status) *status = st;
+  if (st && out_state)   // a failed state keeps nothing
+    for (int i = 0; i < 3 * n + 3; ++i) out_state[i] = std::nan("");
+  return rc;
+} CCGP_GUARD_END(h)
+
 // ---- a8: logpost ------------------------------------------------------------------------------
 // One transformed parameter vector (psi1, psi2, phi[, zeta]) = (log theta1, log theta2, logit p[, log lambda]) -> the C-ABI
 // parameter row (w_1, w_2, theta_1k.., theta_2k..), the log-Jacobian and the script's log-prior (HX:446-463, GV:450, ISO:453,

@@ -171,6 +171,42 @@ void launch_small_reg_loglik(hipStream_t s, const double* X, int n, int d, const
                              int B, double sigma2, int mean_mode, double tau2, double* loglik,
                              double* beta, int* status, bool grid16 = false);
 
+// ---- cgp.hip: the composite GP comparator (CGP / predict.CGP, GV:58-317), n <= 128 -------------------------------------
+// LDS carve of cgp_state_kernel, in doubles:
+//   A[ld][n]: the working matrix (lower triangle + rows y', 1'; G in the strict upper triangle), ld odd >= n + 2
+//   xs[d][n] | y | s | sqrt s | s before scaling | e^2 | temp | Q^-1 1 | x0[d] | theta[d] | alpha[d] | bw theta[d] | red[8]
+struct CgpCarve {
+  int ld;
+  size_t A, xs, yv, s, rs, sn, e2, tv, uv, x0, th, al, tb, red, total;
+  CCGP_HD CgpCarve(int n, int d) {
+    ld = (n + 2) | 1;
+    A = 0;
+    xs = A + (size_t)ld * n;
+    yv = xs + (size_t)n * d;
+    s = yv + n; rs = s + n; sn = rs + n; e2 = sn + n; tv = e2 + n; uv = tv + n;
+    x0 = uv + n; th = x0 + d; al = th + d; tb = al + d;
+    red = tb + d;
+    total = red + 8;
+  }
+};
+// what a `keep` evaluation leaves in HBM for cgp_predict_kernel, in doubles: the factor (n x n column-major: unit-lower L'
+// below the diagonal, the pivots on it) | Q^-1 1 | s | e^2 | temp | sf, beta, tau2, 1'Q^-1 1 -- from s on in the order of
+// ccgp_cgp_predict's out_state, which is one copy
+struct CgpKeep {
+  size_t F, u, s, res2, temp, sc, total;
+  CCGP_HD CgpKeep(int n) {
+    F = 0; u = (size_t)n * n; s = u + n; res2 = s + n; temp = res2 + n; sc = temp + n; total = sc + 8;
+  }
+};
+inline bool cgp_supported(int n, int d) { return n >= 1 && n <= kSmallMaxN && d >= 1 && lds_fits(CgpCarve(n, d).total); }
+// nb evaluations of the CGP state (GV:108-129; with skip, GV:168-197): params nb x (2 d + 2) column-major with leading
+// dimension ldp; skip (nb, -1 = none) and loo may be nullptr; keep != nullptr: evaluation 0 leaves its CgpKeep(n) there
+void launch_cgp_state(hipStream_t s, const double* X, int n, int d, const double* y, const double* params, int ldp, int nb,
+                      const int* skip, double* val, double* beta, double* tau2, double* loo, int* status, double* keep);
+// predict.CGP (GV:287-307) at m sites from a kept state; row: that state's parameter row, contiguous; out m x 6 column-major
+void launch_cgp_predict(hipStream_t s, const double* X, int n, int d, const double* row, const double* Xtest, int m,
+                        const double* keep, const int* status, double* out);
+
 // ---- blocked.hip ---------------------------------------------------------------------
 struct BlockedWs {
   double* A;        // nb matrices of ld x npad (lower tiles + right-hand-side / extra tile rows)

@@ -285,11 +285,24 @@ def factors_frame(gp, start, N, samp_size, batch_size, alpha_geweke, D_train, si
 
 
 # ----------------------------------------------------------------------------- prediction / compare.GP
-def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=None, exact=False):
+def _add_cgp_columns(table, gp, D_test, D_train, y_train, cgp):
+    """compare.GP's CGP columns (GV:654-660): CGP(D.train, y.train), then predict.CGP(cgp, D.test, PI = TRUE)."""
+    from . import cgp as cgp_mod
+    est = cgp_mod.CGP(gp.h, D_train, y_train, **(cgp if isinstance(cgp, dict) else {}))
+    pred = cgp_mod.predict_CGP(gp.h, est, D_test, PI=True)
+    table.update(y_hat_CGP=pred["Yp"], LL_CGP=pred["Y_low"], UL_CGP=pred["Y_up"], CGP=est)
+    return table
+
+
+def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=None, exact=False, cgp=False):
     """HX:713-725 + prediction HX:686-703 (GV:620-646 adds Quant.Combined): one row per test point
     (y.hat.Combined, Quant.Combined, LL.Combined, UL.Combined, y.true).  exact=True takes Quant and the interval from
     the exact posterior predictive on the device (gp.prediction) instead of sampling one variate per draw: rng is
-    ignored, the tables stay on the device, and the keys are the same without mean / var."""
+    ignored, the tables stay on the device, and the keys are the same without mean / var.  cgp (default off; True, or a dict
+    of cgp.CGP's keyword arguments) adds the table's CGP model (GV:654-660): y_hat_CGP, LL_CGP, UL_CGP and the fit as CGP."""
+    if cgp:
+        table = compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng, exact)
+        return _add_cgp_columns(table, gp, D_test, D_train, y_train, cgp)
     if exact:
         r = gp.prediction(D_test, alpha, draws, D_train, sigma2, y_train)
         return dict(y_hat=r["y_hat"], quant=r["Quant"], LL=r["LL"], UL=r["UL"],
@@ -495,15 +508,20 @@ def Combined_GP_fit(gp, D_train, y_train, D_new, start, N_max, samp_size, alpha_
 def write_results_table(path, table, D_test, input_names, comparators=("single", "CGP")):
     """The file compare.GP's result is written to (`write.table(as.matrix(Comp.obj), file = fname)`,
     GV:759-761): the test inputs, y.hat / Quant / LL / UL of the Combined GP, the comparator models'
-    columns (ordinary kriging and CGP are out of scope here: NA) and y.true -- same columns, order and
-    number format as `Results/Size 50 Results 1.txt`, so the two files can be diffed."""
+    columns and y.true -- same columns, order and number format as `Results/Size 50 Results 1.txt`, so the two files can be
+    diffed.  A comparator c whose y_hat_c / LL_c / UL_c the table holds (compare_GP(..., cgp=True) adds CGP's) is written;
+    one it does not hold is NA (the `.single` columns: no prediction route returns mlegp's variance form)."""
     from .tables import write_table
     D_test = np.asarray(D_test, dtype=np.float64)
     m = D_test.shape[0]
     cols = [D_test, table["y_hat"][:, None], table["quant"][:, None], table["LL"][:, None], table["UL"][:, None]]
     names = list(input_names) + ["y.hat.Combined", "Quant.Combined", "LL.Combined", "UL.Combined"]
     for c in comparators:
-        cols.append(np.full((m, 3), np.nan))
+        keys = ["y_hat_%s" % c, "LL_%s" % c, "UL_%s" % c]
+        if all(k in table for k in keys):
+            cols.append(np.stack([np.asarray(table[k], dtype=np.float64) for k in keys], axis=1))
+        else:
+            cols.append(np.full((m, 3), np.nan))
         names += ["y.hat.%s" % c, "LL.%s" % c, "UL.%s" % c]
     cols.append(np.asarray(table["y_true"], dtype=np.float64)[:, None])
     names.append("y.true")

@@ -202,6 +202,37 @@ int ccgp_profile_batch(ccgp_handle* h, const double* X, int n, int d, const doub
                        double* out_beta, double* out_grad /* B x P column-major, may be NULL */,
                        int* status);
 
+/* ---- the CGP comparator of compare.GP: CGP GV:58-236, predict.CGP GV:245-317 ------------------
+ * (the same two functions in every script; compare.GP calls them at GV:654-660, HX:713-725.)  A parameter row is
+ * (lambda, theta[d], alpha[d], bw) on the scale of X as given: G = exp(-D(theta)), L = exp(-D(alpha)), Gbw = exp(-D(bw theta)),
+ * D(r)_ij = sum_k r_k (x_ik - x_jk)^2.  One evaluation is the reference's fixed loop (GV:108-129): s = 1; four times
+ *   Q = G + lambda diag(sqrt s) L diag(sqrt s), beta = 1'Q^-1 y / 1'Q^-1 1, temp = Q^-1 (y - beta 1), e = y - beta - G temp,
+ *   s = (Gbw e^2) / (Gbw 1), sf = mean(s), s /= sf;
+ * then a fifth Q: beta, temp, tau2 = (y - beta 1)'temp / n, val = log det Q + n log tau2 (var.MLE.DK's value, without the
+ * 1e6 of GV:130-131: a non-finite val with status 0 -- sf = 0 for exactly interpolated data -- stays as it is).
+ * ccgp_cgp_state_batch replaces B calls of var.MLE.DK (GV:102-133) and, with skip, the jackknife loop's body (GV:168-197):
+ * skip[b] >= 0 runs evaluation b on the n - 1 other points and out_loo[b] is predict.CGP's value for the held-out point
+ * (v from the fourth pass's e^2 and sf, q = g + lambda sqrt(v) sqrt(s) * l, beta + q'temp); NaN where skip[b] is -1.
+ * params is B x (2 d + 2) column-major.  n <= 128 and d small enough for the design to lie in LDS beside the working matrix
+ * (d <= 21 at n = 128), else CCGP_EUNSUPPORTED before anything is launched.  A pivot <= n eps in any of the five
+ * factorisations (the rule of the mode-0 likelihood: the reference calls solve(Q)) gives status[b] = that pivot's 1-based
+ * index and NaN in every output of evaluation b; returns the number of failed evaluations.  An evaluation depends on its
+ * own row only: not on B, its position, or where the workspace limit cuts the batch.  skip, out_beta, out_tau2, out_loo and
+ * status may be NULL.
+ * ccgp_cgp_predict replaces the final state (GV:200-221) and predict.CGP with PI = TRUE (GV:287-307) for ONE row: the state
+ * stays on the device as its factor, Q^-1 1 and temp, and each test site takes its q'Q^-1 q from a forward substitution
+ * through that factor.  out is m x 6 column-major: Yp gp lp v Y_low Y_up; out_state (3 n + 3, may be NULL) receives
+ * s[n] (the diagonal of Sig_matrix), res2[n], temp[n], sf, beta, tau2.  m may be 0 (state only).  A failed state: *status
+ * = the pivot's index, NaN everywhere, return value 1.
+ * Host pointers; both block.  Not in this version: _dev variants, ccgp_reserve coverage, a ccgp_multi wrapper, an R shim. */
+int ccgp_cgp_state_batch(ccgp_handle* h, const double* X, int n, int d, const double* y,
+                         const double* params /* B x (2d+2) */, int B, const int* skip /* B or NULL */,
+                         double* out_val, double* out_beta, double* out_tau2, double* out_loo /* NULL ok */,
+                         int* status);
+int ccgp_cgp_predict(ccgp_handle* h, const double* X, int n, int d, const double* y,
+                     const double* params /* one row */, const double* Xtest, int m, double* out /* m x 6 */,
+                     double* out_state /* 3n+3, NULL ok */, int* status);
+
 /* ---- a8 (+a13): logpost(D.train, theta, y, sigma2[, pars]) -> list(val, beta, R.Inv) --
  * theta_t = (psi1, psi2, phi[, zeta]) on the transformed scale; prior_pars =
  * (a1,b1,a2,b2) for CCGP_PRIOR_INVGAMMA, ignored otherwise.  out_loglik (the bare
