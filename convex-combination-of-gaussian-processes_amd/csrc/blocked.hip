@@ -4,6 +4,8 @@
 //   update : T_ij = A_ij - sum_{k<j} L_ik L_jk'      all tiles i >= j   (f64 MFMA GEMM)
 //            + for i = j, in the same workgroup: the right-hand-side rows, then L_jj = chol(T_jj), W_j = L_jj^-1
 //   trsm   : L_ij = T_ij W_j'                        tiles i > j        (f64 MFMA GEMM)
+// (CCGP_OPT_FUSED_SOLVE, full chunks without extra rows, j >= 1: the diagonal workgroups are a launch of their own and
+// every tile is solved by the workgroup that updated it, T staying on chip -- update_solve_tile_il.)
 // The right-hand sides [y 1] are rows npad, npad+1 of an (npad+128) x npad array per matrix: the update treats
 // them with the diagonal tile (diag_rhs_tile), trsm as a thin tile row, so when the sweep ends they hold
 // Z' = [y 1]' L^-T, i.e. the forward substitution L z = b is done -- no separate solve pass over the 4n^2 B
@@ -406,6 +408,134 @@ __device__ __forceinline__ void update_tile_il(double* smem, const double* P, in
       *(d4*)(Cl + (size_t)map.dcol(x, r) * ld) = o;
     }
   }
+}
+
+// ---- whole update tile with the panel solve in its epilogue (CCGP_OPT_FUSED_SOLVE) ----------------------
+// L_ij = (C - acc) W_j' without T ever going to memory.  W_j is finished before the launch starts (the diagonal launch
+// chol_diag_solve_kernel), so no workgroup waits for another.  The two stage buffers are free once the k-loop ends and
+// hold T as the panel solve's P image [k][128 rows] (gemm_accumulate's swizzle), one HALF of the tile's columns at a time:
+//   1. waves 0 and 2 (columns 0 - 63 in AccMap<true>) write their T; all waves run the chains' k = 0 .. 63: column
+//      blocks 0 - 3 are complete and stored, blocks 4 - 7 stay as partial accumulators;
+//   2. waves 1 and 3 (columns 64 - 127, T kept in the accumulator registers meanwhile) write theirs; the chains of blocks
+//      4 - 7 go on with k = 64 .. 16 cb + 15 and are stored.
+// Wave w solves rows 32 w .. 32 w + 31 of ALL eight column blocks: 2 x 4 x (1 + 2 + ... + 8) = 288 MFMAs per wave in both
+// halves alike (208 + 80), where trsm's 2 x 2 deal gives 256 and 320.  An output element's chain is that of
+// gemm_accumulate<1, false, true>: from zero, k ascending four at a time, the 16-column blocks of W_j above the diagonal
+// skipped whole (stage kt > cb), the zeros inside the diagonal block multiplied -- the bits of chol_trsm_kernel.
+// W_j's fragments (A operand: W[16 cb + l15][k], 128-byte runs per 16 lanes) come straight from memory: the block is
+// 128 KB per matrix, shared by all tiles of the matrix in its XCD's L2, and each fragment feeds two MFMAs.
+struct SolveGroup { int cb, kt; };
+__device__ __forceinline__ void update_solve_tile_il(double* smem, const double* P, int ldP, const double* Q, int ldQ,
+                                                     int Kdim, double* C, int ld, const double* __restrict__ W) {
+  d4 acc[4][4];
+  tile_accumulate_il(smem, P, ldP, Q, ldQ, Kdim, acc);
+  const AccMap<true> map;
+  {
+    const double* Cl = map.lane_base(C, ld);
+    // two rounds of eight 32-byte loads: all sixteen at once would need 128 registers beside the accumulators' 128
+#pragma unroll
+    for (int x0 = 0; x0 < 4; x0 += 2) {
+      d4 cv[2][4];
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cv[x][r] = *(const d4*)(Cl + (size_t)map.dcol(x0 + x, r) * ld);
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int y = 0; y < 4; ++y) acc[x0 + x][y][r] = cv[x][r][y] - acc[x0 + x][y][r];   // T, exactly as update_tile_il forms it
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  const int wave = __builtin_amdgcn_readfirstlane(tid_now() >> 6);
+  const int l15 = map.l15, l4 = map.l4, sw = l4 & 1;
+  // a lane's four rows of column k = 16 r + 4 l4 + x of its half: one 32-byte write into image row k (parity x & 1)
+  auto dump = [&]() {
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int k = 16 * r + 4 * l4 + x;
+        *(d4*)(smem + k * kTile + ((((map.row0 >> 4) + (l15 >> 2)) ^ (x & 1)) << 4) + 4 * (l15 & 3)) =
+            d4{acc[x][0][r], acc[x][1][r], acc[x][2][r], acc[x][3][r]};
+      }
+  };
+  const int rb0 = 2 * wave;
+  const double* Wl = W + l15 + (size_t)l4 * kTile;
+  int po[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) po[t] = l4 * kTile + (((rb0 + t) ^ sw) << 4) + l15;
+  double* Co = C + rb0 * 16 + l15 + (size_t)l4 * ld;   // D[i = l4 + 4 r][j = l15]: row 16 rb + l15, column 16 cb + l4 + 4 r
+
+  d4 o[8][2];
+  double wf[2][4], pf[4][2];
+  // HALF 0: image rows are k = 0 .. 63, groups (cb, kt <= min(cb, 3)); HALF 1: k = 64 .. 127, groups (cb >= 4, 4 <= kt <= cb).
+  // A group's W fragments are requested a whole group ahead into a second register set; its T fragments come from LDS
+  // and roll through ONE set, each pair of k-steps refilled for the next group as soon as its four MFMAs have been
+  // issued -- four MFMAs ahead of their use (two sets would not fit beside the 128 registers of T that waves 1 and 3
+  // carry through half 0).
+  auto fetch_w = [&](int s, SolveGroup gr) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) wf[s][kk] = Wl[gr.cb * 16 + (size_t)(gr.kt * 16 + kk * 4) * kTile];
+  };
+  auto fetch_p = [&](SolveGroup gr, int half, int kk0) {
+#pragma unroll
+    for (int kk = kk0; kk < kk0 + 2; ++kk)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) pf[kk][t] = smem[((gr.kt - 4 * half) * 16 + kk * 4) * kTile + po[t]];
+  };
+  auto run = [&](auto groups, int half) {
+    constexpr int NG = sizeof(groups.v) / sizeof(groups.v[0]);
+    fetch_w(0, groups.v[0]);
+    fetch_p(groups.v[0], half, 0);
+    fetch_p(groups.v[0], half, 2);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi) {
+      const SolveGroup gr = groups.v[gi];
+      const int s = gi & 1;
+      if (gi + 1 < NG) fetch_w(s ^ 1, groups.v[gi + 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      if (gr.kt == 0) o[gr.cb][0] = o[gr.cb][1] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int kk0 = 0; kk0 < 4; kk0 += 2) {
+#pragma unroll
+        for (int kk = kk0; kk < kk0 + 2; ++kk)
+#pragma unroll
+          for (int t = 0; t < 2; ++t)
+            o[gr.cb][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wf[s][kk], pf[kk][t], o[gr.cb][t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (gi + 1 < NG) fetch_p(groups.v[gi + 1], half, kk0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (gr.kt == gr.cb) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) Co[t * 16 + (size_t)(gr.cb * 16 + 4 * r) * ld] = o[gr.cb][t][r];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  struct Half0 { SolveGroup v[26]; };
+  struct Half1 { SolveGroup v[10]; };
+  constexpr Half0 h0{{{0, 0}, {1, 0}, {1, 1}, {2, 0}, {2, 1}, {2, 2}, {3, 0}, {3, 1}, {3, 2}, {3, 3},
+                      {4, 0}, {4, 1}, {4, 2}, {4, 3}, {5, 0}, {5, 1}, {5, 2}, {5, 3},
+                      {6, 0}, {6, 1}, {6, 2}, {6, 3}, {7, 0}, {7, 1}, {7, 2}, {7, 3}}};
+  constexpr Half1 h1{{{4, 4}, {5, 4}, {5, 5}, {6, 4}, {6, 5}, {6, 6}, {7, 4}, {7, 5}, {7, 6}, {7, 7}}};
+
+  // every wave holds its C in registers and has read the k-loop's last fragments: the tile may be overwritten, the
+  // stages reused
+  __syncthreads();
+  if ((wave & 1) == 0) dump();
+  __syncthreads();
+  run(h0, 0);
+  __syncthreads();   // half 0 read by every wave
+  if ((wave & 1) == 1) dump();
+  __syncthreads();
+  run(h1, 1);
 }
 
 // ---- half- and quarter-width strips with a four-stage ring (tail of an update launch) ---------------------
@@ -1102,7 +1232,38 @@ CCGP_DEFINE_GEMM(chol_update_s2_kernel, 0, 2, 2)
 CCGP_DEFINE_GEMM(chol_trsm_kernel, 1, 1, 2)
 #undef CCGP_DEFINE_GEMM
 
-#include "blocked_sched.inc"   // chol_sched_kernel, sched_init_kernel, sched_check_kernel (round 5)
+// The fused-solve route of block column j >= 1 (CCGP_OPT_FUSED_SOLVE; GroupRun::fused_solve() says when): two launches,
+// no workgroup of either waits for another.
+// D(j): one workgroup per matrix -- the update's diagonal workgroup, which then solves the thin right-hand-side tile row
+// (trsm's unit i == nt, through the same gemm_tile<1, true, TRI>: same bits).
+__global__ __launch_bounds__(256, 2) void chol_diag_solve_kernel(GemmArgs g) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int b = blockIdx.x;
+  if (b >= g.nb) return;
+  diag_unit(g, smem, g.j, b);
+  // The solve reads W_j and the right-hand-side rows that THIS workgroup has just stored.  They went to memory through
+  // this CU's L1, which all waves of the workgroup share, so workgroup scope is enough (the argument diag_unit makes for
+  // T_jj); the barrier also releases diag_factor's LDS scratch to the solve's stages.
+  __syncthreads();
+  gemm_unit<1, 1>(g, smem, g.j, b, g.nt, 0, false);
+}
+
+// U(j): the (nt - 1 - j) nb8 whole tiles below the diagonal in the update launch's order (block % 8 = matrix % 8), each
+// updated and solved in place by update_solve_tile_il.  The host admits the route only where 32-bit panel offsets fit.
+__global__ __launch_bounds__(256, 2) void chol_update_solve_kernel(GemmArgs g) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int per_grp = 8 * (g.nt - 1 - g.j);
+  const int grp = blockIdx.x / per_grp, r = blockIdx.x % per_grp;
+  const int b = grp * 8 + (r & 7);
+  if (b >= g.nb) return;
+  const int i = g.j + 1 + (r >> 3), ld = g.ld;
+  double* Ab = g.A + (size_t)b * g.a_stride;
+  update_solve_tile_il(smem, Ab + (size_t)i * kTile, ld, Ab + (size_t)g.j * kTile, ld, g.j * kTile,
+                       Ab + (size_t)i * kTile + (size_t)g.j * kTile * ld, ld,
+                       g.invd + (size_t)b * g.invd_stride + (size_t)g.j * kTile * kTile);
+}
+
+#include "blocked_sched.inc"  // chol_sched_kernel, sched_init_kernel, sched_check_kernel (round 5)
 
 // Strip count of an update launch: always 1 since round 2.  One workgroup per SIMD-set saturates a CU's four MFMA
 // pipes, so the time of a launch is a step function of its workgroup count in units of 256 (16.3 us per 128-deep
@@ -1737,6 +1898,33 @@ struct GroupRun {
     }
   }
 
+  // CCGP_OPT_FUSED_SOLVE: block columns j >= 1 as D(j) + U(j) (chol_diag_solve_kernel, chol_update_solve_kernel) instead of
+  // update + trsm.  1 (default) takes the route where the chunk is a multiple of 256 matrices: D(j) fills the chip and
+  // every U(j) is whole steps of 256 workgroups (no tail strips to lose); 2 wherever it is structurally possible: no extra tile rows (they are solved by trsm's
+  // launch), the diagonal workgroup factorises its block, and every panel is addressed through 32-bit buffer offsets
+  // (fits_buffer_offsets for the deepest panel).  Same bits either way.
+  bool fused_solve() const {
+    if (!h->opt_fused_solve || w.ne != 0 || !h->opt_fuse_diag || h->opt_wide_offsets) return false;
+    if (((size_t)npad + 32) * (size_t)w.ld * 8 >= 0xFFFF0000ull) return false;
+    return h->opt_fused_solve == 2 || nb % 256 == 0;
+  }
+
+  // D(j) then U(j), both in the update's timing group: the solve's time is there now, its flops are not counted
+  void diag_and_tiles(int j) {
+    g.j = j;
+    g.mode = 0;
+    const int nb8 = round_up(nb, 8);
+    {
+      ScopedTimer t(h, CCGP_T_UPDATE, s);
+      hipLaunchKernelGGL(chol_diag_solve_kernel, dim3(nb8), dim3(256), gemm_lds_bytes<1>(), s, g);
+    }
+    {
+      ScopedTimer t(h, CCGP_T_UPDATE, s);
+      if (j + 1 < nt)   // the last block column has no tiles below its diagonal
+        hipLaunchKernelGGL(chol_update_solve_kernel, dim3(nb8 * (nt - 1 - j)), dim3(256), gemm_lds_bytes<1>(), s, g);
+    }
+  }
+
   void finish() {
     const BlockedJob* pr = job && job->kind == kJobPredict ? job : nullptr;
     double* s2hat = job ? job->s2hat : nullptr;   // the profiled mode: every later stage reads sigma2 per matrix from here
@@ -1838,9 +2026,14 @@ struct GroupRun {
     if (scheduled()) {
       sweep_scheduled();
     } else {
+      const bool fused = fused_solve();
       for (int j = 0; j < nt; ++j) {
-        update(j);
-        panel(j);
+        if (fused && j > 0) {
+          diag_and_tiles(j);
+        } else {
+          update(j);
+          panel(j);
+        }
       }
     }
     finish();
@@ -1861,6 +2054,8 @@ static void raise_blocked_lds_limits() {
     raise_lds_limit((const void*)chol_update_s2_kernel, "chol_update_s2_kernel");
     raise_lds_limit((const void*)chol_trsm_kernel, "chol_trsm_kernel");
     raise_lds_limit((const void*)chol_sched_kernel, "chol_sched_kernel");
+    raise_lds_limit((const void*)chol_diag_solve_kernel, "chol_diag_solve_kernel");
+    raise_lds_limit((const void*)chol_update_solve_kernel, "chol_update_solve_kernel");
     raise_lds_limit((const void*)rinv_tile_kernel<false>, "rinv_tile_kernel<false>");
     raise_lds_limit((const void*)rinv_tile_kernel<true>, "rinv_tile_kernel<true>");
     raise_lds_limit((const void*)rinv_tile_kernel<true, true>, "rinv_tile_kernel<true, profiled>");

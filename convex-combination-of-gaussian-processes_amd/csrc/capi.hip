@@ -788,6 +788,10 @@ int ccgp_set_option(ccgp_handle* h, int option, int value) try {
     h->opt_sched = value;
     return CCGP_OK;
   }
+  if (option == CCGP_OPT_FUSED_SOLVE && value >= 0 && value <= 2) {
+    h->opt_fused_solve = value;
+    return CCGP_OK;
+  }
   if (option == CCGP_OPT_SCHED_POLICY && value >= 0 && value <= 31) {
     h->opt_sched_policy = value;
     return CCGP_OK;

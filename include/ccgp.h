@@ -129,9 +129,18 @@ int ccgp_set_workspace_limit(ccgp_handle* h, size_t bytes);
  *                           time account that ccgp_last_sched_profile reads; bit 3: a workgroup goes on with the first task its
  *                           own arrivals made ready instead of queueing it; bit 4 (tests only): drop the announcements of
  *                           matrix 0's second block column, so that the sweep cannot finish -- it must then abort after
- *                           CCGP_SCHED_TIMEOUT_MS (environment, default 30000) and fail every evaluation of the chunk, not hang */
+ *                           CCGP_SCHED_TIMEOUT_MS (environment, default 30000) and fail every evaluation of the chunk, not hang
+ *   CCGP_OPT_FUSED_SOLVE    the launch-per-phase sweep from block column 1 on: 0 = an update and a panel-solve (trsm) launch per
+ *                           block column; 1 (default) = a diagonal launch (one workgroup per matrix: diagonal tile, block
+ *                           factorisation, right-hand-side rows solved) and a tile launch whose workgroups update a tile AND
+ *                           solve it against the inverted diagonal block in place, so that the updated tile never goes to
+ *                           memory and there is no trsm launch -- taken when the chunk holds a multiple of 256 matrices
+ *                           (whole steps of the chip), there are no extra tile rows (likelihood and factor jobs), CCGP_OPT_FUSE_DIAG is
+ *                           1 and 32-bit panel offsets fit; 2 = the same route whatever the number of matrices.  Block column
+ *                           0 and everything else keep the update / trsm launches.  Same summation order: same bits.  Both
+ *                           launches are timed under CCGP_T_UPDATE; CCGP_T_TRSM is then block column 0 alone. */
 enum { CCGP_OPT_FUSE_DIAG = 2, CCGP_OPT_TAIL_STRIPS = 3, CCGP_OPT_WIDE_OFFSETS = 4, CCGP_OPT_SMALL_GRID16 = 5,
-       CCGP_OPT_SCHED = 7, CCGP_OPT_SCHED_POLICY = 8, CCGP_OPT_PREDICT_FACTOR = 9 };
+       CCGP_OPT_SCHED = 7, CCGP_OPT_SCHED_POLICY = 8, CCGP_OPT_PREDICT_FACTOR = 9, CCGP_OPT_FUSED_SOLVE = 10 };
 int ccgp_set_option(ccgp_handle* h, int option, int value);
 /* pre-size scratch so that later _dev calls of this shape (or of fewer draws B or test sites m), under the kernel family,
  * options and workspace limit in force now, never allocate, synchronise or create a stream or an event.  Covers: the
