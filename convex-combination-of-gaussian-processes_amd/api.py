@@ -20,6 +20,7 @@ T_COV, T_UPDATE, T_DIAG, T_TRSM, T_SOLVE, T_FUSED = range(6)
 KERNEL_GAUSS, KERNEL_MATERN, KERNEL_MATERN_SPLINE = 0, 1, 2
 OPT_FUSE_DIAG, OPT_TAIL_STRIPS, OPT_WIDE_OFFSETS, OPT_SMALL_GRID16 = 2, 3, 4, 5
 OPT_SCHED, OPT_SCHED_POLICY, OPT_PREDICT_FACTOR, OPT_FUSED_SOLVE = 7, 8, 9, 10
+VAR_ORDINARY, VAR_PLUGIN, VAR_UNBIASED = 0, 1, 2   # ccgp_krige_predict_batch's var_form
 TIMING_NAMES = ("cov", "update", "diag", "trsm", "solve", "fused", "sweep")
 
 _dp = POINTER(c_double)
@@ -63,6 +64,8 @@ SIGNATURES = {
     "ccgp_qigamma": (c_int, [_dp, c_int, c_double, c_double, _dp]),
     "ccgp_predict_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, c_int,
                                    c_double, _dp, _dp, _dp, _ip]),
+    "ccgp_krige_predict_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, c_int, _dp, c_int,
+                                         _dp, _dp, _dp, _dp, _ip]),
     "ccgp_predict_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                                        c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
@@ -651,6 +654,30 @@ class Handle:
         self._chk(lib().ccgp_predict_batch(self._h, _p(X), n, d, _p(y), K, _p(params), S, _p(Xtest), m,
                                            float(sigma2), _p(mean), _p(var), _p(beta), _ipt(st)))
         return mean, var, beta, st
+
+    def krige_predict_batch(self, X, y, K, params, sigma2, Xtest, form):
+        """ccgp_krige_predict_batch: the single-GP comparator's prediction.  Row b of params is one fitted model with its own
+        sigma2[b] (ignored, may be None, for VAR_UNBIASED); form: VAR_ORDINARY (predict.post), VAR_PLUGIN (mlegp's
+        se.fit^2 = sigma2 (1 - r'R^-1 r)) or VAR_UNBIASED (Q / (n - 1) in place of sigma2, D1:504-516).
+        Returns (mean[B, m], var[B, m], beta[B], q[B], status[B]); q[b] = (y - beta 1)'R^-1 (y - beta 1)."""
+        X, y = _f(X), _f(np.ravel(y))
+        n, d = X.shape
+        params = _f(np.atleast_2d(params))
+        B = params.shape[0]
+        if params.shape[1] != K + K * d:
+            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
+        s2 = None
+        if sigma2 is not None:
+            s2 = _f(np.broadcast_to(np.asarray(sigma2, dtype=np.float64), (B,)).copy())
+        Xtest = _f(np.atleast_2d(Xtest))
+        m = Xtest.shape[0]
+        mean = np.empty((B, m), dtype=np.float64, order="F")
+        var = np.empty((B, m), dtype=np.float64, order="F")
+        beta, q = np.empty(B), np.empty(B)
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_krige_predict_batch(self._h, _p(X), n, d, _p(y), K, _p(params), B, _p(s2), int(form),
+                                                 _p(Xtest), m, _p(mean), _p(var), _p(beta), _p(q), _ipt(st)))
+        return mean, var, beta, q, st
 
     def predict_summary(self, X, y, K, params, Xtest, sigma2, probs, y_at=None):
         """prediction()'s per-site summaries (HX:686-703) of the S draws, computed on the device from the exact

@@ -1361,6 +1361,7 @@ struct FinishArgs {
   double* beta_out;  // nb doubles, chunk-local copy of beta
   double* logdet_out;   // log det of the factorised matrix (mode 0: the normalised R), indexed like loglik; or nullptr
   double* s2hat;        // PROF: sigma2_hat = q / (n sum w^2) per matrix, indexed like loglik (b0 + b); `sigma2` is not read
+  double* q_out;        // mode 0: Q = (y - beta 1)'R^-1 (y - beta 1) per matrix, indexed like loglik; or nullptr
 };
 
 __device__ inline double block_sum(double v, double* red, int tid) {
@@ -1406,6 +1407,7 @@ __global__ __launch_bounds__(256) void finish_kernel(FinishArgs g) {
       q = fma(v, v, q);
     }
     q = block_sum(q, red, tid);
+    if (tid == 0 && g.q_out) g.q_out[gb] = (g.status && g.status[gb] != 0) ? __longlong_as_double(0x7ff8000000000000LL) : q;
     if constexpr (PROF) {
       const double csh = q / g.n;
       ll = -0.5 * (g.n * kLog2Pi + g.n * log(csh) + logdet + g.n);
@@ -1444,6 +1446,7 @@ struct PredFinishArgs {
   double sigma2;
   double* mean;
   double* var;
+  VarForm vf;        // per-row sigma2 and Q (what finish_kernel left) indexed by b0 + b, the variance form
 };
 
 // A workgroup owns 64 test sites (lane = site: a column of the rows L^-1 r(x_t) is 512 contiguous bytes per wave), its 16
@@ -1474,6 +1477,7 @@ __global__ __launch_bounds__(64 * kPredFinishWaves) void predict_finish_kernel(P
   __syncthreads();
   if (tid >= 64 || t >= g.m) return;
   ww = z1w = zyw = 0.0;
+#pragma unroll 1   // sixteen dependent additions per sum: unrolled, the 48 LDS reads are hoisted into 96 VGPRs and a CU holds one workgroup
   for (int w = 0; w < kPredFinishWaves; ++w) {
     ww += part[0][w][lane];
     z1w += part[1][w][lane];
@@ -1482,7 +1486,8 @@ __global__ __launch_bounds__(64 * kPredFinishWaves) void predict_finish_kernel(P
   const double beta = g.beta[b], s11 = g.s11[b];
   double mean = beta + (zyw - beta * z1w);
   const double u = 1.0 - z1w;
-  double var = g.sigma2 * (1.0 - ww + u * u / s11);
+  const double s2 = g.vf.sigma2_row ? g.vf.sigma2_row[g.b0 + b] : g.sigma2;
+  double var = predict_variance(g.vf.form, s2, ww, u, s11, g.vf.q ? g.vf.q[g.b0 + b] : 0.0, g.n);
   if (g.status && g.status[g.b0 + b] != 0) {
     mean = var = __longlong_as_double(0x7ff8000000000000LL);
   }
@@ -1937,11 +1942,12 @@ struct GroupRun {
       fa.s11_out = w.fin; fa.beta_out = w.fin + nb;
       fa.logdet_out = job && job->kind == kJobLogdet ? job->logdet : nullptr;
       fa.s2hat = s2hat;
+      fa.q_out = pr ? pr->vf.q : nullptr;
       if (s2hat) hipLaunchKernelGGL(finish_kernel<true>, dim3(nb), dim3(256), 0, s, fa);
       else hipLaunchKernelGGL(finish_kernel<false>, dim3(nb), dim3(256), 0, s, fa);
       if (pr) {
         PredFinishArgs pa{w.A, w.a_stride, npad, w.ld, n, pr->m, nullptr, 0, 0, w.fin, w.fin + nb, status, b0, pr->S,
-                          sigma2, pr->mean, pr->var};
+                          sigma2, pr->mean, pr->var, pr->vf};
         hipLaunchKernelGGL(predict_finish_kernel, dim3((pr->m + 63) / 64, nb), dim3(64 * kPredFinishWaves), 0, s, pa);
       }
     }
@@ -2119,7 +2125,7 @@ void blocked_predict_from_factors(ccgp_handle* h, const BlockedWs& w, int n, int
   }
   ScopedTimer t(h, CCGP_T_SOLVE, s);
   PredFinishArgs pa{g.A, w.a_stride, npad, w.ld, n, m, E, e_stride, lde, w.fin + s0, w.fin + S + s0, status, s0, S,
-                    sigma2, mean, var};
+                    sigma2, mean, var, VarForm{}};
   hipLaunchKernelGGL(predict_finish_kernel, dim3((m + 63) / 64, ns), dim3(64 * kPredFinishWaves), 0, s, pa);
 }
 

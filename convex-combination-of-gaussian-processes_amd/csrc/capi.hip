@@ -1690,14 +1690,14 @@ int ccgp_grid_marginal(ccgp_handle* h, const double* X, int n, int d, const doub
 // checked by the callers
 static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const double* dy, const DrawView& dv,
                        const double* dXtest, int m, double sigma2, double* d_mean, double* d_var, double* d_beta,
-                       int* d_status) {
+                       int* d_status, VarForm vf = VarForm{}) {
   const int K = dv.K, S = dv.ldp;
   if (small_route(Op::Predict, dv.fam.id == 0, n, d, K) == Route::Blocked) {
     // the m cross-correlation rows ride along as extra tile rows of the sweep; scratch for the outputs the caller did not
     // ask for lives behind the matrices
     SweepOut sc{};
     BlockedJob pr{};
-    pr.kind = kJobPredict; pr.Xtest = dXtest; pr.m = m; pr.S = S; pr.mean = d_mean; pr.var = d_var;
+    pr.kind = kJobPredict; pr.Xtest = dXtest; pr.m = m; pr.S = S; pr.mean = d_mean; pr.var = d_var; pr.vf = vf;
     return run_sweep(h, dX, n, d, dy, dv, S, (m + kTile - 1) / kTile, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, sc, &pr, 0,
                      [&](Layout& t, int) { sc = predict_tail(t, S, d_beta, d_status); });
   }
@@ -1712,7 +1712,7 @@ static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const dou
       if (scratch) (void)ensure_aux(h);
     }
     launch_small_reg_predict(h->stream, dX, n, d, dy, dv, S, dXtest, m, sigma2, d_mean, d_var, d_beta,
-                             d_status, scratch, sbytes, h->aux_stream, h->aux_fork, h->aux_join);
+                             d_status, scratch, sbytes, h->aux_stream, h->aux_fork, h->aux_join, vf);
   }
   CCGP_LAUNCH_CHECK();
   return CCGP_OK;
@@ -1749,6 +1749,46 @@ int ccgp_predict_batch(ccgp_handle* h, const double* X, int n, int d, const doub
   if (int rc = predict_run(h, s.X, n, d, s.y, dv, s.Xtest, m, sigma2, s.mean, s.var, s.beta, s.status)) return rc;
   return pull_status(h, {piece(s.mean, out_mean, (size_t)S * m), piece(s.var, out_var, (size_t)S * m),
                          piece(s.beta, out_beta, S)}, s.status, S, status);
+} CCGP_GUARD_END(h)
+
+// ---- the single-GP comparator's prediction: ccgp_predict_batch's route with a per-row sigma2 and a variance form ---------
+int ccgp_krige_predict_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                             const double* params, int B, const double* sigma2, int var_form, const double* Xtest, int m,
+                             double* out_mean, double* out_var, double* out_beta, double* out_q, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || B < 1 || m < 1 || !X || !y || !params || !Xtest || !out_mean || !out_var)
+    return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch: bad argument");
+  if (var_form != CCGP_VAR_ORDINARY && var_form != CCGP_VAR_PLUGIN && var_form != CCGP_VAR_UNBIASED)
+    return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch: unknown var_form");
+  const bool own_s2 = var_form != CCGP_VAR_UNBIASED;
+  if (!own_s2 && n < 2) return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch: CCGP_VAR_UNBIASED divides by n - 1");
+  if (own_s2) {
+    if (!sigma2) return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch: this var_form needs sigma2");
+    for (int b = 0; b < B; ++b)
+      if (!(std::isfinite(sigma2[b]) && sigma2[b] >= 0.0))
+        return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch: every sigma2 must be finite and >= 0");
+  }
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  PredictStage s;
+  double *ds2, *dq;
+  if (int rc = stage(h, [&](Layout& c) {
+        s = predict_stage(c, n, d, P, B, m);
+        ds2 = c.take<double>(B);
+        dq = c.take<double>(B);
+      }))
+    return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, B, K, d, &dv)) return frc;
+  if (int prc = push(h, {piece(s.X, X, (size_t)n * d), piece(s.y, y, n), piece(s.params, params, (size_t)B * P),
+                         piece(s.Xtest, Xtest, (size_t)m * d), piece(ds2, own_s2 ? sigma2 : nullptr, B)}))
+    return prc;
+  // the scalar is not read where the per-row pointer is set; UNBIASED reads neither
+  if (int rc = predict_run(h, s.X, n, d, s.y, dv, s.Xtest, m, 1.0, s.mean, s.var, s.beta, s.status,
+                           VarForm{own_s2 ? ds2 : nullptr, var_form, dq}))
+    return rc;
+  return pull_status(h, {piece(s.mean, out_mean, (size_t)B * m), piece(s.var, out_var, (size_t)B * m),
+                         piece(s.beta, out_beta, B), piece(dq, out_q, B)}, s.status, B, status);
 } CCGP_GUARD_END(h)
 
 // ---- prediction(): per-site summaries of the tables, HX:686-703 / GV:620-638 -------------------------------------

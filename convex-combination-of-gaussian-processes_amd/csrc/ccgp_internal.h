@@ -107,6 +107,30 @@ struct DrawView {
   KernelFamily fam;
 };
 
+// ---- the variance form of a prediction (ccgp_krige_predict_batch, ccgp.h) ---------------------------------------------
+// What the three prediction epilogues (small_reg_kernel<NE > 1>, site_solve_kernel, predict_finish_kernel) take beyond the
+// scalar sigma2: a per-row sigma2 indexed by the GLOBAL row (nullptr: the scalar), the form (uniform per launch: a kernel
+// argument, so no kernel is instantiated twice), and where each row's Q = (y - beta 1)'R^-1 (y - beta 1) goes (indexed
+// like sigma2_row; may be nullptr).  All zero: predict.post as ccgp_predict_batch computes it.
+struct VarForm {
+  const double* sigma2_row;
+  int form;
+  double* q;
+};
+#if defined(__HIPCC__)
+// (form, sigma2_b, ww = r'R^-1 r, u = 1 - 1'R^-1 r, s11 = 1'R^-1 1, Q_b, n) -> the predictive variance:
+//   CCGP_VAR_ORDINARY  sigma2 (1 - ww + u^2 / s11)       predict.post, HX:669 / D1:490
+//   CCGP_VAR_PLUGIN    sigma2 (1 - ww)                   mlegp's se.fit^2: no term for the estimated mean
+//   CCGP_VAR_UNBIASED  Q / (n - 1) (1 - ww + u^2 / s11)  D1:504-516
+__device__ __forceinline__ double predict_variance(int form, double sigma2, double ww, double u, double s11, double Q,
+                                                   int n) {
+  // branches, not selects: the form is uniform, and a second division computed for every form costs site_solve_kernel<8> a wave
+  if (form == CCGP_VAR_PLUGIN) return sigma2 * (1.0 - ww);
+  if (form == CCGP_VAR_UNBIASED) sigma2 = Q / (n - 1);
+  return sigma2 * (1.0 - ww + u * u / s11);
+}
+#endif
+
 // ---- cov.hip -------------------------------------------------------------------------
 // Dense cross / Gram matrix for ONE draw: out[t + i*ldo], t in [0,m) rows of A (m x d),
 // i in [0,n) rows of Bm (n x d).  normalise: divide by sum w^2 (Mixed.corr.*).
@@ -152,7 +176,8 @@ void launch_small_grad(hipStream_t s, const double* X, int n, int d, const doubl
 void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                               int S, const double* Xtest, int m, double sigma2, double* mean, double* var,
                               double* beta, int* status, void* scratch = nullptr, size_t scratch_bytes = 0,
-                              hipStream_t aux = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr);
+                              hipStream_t aux = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr,
+                              VarForm vf = VarForm{});
 void launch_small_reg_logdet_designs(hipStream_t s, const double* Xs, int n, int d, DrawView dv, int B,
                                      double* logdet, int* status);
 // solve(R) of ONE draw (logpost with R.Inv, HX:454) on the register-resident scheme; likelihood and beta of the same
@@ -230,6 +255,7 @@ struct BlockedJob {
   int m, S;
   double* mean;         // S x m column-major, device
   double* var;
+  VarForm vf;           // per-row sigma2, variance form, Q per row (all zero: predict.post with the scalar sigma2)
   // kJobInverse (solve(R), HX:454): identity rows ride along; Rinv = n x n per matrix of the chunk
   double* Rinv;
   // kJobGrad: d loglik / d params; grad is Btot x P column-major

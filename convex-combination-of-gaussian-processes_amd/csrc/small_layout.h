@@ -30,7 +30,7 @@ constexpr int kSmallExpTable = CCGP_SMALL_EXP_TABLE ? kExpTableDoubles : 0;
 CCGP_HD constexpr bool lds_fits(size_t total, int per_cu = 1) { return sizeof(double) * total <= (size_t)kLdsBytes / per_cu - 64; }
 
 // ---- the factor a prediction keeps, in HBM (small_reg.hip) -------------------------------------------------------------
-//   hdr[8]: beta, s11, bad, sw | rd[NPF] | zy[NPF] | z1[NPF] | L'
+//   hdr[8]: beta, s11, bad, sw, Q | rd[NPF] | zy[NPF] | z1[NPF] | L'
 // L' in HBM: column-major packed (column k = rows k + 1 .. n - 1, contiguous: the elimination writes a column per step,
 // coalesced); site_solve_kernel re-lays it in LDS by row blocks of eight (lrect / ltri below).
 CCGP_HD constexpr int fac_npf(int n) { return (n + 7) / 8 * 8; }
@@ -73,7 +73,7 @@ struct RegCarve {
     colbuf = w2 + K;                   // [2][NP + XR]
     dvec = colbuf + 2 * (NP + XR);
     zb = dvec + NP;                    // [2][NP]
-    slack = zb + 2 * NP;               // [8]: beta, 1'R^-1 1 for the epilogues
+    slack = zb + 2 * NP;               // [8]: beta, 1'R^-1 1 for the epilogues, cs_hat (PROF), Q (prediction)
     const int tail = slack + 8;
     ut = tail;                         // [K][XR]    (prediction)
     psum = ut + K * XR;                // [3][XR][G] (prediction)

@@ -65,6 +65,7 @@ struct RegArgs {
   double* dgrad;       // INV = 3: d log det R / d X of the free rows, per design (n - n_fixed) x d column-major
   int n_fixed;         // INV = 3: rows below n_fixed are the fixed batch (D.old, BSQ:920-948): no gradient
   double* s2hat;       // PROF instantiations: the draw's own sigma2 = q / (n sum w^2) (sigma2.MLE, D1:411-415); `sigma2` is not read
+  VarForm vf;          // prediction (NE > 1, FAC): per-draw sigma2 and Q indexed by the global draw, the variance form
 };
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
@@ -406,10 +407,9 @@ void small_reg_kernel(RegArgs a) {
       syy += __shfl_xor(syy, off, 64);
     }
     const double kLog2Pi = 1.8378770664093454835606594728112;
-    double beta = 0.0, ll;
+    double beta = 0.0, ll, q = 0.0;
     if (a.mode == 0) {
       beta = s1y / s11;
-      double q = 0.0;
       if (!bad)
         for (int k = lt; k < n; k += 64) {
           const double r = zb[k] - beta * zb[NP + k];
@@ -432,12 +432,15 @@ void small_reg_kernel(RegArgs a) {
     if (lt == 0) {
       slack[0] = beta;      // for the epilogues
       slack[1] = s11;
+      // Q = (y - beta 1)'R^-1 (y - beta 1) as the profiled likelihood sums it (PROF above: q = n sum w^2 sigma2_hat), for the
+      // variance forms of the prediction epilogues
+      if constexpr (NE > 1) slack[3] = q;
     }
     if constexpr (FAC) {
       if (valid) {
         const FacLayout fl(n);
         double* F = a.fac + (size_t)b * a.fac_stride;
-        if (lt == 0) { F[0] = beta; F[1] = s11; F[2] = bad ? 1.0 : 0.0; F[3] = sw; }
+        if (lt == 0) { F[0] = beta; F[1] = s11; F[2] = bad ? 1.0 : 0.0; F[3] = sw; F[4] = q; }
         for (int c = lt; c < n; c += 64) {
           F[fl.rd + c] = bad ? 0.0 : 1.0 / dvec[c];
           F[fl.zy + c] = zb[c];
@@ -450,6 +453,9 @@ void small_reg_kernel(RegArgs a) {
       if (a.beta) a.beta[b] = beta;
       if (a.status) a.status[b] = bad;
       if (a.logdet) a.logdet[b] = bad ? kNaN : logdet;
+      if constexpr (NE > 1 || FAC) {
+        if (a.vf.q) a.vf.q[b] = bad ? kNaN : q;
+      }
     }
   }
   if constexpr (INV) {
@@ -682,7 +688,8 @@ void small_reg_kernel(RegArgs a) {
       psum[(2 * XR + ridx) * G + tx] = zyw;
     }
     mat_sync<G>();
-    const double beta = slack[0], s11 = slack[1];
+    const double beta = slack[0], s11 = slack[1], Q = slack[3];
+    const double s2 = a.vf.sigma2_row ? a.vf.sigma2_row[b] : a.sigma2;
     for (int ridx = 2 + lt; ridx < XR; ridx += TPM) {
       const int t = t0 + ridx - 2;
       if (t >= a.m || !valid) continue;
@@ -695,7 +702,7 @@ void small_reg_kernel(RegArgs a) {
       }
       const double u = 1.0 - z1w;
       double mean = beta + (zyw - beta * z1w);
-      double var = a.sigma2 * (1.0 - ww + u * u / s11);
+      double var = predict_variance(a.vf.form, s2, ww, u, s11, Q, n);
       if (bad) { mean = kNaN; var = kNaN; }
       a.mean[b + (size_t)t * a.S] = mean;
       a.var[b + (size_t)t * a.S] = var;
@@ -772,6 +779,7 @@ struct SiteArgs {
   double* var;
   double* rs;              // per (draw, 64-site batch) NPF x 64 doubles: the correlation vectors, lane-major
   int nbatch, npf;         // ceil(m / 64); n rounded up to a multiple of 8
+  VarForm vf;              // per-draw sigma2 indexed by the global draw (nullptr: sigma2), the variance form; Q comes from the factor header
 };
 
 // r_i(x_t) = Mixed.corr.vec (HX:425-431) in corr.vec's operation order (HX:373: (theta'x^2 - 2 X Theta x) + u_i) for one draw and
@@ -985,7 +993,8 @@ __global__ __launch_bounds__(256, NPF <= 48 ? 3 : 2) void site_solve_kernel(Site
   const double beta = F[0], s11 = F[1];
   const double u = 1.0 - z1w;
   double mean = beta + (zyw - beta * z1w);
-  double var = a.sigma2 * (1.0 - ww + u * u / s11);
+  const double s2 = a.vf.sigma2_row ? a.vf.sigma2_row[a.draw0 + b] : a.sigma2;
+  double var = predict_variance(a.vf.form, s2, ww, u, s11, F[4], n);
   if (F[2] != 0.0) mean = var = __longlong_as_double(0x7ff8000000000000LL);
   a.mean[(a.draw0 + b) + (size_t)t * a.S] = mean;
   a.var[(a.draw0 + b) + (size_t)t * a.S] = var;
@@ -1138,9 +1147,9 @@ void launch_small_reg_logdet_designs(hipStream_t s, const double* Xs, int n, int
 void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                               int S, const double* Xtest, int m, double sigma2, double* mean, double* var,
                               double* beta, int* status, void* scratch, size_t scratch_bytes, hipStream_t aux,
-                              hipEvent_t ev_fork, hipEvent_t ev_join) {
+                              hipEvent_t ev_fork, hipEvent_t ev_join, VarForm vf) {
   RegArgs a = reg_args(X, n, d, y, dv);
-  a.B = S; a.sigma2 = sigma2;
+  a.B = S; a.sigma2 = sigma2; a.vf = vf;
   a.beta = beta; a.status = status; a.Xt = Xtest; a.m = m; a.S = S; a.mean = mean; a.var = var;
   const size_t per = small_reg_sites_scratch(n, d, dv.K, m);
   if (scratch && small_reg_sites_supported(n, d, dv.K) && scratch_bytes >= per) {
@@ -1151,7 +1160,7 @@ void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, cons
     double* rs = fac + (size_t)chunk * fl.total;
     for (int s0 = 0; s0 < S; s0 += chunk) {
       const int ns = std::min(chunk, S - s0);
-      SiteArgs sa{fac, (size_t)fl.total, X, dv.params, dv.ldp, n, d, dv.K, Xtest, m, S, s0, sigma2, mean, var, rs, nbatch, fl.npf};
+      SiteArgs sa{fac, (size_t)fl.total, X, dv.params, dv.ldp, n, d, dv.K, Xtest, m, S, s0, sigma2, mean, var, rs, nbatch, fl.npf, vf};
       // the correlation vectors need nothing from the factorisation: on the second stream beside it (the factorisation is ONE
       // wave per draw -- 1000 draws leave three quarters of the wave slots empty -- and runs at the latency of its n columns)
       if (aux && ev_fork && ev_join) {

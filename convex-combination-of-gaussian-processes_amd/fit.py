@@ -294,12 +294,79 @@ def _add_cgp_columns(table, gp, D_test, D_train, y_train, cgp):
     return table
 
 
-def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=None, exact=False, cgp=False):
+def _t_interval(y_hat, var, alpha, n):
+    """y_hat -+ qt(1 - alpha / 2, n - 1) sqrt(max(var, 0)): the interval of both single-GP forms."""
+    from scipy.stats import t as student_t
+    delta = student_t.ppf(1.0 - alpha / 2.0, n - 1) * np.sqrt(np.maximum(var, 0.0))
+    return y_hat - delta, y_hat + delta
+
+
+def prediction_single(handle, D_train, D_new, y_train, MLE, alpha, nu=None):
+    """prediction.single of the 1-D scripts (D1:548-567 = D1F:872-889) on the device: y.hat.single, and LL / UL.Single with
+    single.var from CIs.single (D1:527-539), whose post.stdev.single^2 = Q / (n - 1) post.var.single / sigma2 (D1:504-516) is
+    ccgp_krige_predict_batch's VAR_UNBIASED.  With nu: one Matern(nu) component at the scalar MLE["theta"] (what matern_MLEs
+    returns).  Without: a Gaussian single GP whose MLE["theta"] holds d scales (ordinary_kriging_fit's).  beta is the
+    profile beta at theta, as MLEs() forms it (D1:467).  Returns dict(y_hat_single, LL_single, UL_single, single_var)."""
+    D = np.asarray(D_train, dtype=np.float64)
+    D = D.reshape(-1, 1) if D.ndim == 1 else D
+    Dn = np.asarray(D_new, dtype=np.float64).reshape(-1, D.shape[1])
+    y = np.asarray(y_train, dtype=np.float64).ravel()
+    theta = np.atleast_1d(np.asarray(MLE["theta"], dtype=np.float64)).ravel()
+    if theta.size != D.shape[1]:
+        raise ValueError("MLE['theta'] must hold one scale per input dimension")
+    h = handle
+    if nu is not None:
+        from .rsurface import _FamilyHandle
+        h = _FamilyHandle(getattr(handle, "_handle", handle), api.KERNEL_MATERN, float(nu))
+    mean, var, _, _, st = h.krige_predict_batch(D, y, 1, np.concatenate([[1.0], theta])[None], None, Dn, api.VAR_UNBIASED)
+    if st[0] != 0:
+        raise RuntimeError("prediction_single: the correlation matrix could not be factorised (pivot %d)" % st[0])
+    lo, hi = _t_interval(mean[0], var[0], alpha, D.shape[0])
+    return dict(y_hat_single=mean[0].copy(), LL_single=lo, UL_single=hi, single_var=var[0].copy())
+
+
+def _add_single_columns(table, gp, D_test, alpha, D_train, y_train, single):
+    """compare.GP's single-GP columns.  The 2-D / emulator scripts: mlegp + predict.gp(se.fit = TRUE), fit -+ se.fit
+    qt(1 - alpha / 2, n - 1) (GV:662-666, ANI:679-683, ISO:665-669, ADV:733-737, BSQ:664-668) -- the plug-in variance.  The
+    1-D scripts: MLEs() + prediction.single (D1:548-567) -- the unbiased form, which also gives single_var."""
+    one_d = hasattr(gp, "nu")
+    base = getattr(gp.h, "_handle", gp.h)
+    given = dict(single) if isinstance(single, dict) else {}
+    model = {k: given.pop(k) for k in ("theta", "sigma2", "beta") if k in given}
+    if one_d:
+        D = np.asarray(D_train, dtype=np.float64).reshape(-1, 1)
+        if "theta" not in model:
+            model = matern_MLEs(base, D, y_train, gp.nu, **given)
+        table.update(prediction_single(base, D, np.asarray(D_test, dtype=np.float64).reshape(-1, 1), y_train, model, alpha,
+                                       nu=gp.nu))
+        table["single"] = model
+        return table
+    D = np.asarray(D_train, dtype=np.float64)
+    if "theta" not in model or "sigma2" not in model:
+        model = ordinary_kriging_fit(base, D, y_train, **given)
+    theta = np.asarray(model["theta"], dtype=np.float64).ravel()
+    mean, var, _, _, st = base.krige_predict_batch(D, y_train, 1, np.concatenate([[1.0], theta])[None], [model["sigma2"]],
+                                                   D_test, api.VAR_PLUGIN)
+    if st[0] != 0:
+        raise RuntimeError("compare_GP: the single GP's correlation matrix could not be factorised (pivot %d)" % st[0])
+    lo, hi = _t_interval(mean[0], var[0], alpha, D.shape[0])
+    table.update(y_hat_single=mean[0].copy(), LL_single=lo, UL_single=hi, single=model)
+    return table
+
+
+def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=None, exact=False, cgp=False, single=False):
     """HX:713-725 + prediction HX:686-703 (GV:620-646 adds Quant.Combined): one row per test point
     (y.hat.Combined, Quant.Combined, LL.Combined, UL.Combined, y.true).  exact=True takes Quant and the interval from
     the exact posterior predictive on the device (gp.prediction) instead of sampling one variate per draw: rng is
     ignored, the tables stay on the device, and the keys are the same without mean / var.  cgp (default off; True, or a dict
-    of cgp.CGP's keyword arguments) adds the table's CGP model (GV:654-660): y_hat_CGP, LL_CGP, UL_CGP and the fit as CGP."""
+    of cgp.CGP's keyword arguments) adds the table's CGP model (GV:654-660): y_hat_CGP, LL_CGP, UL_CGP and the fit as CGP.
+    single (default off) adds the ordinary-kriging model: True fits it on the device (ordinary_kriging_fit; for a 1-D gp
+    matern_MLEs), a dict(theta=..., sigma2=...) takes a given model, and further keys go to the fit.  It adds y_hat_single,
+    LL_single, UL_single = y_hat -+ qt(1 - alpha / 2, n - 1) sqrt(max(var, 0)) -- var in the plug-in form for the 2-D /
+    emulator scripts, in the unbiased form (and returned as single_var) for the 1-D scripts -- and the model as single."""
+    if single:
+        table = compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng, exact, cgp)
+        return _add_single_columns(table, gp, D_test, alpha, D_train, y_train, single)
     if cgp:
         table = compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng, exact)
         return _add_cgp_columns(table, gp, D_test, D_train, y_train, cgp)
@@ -510,7 +577,8 @@ def write_results_table(path, table, D_test, input_names, comparators=("single",
     GV:759-761): the test inputs, y.hat / Quant / LL / UL of the Combined GP, the comparator models'
     columns and y.true -- same columns, order and number format as `Results/Size 50 Results 1.txt`, so the two files can be
     diffed.  A comparator c whose y_hat_c / LL_c / UL_c the table holds (compare_GP(..., cgp=True) adds CGP's) is written;
-    one it does not hold is NA (the `.single` columns: no prediction route returns mlegp's variance form)."""
+    (compare_GP(..., single=True) adds the single GP's: mlegp's variance form is ccgp_krige_predict_batch's VAR_PLUGIN);
+    one it does not hold is NA."""
     from .tables import write_table
     D_test = np.asarray(D_test, dtype=np.float64)
     m = D_test.shape[0]
@@ -530,8 +598,17 @@ def write_results_table(path, table, D_test, input_names, comparators=("single",
 
 
 def comparison_summary(table):
-    """Comparison.Summary's Combined-GP figures (ANI:703-721): RMSPE and interval coverage."""
-    e = table["y_true"] - table["y_hat"]
-    cover = np.mean((table["y_true"] >= table["LL"]) & (table["y_true"] <= table["UL"]))
-    return dict(rmspe=float(np.sqrt(np.mean(e ** 2))), coverage=float(cover),
-                mean_quantile=float(np.mean(table["quant"])))
+    """Comparison.Summary (ANI:703-721, D1:886-899): RMSPE and interval coverage of the Combined GP, and of every comparator
+    whose columns the table holds (rmspe_single / coverage_single, rmspe_CGP / coverage_CGP)."""
+    y = np.asarray(table["y_true"], dtype=np.float64)
+    e = y - table["y_hat"]
+    cover = np.mean((y >= table["LL"]) & (y <= table["UL"]))
+    out = dict(rmspe=float(np.sqrt(np.mean(e ** 2))), coverage=float(cover),
+               mean_quantile=float(np.mean(table["quant"])))
+    for c in ("single", "CGP"):
+        keys = ["y_hat_%s" % c, "LL_%s" % c, "UL_%s" % c]
+        if all(k in table for k in keys):
+            yh, lo, hi = (np.asarray(table[k], dtype=np.float64) for k in keys)
+            out["rmspe_%s" % c] = float(np.sqrt(np.mean((y - yh) ** 2)))
+            out["coverage_%s" % c] = float(np.mean((y >= lo) & (y <= hi)))
+    return out

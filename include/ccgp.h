@@ -290,6 +290,38 @@ int ccgp_predict_batch_dev(ccgp_handle* h, const double* dX, int n, int d, const
                            double sigma2, double* d_mean, double* d_var, double* d_beta,
                            int* d_status);
 
+/* ---- the ordinary-kriging ("single") comparator of compare.GP: its prediction -------------------
+ * compare.GP puts a single GP beside the Combined GP and the CGP.  Row b is one fitted model: its parameter row has the
+ * layout ccgp_predict_batch takes, R_b is the normalised mixed matrix that call uses (HX:408-415), and the row has its
+ * own sigma2_b.  With q = r'R^-1 r, u = 1 - 1'R^-1 r, s11 = 1'R^-1 1, beta_b = 1'R^-1 y / s11 and
+ * Q_b = (y - beta_b 1)'R_b^-1 (y - beta_b 1):
+ *   mean = beta_b + r'R^-1 (y - beta_b 1)              the expression, and the bits, of ccgp_predict_batch
+ *   CCGP_VAR_ORDINARY  var = sigma2_b (1 - q + u^2 / s11)        predict.post (HX:669, D1:490)
+ *   CCGP_VAR_PLUGIN    var = sigma2_b (1 - q)                    mlegp's se.fit^2 (predict.gp(se.fit = TRUE): GV:662-666,
+ *                                                                ANI:679-683, ISO:665-669, ADV:733-737, BSQ:664-668)
+ *   CCGP_VAR_UNBIASED  var = Q_b / (n - 1) (1 - q + u^2 / s11)   the 1-D scripts (D1:504-516; CIs.single D1F:851-889);
+ *                                                                takes no sigma2
+ * ccgp_profile_batch works on the unnormalised M = sum w^2 R, so sigma2_b = sigma2_hat_M sum w^2 and
+ * Q_b = n sigma2_hat_M sum w^2; for a single GP (K = 1, w = 1) they are the same numbers.  out_q is formed with the
+ * expression and summation order of that call's sigma2 on the same route.
+ * out_mean / out_var: B x m column-major as ccgp_predict_batch; out_beta, out_q, status (B each) may be NULL.
+ * CCGP_EINVAL before anything is launched, outputs untouched: var_form outside 0..2; UNBIASED with n < 2; ORDINARY or
+ * PLUGIN with sigma2 NULL or any sigma2_b not finite or negative.  A failed factorisation is reported as
+ * ccgp_predict_batch reports it: status[b] = 1-based pivot index, NaN in row b of both tables, out_beta[b] and out_q[b];
+ * returns the number of failed rows.  A row depends on its own parameters, sigma2_b and Q_b only: not on B, its position,
+ * or where the workspace limit or a route's chunking cuts the call.  The route is ccgp_predict_batch's
+ * (CCGP_OPT_PREDICT_FACTOR included); every family of ccgp_set_kernel (other than Gaussian: the blocked sweep).
+ * Host pointers; blocks.  Not in this version: a _dev variant, ccgp_reserve coverage, a ccgp_multi wrapper, a
+ * factor-set variant, an R shim. */
+enum { CCGP_VAR_ORDINARY = 0, CCGP_VAR_PLUGIN = 1, CCGP_VAR_UNBIASED = 2 };
+int ccgp_krige_predict_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                             const double* params, int B,
+                             const double* sigma2 /* B values; ignored (may be NULL) for UNBIASED */,
+                             int var_form, const double* Xtest, int m,
+                             double* out_mean, double* out_var /* B x m column-major, as ccgp_predict_batch */,
+                             double* out_beta /* B, NULL ok */, double* out_q /* B: Q_b, NULL ok */,
+                             int* status /* B, NULL ok */);
+
 /* ---- prediction(): the per-site summaries of those tables (HX:686-703 / GV:620-638) -------------
  * Every script ends in compare.GP -> prediction(): per test site the mean of the S per-draw means, a
  * prediction interval and Quant.Combined, which the reference estimates from ONE normal variate per draw.
