@@ -2022,7 +2022,7 @@ struct GroupRun {
     a.prof = h->sched_prof_dev;
     a.timeout_10ns = h->sched_timeout_ms >= 40000 ? 4000000000u : (unsigned)h->sched_timeout_ms * 100000u;
     const int wgs = h->n_cus * (sched_mode() == 1 ? 2 : 1);
-    h->sched_prof_wgs = wgs < kSchedProfWgs ? wgs : kSchedProfWgs;
+    h->sched_prof_wgs = !(h->opt_sched_policy & 4) ? 0 : wgs < kSchedProfWgs ? wgs : kSchedProfWgs;   // bit 2 off: no account
     hipLaunchKernelGGL(chol_sched_kernel, dim3(wgs), dim3(256), gemm_lds_bytes<1>(), s, a);
     hipLaunchKernelGGL(sched_check_kernel, dim3(1), dim3(256), 0, s, ctrl, status + b0, nb);
   }

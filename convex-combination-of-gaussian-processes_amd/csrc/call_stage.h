@@ -1,0 +1,239 @@
+// What the host-pointer entry points of capi.hip declare before they touch the device: the pieces a copy moves (Piece,
+// span_of) and the staging layouts that ccgp_reserve or more than one entry point needs.  Each layout is ONE declaration
+// over a Layout (stage_layout.h) and says itself which of its pieces go up (inputs) and which come back (results), so a
+// call's buffer size, its pointers and its copies cannot disagree.  One-off layouts stay as lambdas at their call site.
+// No HIP include: the CPU suite runs these declarations with the host compiler (tests/host_stage).
+#pragma once
+
+#include <cstddef>
+#include <initializer_list>
+#include <vector>
+
+#include "stage_layout.h"
+
+namespace ccgp {
+
+struct Piece {
+  void* dev;
+  void* host;      // source for push, destination for pull; nullptr: skip
+  size_t bytes;
+};
+template <class T>
+Piece piece(T* dev, const T* host, size_t count) {
+  return Piece{dev, const_cast<T*>(host), sizeof(T) * count};
+}
+struct Pieces {   // a braced list at the call site, or a vector
+  const Piece *b, *e;
+  Pieces(std::initializer_list<Piece> l) { b = l.begin(); e = l.end(); }   // both live to the end of the call's expression
+  Pieces(const std::vector<Piece>& v) { b = v.data(); e = v.data() + v.size(); }
+  const Piece* begin() const { return b; }
+  const Piece* end() const { return e; }
+};
+
+// the device range [lo, lo + bytes) that covers the pieces a copy moves; lo == nullptr: none moves
+struct Span {
+  char* lo = nullptr;
+  size_t bytes = 0;
+};
+inline Span span_of(Pieces ps) {
+  char *lo = nullptr, *hi = nullptr;
+  for (const Piece& p : ps) {
+    if (!p.host || !p.bytes) continue;
+    char* d = static_cast<char*>(p.dev);
+    if (!lo || d < lo) lo = d;
+    if (!hi || d + p.bytes > hi) hi = d + p.bytes;
+  }
+  return Span{lo, (size_t)(hi - lo)};
+}
+
+// ---- ccgp_loglik_batch: inputs X | y | params and results loglik | beta | status, each ONE piece, so that each side
+// crosses PCIe as one span
+struct LoglikStage {
+  double *X = nullptr, *y = nullptr, *params = nullptr, *loglik = nullptr, *beta = nullptr;
+  int* status = nullptr;
+  size_t payload = 0;   // bytes of the two pieces
+};
+inline LoglikStage loglik_stage(Layout& c, int n, int d, int P, int B) {
+  const size_t in_d = (size_t)n * d + n + (size_t)B * P, out_d = 2 * (size_t)B + ((size_t)B + 1) / 2;
+  double* in = c.take<double>(in_d);
+  double* out = c.take<double>(out_d);
+  LoglikStage s;
+  s.payload = sizeof(double) * (in_d + out_d);
+  if (!in) return s;   // planning pass
+  s.X = in;
+  s.y = in + (size_t)n * d;
+  s.params = s.y + n;
+  s.loglik = out;
+  s.beta = out + B;
+  s.status = reinterpret_cast<int*>(out + 2 * (size_t)B);
+  return s;
+}
+
+// ---- ccgp_loglik_grad_batch and ccgp_profile_batch: X | y | params | grad? | loglik | s2hat? | beta | status | gpart?
+// the device outputs of a value-and-gradient evaluation (grad_run).  s2hat set: the profiled mode; grad == nullptr: value
+// only, legal in the profiled mode alone; gpart: the partial sums of launch_small_grad, read on the in-LDS route only
+struct GradOut {
+  double *loglik, *beta;
+  int* status;
+  double *grad, *s2hat, *gpart;
+};
+struct GradStage {
+  double *X, *y, *params;
+  GradOut o;
+  size_t nX, ny, nparams, B;
+  std::vector<Piece> inputs(const double* hX, const double* hy, const double* hparams) const {
+    return {piece(X, hX, nX), piece(y, hy, ny), piece(params, hparams, nparams)};
+  }
+  // the status words follow them (pull_status)
+  std::vector<Piece> results(double* grad, double* loglik, double* s2hat, double* beta) const {
+    return {piece(o.grad, grad, o.grad ? nparams : 0), piece(o.loglik, loglik, B), piece(o.s2hat, s2hat, o.s2hat ? B : 0),
+            piece(o.beta, beta, B)};
+  }
+};
+inline GradStage grad_stage(Layout& c, int n, int d, int P, int B, bool grad, bool s2hat, size_t gpart_doubles) {
+  GradStage s;
+  s.nX = (size_t)n * d; s.ny = n; s.nparams = (size_t)B * P; s.B = B;
+  s.X = c.take<double>(s.nX);
+  s.y = c.take<double>(s.ny);
+  s.params = c.take<double>(s.nparams);
+  s.o.grad = grad ? c.take<double>(s.nparams) : nullptr;
+  s.o.loglik = c.take<double>(B);
+  s.o.s2hat = s2hat ? c.take<double>(B) : nullptr;
+  s.o.beta = c.take<double>(B);
+  s.o.status = c.take<int>(B);
+  s.o.gpart = gpart_doubles ? c.take<double>(gpart_doubles) : nullptr;
+  return s;
+}
+
+// ---- prediction: the four inputs every host-pointer prediction call stages and pushes
+struct PredictIn {
+  double *X, *y, *params, *Xtest;
+  size_t nX, ny, nparams, nXtest;
+  std::vector<Piece> inputs(const double* hX, const double* hy, const double* hparams, const double* hXtest) const {
+    return {piece(X, hX, nX), piece(y, hy, ny), piece(params, hparams, nparams), piece(Xtest, hXtest, nXtest)};
+  }
+};
+inline PredictIn predict_in(Layout& c, int n, int d, int P, int S, int m) {
+  PredictIn s;
+  s.nX = (size_t)n * d; s.ny = n; s.nparams = (size_t)S * P; s.nXtest = (size_t)m * d;
+  s.X = c.take<double>(s.nX);
+  s.y = c.take<double>(s.ny);
+  s.params = c.take<double>(s.nparams);
+  s.Xtest = c.take<double>(s.nXtest);
+  return s;
+}
+
+// ccgp_predict_batch, and with the tail ccgp_krige_predict_batch: in | mean | var | beta | status | (sigma2 | q)?
+struct PredictStage {
+  PredictIn in;
+  double *mean, *var, *beta;
+  int* status;
+  double *sigma2, *q;   // the per-row tail; nullptr without it
+  size_t S, m;
+  // sigma2: the per-row values that go up with the inputs (nullptr: none, or no tail)
+  std::vector<Piece> inputs(const double* hX, const double* hy, const double* hparams, const double* hXtest,
+                            const double* hsigma2) const {
+    std::vector<Piece> ps = in.inputs(hX, hy, hparams, hXtest);
+    ps.push_back(piece(sigma2, hsigma2, sigma2 ? S : 0));
+    return ps;
+  }
+  // the status words follow beta (pull_status)
+  std::vector<Piece> results(double* hmean, double* hvar, double* hbeta, double* hq) const {
+    return {piece(mean, hmean, S * m), piece(var, hvar, S * m), piece(beta, hbeta, S), piece(q, hq, q ? S : 0)};
+  }
+};
+inline PredictStage predict_stage(Layout& c, int n, int d, int P, int S, int m, bool tail = false) {
+  PredictStage s;
+  s.S = S; s.m = m;
+  s.in = predict_in(c, n, d, P, S, m);
+  s.mean = c.take<double>(s.S * s.m);
+  s.var = c.take<double>(s.S * s.m);
+  s.beta = c.take<double>(S);
+  s.status = c.take<int>(S);
+  s.sigma2 = tail ? c.take<double>(S) : nullptr;
+  s.q = tail ? c.take<double>(S) : nullptr;
+  return s;
+}
+
+// ---- the prediction summaries (summary.hip).  The S x m tables never leave the device: they lie BETWEEN the inputs (one
+// span up) and the results (one span down), next to the scratch of the summary kernel.
+struct SummaryTables {
+  double *mean, *var;
+  int *idx, *count;
+};
+inline SummaryTables summary_tables(Layout& c, int S, int m) {
+  SummaryTables t;
+  t.mean = c.take<double>((size_t)S * m);
+  t.var = c.take<double>((size_t)S * m);
+  t.idx = c.take<int>(S);
+  t.count = c.take<int>(1);
+  return t;
+}
+// ccgp_predict_summary: in | y_at | tables | out | beta | status
+struct SummaryStage {
+  PredictIn in;
+  double* y_at;
+  SummaryTables t;
+  double *out, *beta;
+  int* status;
+  size_t S, m, nout;
+  std::vector<Piece> inputs(const double* hX, const double* hy, const double* hparams, const double* hXtest,
+                            const double* hy_at) const {
+    std::vector<Piece> ps = in.inputs(hX, hy, hparams, hXtest);
+    ps.push_back(piece(y_at, hy_at, m));
+    return ps;
+  }
+  std::vector<Piece> results(double* hout, double* hbeta) const { return {piece(out, hout, nout), piece(beta, hbeta, S)}; }
+};
+inline SummaryStage summary_stage(Layout& c, int n, int d, int P, int S, int m, int n_probs) {
+  SummaryStage s;
+  s.S = S; s.m = m; s.nout = (size_t)m * (4 + n_probs);
+  s.in = predict_in(c, n, d, P, S, m);
+  s.y_at = c.take<double>(m);
+  s.t = summary_tables(c, S, m);
+  s.out = c.take<double>(s.nout);
+  s.beta = c.take<double>(S);
+  s.status = c.take<int>(S);
+  return s;
+}
+// ccgp_predict_summary_dev: the tables and, where the caller keeps no status words, room for them
+struct SummaryDevStage {
+  SummaryTables t;
+  int* status;
+};
+inline SummaryDevStage summary_dev_stage(Layout& c, int S, int m, bool own_status) {
+  SummaryDevStage s;
+  s.t = summary_tables(c, S, m);
+  s.status = own_status ? c.take<int>(S) : nullptr;
+  return s;
+}
+
+// the staging ccgp_reserve(n, d, K, B, m) provides: the host-pointer likelihood and, with test sites, the prediction
+// (without its tail) and the tables of ccgp_predict_summary_dev
+inline size_t reserve_stage_bytes(int n, int d, int P, int B, int m) {
+  size_t bytes = layout_bytes([&](Layout& c) { loglik_stage(c, n, d, P, B); });
+  if (m > 0) {
+    const size_t pr = layout_bytes([&](Layout& c) { predict_stage(c, n, d, P, B, m); });
+    const size_t sm = layout_bytes([&](Layout& c) { summary_dev_stage(c, B, m, true); });
+    bytes = bytes > pr ? bytes : pr;
+    bytes = bytes > sm ? bytes : sm;
+  }
+  return bytes;
+}
+
+// ---- blocked sweep ---------------------------------------------------------------------------------------------------
+// where a sweep leaves the likelihood, beta and status of its matrices, each indexed by draw
+struct SweepOut {
+  double *loglik, *beta;
+  int* status;
+};
+// blocked prediction: scratch behind the matrices for the outputs the caller did not ask for
+inline SweepOut predict_tail(Layout& t, int S, double* d_beta, int* d_status) {
+  SweepOut p;
+  p.loglik = t.take<double>(S);
+  p.beta = d_beta ? d_beta : t.take<double>(S);
+  p.status = d_status ? d_status : t.take<int>(S);
+  return p;
+}
+
+}  // namespace ccgp

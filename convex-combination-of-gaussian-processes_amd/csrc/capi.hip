@@ -13,9 +13,9 @@
 #include <new>
 #include <vector>
 
+#include "call_stage.h"
 #include "ccgp_internal.h"
 #include "special_math.h"
-#include "stage_layout.h"
 
 using namespace ccgp;
 
@@ -66,56 +66,44 @@ int draw_view(ccgp_handle* h, const KernelFamily& fam, const double* params, int
   return CCGP_OK;
 }
 
-int ensure_ws(ccgp_handle* h, size_t bytes) {
-  if (bytes <= h->ws_bytes) return CCGP_OK;
-  if (h->ws) {
-    CCGP_HIP(hipStreamSynchronize(h->stream));
-    CCGP_HIP(hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_bytes = 0;
-  }
-  hipError_t e = hipMalloc(&h->ws, bytes);
-  if (e != hipSuccess) {
-    h->ws = nullptr;
-    return fail(h, CCGP_ENOMEM, "device workspace allocation of " + std::to_string(bytes) + " B failed");
-  }
-  h->ws_bytes = bytes;
-  return CCGP_OK;
+// the scheduler's time account (ccgp_last_sched_profile) lies inside the memory of the sweep that wrote it: whoever frees
+// [mem, mem + bytes) forgets the account with it
+void forget_sched_profile(ccgp_handle* h, const void* mem, size_t bytes) {
+  const char *p = reinterpret_cast<const char*>(h->sched_prof_dev), *m = static_cast<const char*>(mem);
+  if (!p || p < m || p >= m + bytes) return;
+  h->sched_prof_dev = nullptr;
+  h->sched_prof_wgs = 0;
 }
 
-int ensure_stage(ccgp_handle* h, size_t bytes) {
-  if (bytes <= h->stage_bytes) return CCGP_OK;
-  if (h->stage) {
-    CCGP_HIP(hipStreamSynchronize(h->stream));
-    CCGP_HIP(hipFree(h->stage));
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-  }
-  size_t want = bytes + bytes / 4 + 4096;
-  hipError_t e = hipMalloc(&h->stage, want);
-  if (e != hipSuccess) {
-    h->stage = nullptr;
-    return fail(h, CCGP_ENOMEM, "device staging allocation of " + std::to_string(want) + " B failed");
-  }
-  h->stage_bytes = want;
-  return CCGP_OK;
-}
+// The handle's three buffers -- device workspace, device staging, pinned host buffer of the copy path -- are grow-only:
+// a request beyond the size frees (after the stream has drained) and allocates anew, `slack` adding 25 % + 4096 B so
+// that a slowly growing series of calls does not reallocate each time.  `what` opens the error text.
+struct BufferKind {
+  hipError_t (*alloc)(void**, size_t);
+  hipError_t (*release)(void*);
+  bool slack;
+  const char* what;
+};
+const BufferKind kWorkspace{[](void** p, size_t n) { return hipMalloc(p, n); }, [](void* p) { return hipFree(p); }, false,
+                            "device workspace allocation"};
+const BufferKind kStaging{kWorkspace.alloc, kWorkspace.release, true, "device staging allocation"};
+const BufferKind kPinned{[](void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); },
+                         [](void* p) { return hipHostFree(p); }, true, "pinned host buffer"};
 
-// pinned host buffer of the latency path (ccgp_logpost): grow-only
-int ensure_pin(ccgp_handle* h, size_t bytes) {
-  if (bytes <= h->pin_bytes) return CCGP_OK;
-  if (h->pin) {
+int ensure(ccgp_handle* h, Buffer& b, const BufferKind& k, size_t bytes) {
+  if (bytes <= b.bytes) return CCGP_OK;
+  if (b.ptr) {
     CCGP_HIP(hipStreamSynchronize(h->stream));
-    (void)hipHostFree(h->pin);
-    h->pin = nullptr;
-    h->pin_bytes = 0;
+    forget_sched_profile(h, b.ptr, b.bytes);
+    CCGP_HIP(k.release(b.ptr));
+    b = Buffer{};
   }
-  const size_t want = bytes + bytes / 4 + 4096;
-  if (hipHostMalloc(&h->pin, want, hipHostMallocDefault) != hipSuccess) {
-    h->pin = nullptr;
-    return fail(h, CCGP_ENOMEM, "pinned host buffer of " + std::to_string(want) + " B failed");
+  const size_t want = k.slack ? bytes + bytes / 4 + 4096 : bytes;
+  if (k.alloc(&b.ptr, want) != hipSuccess) {
+    b.ptr = nullptr;
+    return fail(h, CCGP_ENOMEM, std::string(k.what) + " of " + std::to_string(want) + " B failed");
   }
-  h->pin_bytes = want;
+  b.bytes = want;
   return CCGP_OK;
 }
 
@@ -123,8 +111,8 @@ int ensure_pin(ccgp_handle* h, size_t bytes) {
 // once, over the buffer, to hand out the pointers
 template <class F>
 int stage(ccgp_handle* h, F&& lay) {
-  if (int rc = ensure_stage(h, layout_bytes(lay))) return rc;
-  Layout real(h->stage);
+  if (int rc = ensure(h, h->stage, kStaging, layout_bytes(lay))) return rc;
+  Layout real(h->stage.ptr);
   lay(real);
   return CCGP_OK;
 }
@@ -136,34 +124,17 @@ int stage(ccgp_handle* h, F&& lay) {
 // kPinMax the host image of the whole span is assembled in the handle's pinned buffer and crosses PCIe in ONE copy
 // each way; larger payloads are copied piece by piece as before.  pin_max lowers that bound for a call that has
 // measured a smaller one (ccgp_loglik_batch); 0 means piece by piece.
-struct Piece {
-  void* dev;
-  void* host;      // source for push, destination for pull; nullptr: skip
-  size_t bytes;
-};
-struct Pieces {   // a braced list at the call site, or a vector
-  const Piece *b, *e;
-  Pieces(std::initializer_list<Piece> l) : b(l.begin()), e(l.end()) {}
-  Pieces(const std::vector<Piece>& v) : b(v.data()), e(v.data() + v.size()) {}
-  const Piece* begin() const { return b; }
-  const Piece* end() const { return e; }
-};
 constexpr size_t kPinMax = size_t(8) << 20;
 constexpr int kPullSlices = ccgp::kPullSlices;
 
 int push(ccgp_handle* h, Pieces ps, size_t pin_max = kPinMax) {
-  char *lo = nullptr, *hi = nullptr;
-  for (const Piece& p : ps) {
-    if (!p.host || !p.bytes) continue;
-    char* d = static_cast<char*>(p.dev);
-    if (!lo || d < lo) lo = d;
-    if (!hi || d + p.bytes > hi) hi = d + p.bytes;
-  }
+  const Span sp = span_of(ps);
+  char* const lo = sp.lo;
+  const size_t span = sp.bytes;
   h->pin_in = 0;
   if (!lo) return CCGP_OK;
-  const size_t span = (size_t)(hi - lo);
-  if (span <= pin_max && ensure_pin(h, span) == CCGP_OK) {
-    char* pin = static_cast<char*>(h->pin);
+  if (span <= pin_max && ensure(h, h->pin, kPinned, span) == CCGP_OK) {
+    char* pin = static_cast<char*>(h->pin.ptr);
     for (const Piece& p : ps)
       if (p.host && p.bytes) std::memcpy(pin + (static_cast<char*>(p.dev) - lo), p.host, p.bytes);
     CCGP_HIP(hipMemcpyAsync(lo, pin, span, hipMemcpyHostToDevice, h->stream));
@@ -177,20 +148,15 @@ int push(ccgp_handle* h, Pieces ps, size_t pin_max = kPinMax) {
 
 // device -> host of the result pieces, then the stream is synchronised (the call's results are valid on return)
 int pull(ccgp_handle* h, Pieces ps, size_t pin_max = kPinMax) {
-  char *lo = nullptr, *hi = nullptr;
-  for (const Piece& p : ps) {
-    if (!p.host || !p.bytes) continue;
-    char* d = static_cast<char*>(p.dev);
-    if (!lo || d < lo) lo = d;
-    if (!hi || d + p.bytes > hi) hi = d + p.bytes;
-  }
+  const Span sp = span_of(ps);
+  char* const lo = sp.lo;
+  const size_t span = sp.bytes;
   if (!lo) {
     CCGP_HIP(hipStreamSynchronize(h->stream));
     return CCGP_OK;
   }
-  const size_t span = (size_t)(hi - lo);
-  if (span <= pin_max && ensure_pin(h, h->pin_in + span) == CCGP_OK) {
-    char* pin = static_cast<char*>(h->pin) + h->pin_in;
+  if (span <= pin_max && ensure(h, h->pin, kPinned, h->pin_in + span) == CCGP_OK) {
+    char* pin = static_cast<char*>(h->pin.ptr) + h->pin_in;
     // a large result (the S x m tables of ccgp_predict_batch: 2.4 MB per Ground-Vibrations set) comes back in four
     // slices, each followed by an event: the host copies slice c out of the pinned buffer while slice c + 1 is still
     // crossing PCIe, instead of waiting for all of it and then copying all of it
@@ -229,11 +195,6 @@ int pull(ccgp_handle* h, Pieces ps, size_t pin_max = kPinMax) {
   return CCGP_OK;
 }
 
-template <class T>
-Piece piece(T* dev, const T* host, size_t count) {
-  return Piece{dev, const_cast<T*>(host), sizeof(T) * count};
-}
-
 bool bad_shape(int n, int d, int K) {
   return n < 1 || d < 1 || d > kMaxD || K < 1 || K > kMaxK;
 }
@@ -251,14 +212,14 @@ template <class TotalBytes>
 int plan_chunk(ccgp_handle* h, size_t per_item, int count, size_t margin, TotalBytes total_bytes, int* chunk) {
   size_t limit = h->ws_limit, free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-    const size_t avail = free_b + h->ws_bytes > margin ? free_b + h->ws_bytes - margin : 0;
+    const size_t avail = free_b + h->ws.bytes > margin ? free_b + h->ws.bytes - margin : 0;
     if (avail < limit) limit = avail;
   }
   int nb = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)count, 65535), limit / per_item));
-  int rc = ensure_ws(h, total_bytes(nb));
+  int rc = ensure(h, h->ws, kWorkspace, total_bytes(nb));
   while (rc == CCGP_ENOMEM && nb > 1) {
     nb = (nb + 1) / 2;
-    rc = ensure_ws(h, total_bytes(nb));
+    rc = ensure(h, h->ws, kWorkspace, total_bytes(nb));
   }
   *chunk = nb;
   return rc;
@@ -276,16 +237,10 @@ int sweep_plan(ccgp_handle* h, int npad, int ne, int count, size_t scratch_per_i
   if (int rc = plan_chunk(h, blocked_ws_bytes(npad, 1, ne) + scratch_per_item, count, kSweepMargin,
                           [&](int nb) { return layout_bytes([&](Layout& w) { lay(w, nb); }); }, chunk))
     return rc;
-  Layout ws(h->ws);
+  Layout ws(h->ws.ptr);
   lay(ws, *chunk);
   return CCGP_OK;
 }
-
-// where a sweep leaves the likelihood, beta and status of its matrices, each indexed by draw
-struct SweepOut {
-  double *loglik, *beta;
-  int* status;
-};
 
 // One blocked sweep over the `count` draws of dv on resident inputs: plan the chunk, zero the status words, factorise
 // chunk by chunk with `job` riding along, check the launches.  `out` and `job` are read AFTER the plan, so `scratch` may
@@ -300,7 +255,7 @@ int run_sweep(ccgp_handle* h, const double* dX, int n, int d, const double* dy, 
   CCGP_HIP(hipMemsetAsync(out.status, 0, sizeof(int) * (size_t)count, h->stream));
   for (int b0 = 0; b0 < count; b0 += nbc) {
     const int nb = std::min(nbc, count - b0);
-    blocked_loglik(h, dX, n, d, dy, dv, b0, nb, npad, sigma2, mean_mode, tau2, blocked_carve(h->ws, npad, nb, ne),
+    blocked_loglik(h, dX, n, d, dy, dv, b0, nb, npad, sigma2, mean_mode, tau2, blocked_carve(h->ws.ptr, npad, nb, ne),
                    out.loglik, out.beta, out.status, job);
   }
   CCGP_LAUNCH_CHECK();
@@ -339,6 +294,47 @@ int loglik_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy,
   return loglik_run(h, dX, n, d, dy, dv, sigma2, mean_mode, tau2, d_loglik, d_beta, d_status);
 }
 
+// The value and gradient of the B >= 1 draws of dv on resident inputs, the counterpart of loglik_run.  o.s2hat set: the
+// profiled mode -- sigma2 is not read, the evaluation runs at 1.0 and leaves each draw's sigma2_hat there.  o.grad ==
+// nullptr (profiled mode only): value alone, which is a likelihood call and takes the likelihood's route.  `who` names
+// the entry point in a refusal; the callers have refused a gradient outside the Gaussian family.
+int grad_run(ccgp_handle* h, const char* who, const double* dX, int n, int d, const double* dy, const DrawView& dv,
+             double sigma2, const GradOut& o) {
+  const int K = dv.K, B = dv.ldp, P = K + K * d;
+  if (o.s2hat) sigma2 = 1.0;
+  const Route route = small_route(o.grad ? Op::Grad : Op::Loglik, dv.fam.id == 0, n, d, K);
+  if (o.grad && route == Route::Blocked && !blocked_grad_supported(d, K))
+    return fail(h, CCGP_EUNSUPPORTED, std::string(who) + ": d + K too large for the contraction kernel's LDS");
+  if (route == Route::Blocked) {
+    // With a gradient, identity rows ride along as extra tile rows, then the tiles of R^-1 are formed (rinv_tile_kernel),
+    // turned into M and contracted with the kernel derivatives (grad_contract_kernel; blocked.hip).  Behind the chunk's
+    // matrices, from the next 256-byte line: the contraction's partial sums and alpha for every matrix of the chunk.
+    // Profiled: finish_kernel leaves sigma2_hat per matrix in o.s2hat (indexed by draw across the chunks, as loglik, beta
+    // and status are) and the gradient stages read it there.
+    const int npad = round_up(n, kTile);
+    const size_t ntiles = blocked_grad_partials(npad);
+    BlockedJob job{};
+    job.kind = o.grad ? kJobGrad : kJobNone; job.grad = o.grad; job.Btot = B; job.s2hat = o.s2hat;
+    return run_sweep(h, dX, n, d, dy, dv, B, o.grad ? npad / kTile : 0, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0,
+                     {o.loglik, o.beta, o.status}, &job, o.grad ? sizeof(double) * (ntiles * P + npad) : 0,
+                     [&](Layout& w, int nb) {
+                       if (!o.grad) return;
+                       w.off = Layout::al(w.off);
+                       job.gpart = w.take<double>((size_t)nb * ntiles * P);
+                       job.alpha = w.take<double>((size_t)nb * npad);
+                     });
+  }
+  ScopedTimer t(h, CCGP_T_FUSED);
+  if (route == Route::Lds)
+    launch_small_grad(h->stream, dX, n, d, dy, dv, B, sigma2, o.loglik, o.beta, o.grad, o.status, o.gpart, o.s2hat);
+  else if (o.s2hat)
+    launch_small_reg_profile(h->stream, dX, n, d, dy, dv, B, o.loglik, o.s2hat, o.beta, o.grad, o.status, h->opt_small_grid16 != 0);
+  else
+    launch_small_reg_grad(h->stream, dX, n, d, dy, dv, B, sigma2, o.loglik, o.beta, o.grad, o.status);
+  CCGP_LAUNCH_CHECK();
+  return CCGP_OK;
+}
+
 // the end of a batch call: the status words go to the caller if asked for, and the number of failed evaluations is the
 // C ABI's positive return value
 int report_status(const std::vector<int>& st, int* status) {
@@ -351,92 +347,38 @@ int report_status(const std::vector<int>& st, int* status) {
 // pull the result pieces and the B status words at dst, then report_status.  whole_doubles: one word more when B is odd,
 // for a caller whose status words close a piece of doubles (ccgp_loglik_batch: the copy back stays a multiple of 8 bytes;
 // 140 instead of 144 bytes for 7 candidates measured 1.2 us more per call)
-int pull_status(ccgp_handle* h, std::initializer_list<Piece> ps, int* dst, int B, int* status, size_t pin_max = kPinMax,
+int pull_status(ccgp_handle* h, Pieces ps, int* dst, int B, int* status, size_t pin_max = kPinMax,
                 bool whole_doubles = false) {
   std::vector<int> st((size_t)B + (whole_doubles ? B & 1 : 0));
   std::vector<Piece> all;
-  all.reserve(ps.size() + 1);
-  all.assign(ps);
+  all.reserve((size_t)(ps.end() - ps.begin()) + 1);
+  all.assign(ps.begin(), ps.end());
   all.push_back(piece(dst, st.data(), st.size()));
   if (int rc = pull(h, all, pin_max)) return rc;
   st.resize(B);
   return report_status(st, status);
 }
 
-// ---- layouts that more than one function needs (ccgp_reserve sizes the buffers of the calls it reserves for) --------
-// staging of ccgp_loglik_batch: inputs X | y | params and results loglik | beta | status, each ONE piece, so that each
-// side crosses PCIe as one span
-struct LoglikStage {
-  double *X = nullptr, *y = nullptr, *params = nullptr, *loglik = nullptr, *beta = nullptr;
-  int* status = nullptr;
-  size_t payload = 0;   // bytes of the two pieces
-};
-LoglikStage loglik_stage(Layout& c, int n, int d, int P, int B) {
-  const size_t in_d = (size_t)n * d + n + (size_t)B * P, out_d = 2 * (size_t)B + ((size_t)B + 1) / 2;
-  double* in = c.take<double>(in_d);
-  double* out = c.take<double>(out_d);
-  LoglikStage s;
-  s.payload = sizeof(double) * (in_d + out_d);
-  if (!in) return s;   // planning pass
-  s.X = in;
-  s.y = in + (size_t)n * d;
-  s.params = s.y + n;
-  s.loglik = out;
-  s.beta = out + B;
-  s.status = reinterpret_cast<int*>(out + 2 * (size_t)B);
-  return s;
-}
-
-// staging of ccgp_predict_batch
-struct PredictStage {
-  double *X, *y, *params, *Xtest, *mean, *var, *beta;
-  int* status;
-};
-PredictStage predict_stage(Layout& c, int n, int d, int P, int S, int m) {
-  PredictStage s;
-  s.X = c.take<double>((size_t)n * d);
-  s.y = c.take<double>(n);
-  s.params = c.take<double>((size_t)S * P);
-  s.Xtest = c.take<double>((size_t)m * d);
-  s.mean = c.take<double>((size_t)S * m);
-  s.var = c.take<double>((size_t)S * m);
-  s.beta = c.take<double>(S);
-  s.status = c.take<int>(S);
-  return s;
-}
-
-// staging of the prediction summaries (summary.hip).  The S x m tables never leave the device: they lie BETWEEN the
-// inputs (one span up) and the results (one span down), next to the scratch of the summary kernel.
-struct SummaryTables {
-  double *mean, *var;
-  int *idx, *count;
-};
-SummaryTables summary_tables(Layout& c, int S, int m) {
-  SummaryTables t;
-  t.mean = c.take<double>((size_t)S * m);
-  t.var = c.take<double>((size_t)S * m);
-  t.idx = c.take<int>(S);
-  t.count = c.take<int>(1);
-  return t;
-}
-struct SummaryStage {
-  double *X, *y, *params, *Xtest, *y_at;
-  SummaryTables t;
-  double *out, *beta;
-  int* status;
-};
-SummaryStage summary_stage(Layout& c, int n, int d, int P, int S, int m, int n_probs) {
-  SummaryStage s;
-  s.X = c.take<double>((size_t)n * d);
-  s.y = c.take<double>(n);
-  s.params = c.take<double>((size_t)S * P);
-  s.Xtest = c.take<double>((size_t)m * d);
-  s.y_at = c.take<double>(m);
-  s.t = summary_tables(c, S, m);
-  s.out = c.take<double>((size_t)m * (4 + n_probs));
-  s.beta = c.take<double>(S);
-  s.status = c.take<int>(S);
-  return s;
+// ccgp_loglik_grad_batch and, with out_sigma2, ccgp_profile_batch behind their argument checks: stage, push, grad_run, pull
+int grad_call(ccgp_handle* h, const char* who, const double* X, int n, int d, const double* y, int K, const double* params,
+              int B, double sigma2, double* out_loglik, double* out_sigma2, double* out_beta, double* out_grad, int* status) {
+  const bool gauss = h->fam.id == 0;
+  if (out_grad && !gauss)
+    return fail(h, CCGP_EUNSUPPORTED, std::string(who) + ": analytic gradient is implemented for the Gaussian family only");
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  // the partial sums of launch_small_grad: staged where grad_run takes the in-LDS route
+  const bool lds = small_route(out_grad ? Op::Grad : Op::Loglik, gauss, n, d, K) == Route::Lds;
+  GradStage s;
+  if (int rc = stage(h, [&](Layout& c) {
+        s = grad_stage(c, n, d, P, B, out_grad, out_sigma2, lds ? (size_t)B * small_grad_chunks(n, d) * P : 0);
+      }))
+    return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, B, K, d, &dv)) return frc;
+  if (int prc = push(h, s.inputs(X, y, params))) return prc;
+  if (int rc = grad_run(h, who, s.X, n, d, s.y, dv, sigma2, s.o)) return rc;
+  return pull_status(h, s.results(out_grad, out_loglik, out_sigma2, out_beta), s.o.status, B, status);
 }
 
 int check_summary_args(ccgp_handle* h, int m, const double* probs, int n_probs) {
@@ -446,18 +388,6 @@ int check_summary_args(ccgp_handle* h, int m, const double* probs, int n_probs) 
     if (!(probs[j] > 0.0 && probs[j] < 1.0))
       return fail(h, CCGP_EINVAL, "ccgp_predict_summary: every level of probs must lie strictly inside (0, 1)");
   return CCGP_OK;
-}
-
-// staging of ccgp_predict_summary_dev: the tables and, where the caller keeps no status words, room for them
-struct SummaryDevStage {
-  SummaryTables t;
-  int* status;
-};
-SummaryDevStage summary_dev_stage(Layout& c, int S, int m, bool own_status) {
-  SummaryDevStage s;
-  s.t = summary_tables(c, S, m);
-  s.status = own_status ? c.take<int>(S) : nullptr;
-  return s;
 }
 
 // ---- kept-factor prediction: what predict_run needs beyond the launches, shared with ccgp_reserve ---------------------
@@ -480,15 +410,6 @@ bool ensure_aux(ccgp_handle* h) {
     h->aux_stream = nullptr;
   }
   return h->aux_stream != nullptr;
-}
-
-// blocked prediction: scratch behind the matrices for the outputs the caller did not ask for
-SweepOut predict_tail(Layout& t, int S, double* d_beta, int* d_status) {
-  SweepOut p;
-  p.loglik = t.take<double>(S);
-  p.beta = d_beta ? d_beta : t.take<double>(S);
-  p.status = d_status ? d_status : t.take<int>(S);
-  return p;
 }
 
 // ---- tiny kernels for the literal R.Inv-based helpers (a6, a7, a10, a11) -----------------
@@ -721,9 +642,9 @@ int ccgp_destroy(ccgp_handle* h) try {
     (void)hipEventDestroy(s.e0);
     (void)hipEventDestroy(s.e1);
   }
-  if (h->ws) (void)hipFree(h->ws);
-  if (h->stage) (void)hipFree(h->stage);
-  if (h->pin) (void)hipHostFree(h->pin);
+  if (h->ws.ptr) (void)kWorkspace.release(h->ws.ptr);
+  if (h->stage.ptr) (void)kStaging.release(h->stage.ptr);
+  if (h->pin.ptr) (void)kPinned.release(h->pin.ptr);
   for (auto& e : h->pull_ev)
     if (e) (void)hipEventDestroy(e);
   if (h->aux_fork) (void)hipEventDestroy(h->aux_fork);
@@ -821,16 +742,12 @@ int ccgp_reserve(ccgp_handle* h, int n, int d, int K, int B, int m) try {
   // kept-factor prediction: its scratch (the size predict_run asks for) and its second stream with the two events
   if (m > 0) {
     if (const size_t want = kept_factor_ws_bytes(h, gauss, n, d, K, B, m)) {
-      if (int rc = ensure_ws(h, want)) return rc;
+      if (int rc = ensure(h, h->ws, kWorkspace, want)) return rc;
       if (!ensure_aux(h)) return fail(h, CCGP_EHIP, "ccgp_reserve: the second stream of the kept-factor prediction could not be created");
     }
   }
   // staging: the host-pointer likelihood and prediction, and the tables of ccgp_predict_summary_dev
-  const int P = K + K * d;
-  const size_t st_ll = layout_bytes([&](Layout& c) { loglik_stage(c, n, d, P, B); });
-  const size_t st_pr = m ? layout_bytes([&](Layout& c) { predict_stage(c, n, d, P, B, m); }) : 0;
-  const size_t st_sm = m ? layout_bytes([&](Layout& c) { summary_dev_stage(c, B, m, true); }) : 0;
-  return ensure_stage(h, std::max({st_ll, st_pr, st_sm}));
+  return ensure(h, h->stage, kStaging, reserve_stage_bytes(n, d, K + K * d, B, m));
 } CCGP_GUARD_END(h)
 
 int ccgp_enable_timing(ccgp_handle* h, int on) try {
@@ -862,18 +779,17 @@ int ccgp_get_timing(ccgp_handle* h, int id, double* out_ms, int* out_launches) t
 int ccgp_last_sched_profile(ccgp_handle* h, unsigned long long* out, int max_workgroups, int* out_workgroups) try {
   if (!h || !out || max_workgroups < 1) return CCGP_EINVAL;
   CCGP_HIP(hipSetDevice(h->device));
-  CCGP_HIP(hipStreamSynchronize(h->stream));
+  // sched_prof_wgs > 0 only while the account exists: a sweep without policy bit 2 records 0, and whoever frees the
+  // memory the account lies in forgets it (forget_sched_profile)
   const int nw = std::min(max_workgroups, h->sched_prof_wgs);
   if (out_workgroups) *out_workgroups = nw;
-  if (nw > 0 && h->sched_prof_dev)
-    CCGP_HIP(hipMemcpy(out, h->sched_prof_dev, sizeof(unsigned long long) * 8 * (size_t)nw, hipMemcpyDeviceToHost));
-  return CCGP_OK;
+  return pull(h, {piece(h->sched_prof_dev, out, 8 * (size_t)std::max(nw, 0))});
 } CCGP_GUARD_END(h)
 
 int ccgp_workspace_bytes(const ccgp_handle* h, size_t* ws_bytes, size_t* stage_bytes) {
   if (!h) return CCGP_EINVAL;
-  if (ws_bytes) *ws_bytes = h->ws_bytes;
-  if (stage_bytes) *stage_bytes = h->stage_bytes;
+  if (ws_bytes) *ws_bytes = h->ws.bytes;
+  if (stage_bytes) *stage_bytes = h->stage.bytes;
   return CCGP_OK;
 }
 
@@ -1085,55 +1001,7 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
   if (!h) return CCGP_EINVAL;
   if (bad_shape(n, d, K) || B < 1 || !X || !y || !params || !out_grad)
     return fail(h, CCGP_EINVAL, "ccgp_loglik_grad_batch: bad argument");
-  if (h->fam.id != 0)
-    return fail(h, CCGP_EUNSUPPORTED, "ccgp_loglik_grad_batch: analytic gradient is implemented for the Gaussian family only");
-  CCGP_HIP(hipSetDevice(h->device));
-  const int P = K + K * d;
-  const Route route = small_route(Op::Grad, true, n, d, K);
-  if (route == Route::Blocked && !blocked_grad_supported(d, K))
-    return fail(h, CCGP_EUNSUPPORTED, "ccgp_loglik_grad_batch: d + K too large for the contraction kernel's LDS");
-  const int nch = route == Route::Blocked ? 0 : small_grad_chunks(n, d);
-  double *dX, *dy, *dp, *dg, *dll, *dbeta, *dgp = nullptr;
-  int* dst;
-  if (int rc = stage(h, [&](Layout& c) {
-        dX = c.take<double>((size_t)n * d);
-        dy = c.take<double>(n);
-        dp = c.take<double>((size_t)B * P);
-        dg = c.take<double>((size_t)B * P);
-        dll = c.take<double>(B);
-        dbeta = c.take<double>(B);
-        dst = c.take<int>(B);
-        if (route != Route::Blocked) dgp = c.take<double>((size_t)B * nch * P);   // partial sums of launch_small_grad
-      }))
-    return rc;
-  DrawView dv;
-  if (int frc = draw_view(h, h->fam, dp, B, K, d, &dv)) return frc;
-  if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, (size_t)B * P)})) return prc;
-  if (route == Route::Blocked) {
-    // identity rows ride along as extra tile rows, then the tiles of R^-1 are formed (rinv_tile_kernel), turned into M and
-    // contracted with the kernel derivatives (grad_contract_kernel; blocked.hip).  Behind the chunk's matrices, from the
-    // next 256-byte line: the contraction's partial sums and alpha for every matrix of the chunk
-    const int npad = round_up(n, kTile);
-    const size_t ntiles = blocked_grad_partials(npad);
-    BlockedJob job{};
-    job.kind = kJobGrad; job.grad = dg; job.Btot = B;
-    if (int rc = run_sweep(h, dX, n, d, dy, dv, B, npad / kTile, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, {dll, dbeta, dst}, &job,
-                           sizeof(double) * (ntiles * P + npad), [&](Layout& w, int nb) {
-                             w.off = Layout::al(w.off);
-                             job.gpart = w.take<double>((size_t)nb * ntiles * P);
-                             job.alpha = w.take<double>((size_t)nb * npad);
-                           }))
-      return rc;
-  } else {
-    ScopedTimer t(h, CCGP_T_FUSED);
-    if (route == Route::Reg)
-      launch_small_reg_grad(h->stream, dX, n, d, dy, dv, B, sigma2, dll, dbeta, dg, dst);
-    else
-      launch_small_grad(h->stream, dX, n, d, dy, dv, B, sigma2, dll, dbeta, dg, dst, dgp);
-    CCGP_LAUNCH_CHECK();
-  }
-  return pull_status(h, {piece(dg, out_grad, (size_t)B * P), piece(dll, out_loglik, B), piece(dbeta, out_beta, B)}, dst, B,
-                     status);
+  return grad_call(h, "ccgp_loglik_grad_batch", X, n, d, y, K, params, B, sigma2, out_loglik, nullptr, out_beta, out_grad, status);
 } CCGP_GUARD_END(h)
 
 // ---- ordinary-kriging MLE: the likelihood with sigma2 concentrated out (ccgp.h) -----------------------------------------
@@ -1144,61 +1012,7 @@ int ccgp_profile_batch(ccgp_handle* h, const double* X, int n, int d, const doub
   if (bad_shape(n, d, K) || B < 0 || !X || !y || !params || !out_loglik || !out_sigma2)
     return fail(h, CCGP_EINVAL, "ccgp_profile_batch: bad argument");
   if (B == 0) return CCGP_OK;
-  const bool want_grad = out_grad != nullptr, gauss = h->fam.id == 0;
-  if (want_grad && !gauss)
-    return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch: analytic gradient is implemented for the Gaussian family only");
-  CCGP_HIP(hipSetDevice(h->device));
-  const int P = K + K * d;
-  // no route of its own: the value is a likelihood call, the gradient a gradient call
-  const Route route = want_grad ? small_route(Op::Grad, true, n, d, K) : small_route(Op::Loglik, gauss, n, d, K);
-  if (want_grad && route == Route::Blocked && !blocked_grad_supported(d, K))
-    return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch: d + K too large for the contraction kernel's LDS");
-  const int nch = route == Route::Lds ? small_grad_chunks(n, d) : 0;
-  double *dX, *dy, *dp, *dg = nullptr, *dll, *ds2, *dbeta, *dgp = nullptr;
-  int* dst;
-  if (int rc = stage(h, [&](Layout& c) {
-        dX = c.take<double>((size_t)n * d);
-        dy = c.take<double>(n);
-        dp = c.take<double>((size_t)B * P);
-        if (want_grad) dg = c.take<double>((size_t)B * P);
-        dll = c.take<double>(B);
-        ds2 = c.take<double>(B);
-        dbeta = c.take<double>(B);
-        dst = c.take<int>(B);
-        if (route == Route::Lds) dgp = c.take<double>((size_t)B * nch * P);   // partial sums of launch_small_grad
-      }))
-    return rc;
-  DrawView dv;
-  if (int frc = draw_view(h, h->fam, dp, B, K, d, &dv)) return frc;
-  if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, (size_t)B * P)})) return prc;
-  if (route == Route::Blocked) {
-    // the sweep of ccgp_loglik_batch / ccgp_loglik_grad_batch; finish_kernel leaves sigma2_hat per matrix in ds2 (indexed by
-    // draw across the chunks, as loglik, beta and status are) and the gradient stages read it there
-    const int npad = round_up(n, kTile);
-    const size_t ntiles = blocked_grad_partials(npad);
-    BlockedJob job{};
-    job.kind = want_grad ? kJobGrad : kJobNone; job.grad = dg; job.Btot = B; job.s2hat = ds2;
-    int rc;
-    if (want_grad)
-      rc = run_sweep(h, dX, n, d, dy, dv, B, npad / kTile, 1.0, CCGP_MEAN_PROFILE_BETA, 0.0, {dll, dbeta, dst}, &job,
-                     sizeof(double) * (ntiles * P + npad), [&](Layout& w, int nb) {
-                       w.off = Layout::al(w.off);
-                       job.gpart = w.take<double>((size_t)nb * ntiles * P);
-                       job.alpha = w.take<double>((size_t)nb * npad);
-                     });
-    else
-      rc = run_sweep(h, dX, n, d, dy, dv, B, 0, 1.0, CCGP_MEAN_PROFILE_BETA, 0.0, {dll, dbeta, dst}, &job, 0, no_scratch);
-    if (rc) return rc;
-  } else {
-    ScopedTimer t(h, CCGP_T_FUSED);
-    if (route == Route::Reg)
-      launch_small_reg_profile(h->stream, dX, n, d, dy, dv, B, dll, ds2, dbeta, dg, dst, h->opt_small_grid16 != 0);
-    else
-      launch_small_grad(h->stream, dX, n, d, dy, dv, B, 1.0, dll, dbeta, dg, dst, dgp, ds2);
-    CCGP_LAUNCH_CHECK();
-  }
-  return pull_status(h, {piece(dg, out_grad, want_grad ? (size_t)B * P : 0), piece(dll, out_loglik, B), piece(ds2, out_sigma2, B),
-                         piece(dbeta, out_beta, B)}, dst, B, status);
+  return grad_call(h, "ccgp_profile_batch", X, n, d, y, K, params, B, 1.0, out_loglik, out_sigma2, out_beta, out_grad, status);
 } CCGP_GUARD_END(h)
 
 // ---- the CGP comparator of compare.GP (ccgp.h; kernels: cgp.hip) ---------------------------------------------------------
@@ -1243,7 +1057,7 @@ int ccgp_cgp_state_batch(ccgp_handle* h, const double* X, int n, int d, const do
   if (int rc = plan_chunk(h, sizeof(double) * (P + 4) + 2 * sizeof(int), B, kSweepMargin,
                           [&](int nb) { return layout_bytes([&](Layout& w) { lay(w, nb); }); }, &nbc))
     return rc;
-  Layout ws(h->ws);
+  Layout ws(h->ws.ptr);
   lay(ws, nbc);
   std::vector<double> rows;
   int failed = 0;
@@ -1295,8 +1109,8 @@ int ccgp_cgp_predict(ccgp_handle* h, const double* X, int n, int d, const double
     dst = w.take<int>(2);
     dkeep = w.take<double>(kp.total);
   };
-  if (int rc = ensure_ws(h, layout_bytes(lay))) return rc;
-  Layout ws(h->ws);
+  if (int rc = ensure(h, h->ws, kWorkspace, layout_bytes(lay))) return rc;
+  Layout ws(h->ws.ptr);
   lay(ws);
   if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, params, P), piece(dXt, Xtest, (size_t)m * d)}))
     return prc;
@@ -1408,7 +1222,7 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
   Route route = small_route(out_Rinv ? Op::Inverse : Op::Loglik, gauss, n, d, K);
   const size_t in_d = (size_t)n * d + n + P;                       // X | y | row
   const size_t out_d = 3 + (out_Rinv ? (size_t)n * n : 0);         // ll, beta, status (as one double slot) | R^-1
-  if (route == Route::Reg && ensure_pin(h, sizeof(double) * (in_d + out_d)) == CCGP_OK) {
+  if (route == Route::Reg && ensure(h, h->pin, kPinned, sizeof(double) * (in_d + out_d)) == CCGP_OK) {
     // The sequential caller's path (Metro evaluates ONE proposal per logpost call, HX:505-512): latency, not
     // throughput.  Inputs are packed into a pinned host buffer and cross PCIe in ONE copy, the results (log-lik,
     // beta, status[, R^-1]) come back in one: 300 -> ~100 us per call with R.Inv at n = 64, 113 -> ~60 us without (round 2).
@@ -1422,7 +1236,7 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
           if (!zo) dout = c.take<double>(out_d);
         }))
       return rc2;
-    double* pout = static_cast<double*>(h->pin) + in_d;
+    double* pout = static_cast<double*>(h->pin.ptr) + in_d;
     if (zo) dout = pout;
     double* dX = din;
     double* dy = din + (size_t)n * d;
@@ -1465,9 +1279,7 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
       return rc2;
     DrawView dv;
     if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
-    CCGP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream));
-    CCGP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    CCGP_HIP(hipMemcpyAsync(dp, row.data(), sizeof(double) * P, hipMemcpyHostToDevice, h->stream));
+    if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dp, row.data(), P)})) return prc;
     if (route == Route::Blocked) {
       // identity as extra tile rows of the blocked sweep, then R^-1 = Z Z' tile by tile
       BlockedJob job{};
@@ -1481,11 +1293,9 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
       launch_small_inverse(h->stream, dX, n, d, dy, dv, 0, sigma2, dR, dll, dbt, dst);
       CCGP_LAUNCH_CHECK();
     }
-    CCGP_HIP(hipMemcpyAsync(out_Rinv, dR, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipMemcpyAsync(&ll, dll, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipMemcpyAsync(&beta, dbt, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipMemcpyAsync(&st, dst, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CCGP_HIP(hipStreamSynchronize(h->stream));
+    if (int rc2 = pull_status(h, {piece(dR, out_Rinv, (size_t)n * n), piece(dll, &ll, 1), piece(dbt, &beta, 1)}, dst, 1, &st);
+        rc2 < 0)
+      return rc2;
   }
   *out_val = ll + log_jacob + log_prior;
   if (out_beta) *out_beta = beta;
@@ -1521,14 +1331,14 @@ int ccgp_mixed_logdet_designs(ccgp_handle* h, const double* Xs, int n, int d, in
         dst = c.take<int>(B);
       }))
     return rc;
-  if (int rc = blocked ? ensure_ws(h, blocked_ws_bytes(npad, 1, 0) + 512) : CCGP_OK) return rc;
+  if (int rc = blocked ? ensure(h, h->ws, kWorkspace, blocked_ws_bytes(npad, 1, 0) + 512) : CCGP_OK) return rc;
   DrawView dv;
   if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
   if (int prc = push(h, {piece(dXs, Xs, (size_t)B * n * d), piece(dp, params, P)})) return prc;
   if (blocked) {
     CCGP_HIP(hipMemsetAsync(dy, 0, sizeof(double) * n, h->stream));
     CCGP_HIP(hipMemsetAsync(dst, 0, sizeof(int) * (size_t)B, h->stream));
-    BlockedWs w = blocked_carve(h->ws, npad, 1, 0);
+    BlockedWs w = blocked_carve(h->ws.ptr, npad, 1, 0);
     for (int i = 0; i < B; ++i) {
       BlockedJob job{};
       job.kind = kJobLogdet;
@@ -1642,18 +1452,16 @@ int ccgp_grid_marginal(ccgp_handle* h, const double* X, int n, int d, const doub
         dsi = c.take<int>((size_t)2 * G);
         dq = c.take<double>(ns * N);
         dp = c.take<double>(B * P);
-        dll = c.take<double>(B);
         dbeta = c.take<double>(B);
         dst = c.take<int>(B);
+        dll = c.take<double>(B);   // the results close the buffer, logs | out | bad: one span down with out_logs or without
         dout = c.take<double>(G);
         dbad = c.take<int>(1);
       }))
     return rc;
-  CCGP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream));
-  CCGP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-  CCGP_HIP(hipMemcpyAsync(dhy, hyper, sizeof(double) * 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
-  CCGP_HIP(hipMemcpyAsync(dsh, shapes.data(), sizeof(double) * ns, hipMemcpyHostToDevice, h->stream));
-  CCGP_HIP(hipMemcpyAsync(dsi, shape_idx.data(), sizeof(int) * 2 * (size_t)G, hipMemcpyHostToDevice, h->stream));
+  if (int prc = push(h, {piece(dX, X, (size_t)n * d), piece(dy, y, n), piece(dhy, hyper, (size_t)4 * G),
+                         piece(dsh, shapes.data(), ns), piece(dsi, shape_idx.data(), (size_t)2 * G)}))
+    return prc;
   CCGP_HIP(hipMemsetAsync(dbad, 0, sizeof(int), h->stream));
   {
     ScopedTimer t(h, CCGP_T_COV);
@@ -1671,10 +1479,7 @@ int ccgp_grid_marginal(ccgp_handle* h, const double* X, int n, int d, const doub
   hipLaunchKernelGGL(count_bad_kernel, dim3((unsigned)((B + 1023) / 1024)), dim3(256), 0, h->stream, dst, (int)B, dbad);
   CCGP_LAUNCH_CHECK();
   int bad = 0;
-  CCGP_HIP(hipMemcpyAsync(out, dout, sizeof(double) * G, hipMemcpyDeviceToHost, h->stream));
-  CCGP_HIP(hipMemcpyAsync(&bad, dbad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (out_logs) CCGP_HIP(hipMemcpyAsync(out_logs, dll, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-  CCGP_HIP(hipStreamSynchronize(h->stream));
+  if (int rc = pull(h, {piece(dll, out_logs, B), piece(dout, out, G), piece(dbad, &bad, 1)})) return rc;
   if (out_argmax) {
     // which.max: first maximum, NaN skipped
     int best = -1;
@@ -1708,7 +1513,7 @@ static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const dou
     void* scratch = nullptr;
     size_t sbytes = 0;
     if (const size_t want = kept_factor_ws_bytes(h, dv.fam.id == 0, n, d, K, S, m)) {
-      if (ensure_ws(h, want) == CCGP_OK) { scratch = h->ws; sbytes = h->ws_bytes; }
+      if (ensure(h, h->ws, kWorkspace, want) == CCGP_OK) { scratch = h->ws.ptr; sbytes = h->ws.bytes; }
       if (scratch) (void)ensure_aux(h);
     }
     launch_small_reg_predict(h->stream, dX, n, d, dy, dv, S, dXtest, m, sigma2, d_mean, d_var, d_beta,
@@ -1731,24 +1536,32 @@ int ccgp_predict_batch_dev(ccgp_handle* h, const double* dX, int n, int d, const
   return predict_run(h, dX, n, d, dy, dv, dXtest, m, sigma2, d_mean, d_var, d_beta, d_status);
 } CCGP_GUARD_END(h)
 
+// ccgp_predict_batch and, with `krige`, ccgp_krige_predict_batch behind their argument checks.  krige: the
+// staging carries the per-row tail, sigma2_row (nullptr: CCGP_VAR_UNBIASED reads none) goes up with the inputs and Q comes
+// back with the results; the scalar is not read where the per-row pointer is set.
+static int predict_call(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                        const double* params, int S, const double* Xtest, int m, double sigma2, bool krige,
+                        const double* sigma2_row, int var_form, double* out_mean, double* out_var, double* out_beta,
+                        double* out_q, int* status) {
+  CCGP_HIP(hipSetDevice(h->device));
+  PredictStage s;
+  if (int rc = stage(h, [&](Layout& c) { s = predict_stage(c, n, d, K + K * d, S, m, krige); })) return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.in.params, S, K, d, &dv)) return frc;
+  if (int prc = push(h, s.inputs(X, y, params, Xtest, sigma2_row))) return prc;
+  const VarForm vf = krige ? VarForm{sigma2_row ? s.sigma2 : nullptr, var_form, s.q} : VarForm{};
+  if (int rc = predict_run(h, s.in.X, n, d, s.in.y, dv, s.in.Xtest, m, sigma2, s.mean, s.var, s.beta, s.status, vf)) return rc;
+  return pull_status(h, s.results(out_mean, out_var, out_beta, out_q), s.status, S, status);
+}
+
 int ccgp_predict_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
                        const double* params, int S, const double* Xtest, int m, double sigma2,
                        double* out_mean, double* out_var, double* out_beta, int* status) try {
   if (!h) return CCGP_EINVAL;
   if (bad_shape(n, d, K) || S < 1 || m < 1 || !X || !y || !params || !Xtest || !out_mean || !out_var)
     return fail(h, CCGP_EINVAL, "ccgp_predict_batch: bad argument");
-  CCGP_HIP(hipSetDevice(h->device));
-  const int P = K + K * d;
-  PredictStage s;
-  if (int rc = stage(h, [&](Layout& c) { s = predict_stage(c, n, d, P, S, m); })) return rc;
-  DrawView dv;
-  if (int frc = draw_view(h, h->fam, s.params, S, K, d, &dv)) return frc;
-  if (int prc = push(h, {piece(s.X, X, (size_t)n * d), piece(s.y, y, n), piece(s.params, params, (size_t)S * P),
-                         piece(s.Xtest, Xtest, (size_t)m * d)}))
-    return prc;
-  if (int rc = predict_run(h, s.X, n, d, s.y, dv, s.Xtest, m, sigma2, s.mean, s.var, s.beta, s.status)) return rc;
-  return pull_status(h, {piece(s.mean, out_mean, (size_t)S * m), piece(s.var, out_var, (size_t)S * m),
-                         piece(s.beta, out_beta, S)}, s.status, S, status);
+  return predict_call(h, X, n, d, y, K, params, S, Xtest, m, sigma2, false, nullptr, 0, out_mean, out_var,
+                      out_beta, nullptr, status);
 } CCGP_GUARD_END(h)
 
 // ---- the single-GP comparator's prediction: ccgp_predict_batch's route with a per-row sigma2 and a variance form ---------
@@ -1768,27 +1581,8 @@ int ccgp_krige_predict_batch(ccgp_handle* h, const double* X, int n, int d, cons
       if (!(std::isfinite(sigma2[b]) && sigma2[b] >= 0.0))
         return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch: every sigma2 must be finite and >= 0");
   }
-  CCGP_HIP(hipSetDevice(h->device));
-  const int P = K + K * d;
-  PredictStage s;
-  double *ds2, *dq;
-  if (int rc = stage(h, [&](Layout& c) {
-        s = predict_stage(c, n, d, P, B, m);
-        ds2 = c.take<double>(B);
-        dq = c.take<double>(B);
-      }))
-    return rc;
-  DrawView dv;
-  if (int frc = draw_view(h, h->fam, s.params, B, K, d, &dv)) return frc;
-  if (int prc = push(h, {piece(s.X, X, (size_t)n * d), piece(s.y, y, n), piece(s.params, params, (size_t)B * P),
-                         piece(s.Xtest, Xtest, (size_t)m * d), piece(ds2, own_s2 ? sigma2 : nullptr, B)}))
-    return prc;
-  // the scalar is not read where the per-row pointer is set; UNBIASED reads neither
-  if (int rc = predict_run(h, s.X, n, d, s.y, dv, s.Xtest, m, 1.0, s.mean, s.var, s.beta, s.status,
-                           VarForm{own_s2 ? ds2 : nullptr, var_form, dq}))
-    return rc;
-  return pull_status(h, {piece(s.mean, out_mean, (size_t)B * m), piece(s.var, out_var, (size_t)B * m),
-                         piece(s.beta, out_beta, B), piece(dq, out_q, B)}, s.status, B, status);
+  return predict_call(h, X, n, d, y, K, params, B, Xtest, m, 1.0, true, own_s2 ? sigma2 : nullptr,
+                      var_form, out_mean, out_var, out_beta, out_q, status);
 } CCGP_GUARD_END(h)
 
 // ---- prediction(): per-site summaries of the tables, HX:686-703 / GV:620-638 -------------------------------------
@@ -1826,15 +1620,13 @@ int ccgp_predict_summary(ccgp_handle* h, const double* X, int n, int d, const do
   SummaryStage s;
   if (int rc = stage(h, [&](Layout& c) { s = summary_stage(c, n, d, P, S, m, n_probs); })) return rc;
   DrawView dv;
-  if (int frc = draw_view(h, h->fam, s.params, S, K, d, &dv)) return frc;
-  if (int prc = push(h, {piece(s.X, X, (size_t)n * d), piece(s.y, y, n), piece(s.params, params, (size_t)S * P),
-                         piece(s.Xtest, Xtest, (size_t)m * d), piece(s.y_at, y_at, m)}))
-    return prc;
-  if (int rc = predict_run(h, s.X, n, d, s.y, dv, s.Xtest, m, sigma2, s.t.mean, s.t.var, s.beta, s.status)) return rc;
+  if (int frc = draw_view(h, h->fam, s.in.params, S, K, d, &dv)) return frc;
+  if (int prc = push(h, s.inputs(X, y, params, Xtest, y_at))) return prc;
+  if (int rc = predict_run(h, s.in.X, n, d, s.in.y, dv, s.in.Xtest, m, sigma2, s.t.mean, s.t.var, s.beta, s.status)) return rc;
   launch_predict_summary(h->stream, s.t.mean, s.t.var, s.status, S, m, probs, n_probs, y_at ? s.y_at : nullptr, s.t.idx,
                          s.t.count, s.out);
   CCGP_LAUNCH_CHECK();
-  return pull_status(h, {piece(s.out, out, (size_t)m * (4 + n_probs)), piece(s.beta, out_beta, S)}, s.status, S, status);
+  return pull_status(h, s.results(out, out_beta), s.status, S, status);
 } CCGP_GUARD_END(h)
 
 // ---- 8(f)-2: device-resident factor set --------------------------------------------------------------
@@ -1857,7 +1649,9 @@ struct ccgp_factorset {
 
 // owner of a factor set and of its device memory
 struct FactorsetFree {
+  ccgp_handle* h;   // the handle whose last scheduled sweep may have left its time account in the set; may be nullptr
   void operator()(ccgp_factorset* fs) const {
+    if (h) forget_sched_profile(h, fs->mem, fs->bytes);
     if (fs->mem) (void)hipFree(fs->mem);
     delete fs;
   }
@@ -1878,7 +1672,7 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
   const int npad = round_up(n, kTile);
   if (!fused && S > 65535)   // the draw index is a grid y / z dimension in cov_kernel, rhs_rows_kernel, ...
     return fail(h, CCGP_EINVAL, "ccgp_factor_batch: at most 65535 factors per set on the blocked path (n > 128)");
-  std::unique_ptr<ccgp_factorset, FactorsetFree> fs(new ccgp_factorset());
+  std::unique_ptr<ccgp_factorset, FactorsetFree> fs(new ccgp_factorset(), FactorsetFree{h});
   char* factors = nullptr;
   auto lay = [&](Layout& c) {
     fs->X = c.take<double>((size_t)n * d);
@@ -1900,11 +1694,9 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
   Layout c(fs->mem);
   lay(c);
   dv.params = fs->params;
-  if (hipMemcpyAsync(fs->X, X, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-      hipMemcpyAsync(fs->y, y, sizeof(double) * n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-      hipMemcpyAsync(fs->params, params, sizeof(double) * (size_t)S * P, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-      hipMemsetAsync(fs->status, 0, sizeof(int) * (size_t)S, h->stream) != hipSuccess)
-    return fail(h, CCGP_EHIP, "ccgp_factor_batch: upload failed");
+  if (int prc = push(h, {piece(fs->X, X, (size_t)n * d), piece(fs->y, y, n), piece(fs->params, params, (size_t)S * P)}))
+    return prc;
+  CCGP_HIP(hipMemsetAsync(fs->status, 0, sizeof(int) * (size_t)S, h->stream));
   if (fused) {
     // n <= 128: the factor of a draw lives and dies in registers / LDS inside the fused evaluator (10 us);
     // storing it would cost more HBM traffic than regenerating it.  The set keeps the draws; likelihood
@@ -1915,20 +1707,11 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
     fs->w = blocked_carve(factors, npad, S, 0);
     blocked_loglik(h, fs->X, n, d, fs->y, dv, 0, S, npad, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, fs->w, fs->ll,
                    fs->beta, fs->status);
-    if (hipGetLastError() != hipSuccess) return fail(h, CCGP_EHIP, "ccgp_factor_batch: launch failed");
-    const std::string ae = ccgp::attr_error(h->device);
-    if (!ae.empty()) return fail(h, CCGP_EHIP, ae);
+    CCGP_LAUNCH_CHECK();
   }
-  std::vector<int> st(S);
-  hipError_t e = hipSuccess;
-  if (out_loglik) e = hipMemcpyAsync(out_loglik, fs->ll, sizeof(double) * S, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && out_beta)
-    e = hipMemcpyAsync(out_beta, fs->beta, sizeof(double) * S, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(st.data(), fs->status, sizeof(int) * (size_t)S, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, CCGP_EHIP, std::string("ccgp_factor_batch: ") + hipGetErrorString(e));
-  *out = fs.release();
-  return report_status(st, status);
+  const int failed = pull_status(h, {piece(fs->ll, out_loglik, S), piece(fs->beta, out_beta, S)}, fs->status, S, status);
+  if (failed >= 0) *out = fs.release();
+  return failed;
 } CCGP_GUARD_END(h)
 
 // the S x m tables of a factor set at the m resident test sites dXt; arguments are checked by the callers
@@ -1945,7 +1728,7 @@ static int factorset_predict_run(ccgp_handle* h, const ccgp_factorset* fs, const
   if (int rc = plan_chunk(h, sizeof(double) * e_stride, S, kFactorsetMargin,
                           [&](int ns) { return sizeof(double) * e_stride * (size_t)ns; }, &sc))
     return rc;
-  double* E = static_cast<double*>(h->ws);
+  double* E = static_cast<double*>(h->ws.ptr);
   for (int s0 = 0; s0 < S; s0 += sc) {
     const int ns = std::min(sc, S - s0);
     CCGP_HIP(hipMemsetAsync(E, 0, sizeof(double) * e_stride * ns, h->stream));
@@ -1975,12 +1758,9 @@ int ccgp_predict_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const 
         dvar = c.take<double>((size_t)S * m);
       }))
     return rc;
-  CCGP_HIP(hipMemcpyAsync(dXt, Xtest, sizeof(double) * (size_t)m * d, hipMemcpyHostToDevice, h->stream));
+  if (int prc = push(h, {piece(dXt, Xtest, (size_t)m * d)})) return prc;
   if (int rc = factorset_predict_run(h, fs, dXt, m, dmean, dvar)) return rc;
-  CCGP_HIP(hipMemcpyAsync(out_mean, dmean, sizeof(double) * (size_t)S * m, hipMemcpyDeviceToHost, h->stream));
-  CCGP_HIP(hipMemcpyAsync(out_var, dvar, sizeof(double) * (size_t)S * m, hipMemcpyDeviceToHost, h->stream));
-  CCGP_HIP(hipStreamSynchronize(h->stream));
-  return CCGP_OK;
+  return pull(h, {piece(dmean, out_mean, (size_t)S * m), piece(dvar, out_var, (size_t)S * m)});
 } CCGP_GUARD_END(h)
 
 int ccgp_summary_from_factorset(ccgp_handle* h, const ccgp_factorset* fs, const double* Xtest, int m,
@@ -2019,7 +1799,7 @@ int ccgp_factorset_free(ccgp_handle* h, ccgp_factorset* fs) try {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
   }
-  FactorsetFree()(fs);
+  FactorsetFree{h}(fs);
   return CCGP_OK;
 } CCGP_GUARD_END(h)
 

@@ -56,6 +56,10 @@ struct KernelFamily {
 
 namespace ccgp {
 constexpr int kPullSlices = 4;
+struct Buffer {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+};
 }
 
 struct ccgp_handle {
@@ -76,15 +80,9 @@ struct ccgp_handle {
   int n_cus = 256;                      // multiProcessorCount of the handle's device
   unsigned long long* sched_prof_dev = nullptr;   // where the last scheduled sweep left its per-workgroup time account (policy bit 2)
   int sched_prof_wgs = 0;
-  // grow-only device scratch
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
-  // small staging buffers for the host-pointer entry points
-  void* stage = nullptr;
-  size_t stage_bytes = 0;
-  // pinned host buffer: inputs and results of the one-draw-per-call path (ccgp_logpost) cross PCIe in one copy each
-  void* pin = nullptr;
-  size_t pin_bytes = 0;
+  // the grow-only buffers (capi.hip: ensure): device scratch; the staging of the host-pointer entry points; the pinned
+  // host buffer through which their inputs and results cross PCIe in one copy each
+  ccgp::Buffer ws, stage, pin;
   size_t pin_in = 0;     // bytes of `pin` holding the inputs of the call in flight (results land behind them)
   hipStream_t aux_stream = nullptr;     // second stream of the kept-factor prediction (ccgp_reserve, or first use)
   hipEvent_t aux_fork = nullptr, aux_join = nullptr;
