@@ -66,6 +66,9 @@ SIGNATURES = {
                                    c_double, _dp, _dp, _dp, _ip]),
     "ccgp_krige_predict_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, c_int, _dp, c_int,
                                          _dp, _dp, _dp, _dp, _ip]),
+    "ccgp_loo_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, c_int, _dp, _dp, _dp, _dp, _ip]),
+    "ccgp_loo_summary": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, c_double, _dp, c_int, _dp, _dp,
+                                 _ip]),
     "ccgp_predict_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                                        c_int, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
@@ -698,6 +701,45 @@ class Handle:
         bad = self._chk(lib().ccgp_predict_summary(self._h, _p(X), n, d, _p(y), K, _p(params), S, _p(Xtest), m,
                                                    float(sigma2), _p(probs), probs.size, _p(y_at), _p(out), _p(beta),
                                                    _ipt(st)))
+        return _summary_dict(out, bad, beta, st)
+
+    # -- leave-one-out cross-validation ------------------------------------------------------
+    def loo_batch(self, X, y, K, params, sigma2, form=VAR_ORDINARY):
+        """ccgp_loo_batch: the leave-one-out mean and variance of every training point for each of the B rows of params,
+        from one factorisation per row (Dubrule 1983) -- what B x n calls of predict_batch on the n - 1 other points
+        return.  sigma2: a scalar, an array of B values, or None (VAR_UNBIASED reads none); form as for
+        krige_predict_batch, the UNBIASED form with n - 2 degrees of freedom (a fold has n - 1 points).
+        Returns (mean[B, n], var[B, n], beta[B], q[B], status[B]); beta and q are the full-data values."""
+        X, y = _f(X), _f(np.ravel(y))
+        n, d = X.shape
+        params = _f(np.atleast_2d(params))
+        B = params.shape[0]
+        if params.shape[1] != K + K * d:
+            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
+        s2 = None
+        if sigma2 is not None:
+            s2 = _f(np.broadcast_to(np.asarray(sigma2, dtype=np.float64), (B,)).copy())
+        mean = np.empty((B, n), dtype=np.float64, order="F")
+        var = np.empty((B, n), dtype=np.float64, order="F")
+        beta, q = np.empty(B), np.empty(B)
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_loo_batch(self._h, _p(X), n, d, _p(y), K, _p(params), B, _p(s2), int(form), _p(mean),
+                                       _p(var), _p(beta), _p(q), _ipt(st)))
+        return mean, var, beta, q, st
+
+    def loo_summary(self, X, y, K, params, sigma2, probs):
+        """ccgp_loo_summary: predict_summary's per-site summaries of the leave-one-out posterior predictive, the sites
+        being the n training points and y_at = y: the dict of predict_summary, cdf_at[i] = the PIT value F(y_i)."""
+        X, y = _f(X), _f(np.ravel(y))
+        n, d = X.shape
+        params = _f(np.atleast_2d(params))
+        S = params.shape[0]
+        probs = _probs(probs)
+        out = np.empty((n, 4 + probs.size), dtype=np.float64, order="F")
+        beta = np.empty(S)
+        st = np.zeros(S, dtype=np.int32)
+        bad = self._chk(lib().ccgp_loo_summary(self._h, _p(X), n, d, _p(y), K, _p(params), S, float(sigma2), _p(probs),
+                                               probs.size, _p(out), _p(beta), _ipt(st)))
         return _summary_dict(out, bad, beta, st)
 
     # -- 8(f)-2: device-resident factor set -------------------------------------------------

@@ -1537,6 +1537,69 @@ __global__ __launch_bounds__(64 * kAlphaWaves) void alpha_kernel(AlphaArgs g) {
   }
 }
 
+// ---- leave-one-out tables from the identity rows (ccgp_loo_batch; Dubrule 1983) -----------------------------------
+// With Z = L^-T in the extra rows:  (R^-1)_ii = sum_c Z[i][c]^2,  (R^-1 1)_i = sum_c Z[i][c] z_1[c],  (R^-1 y)_i = sum_c
+// Z[i][c] z_y[c]  (c >= i).  Z is read ONCE, on alpha_kernel's scheme: a workgroup owns 64 training points (lane = point: a
+// column of Z is 512 contiguous bytes per wave), its 16 waves take the columns c = a0 + w, a0 + w + 16, ...; three running
+// sums per lane, combined in LDS in fixed order, so a draw's bits do not depend on the chunk it rides in.  The first wave
+// then finishes its 64 points (loo_point) from what finish_kernel left: s11, beta (chunk-local) and Q (by global draw).
+// No tile of R^-1 is formed and nothing is contracted.
+struct LooArgs {
+  const double* A;
+  size_t a_stride;
+  int npad, ld, n;
+  const double* y;
+  const double* s11;    // chunk-local (fin)
+  const double* beta;   // chunk-local (fin + nb)
+  const int* status;    // by global draw
+  int b0, S;
+  double sigma2;
+  VarForm vf;           // per-row sigma2 and Q indexed by b0 + b, the variance form
+  double* mean;         // S x n column-major
+  double* var;
+};
+__global__ __launch_bounds__(64 * kAlphaWaves) void loo_kernel(LooArgs g) {
+  __shared__ double part[3][kAlphaWaves][64];
+  const int b = blockIdx.y, a0 = blockIdx.x * 64, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int a = a0 + lane;
+  const double* Ab = g.A + (size_t)b * g.a_stride;
+  const double* zrow = Ab + g.npad;
+  const double* Zrow = Ab + g.npad + kTile + a;
+  double gg = 0.0, v1 = 0.0, vy = 0.0;
+  if (a < g.n) {
+#pragma unroll 4
+    for (int c = a0 + wave; c < g.n; c += kAlphaWaves) {
+      const double z = Zrow[(size_t)c * g.ld];
+      const double zy = zrow[(size_t)c * g.ld], z1 = zrow[1 + (size_t)c * g.ld];
+      if (c >= a) {
+        gg = fma(z, z, gg);
+        v1 = fma(z, z1, v1);
+        vy = fma(z, zy, vy);
+      }
+    }
+  }
+  part[0][wave][lane] = gg;
+  part[1][wave][lane] = v1;
+  part[2][wave][lane] = vy;
+  __syncthreads();
+  if (tid >= 64 || a >= g.n) return;
+  gg = v1 = vy = 0.0;
+#pragma unroll 1
+  for (int w = 0; w < kAlphaWaves; ++w) {
+    gg += part[0][w][lane];
+    v1 += part[1][w][lane];
+    vy += part[2][w][lane];
+  }
+  const int gb = g.b0 + b;
+  const double s2 = g.vf.sigma2_row ? g.vf.sigma2_row[gb] : g.sigma2;
+  double mean, var;
+  loo_point(g.vf.form, s2, g.y[a], gg, v1, vy, g.s11[b], g.beta[b], g.vf.q[gb], g.n, &mean, &var);
+  if (g.status[gb] != 0) mean = var = __longlong_as_double(0x7ff8000000000000LL);
+  g.mean[gb + (size_t)a * g.S] = mean;
+  g.var[gb + (size_t)a * g.S] = var;
+}
+
 struct RinvArgs {
   const double* A;
   size_t a_stride;
@@ -1942,7 +2005,7 @@ struct GroupRun {
       fa.s11_out = w.fin; fa.beta_out = w.fin + nb;
       fa.logdet_out = job && job->kind == kJobLogdet ? job->logdet : nullptr;
       fa.s2hat = s2hat;
-      fa.q_out = pr ? pr->vf.q : nullptr;
+      fa.q_out = pr ? pr->vf.q : (job && job->kind == kJobLoo ? job->vf.q : nullptr);
       if (s2hat) hipLaunchKernelGGL(finish_kernel<true>, dim3(nb), dim3(256), 0, s, fa);
       else hipLaunchKernelGGL(finish_kernel<false>, dim3(nb), dim3(256), 0, s, fa);
       if (pr) {
@@ -1951,7 +2014,11 @@ struct GroupRun {
         hipLaunchKernelGGL(predict_finish_kernel, dim3((pr->m + 63) / 64, nb), dim3(64 * kPredFinishWaves), 0, s, pa);
       }
     }
-    if (job && job->kind >= kJobInverse) {
+    if (job && job->kind == kJobLoo) {
+      ScopedTimer t(h, CCGP_T_SOLVE, s);
+      LooArgs la{w.A, w.a_stride, npad, w.ld, n, y, w.fin, w.fin + nb, status, b0, job->S, sigma2, job->vf, job->mean, job->var};
+      hipLaunchKernelGGL(loo_kernel, dim3(npad / 64, nb), dim3(64 * kAlphaWaves), 0, s, la);
+    } else if (job && job->kind >= kJobInverse) {
       ScopedTimer t(h, CCGP_T_SOLVE, s);
       const int ntiles = nt * (nt + 1) / 2;
       RinvArgs ra{};

@@ -208,6 +208,62 @@ inline SummaryDevStage summary_dev_stage(Layout& c, int S, int m, bool own_statu
   return s;
 }
 
+// ---- leave-one-out (ccgp_loo_batch, ccgp_loo_summary): the training points are the sites, so no test set goes up.
+// ccgp_loo_batch: X | y | params | sigma2? | mean | var | beta | q | status.  Q is always staged: CCGP_VAR_UNBIASED reads it
+// on the device whether or not the caller wants it back.
+struct LooStage {
+  double *X, *y, *params, *sigma2;
+  double *mean, *var, *beta, *q;
+  int* status;
+  size_t nX, n, nparams, B;
+  std::vector<Piece> inputs(const double* hX, const double* hy, const double* hparams, const double* hsigma2) const {
+    return {piece(X, hX, nX), piece(y, hy, n), piece(params, hparams, nparams), piece(sigma2, hsigma2, sigma2 ? B : 0)};
+  }
+  // the status words follow q (pull_status)
+  std::vector<Piece> results(double* hmean, double* hvar, double* hbeta, double* hq) const {
+    return {piece(mean, hmean, B * n), piece(var, hvar, B * n), piece(beta, hbeta, B), piece(q, hq, B)};
+  }
+};
+inline LooStage loo_stage(Layout& c, int n, int d, int P, int B, bool own_sigma2) {
+  LooStage s;
+  s.nX = (size_t)n * d; s.n = n; s.nparams = (size_t)B * P; s.B = B;
+  s.X = c.take<double>(s.nX);
+  s.y = c.take<double>(s.n);
+  s.params = c.take<double>(s.nparams);
+  s.sigma2 = own_sigma2 ? c.take<double>(B) : nullptr;
+  s.mean = c.take<double>(s.B * s.n);
+  s.var = c.take<double>(s.B * s.n);
+  s.beta = c.take<double>(B);
+  s.q = c.take<double>(B);
+  s.status = c.take<int>(B);
+  return s;
+}
+// ccgp_loo_summary: X | y | params | tables | q | out | beta | status -- the tables stay on the device, as in SummaryStage
+struct LooSummaryStage {
+  double *X, *y, *params;
+  SummaryTables t;
+  double *q, *out, *beta;
+  int* status;
+  size_t nX, n, nparams, S, nout;
+  std::vector<Piece> inputs(const double* hX, const double* hy, const double* hparams) const {
+    return {piece(X, hX, nX), piece(y, hy, n), piece(params, hparams, nparams)};
+  }
+  std::vector<Piece> results(double* hout, double* hbeta) const { return {piece(out, hout, nout), piece(beta, hbeta, S)}; }
+};
+inline LooSummaryStage loo_summary_stage(Layout& c, int n, int d, int P, int S, int n_probs) {
+  LooSummaryStage s;
+  s.nX = (size_t)n * d; s.n = n; s.nparams = (size_t)S * P; s.S = S; s.nout = (size_t)n * (4 + n_probs);
+  s.X = c.take<double>(s.nX);
+  s.y = c.take<double>(s.n);
+  s.params = c.take<double>(s.nparams);
+  s.t = summary_tables(c, S, n);
+  s.q = c.take<double>(S);
+  s.out = c.take<double>(s.nout);
+  s.beta = c.take<double>(S);
+  s.status = c.take<int>(S);
+  return s;
+}
+
 // the staging ccgp_reserve(n, d, K, B, m) provides: the host-pointer likelihood and, with test sites, the prediction
 // (without its tail) and the tables of ccgp_predict_summary_dev
 inline size_t reserve_stage_bytes(int n, int d, int P, int B, int m) {

@@ -1629,6 +1629,78 @@ int ccgp_predict_summary(ccgp_handle* h, const double* X, int n, int d, const do
   return pull_status(h, s.results(out, out_beta), s.status, S, status);
 } CCGP_GUARD_END(h)
 
+// ---- leave-one-out cross-validation of the Combined GP: the closed form from ONE factorisation per draw ---------------
+// the tables of the B draws of dv on resident inputs; arguments are checked by the callers.  vf.q is never nullptr.  The
+// route is asked once (small_route_loo): the fourth inverse instance of small_reg.hip, timed under CCGP_T_FUSED, or identity
+// rows on the blocked sweep with loo_kernel behind it, timed under CCGP_T_SOLVE.
+static int loo_run(ccgp_handle* h, const double* dX, int n, int d, const double* dy, const DrawView& dv, double sigma2,
+                   VarForm vf, double* d_mean, double* d_var, double* d_beta, int* d_status) {
+  const int K = dv.K, B = dv.ldp;
+  if (small_route_loo(dv.fam.id == 0, n, d, K) == Route::Blocked) {
+    const int npad = round_up(n, kTile);
+    SweepOut sc{};
+    BlockedJob job{};
+    job.kind = kJobLoo; job.S = B; job.mean = d_mean; job.var = d_var; job.vf = vf;
+    return run_sweep(h, dX, n, d, dy, dv, B, npad / kTile, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, sc, &job, 0,
+                     [&](Layout& t, int) { sc = predict_tail(t, B, d_beta, d_status); });
+  }
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    launch_small_reg_loo(h->stream, dX, n, d, dy, dv, B, sigma2, vf, d_mean, d_var, d_beta, d_status);
+  }
+  CCGP_LAUNCH_CHECK();
+  return CCGP_OK;
+}
+
+int ccgp_loo_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K, const double* params, int B,
+                   const double* sigma2, int var_form, double* out_mean, double* out_var, double* out_beta, double* out_q,
+                   int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || B < 0 || !X || !y || !params || !out_mean || !out_var)
+    return fail(h, CCGP_EINVAL, "ccgp_loo_batch: bad argument");
+  if (var_form != CCGP_VAR_ORDINARY && var_form != CCGP_VAR_PLUGIN && var_form != CCGP_VAR_UNBIASED)
+    return fail(h, CCGP_EINVAL, "ccgp_loo_batch: unknown var_form");
+  const bool own_s2 = var_form != CCGP_VAR_UNBIASED;
+  if (n < 2) return fail(h, CCGP_EINVAL, "ccgp_loo_batch: a fold needs at least one other point (n >= 2)");
+  if (!own_s2 && n < 3) return fail(h, CCGP_EINVAL, "ccgp_loo_batch: CCGP_VAR_UNBIASED divides by n - 2");
+  if (own_s2) {
+    if (!sigma2) return fail(h, CCGP_EINVAL, "ccgp_loo_batch: this var_form needs sigma2");
+    for (int b = 0; b < B; ++b)
+      if (!(std::isfinite(sigma2[b]) && sigma2[b] >= 0.0))
+        return fail(h, CCGP_EINVAL, "ccgp_loo_batch: every sigma2 must be finite and >= 0");
+  }
+  if (B == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  LooStage s;
+  if (int rc = stage(h, [&](Layout& c) { s = loo_stage(c, n, d, K + K * d, B, own_s2); })) return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, B, K, d, &dv)) return frc;
+  if (int prc = push(h, s.inputs(X, y, params, own_s2 ? sigma2 : nullptr))) return prc;
+  if (int rc = loo_run(h, s.X, n, d, s.y, dv, 1.0, VarForm{s.sigma2, var_form, s.q}, s.mean, s.var, s.beta, s.status)) return rc;
+  return pull_status(h, s.results(out_mean, out_var, out_beta, out_q), s.status, B, status);
+} CCGP_GUARD_END(h)
+
+int ccgp_loo_summary(ccgp_handle* h, const double* X, int n, int d, const double* y, int K, const double* params, int S,
+                     double sigma2, const double* probs, int n_probs, double* out, double* out_beta, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || n < 2 || S < 1 || !X || !y || !params || !out || !(std::isfinite(sigma2) && sigma2 >= 0.0))
+    return fail(h, CCGP_EINVAL, "ccgp_loo_summary: bad argument");
+  if (int rc = check_summary_args(h, n, probs, n_probs)) return rc;
+  CCGP_HIP(hipSetDevice(h->device));
+  LooSummaryStage s;
+  if (int rc = stage(h, [&](Layout& c) { s = loo_summary_stage(c, n, d, K + K * d, S, n_probs); })) return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, S, K, d, &dv)) return frc;
+  if (int prc = push(h, s.inputs(X, y, params))) return prc;
+  if (int rc = loo_run(h, s.X, n, d, s.y, dv, sigma2, VarForm{nullptr, CCGP_VAR_ORDINARY, s.q}, s.t.mean, s.t.var, s.beta,
+                       s.status))
+    return rc;
+  // the sites are the training points and y_at the resident y: column 3 is the PIT value F(y_i)
+  launch_predict_summary(h->stream, s.t.mean, s.t.var, s.status, S, n, probs, n_probs, s.y, s.t.idx, s.t.count, s.out);
+  CCGP_LAUNCH_CHECK();
+  return pull_status(h, s.results(out, out_beta), s.status, S, status);
+} CCGP_GUARD_END(h)
+
 // ---- 8(f)-2: device-resident factor set --------------------------------------------------------------
 struct ccgp_factorset {
   int device = 0;

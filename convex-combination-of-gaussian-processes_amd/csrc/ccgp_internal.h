@@ -127,6 +127,18 @@ __device__ __forceinline__ double predict_variance(int form, double sigma2, doub
   if (form == CCGP_VAR_UNBIASED) sigma2 = Q / (n - 1);
   return sigma2 * (1.0 - ww + u * u / s11);
 }
+// Leave-one-out at training point i from the full-data quantities (Dubrule 1983): g = (R^-1)_ii, v1 = (R^-1 1)_i,
+// vy = (R^-1 y)_i, s11 = 1'R^-1 1, beta, Q = (y - beta 1)'R^-1 (y - beta 1):
+//   c = g - v1^2 / s11,  a = vy - beta v1,  mean = y_i - a / c                 predict.post on the n - 1 other points
+//   CCGP_VAR_ORDINARY  sigma2 / c          CCGP_VAR_PLUGIN  sigma2 / g          CCGP_VAR_UNBIASED  (Q - a^2 / c) / (n - 2) / c
+__device__ __forceinline__ void loo_point(int form, double sigma2, double yi, double g, double v1, double vy, double s11,
+                                          double beta, double Q, int n, double* mean, double* var) {
+  const double c = g - v1 * v1 / s11, a = vy - beta * v1;
+  *mean = yi - a / c;
+  if (form == CCGP_VAR_PLUGIN) *var = sigma2 / g;
+  else if (form == CCGP_VAR_UNBIASED) *var = (Q - a * a / c) / (n - 2) / c;
+  else *var = sigma2 / c;
+}
 #endif
 
 // ---- cov.hip -------------------------------------------------------------------------
@@ -194,6 +206,11 @@ void launch_small_reg_logdet_grad_designs(hipStream_t s, const double* Xs, int n
 void launch_small_reg_loglik(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                              int B, double sigma2, int mean_mode, double tau2, double* loglik,
                              double* beta, int* status, bool grid16 = false);
+// leave-one-out mean / variance of every training point for B draws (ccgp_loo_batch where small_route_loo says Reg): one
+// workgroup per draw on the inverse instances' scheme; mean / var are B x n column-major, sigma2 is the scalar that
+// vf.sigma2_row (indexed by draw) replaces, vf.q (may be nullptr) receives Q per draw
+void launch_small_reg_loo(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B, double sigma2,
+                          VarForm vf, double* mean, double* var, double* beta, int* status);
 
 // ---- cgp.hip: the composite GP comparator (CGP / predict.CGP, GV:58-317), n <= 128 -------------------------------------
 // LDS carve of cgp_state_kernel, in doubles:
@@ -245,7 +262,7 @@ struct BlockedWs {
   int ne;           // extra full tile rows (ceil(m / 128) for prediction, else 0)
 };
 // optional extra work riding on a blocked sweep (n > 128)
-enum { kJobLogdet = -1, kJobNone = 0, kJobPredict = 1, kJobInverse = 2, kJobGrad = 3 };   // >= kJobInverse: identity rows ride along
+enum { kJobLogdet = -1, kJobNone = 0, kJobPredict = 1, kJobInverse = 2, kJobGrad = 3, kJobLoo = 4 };   // >= kJobInverse: identity rows ride along
 struct BlockedJob {
   int kind;
   // kJobPredict (a10 + a11): m cross-correlation rows ride along as extra tile rows
@@ -261,6 +278,8 @@ struct BlockedJob {
   int Btot;
   double* gpart;        // scratch: nb x blocked_grad_partials(npad) x P partial sums
   double* alpha;        // scratch: nb x npad,  R^-1 (y - beta 1)
+  // kJobLoo (ccgp_loo_batch): identity rows ride along; the leave-one-out tables go to mean / var (S x n column-major, S in
+  // `S`), the form, the per-row sigma2 and Q (never nullptr here: CCGP_VAR_UNBIASED reads it back) are in vf
   // kJobLogdet: log det of the normalised mixed correlation matrix (entropy criteria, BSQ:856-877), indexed like loglik
   double* logdet;
   // any kind (kJobNone: nothing else rides): the profiled mode of ccgp_profile_batch.  finish_kernel concentrates sigma2 out

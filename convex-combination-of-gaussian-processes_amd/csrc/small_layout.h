@@ -218,5 +218,11 @@ inline Route small_route(Op op, bool gauss, int n, int d, int K) {
   }
   return Route::Unsupported;
 }
+// leave-one-out tables (ccgp_loo_batch, ccgp_loo_summary): the fourth inverse instance (INV = 4) on the carve of the other
+// three where it fits, else identity rows on the blocked sweep -- which is every family but the Gaussian.  A function of its
+// own, not an Op: the check program switches over Op and holds each of its cells to the expression it replaced.
+inline Route small_route_loo(bool gauss, int n, int d, int K) {
+  return gauss && small_reg_inverse_supported(n, d, K) ? Route::Reg : Route::Blocked;
+}
 
 }  // namespace ccgp

@@ -114,7 +114,8 @@ __device__ __forceinline__ void mat_sync() {
 #define CCGP_SMALL_OCC_PRED 3
 #endif
 // INV: 0 = none, 1 = explicit inverse (solve(R), HX:454), 2 = analytic gradient of the profile-beta log-likelihood,
-// 3 = gradient of log det R with respect to the design (per-design form, entropy criteria BSQ:856-948)
+// 3 = gradient of log det R with respect to the design (per-design form, entropy criteria BSQ:856-948),
+// 4 = leave-one-out mean and variance of every training point (ccgp_loo_batch)
 // PROF: sigma2 concentrated out (ordinary kriging, `ord$sig2` HX:759-760; log.likeli D1:424-444): where the likelihood is
 // finished the quadratic form q is at hand, so cs = sigma2 sum w^2 becomes the draw's own q / n, and the gradient epilogue
 // reads that value instead of the caller's -- by the envelope theorem the closed form at (beta_hat, sigma2_hat) IS the
@@ -598,6 +599,37 @@ void small_reg_kernel(RegArgs a) {
       };
       if (d <= 8) contract(std::integral_constant<int, 3>{}, std::integral_constant<int, 8>{});
       else contract(std::integral_constant<int, 1>{}, std::integral_constant<int, 16>{});
+    } else if constexpr (INV == 4) {
+      // ---- leave-one-out tables (ccgp_loo_batch; Dubrule 1983) ----------------------------------------------------------
+      // Everything comes from the scaled Z already in LDS: g_i = (R^-1)_ii = row_dot(i, i), and (R^-1 1)_i, (R^-1 y)_i are
+      // row i of Z against the two scaled right-hand-side columns, as alpha is formed for INV = 2.  One thread per training
+      // point, each sum in index order; s11, beta and Q are the likelihood's own (slack).  O(n^2) after the factorisation.
+      double* ry = zb;          // z_y d^-1/2 in place of z_y
+      double* r1 = zb + NP;     // z_1 d^-1/2 in place of z_1
+      for (int c = lt; c < NP; c += TPM) {
+        const double sc = c < n ? dvec[c] : 0.0;
+        ry[c] = c < n ? zb[c] * sc : 0.0;
+        r1[c] = c < n ? zb[NP + c] * sc : 0.0;
+      }
+      mat_sync<G>();
+      const double beta = slack[0], s11 = slack[1], Q = slack[3];
+      const double s2 = a.vf.sigma2_row ? a.vf.sigma2_row[b] : a.sigma2;
+      for (int i = lt; i < n; i += TPM) {
+        const double g = row_dot(i, i);
+        double v1 = 0.0, vy = 0.0;
+        for (int c = i; c < n; ++c) {
+          const double z = zmat[i * ZS + c];
+          v1 = fma(z, r1[c], v1);
+          vy = fma(z, ry[c], vy);
+        }
+        double mean, var;
+        loo_point(a.vf.form, s2, a.y[i], g, v1, vy, s11, beta, Q, n, &mean, &var);
+        if (bad) { mean = kNaN; var = kNaN; }
+        if (valid) {
+          a.mean[b + (size_t)i * a.S] = mean;
+          a.var[b + (size_t)i * a.S] = var;
+        }
+      }
     } else {
       // ---- design gradient (entropy criteria, BSQ:856-948; the reference's optim() differences numerically) --------
       //   d log det R / d x_ik = -4 sum_{j != i} (R^-1)_ij (x_ik - x_jk) sum_q (w_q^2 / sw) theta_qk R_q,ij
@@ -1035,7 +1067,8 @@ static void launch_inv(hipStream_t s, const RegArgs& a) {
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
     raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF>,
-                    INV == 1 ? "small_reg_kernel<inverse>" : INV == 2 ? "small_reg_kernel<gradient>" : "small_reg_kernel<design gradient>");
+                    INV == 1 ? "small_reg_kernel<inverse>" : INV == 2 ? "small_reg_kernel<gradient>" :
+                    INV == 3 ? "small_reg_kernel<design gradient>" : "small_reg_kernel<leave-one-out>");
   });
   const size_t lds = sizeof(double) * reg_lds_doubles(16, NB, NB + 1, true, a.x_stride != 0, a.n, a.d, a.K);
   const int kMaxGrid = 1 << 20;
@@ -1093,6 +1126,15 @@ void launch_small_reg_grad(hipStream_t s, const double* X, int n, int d, const d
   a.B = B; a.sigma2 = sigma2;
   a.loglik = loglik; a.beta = beta; a.status = status; a.grad = grad; a.Btot = B;
   dispatch_inv<2>(s, a);
+}
+
+// the leave-one-out tables of B draws (ccgp_loo_batch, ccgp_loo_summary): one workgroup per draw, one launch
+void launch_small_reg_loo(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B, double sigma2,
+                          VarForm vf, double* mean, double* var, double* beta, int* status) {
+  RegArgs a = reg_args(X, n, d, y, dv);
+  a.B = B; a.sigma2 = sigma2; a.vf = vf;
+  a.beta = beta; a.status = status; a.mean = mean; a.var = var; a.S = B;
+  dispatch_inv<4>(s, a);
 }
 
 // ccgp_profile_batch at n <= 128: likelihood with sigma2 concentrated out, the draw's sigma2_hat, and (grad != nullptr) the

@@ -386,6 +386,55 @@ def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=N
                 mean=mean, var=var)
 
 
+def _add_single_loo_columns(table, gp, alpha, D_train, y_train, single):
+    """leave_one_out's single-GP columns: the model as _add_single_columns takes or fits it (ONCE, on all n points: the
+    parameters stay fixed across the folds, as for the Combined GP's draws), then one ccgp_loo_batch row with K = 1 -- the
+    plug-in variance for the 2-D / emulator scripts, the unbiased form for the 1-D scripts -- and the interval
+    y_hat -+ qt(1 - alpha / 2, n - 2) sqrt(max(var, 0)): a fold has n - 1 points."""
+    one_d = hasattr(gp, "nu")
+    base = getattr(gp.h, "_handle", gp.h)
+    given = dict(single) if isinstance(single, dict) else {}
+    model = {k: given.pop(k) for k in ("theta", "sigma2", "beta") if k in given}
+    y = np.asarray(y_train, dtype=np.float64).ravel()
+    if one_d:
+        from .rsurface import _FamilyHandle
+        D = np.asarray(D_train, dtype=np.float64).reshape(-1, 1)
+        if "theta" not in model:
+            model = matern_MLEs(base, D, y, gp.nu, **given)
+        h, s2, form = _FamilyHandle(base, api.KERNEL_MATERN, float(gp.nu)), None, api.VAR_UNBIASED
+    else:
+        D = np.asarray(D_train, dtype=np.float64)
+        if "theta" not in model or "sigma2" not in model:
+            model = ordinary_kriging_fit(base, D, y, **given)
+        h, s2, form = base, [model["sigma2"]], api.VAR_PLUGIN
+    theta = np.atleast_1d(np.asarray(model["theta"], dtype=np.float64)).ravel()
+    if theta.size != D.shape[1]:
+        raise ValueError("the single GP's theta must hold one scale per input dimension")
+    mean, var, _, _, st = h.loo_batch(D, y, 1, np.concatenate([[1.0], theta])[None], s2, form)
+    if st[0] != 0:
+        raise RuntimeError("leave_one_out: the single GP's correlation matrix could not be factorised (pivot %d)" % st[0])
+    lo, hi = _t_interval(mean[0], var[0], alpha, D.shape[0] - 1)
+    table.update(y_hat_single=mean[0].copy(), LL_single=lo, UL_single=hi, single=model)
+    if one_d:
+        table["single_var"] = var[0].copy()
+    return table
+
+
+def leave_one_out(gp, alpha, draws, D_train, sigma2, y_train, single=False):
+    """compare_GP(exact=True)'s table with the training points as their own test set: row i is the exact posterior
+    predictive of y_i given the n - 1 other points under the posterior draws (gp.leave_one_out: one factorisation per draw,
+    no refitting), y_true = y_train.  comparison_summary of it gives the Combined GP's leave-one-out RMSPE (what GV:199 calls
+    rmscv for the CGP), interval coverage and mean quantile without a held-out set; `pit` holds F(y_i).  single as in
+    compare_GP (True fits, a dict gives the model) adds y_hat_single, LL_single, UL_single.  No CGP columns: its jackknife is
+    cgp.CGP's Yjfp / rmscv and has no interval in the reference."""
+    r = gp.leave_one_out(alpha, draws, D_train, sigma2, y_train)
+    table = dict(y_hat=r["y_hat"], quant=r["Quant"], LL=r["LL"], UL=r["UL"],
+                 y_true=np.asarray(y_train, dtype=np.float64).ravel(), pit=r["pit"])
+    if single:
+        _add_single_loo_columns(table, gp, alpha, D_train, y_train, single)
+    return table
+
+
 def ordinary_kriging_sigma2(handle, D_train, y_train, starts=8, rng=0):
     """sigma2 of the ordinary-kriging MLE with one anisotropic Gaussian kernel -- what the scripts
     take from mlegp (`ord$sig2`, HX:759-760).  Deterministic multi-start L-BFGS on the concentrated

@@ -309,6 +309,17 @@ class CombinedGP:
         return dict(y_hat=r["y_hat"], Quant=r["quant"], LL=r["quantiles"][:, 0], UL=r["quantiles"][:, 1],
                     pred_var=r["pred_var"], cdf_at=r["cdf_at"], beta=r["beta"], status=r["status"])
 
+    def leave_one_out(self, alpha, draws, D_train, sigma2, y_train):
+        """Leave-one-out cross-validation of the posterior sample, the counterpart of prediction() with the training
+        points as sites: per point i the exact posterior predictive of y_i given the n - 1 OTHER points -- per draw
+        predict.post(x_i, D[-i,], ...) with factors() recomputed there, in closed form from the draw's one factorisation
+        (ccgp_loo_summary) -- summarised as prediction() does: y_hat, Quant, LL / UL at alpha/2 and 1 - alpha/2, and pit =
+        the predictive CDF at the held-out y_i.  Needs no test set."""
+        params = self.draws_to_params(D_train, draws)
+        r = self.h.loo_summary(D_train, y_train, 2, params, sigma2, (alpha / 2.0, 1.0 - alpha / 2.0))
+        return dict(y_hat=r["y_hat"], Quant=r["quant"], LL=r["quantiles"][:, 0], UL=r["quantiles"][:, 1],
+                    pred_var=r["pred_var"], pit=r["cdf_at"], beta=r["beta"], status=r["status"])
+
     def factors_frame_from_draws(self, draws, D_train, sigma2, y_train):
         """Materialise the data frame factors.frame() returns (HX:625-644) for drop-in
         callers, given the posterior draws (the Metropolis chain itself is out of scope):
@@ -404,6 +415,9 @@ class CombinedGP1D(CombinedGP):
 
     def prediction(self, D_test, alpha, draws, D_train, sigma2, y_train, y_test=None):
         return super().prediction(self._col(D_test), alpha, draws, self._col(D_train), sigma2, y_train, y_test)
+
+    def leave_one_out(self, alpha, draws, D_train, sigma2, y_train):
+        return super().leave_one_out(alpha, draws, self._col(D_train), sigma2, y_train)
 
     def factors_frame_from_draws(self, draws, D_train, sigma2, y_train):
         return super().factors_frame_from_draws(draws, self._col(D_train), sigma2, y_train)

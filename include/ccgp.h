@@ -322,6 +322,44 @@ int ccgp_krige_predict_batch(ccgp_handle* h, const double* X, int n, int d, cons
                              double* out_beta /* B, NULL ok */, double* out_q /* B: Q_b, NULL ok */,
                              int* status /* B, NULL ok */);
 
+/* ---- leave-one-out cross-validation of the Combined GP (Dubrule 1983) --------------------------------
+ * What n calls of ccgp_predict_batch -- each on the n - 1 other points and the one held-out site -- return, from ONE
+ * factorisation per draw.  For draw b with parameters fixed, R the normalised mixed matrix ccgp_predict_batch uses:
+ *   v1 = R^-1 1,  v2 = 1'v1,  beta = v1'y / v2,  a = R^-1 (y - beta 1),  Q = (y - beta 1)'a
+ *   g_i = (R^-1)_ii,   c_i = g_i - v1_i^2 / v2
+ *   mean[b,i] = y_i - a_i / c_i
+ *   var[b,i]  = sigma2_b / c_i                        CCGP_VAR_ORDINARY  (predict.post, HX:669)
+ *             = sigma2_b / g_i                        CCGP_VAR_PLUGIN    (mlegp's se.fit^2)
+ *             = (Q - a_i^2 / c_i) / (n - 2) / c_i     CCGP_VAR_UNBIASED  (D1:504-516 on n - 1 points); takes no sigma2
+ * mean[b,i] and the ORDINARY var[b,i] are predict.post(x_i, D[-i,], ...) (HX:655-673) with factors() recomputed on the
+ * n - 1 other points and beta re-estimated there; out_beta[b] and out_q[b] are the FULL-data beta and Q above.
+ * out_mean / out_var: B x n column-major (element (b, i) at [b + i*B]); out_beta, out_q, status (B each) may be NULL.
+ * CCGP_EINVAL before anything is launched, outputs untouched: var_form outside 0..2; n < 2, or n < 3 with UNBIASED;
+ * ORDINARY or PLUGIN with sigma2 NULL or any sigma2_b not finite or negative.  B == 0 returns CCGP_OK.  A failed
+ * factorisation (the pivot rule of the mode-0 likelihood): status[b] = 1-based pivot index, NaN in row b of both tables,
+ * out_beta[b] and out_q[b]; returns the number of failed rows.  A row depends on its own parameters and sigma2_b only: not
+ * on B, its position, or where the workspace limit cuts the call.
+ * Route: Gaussian family where the register-resident inverse instance fits (n <= 128, small d, K): one launch, one
+ * workgroup per draw, an O(n^2) epilogue behind the factorisation (CCGP_T_FUSED).  Everything else -- larger n, and every
+ * other family of ccgp_set_kernel -- carries the identity as extra tile rows of the blocked sweep and reads L^-1 once,
+ * O(n^2) per draw, with no R^-1 tile product (the epilogue is timed under CCGP_T_SOLVE).
+ * Under CCGP_KERNEL_MATERN_SPLINE the result is this closed form on the NORMALISED R.  The script's predict.post uses the
+ * un-normalised corr.vec.combined there (D1F:470-480), so the closed form is NOT what ccgp_predict_batch returns on the
+ * reduced sets for that family; for the other two families it is.
+ * ccgp_loo_summary runs the same evaluation (CCGP_VAR_ORDINARY, one sigma2) into device tables and summarises them as
+ * ccgp_predict_summary does with the training points as sites and y_at = y: out is n x (4 + n_probs) column-major, column 3
+ * is the PIT value F(y_i) of the leave-one-out posterior predictive; failed draws are left out and counted as there.
+ * Host pointers; both block.  Not in this version: _dev variants, ccgp_reserve coverage, a ccgp_multi wrapper, an R shim. */
+int ccgp_loo_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                   const double* params, int B,
+                   const double* sigma2 /* B values; ignored, may be NULL, for UNBIASED */,
+                   int var_form, double* out_mean, double* out_var /* B x n column-major: [b + i*B] */,
+                   double* out_beta /* B, NULL ok */, double* out_q /* B: Q_b, NULL ok */, int* status /* B, NULL ok */);
+int ccgp_loo_summary(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
+                     const double* params, int S, double sigma2, const double* probs, int n_probs,
+                     double* out /* n x (4 + n_probs), the columns of ccgp_predict_summary with y_at = y */,
+                     double* out_beta, int* status);
+
 /* ---- prediction(): the per-site summaries of those tables (HX:686-703 / GV:620-638) -------------
  * Every script ends in compare.GP -> prediction(): per test site the mean of the S per-draw means, a
  * prediction interval and Quant.Combined, which the reference estimates from ONE normal variate per draw.
