@@ -56,6 +56,10 @@ SIGNATURES = {
     "ccgp_logpost": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, c_int, _dp, _dp, _dp, _dp,
                              _dp, _dp, _ip]),
     "ccgp_logpost_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, c_int, _dp, c_int, _dp, _dp, _dp, _dp, _ip]),
+    "ccgp_loglik_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, _ip, c_int, c_int, c_double,
+                                       _dp, _dp, _ip]),
+    "ccgp_logpost_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, _ip, c_int, _dp, _dp, _dp, _dp,
+                                  _ip]),
     "ccgp_grid_marginal": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, _dp, c_int, c_int,
                                    c_double, c_int, c_double, _dp, _ip, _dp]),
     "ccgp_mixed_logdet_designs": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, _dp, _ip]),
@@ -598,6 +602,48 @@ class Handle:
         st = np.zeros(B, dtype=np.int32)
         self._chk(lib().ccgp_logpost_batch(self._h, _p(X), n, d, _p(y), float(sigma2), int(prior_id), _p(theta_t), B,
                                            _p(pp), _p(val), _p(beta), _p(ll), _ipt(st)))
+        return val, beta, ll, st
+
+    @staticmethod
+    def _sets(Xs, ys, sigma2s, set_of, B):
+        """The C training sets of one shape as the sets calls take them: designs [C, n, d] -> C column-major blocks,
+        responses [C, n], variances [C], and the rows' set indices as int32[B]."""
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if Xs.ndim != 3:
+            raise ValueError("Xs must be [C, n, d]: the sets of one call have one shape")
+        C, n, d = Xs.shape
+        blocks = np.ascontiguousarray(np.transpose(Xs, (0, 2, 1)))
+        ys = np.ascontiguousarray(np.asarray(ys, dtype=np.float64).reshape(C, n))
+        s2 = np.ascontiguousarray(np.asarray(sigma2s, dtype=np.float64).reshape(C))
+        idx = np.ascontiguousarray(np.asarray(set_of).reshape(B).astype(np.int32))
+        return blocks, ys, s2, idx, C, n, d
+
+    def loglik_batch_sets(self, Xs, ys, sigma2s, K, params, set_of, mean_mode=MEAN_PROFILE_BETA, tau2=0.0):
+        """ccgp_loglik_batch_sets: row b of params [B, K + K*d] on training set set_of[b] of the C sets Xs [C, n, d],
+        ys [C, n], sigma2s [C] in one call.  Returns (loglik[B], beta[B], status[B]), each row with the bits loglik_batch
+        gives it on its set alone."""
+        params = _f(np.atleast_2d(params))
+        B, P = params.shape
+        Xb, yb, s2, idx, C, n, d = self._sets(Xs, ys, sigma2s, set_of, B)
+        if P != K + K * d:
+            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
+        ll, beta = np.empty(B), np.empty(B)
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_loglik_batch_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, K, _p(params), _ipt(idx), B,
+                                               int(mean_mode), float(tau2), _p(ll), _p(beta), _ipt(st)))
+        return ll, beta, st
+
+    def logpost_sets(self, Xs, ys, sigma2s, prior_id, theta_t, set_of, prior_pars=None):
+        """ccgp_logpost_sets: logpost of row b of theta_t on training set set_of[b] -> (val, beta, loglik, status), each
+        value as logpost_batch returns it on that set alone, bit for bit."""
+        theta_t = _f(np.atleast_2d(theta_t))
+        B = theta_t.shape[0]
+        Xb, yb, s2, idx, C, n, d = self._sets(Xs, ys, sigma2s, set_of, B)
+        pp = _f(np.ravel(prior_pars)) if prior_pars is not None else None
+        val, beta, ll = np.empty(B), np.empty(B), np.empty(B)
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_logpost_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, int(prior_id), _p(theta_t), _ipt(idx), B,
+                                          _p(pp), _p(val), _p(beta), _p(ll), _ipt(st)))
         return val, beta, ll, st
 
     def grid_marginal(self, X, y, sigma2, hyper, N, tau, take_log, aniso_lambda=-1.0, want_logs=False):

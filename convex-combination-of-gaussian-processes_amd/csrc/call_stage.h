@@ -264,6 +264,36 @@ inline LooSummaryStage loo_summary_stage(Layout& c, int n, int d, int P, int S, 
   return s;
 }
 
+// ---- the sets form of the likelihood (ccgp_loglik_batch_sets): C training sets of one shape go up with the B parameter rows
+// and the set every row belongs to: Xs | ys | sigma2 | params | set | loglik | beta | status
+struct SetsStage {
+  double *Xs, *ys, *sigma2, *params;
+  int* set;
+  double *loglik, *beta;
+  int* status;
+  size_t nXs, nys, C, nparams, B;
+  std::vector<Piece> inputs(const double* hXs, const double* hys, const double* hsigma2, const double* hparams,
+                            const int* hset) const {
+    return {piece(Xs, hXs, nXs), piece(ys, hys, nys), piece(sigma2, hsigma2, C), piece(params, hparams, nparams),
+            piece(set, hset, B)};
+  }
+  // the status words follow beta (pull_status)
+  std::vector<Piece> results(double* hloglik, double* hbeta) const { return {piece(loglik, hloglik, B), piece(beta, hbeta, B)}; }
+};
+inline SetsStage sets_stage(Layout& c, int n, int d, int P, int C, int B) {
+  SetsStage s;
+  s.nXs = (size_t)C * n * d; s.nys = (size_t)C * n; s.C = C; s.nparams = (size_t)B * P; s.B = B;
+  s.Xs = c.take<double>(s.nXs);
+  s.ys = c.take<double>(s.nys);
+  s.sigma2 = c.take<double>(s.C);
+  s.params = c.take<double>(s.nparams);
+  s.set = c.take<int>(s.B);
+  s.loglik = c.take<double>(s.B);
+  s.beta = c.take<double>(s.B);
+  s.status = c.take<int>(s.B);
+  return s;
+}
+
 // the staging ccgp_reserve(n, d, K, B, m) provides: the host-pointer likelihood and, with test sites, the prediction
 // (without its tail) and the tables of ccgp_predict_summary_dev
 inline size_t reserve_stage_bytes(int n, int d, int P, int B, int m) {

@@ -995,6 +995,70 @@ int ccgp_loglik_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
   return pull_status(h, {piece(s.loglik, out_loglik, B), piece(s.beta, out_beta, B)}, s.status, B, status, pin_max, true);
 } CCGP_GUARD_END(h)
 
+// ---- many training sets of one shape in one call (ccgp.h) -----------------------------------------------------------------
+// what ccgp_loglik_batch_sets and ccgp_logpost_sets refuse before anything is copied or launched
+static bool sets_args_ok(const double* Xs, const double* ys, const double* sigma2, int C, const int* set, int B) {
+  if (C < 1 || B < 1 || !Xs || !ys || !sigma2 || !set) return false;
+  for (int b = 0; b < B; ++b)
+    if (set[b] < 0 || set[b] >= C) return false;
+  return true;
+}
+
+// small_route_sets says Blocked: the rows of every set, in their order, through the single-set call
+static int sets_by_group(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C, int K,
+                         const double* params, const int* set, int B, int mean_mode, double tau2, double* out_loglik,
+                         double* out_beta, int* status) {
+  const int P = K + K * d;
+  std::vector<std::vector<int>> rows_of(C);
+  for (int b = 0; b < B; ++b) rows_of[set[b]].push_back(b);
+  int failed = 0;
+  std::vector<double> rows, ll, beta;
+  std::vector<int> st;
+  for (int c = 0; c < C; ++c) {
+    const std::vector<int>& idx = rows_of[c];
+    const int nb = (int)idx.size();
+    if (!nb) continue;
+    rows.resize((size_t)nb * P); ll.resize(nb); beta.resize(nb); st.resize(nb);
+    for (int j = 0; j < P; ++j)
+      for (int i = 0; i < nb; ++i) rows[i + (size_t)j * nb] = params[idx[i] + (size_t)j * B];
+    const int rc = ccgp_loglik_batch(h, Xs + (size_t)c * n * d, n, d, ys + (size_t)c * n, K, rows.data(), nb, sigma2[c],
+                                     mean_mode, tau2, ll.data(), beta.data(), st.data());
+    if (rc < 0) return rc;
+    failed += rc;
+    for (int i = 0; i < nb; ++i) {
+      out_loglik[idx[i]] = ll[i];
+      if (out_beta) out_beta[idx[i]] = beta[i];
+      if (status) status[idx[i]] = st[i];
+    }
+  }
+  return failed;
+}
+
+int ccgp_loglik_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                           int K, const double* params, const int* set, int B, int mean_mode, double tau2,
+                           double* out_loglik, double* out_beta, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || !params || !out_loglik || !sets_args_ok(Xs, ys, sigma2, C, set, B))
+    return fail(h, CCGP_EINVAL, "ccgp_loglik_batch_sets: bad argument");
+  if (int rc = check_mean_mode(h, mean_mode)) return rc;
+  if (small_route_sets(h->fam.id == 0, n, d, K) == Route::Blocked)
+    return sets_by_group(h, Xs, n, d, ys, sigma2, C, K, params, set, B, mean_mode, tau2, out_loglik, out_beta, status);
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  SetsStage s;
+  if (int rc = stage(h, [&](Layout& c) { s = sets_stage(c, n, d, P, C, B); })) return rc;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, B, K, d, &dv)) return frc;
+  if (int prc = push(h, s.inputs(Xs, ys, sigma2, params, set))) return prc;
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    launch_small_reg_loglik_sets(h->stream, s.Xs, n, d, s.ys, s.sigma2, s.set, dv, B, mean_mode, tau2, s.loglik, s.beta,
+                                 s.status);
+    CCGP_LAUNCH_CHECK();
+  }
+  return pull_status(h, s.results(out_loglik, out_beta), s.status, B, status);
+} CCGP_GUARD_END(h)
+
 int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
                            const double* params, int B, double sigma2, double* out_loglik,
                            double* out_beta, double* out_grad, int* status) try {
@@ -1194,6 +1258,36 @@ int ccgp_logpost_batch(ccgp_handle* h, const double* X, int n, int d, const doub
   if (rc < 0) return rc;
   for (int b = 0; b < B; ++b) {
     out_val[b] = ll[b] + ljac[b] + lpri[b];   // ccgp_logpost's order of additions; NaN where the factorisation failed: the reference's NA
+    if (out_beta) out_beta[b] = beta[b];
+    if (out_loglik) out_loglik[b] = ll[b];
+    if (status) status[b] = st[b];
+  }
+  return rc;
+} CCGP_GUARD_END(h)
+
+// ccgp_logpost_batch over many training sets: the same host arithmetic around ccgp_loglik_batch_sets
+int ccgp_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                      int prior_id, const double* theta_t, const int* set, int B, const double* prior_pars, double* out_val,
+                      double* out_beta, double* out_loglik, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (int rc = logpost_args(h, "ccgp_logpost_sets",
+                            n >= 1 && d >= 1 && d <= kMaxD && theta_t && out_val && sets_args_ok(Xs, ys, sigma2, C, set, B), d,
+                            prior_id, prior_pars))
+    return rc;
+  const int K = 2, P = K + K * d;
+  std::vector<double> rows((size_t)B * P), ljac(B), lpri(B), ll(B), beta(B);
+  std::vector<int> st(B);
+  for (int b = 0; b < B; ++b) {
+    double lj = 0.0, lp = 0.0;
+    logpost_terms(prior_id, d, theta_t + b, B, prior_pars, rows.data() + b, B, &lj, &lp);
+    ljac[b] = lj;
+    lpri[b] = lp;
+  }
+  const int rc = ccgp_loglik_batch_sets(h, Xs, n, d, ys, sigma2, C, K, rows.data(), set, B, CCGP_MEAN_PROFILE_BETA, 0.0,
+                                        ll.data(), beta.data(), st.data());
+  if (rc < 0) return rc;
+  for (int b = 0; b < B; ++b) {
+    out_val[b] = ll[b] + ljac[b] + lpri[b];   // ccgp_logpost_batch's order of additions
     if (out_beta) out_beta[b] = beta[b];
     if (out_loglik) out_loglik[b] = ll[b];
     if (status) status[b] = st[b];

@@ -206,6 +206,10 @@ void launch_small_reg_logdet_grad_designs(hipStream_t s, const double* Xs, int n
 void launch_small_reg_loglik(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv,
                              int B, double sigma2, int mean_mode, double tau2, double* loglik,
                              double* beta, int* status, bool grid16 = false);
+// the sets form of launch_small_reg_loglik (ccgp_loglik_batch_sets where small_route_sets says Reg): row b on set set[b]
+void launch_small_reg_loglik_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
+                                  const int* set, DrawView dv, int B, int mean_mode, double tau2, double* loglik,
+                                  double* beta, int* status);
 // leave-one-out mean / variance of every training point for B draws (ccgp_loo_batch where small_route_loo says Reg): one
 // workgroup per draw on the inverse instances' scheme; mean / var are B x n column-major, sigma2 is the scalar that
 // vf.sigma2_row (indexed by draw) replaces, vf.q (may be nullptr) receives Q per draw

@@ -50,7 +50,8 @@ CCGP_HD constexpr int lrect(int I, int k, int j) { return 32 * I * I + k * 8 + j
 CCGP_HD constexpr int ltri(int I, int j, int c) { return 32 * I * I + 64 * I + j * (j - 1) / 2 + c; }
 
 // ---- small_reg_kernel<G, NB, NE, ., INV> -----------------------------------------------------------------------------
-//   etab | xs[d][n] | 256 / G^2 matrices of per_mat words | xt[d][G NE] (NE > 1) | one xs[d][n] per matrix (per-design)
+//   etab | xs[d][n] | 256 / G^2 matrices of per_mat words | xt[d][G NE] (NE > 1) | one xs[d][n] per matrix (per-design, and
+//   the sets form on the 8 x 8 grid; on the 16 x 16 grid the sets form's one matrix reads its set's design from the shared xs)
 // (the inverse / gradient instances run one matrix per workgroup, so zmat's bump depends on nothing but the shape)
 // one matrix:  us[K][NP] | th[K][d] | w2[K] | colbuf[2][NP + G NE] | dvec[NP] | zb[2][NP] | slack[8] | tail
 //   tail, prediction (NE > 1): ut[K][G NE] | psum[3][G NE][G]
@@ -223,6 +224,27 @@ inline Route small_route(Op op, bool gauss, int n, int d, int K) {
 // own, not an Op: the check program switches over Op and holds each of its cells to the expression it replaced.
 inline Route small_route_loo(bool gauss, int n, int d, int K) {
   return gauss && small_reg_inverse_supported(n, d, K) ? Route::Reg : Route::Blocked;
+}
+// the sets form of the likelihood (ccgp_loglik_batch_sets, ccgp_logpost_sets): C training sets of one shape, row b on set
+// set[b].  Which grid a call of B rows takes: at most 64 rows are a latency problem and run four waves per matrix on the
+// 16 x 16 grid (one matrix per workgroup: the set's design lies in the shared xs slot); a larger call runs one wave per
+// matrix on the 8 x 8 grid with a design copy per matrix (RegCarve::xs_own) up to 13 x 13 blocks where that carve fits, and
+// stays on the 16 x 16 grid beyond.  The two grids give the same bits, so the choice is one of speed only.
+inline int small_reg_sets_grid(int n, int d, int K, int B) {
+  if (B <= 64 || n > 104) return 16;
+  return small_reg_fits8(n, d, K, true) ? 8 : 16;
+}
+// both carves a call may need: the 16 x 16 grid's for any B, and at n <= 64 the 8 x 8 grid's with four designs (above 64
+// a large call falls back to the 16 x 16 grid where the 8 x 8 carve does not fit)
+inline bool small_reg_sets_supported(int n, int d, int K) {
+  if (n > kSmallMaxN) return false;
+  if (!lds_fits(reg_lds_doubles(16, (n + 15) / 16, 1, false, false, n, d, K))) return false;
+  return n > 64 || small_reg_fits8(n, d, K, true);
+}
+// Reg: one launch of the sets instances.  Blocked: the host groups the rows by set and runs each group through the
+// single-set call (whatever route that call takes), which covers n > 128 and the Matern and spline families.
+inline Route small_route_sets(bool gauss, int n, int d, int K) {
+  return gauss && small_reg_sets_supported(n, d, K) ? Route::Reg : Route::Blocked;
 }
 
 }  // namespace ccgp

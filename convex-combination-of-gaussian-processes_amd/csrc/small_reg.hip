@@ -66,6 +66,10 @@ struct RegArgs {
   int n_fixed;         // INV = 3: rows below n_fixed are the fixed batch (D.old, BSQ:920-948): no gradient
   double* s2hat;       // PROF instantiations: the draw's own sigma2 = q / (n sum w^2) (sigma2.MLE, D1:411-415); `sigma2` is not read
   VarForm vf;          // prediction (NE > 1, FAC): per-draw sigma2 and Q indexed by the global draw, the variance form
+  // sets form (SETS instantiations, ccgp_loglik_batch_sets): evaluation b belongs to training set set[b] and reads its design at
+  // X + set[b] n d, its right-hand side at y + set[b] n and its sigma2 at sigma2_set[set[b]]; `sigma2` is not read
+  const int* set;
+  const double* sigma2_set;
 };
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
@@ -121,12 +125,17 @@ __device__ __forceinline__ void mat_sync() {
 // reads that value instead of the caller's -- by the envelope theorem the closed form at (beta_hat, sigma2_hat) IS the
 // gradient of the profiled likelihood.  A template parameter, not a branch: the n <= 64 instances sit at the edge of their
 // register budget (CCGP_SMALL_OCC_G8 above) and the existing instantiations compile from unchanged code.
-template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false>
+// SETS: many training sets of one shape in one launch (the lockstep fit of a simulation study): the evaluation's design,
+// right-hand side and sigma2 come from its set, everything after the loads is the code of the single-set instances in the
+// same order, hence their bits.  A template parameter for the same reason as PROF.  G = 16 has one matrix per workgroup, so
+// the set's design goes into the shared xs slot; G = 8 keeps one copy per matrix where the per-design form keeps it.
+template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
   static_assert(!FAC || (NE == 1 && !FULL && !INV), "the factor is kept by the plain likelihood instantiation");
   static_assert(!PROF || ((NE == 1 || INV == 2) && INV != 1 && INV != 3 && !FAC), "sigma2 is concentrated out of the likelihood and of its gradient only");
+  static_assert(!SETS || (NE == 1 && !INV && !FAC && !PROF), "the sets form exists for the plain likelihood only");
   constexpr int TPM = G * G;       // threads per matrix
   constexpr int MPW = 256 / TPM;   // matrices per workgroup
   constexpr int NP = G * NB;       // padded order
@@ -162,7 +171,15 @@ void small_reg_kernel(RegArgs a) {
 
   const int pb = a.shared_params ? 0 : b;
   if (CCGP_SMALL_EXP_TABLE) exp_table_load(etab, tid, 256);
-  if (a.x_stride == 0) {
+  int st = 0;   // SETS: this evaluation's training set
+  if constexpr (SETS) {
+    // a matrix's threads are whole waves on both grids: the set index is wave-uniform, and saying so keeps it -- and the
+    // addresses formed from it -- in scalar registers across the generation phase
+    st = __builtin_amdgcn_readfirstlane(a.set[b]);
+    const double* Xb = a.X + (size_t)st * n * d;
+    if constexpr (MPW > 1) xs = smem + cv.xs_own + (size_t)sub * d * n;
+    for (int e = lt; e < n * d; e += TPM) xs[e] = Xb[e];
+  } else if (a.x_stride == 0) {
     for (int e = tid; e < n * d; e += 256) xs[e] = a.X[e];
   } else {
     // per-evaluation designs: each matrix keeps its own copy right behind the shared slot
@@ -199,7 +216,9 @@ void small_reg_kernel(RegArgs a) {
 
   double sw = 0.0;
   for (int c = 0; c < K; ++c) sw += w2[c];
-  const double cs = a.sigma2 * sw;
+  double sigma2 = a.sigma2;
+  if constexpr (SETS) sigma2 = a.sigma2_set[st];
+  const double cs = sigma2 * sw;
   // (p^2 R1 + (1-p)^2 R2) / (p^2 + (1-p)^2) (HX:412) as a multiplication by the reciprocal: one
   // fp64 division costs ~30 instructions and this kernel is instruction-issue bound (<= 1 ulp apart)
   const double post_scale = (a.mode == 1 ? cs : 1.0) / sw;
@@ -288,7 +307,7 @@ void small_reg_kernel(RegArgs a) {
       const int ridx = ty + G * e;
       double v = 0.0;
       if (FULL || c < n) {
-        if (ridx == 0) v = a.y[c];
+        if (ridx == 0) v = SETS ? a.y[(size_t)st * n + c] : a.y[c];
         else if (ridx == 1) v = 1.0;
         else if (INV) v = (ridx - 2 == c) ? 1.0 : 0.0;   // identity rows: row 2 + t = e_t'
         else if (NE > 1 && t0 + ridx - 2 < a.m) {
@@ -761,7 +780,9 @@ RegArgs reg_args(const double* X, int n, int d, const double* y, DrawView dv) {
 template <int G, int NB, int NE = 1>
 void launch_one(hipStream_t s, const RegArgs& a) {
   constexpr int MPW = 256 / (G * G);
-  const size_t lds = sizeof(double) * reg_lds_doubles(G, NB, NE, false, a.x_stride != 0, a.n, a.d, a.K);
+  // the sets form keeps a design per matrix where a workgroup holds several matrices (G = 8), as the per-design form does
+  const bool own_design = a.set ? MPW > 1 : a.x_stride != 0;
+  const size_t lds = sizeof(double) * reg_lds_doubles(G, NB, NE, false, own_design, a.n, a.d, a.K);
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
     raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false>, "small_reg_kernel");
@@ -769,7 +790,15 @@ void launch_one(hipStream_t s, const RegArgs& a) {
   });
   void (*kernel)(RegArgs) = small_reg_kernel<G, NB, NE, false>;
   if constexpr (NE == 1) {
-    if (a.fac) {   // the likelihood instantiation that keeps its factor for site_solve_kernel
+    if (a.set) {   // the sets form of the same two instances (general, FULL): the FULL one where the single-set call takes it
+      static unsigned long long sets_mask = 0;
+      once_per_device(sets_mask, [] {
+        raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false, 0, false, false, true>, "small_reg_kernel<sets>");
+        raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, true, 0, false, false, true>, "small_reg_kernel<full, sets>");
+      });
+      if (a.n == G * NB) kernel = small_reg_kernel<G, NB, NE, true, 0, false, false, true>;
+      else kernel = small_reg_kernel<G, NB, NE, false, 0, false, false, true>;
+    } else if (a.fac) {   // the likelihood instantiation that keeps its factor for site_solve_kernel
       static unsigned long long fac_mask = 0;
       once_per_device(fac_mask, [] { raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false, 0, true>, "small_reg_kernel<fac>"); });
       kernel = small_reg_kernel<G, NB, NE, false, 0, true>;
@@ -1109,7 +1138,30 @@ static void dispatch(hipStream_t s, const RegArgs& a) {
   else pick<(NE == 1 ? 1 : 5), 8>((n + 15) / 16, [&](auto nb) { launch_one<16, decltype(nb)::value, NE>(s, a); });
 }
 
+// The sets form's grid (small_reg_sets_grid, small_layout.h): a lockstep step of a few dozen matrices is the latency case of
+// dispatch() above and takes four waves per matrix; a larger call takes one wave per matrix up to 13 x 13 blocks.
+static void dispatch_sets(hipStream_t s, const RegArgs& a) {
+  const int n = a.n;
+  if (small_reg_sets_grid(n, a.d, a.K, a.B) == 8) {
+    if (n <= 64) pick<1, 8>((n + 7) / 8, [&](auto nb) { launch_one<8, decltype(nb)::value, 1>(s, a); });
+    else pick<9, 13>((n + 7) / 8, [&](auto nb) { launch_one<8, decltype(nb)::value, 1>(s, a); });
+    return;
+  }
+  pick<1, 8>((n + 15) / 16, [&](auto nb) { launch_one<16, decltype(nb)::value, 1>(s, a); });
+}
+
 }  // namespace
+
+// ccgp_loglik_batch_sets where small_route_sets says Reg: the B rows of dv, row b on training set set[b] of the C sets at
+// Xs (C blocks of n x d, column-major each), ys (C blocks of n) and sigma2 (C values)
+void launch_small_reg_loglik_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
+                                  const int* set, DrawView dv, int B, int mean_mode, double tau2, double* loglik,
+                                  double* beta, int* status) {
+  RegArgs a = reg_args(Xs, n, d, ys, dv);
+  a.B = B; a.mode = mean_mode; a.tau2 = tau2; a.set = set; a.sigma2_set = sigma2;
+  a.loglik = loglik; a.beta = beta; a.status = status;
+  dispatch_sets(s, a);
+}
 
 void launch_small_reg_inverse(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int draw,
                               double sigma2, double* Rinv, double* loglik, double* beta, int* status) {

@@ -167,6 +167,97 @@ def geweke_window(samp, k, samp_size):
 
 
 # ----------------------------------------------------------------------------- Metro / factors.frame
+class _Chain:
+    """The state of one chain of HX:483-540 and everything about it that does not evaluate: the random numbers of a proposal
+    (draw_pair), what a proposal does given its value (consume), the tree of candidates the chain can reach over its next m
+    proposals (tree) and the walk through it once the values are known (walk).  Metro drives one of these with one
+    evaluator call per step, Metro_sets many of them with one call per step for all: same code, same chain."""
+
+    def __init__(self, est, l0, N, samp_size, batch_size, alpha, rng, max_proposals):
+        self.est = est
+        self.cov = math.sqrt(2.0) * est["var"]
+        p = est["mode"].size
+        self.zero = np.zeros(p)
+        self.samp = np.zeros((N, p))
+        self.betas = np.zeros(N)
+        self.N, self.samp_size, self.batch_size, self.alpha, self.rng = N, samp_size, batch_size, alpha, rng
+        self.theta, self.l, self.k, self.pv, self.proposals, self.batches = est["mode"].copy(), l0, 0, 0.0, 0, 0
+        self.max_proposals = max_proposals or 200 * N
+        self.state0 = rng.bit_generator.state
+        self.pending = []                     # pre-drawn (u, e) pairs not yet consumed
+
+    def draw_pair(self):
+        # same stream as `u <- runif(1); rmnorm(1, theta.old, cov)` (HX:507-511): the proposal is
+        # theta.old + e with e ~ N(0, cov), and adding the mean afterwards is what numpy does too
+        u = self.rng.random()
+        return u, self.rng.multivariate_normal(self.zero, self.cov)
+
+    def running(self):
+        return self.k < self.N and self.pv < self.alpha and self.proposals < self.max_proposals
+
+    def consume(self, u, cand, l_cand, b_cand):
+        """One proposal of HX:505-535 given its value.  Returns True when it was accepted."""
+        from scipy.stats import norm
+
+        self.proposals += 1
+        if not (math.isfinite(l_cand) and (l_cand - self.l) > math.log(u)):
+            return False
+        k = self.k
+        self.samp[k] = cand
+        self.betas[k] = b_cand
+        self.theta, self.l, self.k = cand, l_cand, k + 1
+        k += 1
+        if k >= self.samp_size and k % self.batch_size == 0:
+            try:   # first parameter's chain over the last samp_size accepted draws (HX:530, GV:518)
+                z = geweke_z(geweke_window(self.samp, k, self.samp_size))
+                self.pv = float(2.0 * (1.0 - norm.cdf(abs(z))))
+            except Exception:
+                self.pv = 0.0
+        return True
+
+    def propose(self):
+        """The sequential step: one (u, candidate)."""
+        u, e = self.draw_pair()
+        return u, self.theta + e
+
+    def tree(self, m):
+        """The 2^m - 1 candidates reachable over the next m proposals, level by level."""
+        while len(self.pending) < m:
+            self.pending.append(self.draw_pair())
+        # level t holds the 2^t candidates reachable after t proposals; history bits: 1 = accepted
+        states, levels = np.asarray(self.theta, dtype=float)[None, :], []
+        for t in range(m):
+            cands = states + self.pending[t][1]              # same additions as the sequential chain: same bits
+            levels.append(cands)
+            states = np.stack([states, cands], axis=1).reshape(2 * states.shape[0], -1)   # (s0, c0, s1, c1, ...)
+        return levels
+
+    def walk(self, levels, l_all, b_all):
+        """The accept / reject walk over a tree whose values (level after level) are l_all, b_all."""
+        idx, off, used = 0, 0, 0
+        for t in range(len(levels)):
+            if not self.running():
+                break
+            acc = self.consume(self.pending[t][0], levels[t][idx], float(l_all[off + idx]), float(b_all[off + idx]))
+            used += 1
+            off += 1 << t
+            idx = 2 * idx + (1 if acc else 0)
+        self.pending = self.pending[used:]
+
+    def rewind(self):
+        """After speculation: leave the generator where the sequential chain leaves it, exactly `proposals` pairs drawn."""
+        self.rng.bit_generator.state = self.state0
+        for _ in range(self.proposals):
+            self.draw_pair()
+
+    def result(self, who="Metro"):
+        k = self.k
+        if k < self.samp_size:
+            raise RuntimeError("%s: only %d accepted draws after %d proposals" % (who, k, self.proposals))
+        return dict(sample=self.samp[k - self.samp_size:k].copy(), beta=self.betas[k - self.samp_size:k].copy(), accepted=k,
+                    proposals=self.proposals, laplace=self.est, geweke_p=self.pv, device_batches=self.batches)
+
+
 def Metro(gp, start, N, samp_size, batch_size, alpha, D_train, sigma2, y, theta1_pars=None,
           theta2_pars=None, rng=None, max_proposals=None, speculate=0, logpost_fn=None):
     """HX:483-540 (and its per-script copies).  Returns dict(sample[samp_size, p], beta[samp_size],
@@ -180,8 +271,6 @@ def Metro(gp, start, N, samp_size, batch_size, alpha, D_train, sigma2, y, theta1
     bit-for-bit the sequential one; only the number of device round trips drops m-fold
     (the sequential caller on the batched path).  `logpost_fn(rows) -> (val, beta)`
     replaces the device evaluator (tests)."""
-    from scipy.stats import norm
-
     rng = np.random.default_rng(rng)
     pars = None
     if logpost_fn is None:
@@ -195,82 +284,191 @@ def Metro(gp, start, N, samp_size, batch_size, alpha, D_train, sigma2, y, theta1
         return logpost_fn(rows)[0]
 
     est = laplace(val_batch, start)
-    mu, V = est["mode"], est["var"]
-    cov = math.sqrt(2.0) * V
-    p = mu.size
-    zero = np.zeros(p)
-    samp = np.zeros((N, p))
-    betas = np.zeros(N)
-    st = dict(theta=mu.copy(), l=float(logpost_fn(mu[None])[0][0]), k=0, pv=0.0, proposals=0, batches=0)
-    max_proposals = max_proposals or 200 * N
-
-    def draw_pair():
-        # same stream as `u <- runif(1); rmnorm(1, theta.old, cov)` (HX:507-511): the proposal is
-        # theta.old + e with e ~ N(0, cov), and adding the mean afterwards is what numpy does too
-        u = rng.random()
-        return u, rng.multivariate_normal(zero, cov)
-
-    def running():
-        return st["k"] < N and st["pv"] < alpha and st["proposals"] < max_proposals
-
-    def consume(u, cand, l_cand, b_cand):
-        """One proposal of HX:505-535 given its value.  Returns True when it was accepted."""
-        st["proposals"] += 1
-        if not (math.isfinite(l_cand) and (l_cand - st["l"]) > math.log(u)):
-            return False
-        k = st["k"]
-        samp[k] = cand
-        betas[k] = b_cand
-        st["theta"], st["l"], st["k"] = cand, l_cand, k + 1
-        k += 1
-        if k >= samp_size and k % batch_size == 0:
-            try:   # first parameter's chain over the last samp_size accepted draws (HX:530, GV:518)
-                z = geweke_z(geweke_window(samp, k, samp_size))
-                st["pv"] = float(2.0 * (1.0 - norm.cdf(abs(z))))
-            except Exception:
-                st["pv"] = 0.0
-        return True
-
+    ch = _Chain(est, float(logpost_fn(est["mode"][None])[0][0]), N, samp_size, batch_size, alpha, rng, max_proposals)
     m = int(speculate)
     if m <= 1:
-        while running():
-            u, e = draw_pair()
-            cand = st["theta"] + e
+        while ch.running():
+            u, cand = ch.propose()
             l_cand, b_cand = logpost_fn(cand[None])
-            st["batches"] += 1
-            consume(u, cand, float(l_cand[0]), float(b_cand[0]))
+            ch.batches += 1
+            ch.consume(u, cand, float(l_cand[0]), float(b_cand[0]))
     else:
-        state0 = rng.bit_generator.state
-        pending = []                      # pre-drawn (u, e) pairs not yet consumed
-        while running():
-            while len(pending) < m:
-                pending.append(draw_pair())
-            # level t holds the 2^t candidates reachable after t proposals; history bits: 1 = accepted
-            states, levels = np.asarray(st["theta"], dtype=float)[None, :], []
-            for t in range(m):
-                cands = states + pending[t][1]              # same additions as the sequential chain: same bits
-                levels.append(cands)
-                states = np.stack([states, cands], axis=1).reshape(2 * states.shape[0], -1)   # (s0, c0, s1, c1, ...)
+        while ch.running():
+            levels = ch.tree(m)
             l_all, b_all = logpost_fn(np.concatenate(levels, axis=0))
-            st["batches"] += 1
-            idx, off, used = 0, 0, 0
-            for t in range(m):
-                if not running():
-                    break
-                acc = consume(pending[t][0], levels[t][idx], float(l_all[off + idx]), float(b_all[off + idx]))
-                used += 1
-                off += 1 << t
-                idx = 2 * idx + (1 if acc else 0)
-            pending = pending[used:]
-        # leave the generator where the sequential chain leaves it: exactly `proposals` pairs drawn
-        rng.bit_generator.state = state0
-        for _ in range(st["proposals"]):
-            draw_pair()
-    k = st["k"]
-    if k < samp_size:
-        raise RuntimeError("Metro: only %d accepted draws after %d proposals" % (k, st["proposals"]))
-    return dict(sample=samp[k - samp_size:k].copy(), beta=betas[k - samp_size:k].copy(), accepted=k,
-                proposals=st["proposals"], laplace=est, geweke_p=st["pv"], device_batches=st["batches"])
+            ch.batches += 1
+            ch.walk(levels, l_all, b_all)
+        ch.rewind()
+    return ch.result()
+
+
+def logpost_sets_batch(gp, D_trains, theta_t, ys, sigma2s, set_of, prior_pars=None):
+    """logpost_batch over many training sets of one shape: row b of theta_t on set set_of[b], ONE device call
+    (ccgp_logpost_sets) -> (val, beta), each value with the bits logpost_batch gives it on its set alone."""
+    val, beta, _, _ = gp.h.logpost_sets(D_trains, ys, sigma2s, gp.cfg["prior"], theta_t, set_of, prior_pars)
+    return val, beta
+
+
+def laplace_sets(fn_sets, starts, hess_step=1e-3, maxiter=2000):
+    """laplace for C sets in lockstep.  `fn_sets(rows, set_of) -> values` evaluates row b on set set_of[b]; starts is [C, p].
+    The search is a Nelder-Mead written here (coefficients 1, 2, 1/2, 1/2; the initial simplex and the stop rule -- xatol
+    1e-6, fatol 1e-9 -- are those of the search laplace runs): per iteration the reflection, expansion and both contraction
+    points of every unfinished set go out as ONE call, the shrink steps of the sets that need one as a second; then the
+    central-difference Hessian points of all sets go out as one call.  Every decision of a set reads that set's values
+    only, so its result has the same bits alone and among others.  Returns one dict per set with laplace's keys, plus the
+    iterations and evaluations the set took."""
+    starts = np.atleast_2d(np.asarray(starts, dtype=np.float64))
+    C, p = starts.shape
+    xatol, fatol = 1e-6, 1e-9
+
+    def neg(rows, set_of):
+        v = np.asarray(fn_sets(np.asarray(rows), np.asarray(set_of, dtype=np.int64)), dtype=np.float64)
+        return np.where(np.isfinite(v), -v, 1e300)
+
+    sim = np.empty((C, p + 1, p))
+    for c in range(C):
+        sim[c, 0] = starts[c]
+        for k in range(p):
+            x = starts[c].copy()
+            x[k] = (1.0 + 0.05) * x[k] if x[k] != 0.0 else 0.00025
+            sim[c, k + 1] = x
+    fsim = neg(sim.reshape(-1, p), np.repeat(np.arange(C), p + 1)).reshape(C, p + 1)
+    iters, evals, done = np.zeros(C, dtype=int), np.full(C, p + 1), np.zeros(C, dtype=bool)
+    converged = np.zeros(C, dtype=bool)
+    for c in range(C):
+        o = np.argsort(fsim[c], kind="stable")
+        sim[c], fsim[c] = sim[c][o], fsim[c][o]
+    while True:
+        for c in range(C):
+            if done[c]:
+                continue
+            if np.max(np.abs(sim[c, 1:] - sim[c, 0])) <= xatol and np.max(np.abs(fsim[c, 0] - fsim[c, 1:])) <= fatol:
+                done[c] = converged[c] = True
+            elif iters[c] >= maxiter or evals[c] >= maxiter:
+                done[c] = True
+        live = [c for c in range(C) if not done[c]]
+        if not live:
+            break
+        rows = []
+        for c in live:
+            xbar, worst = sim[c, :-1].sum(axis=0) / p, sim[c, -1]
+            rows += [2.0 * xbar - worst, 3.0 * xbar - 2.0 * worst, 1.5 * xbar - 0.5 * worst, 0.5 * xbar + 0.5 * worst]
+        f = neg(rows, np.repeat(live, 4)).reshape(-1, 4)
+        shrink = []
+        for j, c in enumerate(live):
+            (xr, xe, xoc, xic), (fr, fe, foc, fic) = rows[4 * j:4 * j + 4], f[j]
+            iters[c] += 1
+            evals[c] += 4
+            if fr < fsim[c, 0]:
+                sim[c, -1], fsim[c, -1] = (xe, fe) if fe < fr else (xr, fr)
+            elif fr < fsim[c, -2]:
+                sim[c, -1], fsim[c, -1] = xr, fr
+            elif fr < fsim[c, -1] and foc <= fr:
+                sim[c, -1], fsim[c, -1] = xoc, foc
+            elif fr >= fsim[c, -1] and fic < fsim[c, -1]:
+                sim[c, -1], fsim[c, -1] = xic, fic
+            else:
+                shrink.append(c)
+        if shrink:
+            for c in shrink:
+                sim[c, 1:] = sim[c, 0] + 0.5 * (sim[c, 1:] - sim[c, 0])
+            fs = neg(np.concatenate([sim[c, 1:] for c in shrink]), np.repeat(shrink, p)).reshape(-1, p)
+            for j, c in enumerate(shrink):
+                fsim[c, 1:] = fs[j]
+                evals[c] += p
+        for c in live:
+            o = np.argsort(fsim[c], kind="stable")
+            sim[c], fsim[c] = sim[c][o], fsim[c][o]
+    pts, idx = [], []
+    for c in range(C):
+        mode = sim[c, 0]
+        for i in range(p):
+            for j in range(i, p):
+                for si, sj in ((1, 1), (1, -1), (-1, 1), (-1, -1)):
+                    x = mode.copy()
+                    x[i] += si * hess_step
+                    x[j] += sj * hess_step
+                    pts.append(x)
+                if c == 0:
+                    idx.append((i, j))
+    per = 4 * len(idx)
+    vals = np.asarray(fn_sets(np.asarray(pts), np.repeat(np.arange(C), per)), dtype=np.float64).reshape(C, -1, 4)
+    out = []
+    for c in range(C):
+        H = np.zeros((p, p))
+        for (i, j), v in zip(idx, vals[c]):
+            H[i, j] = H[j, i] = (v[0] - v[1] - v[2] + v[3]) / (4.0 * hess_step ** 2)
+        try:
+            var = -np.linalg.inv(H)
+            np.linalg.cholesky(var)
+        except np.linalg.LinAlgError:
+            var = np.diag(1.0 / np.maximum(-np.diag(H), 1e-6))   # not negative definite: fall back to its diagonal
+        out.append(dict(mode=sim[c, 0].copy(), var=var, converged=bool(converged[c]), value=-float(fsim[c, 0]),
+                        iterations=int(iters[c]), evaluations=int(evals[c])))
+    return out
+
+
+def Metro_sets(gp, starts, N, samp_size, batch_size, alpha, D_trains, sigma2s, ys, theta1_pars=None, theta2_pars=None,
+               rngs=None, max_proposals=None, speculate=0, laplace=None, logpost_sets_fn=None):
+    """Metro for C training sets of one shape in lockstep: one generator per chain (rngs[c]) and ONE device call per step
+    that carries the candidates of every chain still running -- C (2^m - 1) of them with speculate = m.  A chain that stops
+    (Geweke, N, max_proposals) leaves the batch.  Each chain is Metro's chain for its set and generator, bit for bit, and
+    leaves its generator where Metro leaves it.  laplace: ready estimates, one per set (laplace's dicts); without them
+    laplace_sets runs from starts [C, p].  `logpost_sets_fn(rows, set_of) -> (val, beta)` replaces the device evaluator.
+    Returns dict(chains: one Metro result per set -- its device_batches counts the steps the chain took part in --,
+    device_batches: the calls this function made for the chains, laplace_calls: those of the Laplace stage)."""
+    C = len(D_trains)
+    rngs = [np.random.default_rng(r) for r in (rngs if rngs is not None else [None] * C)]
+    if len(rngs) != C:
+        raise ValueError("Metro_sets takes one generator per set")
+    calls = dict(n=0)
+    if logpost_sets_fn is None:
+        pars = None
+        if gp.script in ("HX", "ADV"):
+            pars = (*np.ravel(theta1_pars)[:2], *np.ravel(theta2_pars)[:2])
+        Xs = np.stack([np.asarray(D, dtype=np.float64) for D in D_trains])
+        Y = np.stack([np.asarray(y, dtype=np.float64).ravel() for y in ys])
+
+        def logpost_sets_fn(rows, set_of):
+            return logpost_sets_batch(gp, Xs, rows, Y, sigma2s, set_of, pars)
+
+    def evaluate(rows, set_of):
+        calls["n"] += 1
+        return logpost_sets_fn(np.asarray(rows), np.asarray(set_of, dtype=np.int64))
+
+    if laplace is None:
+        ests = laplace_sets(lambda rows, set_of: evaluate(rows, set_of)[0], starts)
+    else:
+        ests = list(laplace)
+        if len(ests) != C:
+            raise ValueError("Metro_sets takes one Laplace estimate per set")
+    laplace_calls, calls["n"] = calls["n"], 0
+    l0 = evaluate(np.stack([e["mode"] for e in ests]), np.arange(C))[0]
+    chains = [_Chain(ests[c], float(l0[c]), N, samp_size, batch_size, alpha, rngs[c], max_proposals) for c in range(C)]
+    calls["n"] = 0
+    m = int(speculate)
+    while True:
+        live = [c for c in range(C) if chains[c].running()]
+        if not live:
+            break
+        if m <= 1:
+            pairs = [chains[c].propose() for c in live]
+            l_all, b_all = evaluate(np.stack([cand for _, cand in pairs]), live)
+            for j, c in enumerate(live):
+                chains[c].batches += 1
+                chains[c].consume(pairs[j][0], pairs[j][1], float(l_all[j]), float(b_all[j]))
+        else:
+            trees = [chains[c].tree(m) for c in live]
+            per = (1 << m) - 1
+            l_all, b_all = evaluate(np.concatenate([np.concatenate(t, axis=0) for t in trees], axis=0), np.repeat(live, per))
+            for j, c in enumerate(live):
+                chains[c].batches += 1
+                chains[c].walk(trees[j], l_all[j * per:(j + 1) * per], b_all[j * per:(j + 1) * per])
+    if m > 1:
+        for ch in chains:
+            ch.rewind()
+    return dict(chains=[ch.result("Metro_sets (set %d)" % c) for c, ch in enumerate(chains)], device_batches=calls["n"],
+                laplace_calls=laplace_calls)
 
 
 def factors_frame(gp, start, N, samp_size, batch_size, alpha_geweke, D_train, sigma2, y_train,
@@ -661,3 +859,116 @@ def comparison_summary(table):
             out["rmspe_%s" % c] = float(np.sqrt(np.mean((y - yh) ** 2)))
             out["coverage_%s" % c] = float(np.mean((y >= lo) & (y <= hi)))
     return out
+
+
+# ----------------------------------------------------------------------------- the simulation study (GV:689-762)
+def group_sets(sets):
+    """The indices of `sets` (tuples whose first entry is the training design) grouped by the design's shape (n, d), in
+    order of first appearance: the sets of a group can be fitted in lockstep."""
+    groups = {}
+    for i, s in enumerate(sets):
+        D = np.asarray(s[0])
+        if D.ndim != 2:
+            raise ValueError("set %d: the training design must be n x d" % i)
+        groups.setdefault(D.shape, []).append(i)
+    return groups
+
+
+def stack_tables(tables):
+    """The rows of several compare_GP tables under one another: every per-test-point column they all hold."""
+    first = tables[0]
+    cols = [k for k in first if isinstance(first[k], np.ndarray) and first[k].ndim == 1 and first[k].size == first["y_true"].size]
+    cols = [k for k in cols if all(k in t for t in tables)]
+    return {k: np.concatenate([np.asarray(t[k], dtype=np.float64) for t in tables]) for k in cols}
+
+
+def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size=None, start=None, sigma2s=None,
+          theta1_pars=None, theta2_pars=None, rngs=None, max_proposals=None, speculate=0, laplace=None, cgp=False,
+          single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None):
+    """The reference's simulation study (GV:689-762 declares nine training sets and fits one): every set of `sets` -- a list
+    of (D_train, y_train, D_test, y_test) -- fitted and compared, the sets of one shape (n, d) in lockstep.  Per group:
+    sigma2 per set from ordinary_kriging_fit (or sigma2s[i] as given), then laplace_sets and Metro_sets with one generator
+    per set (rngs[i]; one device call per step for all the group's chains).  Per set: the retained draws (the last
+    net_samp_size of the chain, factors_frame's), compare_GP(..., exact=True, cgp=cgp, single=single) and
+    comparison_summary.  laplace: ready estimates per set.  start: one transformed start for all sets ((1, 1, 0) as GV:692
+    by default, a zero appended where the script has a fourth parameter), or one per set.  out_dir: one results table per
+    set through write_results_table (`results_<i>.txt`, i from 1; input_names default x1 ..).  logpost_sets_fn(group
+    indices) -> evaluator and compare_fn replace the device (tests).
+    Returns dict(tables, summaries, pooled: comparison_summary of the stacked tables, sigma2, draws, beta, chains,
+    groups: {(n, d): indices}, calls and seconds: device calls and wall time of the sigma2, laplace, metro and predict
+    parts)."""
+    import time
+
+    sets = list(sets)
+    if not sets:
+        raise ValueError("study: no sets")
+    C = len(sets)
+    groups = group_sets(sets)
+    net = net_samp_size or samp_size
+    rngs = list(rngs) if rngs is not None else [None] * C
+    if len(rngs) != C or (sigma2s is not None and len(sigma2s) != C) or (laplace is not None and len(laplace) != C):
+        raise ValueError("study: rngs, sigma2s and laplace hold one entry per set")
+    npar = gp.cfg["npar"] if hasattr(gp, "cfg") else 3
+    if start is None:
+        start = np.concatenate([[1.0, 1.0, 0.0], np.zeros(npar - 3)])
+    starts = np.broadcast_to(np.asarray(start, dtype=np.float64), (C, np.shape(start)[-1]))
+    compare_fn = compare_fn or compare_GP
+    calls = dict(sigma2=0, laplace=0, metro=0, predict=0)
+    secs = dict(sigma2=0.0, laplace=0.0, metro=0.0, predict=0.0)
+    s2 = [None] * C if sigma2s is None else [float(v) for v in sigma2s]
+    chains, tables, summaries = [None] * C, [None] * C, [None] * C
+    t0 = time.perf_counter()
+    for i in range(C):
+        if s2[i] is None:
+            okf = ordinary_kriging_fit(getattr(gp.h, "_handle", gp.h), sets[i][0], sets[i][1])
+            s2[i] = okf["sigma2"]
+            calls["sigma2"] += okf["calls"]
+    secs["sigma2"] = time.perf_counter() - t0
+    for shape, idx in groups.items():
+        D_trains = [np.asarray(sets[i][0], dtype=np.float64) for i in idx]
+        ys = [np.asarray(sets[i][1], dtype=np.float64).ravel() for i in idx]
+        g_s2 = [s2[i] for i in idx]
+        fn = logpost_sets_fn(idx) if logpost_sets_fn is not None else None
+        if fn is None:
+            pars = None
+            if gp.script in ("HX", "ADV"):
+                pars = (*np.ravel(theta1_pars)[:2], *np.ravel(theta2_pars)[:2])
+            Xs, Y = np.stack(D_trains), np.stack(ys)
+
+            def fn(rows, set_of, Xs=Xs, Y=Y, g_s2=g_s2, pars=pars):
+                return logpost_sets_batch(gp, Xs, rows, Y, g_s2, set_of, pars)
+        count = dict(n=0)
+
+        def counted(rows, set_of, fn=fn, count=count):
+            count["n"] += 1
+            return fn(rows, set_of)
+
+        t0 = time.perf_counter()
+        ests = [laplace[i] for i in idx] if laplace is not None else \
+            laplace_sets(lambda rows, set_of: counted(rows, set_of)[0], starts[idx])
+        secs["laplace"] += time.perf_counter() - t0
+        calls["laplace"] += count["n"]
+        t0 = time.perf_counter()
+        r = Metro_sets(gp, None, N, samp_size, batch_size, alpha_geweke, D_trains, g_s2, ys, theta1_pars, theta2_pars,
+                       [rngs[i] for i in idx], max_proposals, speculate, laplace=ests, logpost_sets_fn=fn)
+        secs["metro"] += time.perf_counter() - t0
+        calls["metro"] += r["device_batches"] + 1   # the chains' starting values are one call
+        for j, i in enumerate(idx):
+            chains[i] = r["chains"][j]
+    keep = slice(samp_size - net, samp_size)
+    draws = [transformed_to_draws(ch["sample"][keep]) for ch in chains]
+    betas = [ch["beta"][keep] for ch in chains]
+    t0 = time.perf_counter()
+    for i, (D_train, y_train, D_test, y_test) in enumerate(sets):
+        tables[i] = compare_fn(gp, D_test, alpha, y_test, draws[i], D_train, s2[i], y_train, exact=True, cgp=cgp, single=single)
+        summaries[i] = comparison_summary(tables[i])
+        calls["predict"] += 1
+    secs["predict"] = time.perf_counter() - t0
+    if out_dir is not None:
+        import os
+        os.makedirs(out_dir, exist_ok=True)
+        for i, (D_train, _, D_test, _) in enumerate(sets):
+            names = input_names or ["x%d" % (k + 1) for k in range(np.asarray(D_test).shape[1])]
+            write_results_table(os.path.join(out_dir, "results_%d.txt" % (i + 1)), tables[i], D_test, names)
+    return dict(tables=tables, summaries=summaries, pooled=comparison_summary(stack_tables(tables)), sigma2=s2, draws=draws,
+                beta=betas, chains=chains, groups={k: list(v) for k, v in groups.items()}, calls=calls, seconds=secs)

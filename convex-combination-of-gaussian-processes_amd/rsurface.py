@@ -132,6 +132,21 @@ class CombinedGP:
             out["like"] = float(np.exp(r["loglik"]))  # ADV:470
         return out
 
+    def logpost_sets(self, D_trains, theta, ys, sigma2s, set_of, theta1_pars=None, theta2_pars=None):
+        """logpost(...)$val and $beta of row b of theta on training set set_of[b] of the C sets (D_trains [C, n, d], ys
+        [C, n], sigma2s [C]) in ONE device call: the evaluator of a study's lockstep fit (fit.laplace_sets, fit.Metro_sets).
+        Each row has the bits the per-set batch call gives it.  Returns dict(val[B], beta[B], status[B])."""
+        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        if theta.shape[1] != self.cfg["npar"]:
+            raise ValueError("%s logpost takes %d transformed parameters" % (self.script, self.cfg["npar"]))
+        pars = None
+        if self.cfg["prior"] == api.PRIOR_INVGAMMA:
+            if theta1_pars is None or theta2_pars is None:
+                raise TypeError("%s logpost needs theta1.pars and theta2.pars" % self.script)
+            pars = np.concatenate([np.ravel(theta1_pars)[:2], np.ravel(theta2_pars)[:2]])
+        val, beta, _, st = self.h.logpost_sets(D_trains, ys, sigma2s, self.cfg["prior"], theta, set_of, pars)
+        return dict(val=val, beta=beta, status=st)
+
     # ------------------------------------------------------------------ a9
     def likeli_hyperpars(self, D_train, y_train, theta1_pars, theta2_pars, sigma2, aniso_lambda=None):
         """HX:549-575 / ADV:552-578: mean over the Halton nodes of exp(cond.like)."""

@@ -260,6 +260,28 @@ int ccgp_logpost_batch(ccgp_handle* h, const double* X, int n, int d, const doub
                        const double* theta_t, int B, const double* prior_pars, double* out_val, double* out_beta,
                        double* out_loglik, int* status);
 
+/* ---- many training sets of one shape in one call: the lockstep fit of a simulation study (GV:689-708 declares nine sets) --
+ * Xs holds C designs (blocks of n x d, column-major each), ys their C responses (blocks of n), sigma2 their C variances; row b
+ * of params (B x P column-major, as in ccgp_loglik_batch) is evaluated on set set[b] in 0 .. C-1.
+ *   Bits.  Row b has exactly the bits ccgp_loglik_batch / ccgp_logpost_batch returns for it on set set[b] alone: they do not
+ *     depend on C, B, the row's position, the order of `set`, or where the workspace limit cuts the call.
+ *   Failure.  status[b] is the 1-based pivot and the row's outputs are NaN; the other rows are untouched; the return value is
+ *     the number of failed rows.
+ *   Arguments.  C < 1, B < 1, a set[b] outside 0 .. C-1 or a NULL required pointer (everything but out_beta, out_loglik of
+ *     ccgp_logpost_sets, status, and prior_pars where the prior ignores it) return CCGP_EINVAL before anything is copied or
+ *     launched.  A set no row refers to is legal.
+ *   Shapes.  Every shape and kernel family the single-set call serves: Gaussian sets of n <= 128 whose instance fits run as
+ *     ONE launch; otherwise the rows are grouped by set and each group goes through the single-set call.
+ * Host pointers only, blocking; ccgp_reserve does not cover the staging.  ccgp_logpost_sets: K = 2, theta_t is B x q as in
+ * ccgp_logpost_batch, Jacobian and prior by the same host code. */
+int ccgp_loglik_batch_sets(ccgp_handle* h, const double* Xs /* C blocks n x d, column-major each */, int n, int d,
+                           const double* ys /* C blocks of n */, const double* sigma2 /* C */, int C, int K,
+                           const double* params /* B x P column-major */, const int* set /* B, 0 .. C-1 */, int B,
+                           int mean_mode, double tau2, double* out_loglik, double* out_beta, int* status);
+int ccgp_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                      int prior_id, const double* theta_t /* B x q */, const int* set, int B,
+                      const double* prior_pars, double* out_val, double* out_beta, double* out_loglik, int* status);
+
 /* ---- a9: likeli.hyperpars HX:549-575 / choose.hyperpars HX:584-595, ADV:552-599 -------
  * hyper is G x 4 (alpha1 beta1 alpha2 beta2).  For each row: N base-2 Halton quantiles
  * u_j, p = u_j, theta1 = qigamma(u_j, a1, b1), theta2 = qigamma(u_j, a2, b2), mode-1

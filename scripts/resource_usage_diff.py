@@ -1,0 +1,84 @@
+"""Compare the compiler's per-kernel resource usage of two builds of one source file: registers, scratch, LDS, occupancy.
+Input: the remark output of each build, e.g. for csrc/small_reg.hip
+    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c small_reg.hip -o /dev/null 2> new.txt
+(`make -C csrc resource-usage` prints the same remarks) and the same command on the other tree.  Kernels are matched by
+demangled name; a template argument the new build appended with its default value (`, false` at the end of
+small_reg_kernel's list) is dropped for the match, so an instance that existed before is compared with itself.  Prints every
+difference, the counts, and the kernels only the new build has -- each beside the pre-existing instance with the same
+leading arguments.  Needs c++filt.  Exit status 1 when a pre-existing kernel differs.
+    python scripts/resource_usage_diff.py parent.txt new.txt [--appended 1]"""
+import argparse
+import re
+import subprocess
+import sys
+
+KEYS = ["VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]", "TotalSGPRs",
+        "SGPRs Spill", "VGPRs Spill"]
+
+
+def parse(path):
+    out, cur = {}, None
+    for line in open(path):
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            cur = m.group(1)
+            out[cur] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+(?:\[[^\]]*\])?): (\S+) \[-Rpass", line)
+        if m and cur:
+            out[cur][m.group(1).strip()] = m.group(2)
+    return out
+
+
+def demangle(names):
+    r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
+    return dict(zip(names, r.stdout.split("\n")))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("parent")
+    ap.add_argument("new")
+    ap.add_argument("--appended", type=int, default=1, help="template arguments the new build appended to its kernels")
+    args = ap.parse_args()
+    par, new = parse(args.parent), parse(args.new)
+    dp, dn = demangle(list(par)), demangle(list(new))
+    nargs = {len(re.match(r".*?<([^>]*)>", v).group(1).split(",")) for v in dp.values() if "small_reg_kernel<" in v}
+
+    def split(name):
+        """(name without the appended arguments, True when they are not all `false`)"""
+        m = re.match(r"(.*?<)([^>]*)(>.*)", name)
+        if not m or "small_reg_kernel<" not in name:
+            return name, False
+        a = [x.strip() for x in m.group(2).split(",")]
+        if len(a) - args.appended not in nargs:
+            return name, False
+        tail = a[len(a) - args.appended:]
+        return m.group(1) + ", ".join(a[:len(a) - args.appended]) + m.group(3), any(t != "false" for t in tail)
+
+    old_form, added = {}, {}
+    for k, v in dn.items():
+        name, is_new = split(v)
+        (added if is_new else old_form)[name] = new[k]
+    differ = 0
+    for k, v in dp.items():
+        if v not in old_form:
+            print("MISSING in the new build:", v)
+            differ += 1
+            continue
+        for q in KEYS:
+            if par[k].get(q) != old_form[v].get(q):
+                print("DIFFERS %s: %s %s -> %s" % (v, q, par[k].get(q), old_form[v].get(q)))
+                differ += 1
+    print("kernels in the parent build: %d; compared: %d; differing figures (%s): %d; kernels only in the new build: %d" % (
+        len(par), len(par), ", ".join(k.split(" [")[0] for k in KEYS), differ, len(added) + len(set(old_form) - set(dp.values()))))
+    show = KEYS[:1] + KEYS[2:5]
+    for name in sorted(added, key=lambda s: [int(x) for x in re.findall(r"\d+", s)] + [s]):
+        base = old_form.get(name, {})
+        print("new %s: %s" % (re.search(r"<([^>]*)>", name).group(1),
+                              " | ".join("%s %s (%s)" % (q.split(" [")[0], added[name].get(q), base.get(q, "-")) for q in show)))
+    sys.exit(1 if differ else 0)
+
+
+if __name__ == "__main__":
+    main()
