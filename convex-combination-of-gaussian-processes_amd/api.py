@@ -107,6 +107,7 @@ SIGNATURES = {
     "ccgp_get_timing": (c_int, [c_void_p, c_int, _dp, _ip]),
     "ccgp_last_sched_profile": (c_int, [c_void_p, c_void_p, c_int, _ip]),
     "ccgp_workspace_bytes": (c_int, [c_void_p, POINTER(c_size_t), POINTER(c_size_t)]),
+    "ccgp_debug_fill_scratch": (c_int, [c_void_p, c_int]),
 }
 
 _bound = None
@@ -273,6 +274,11 @@ class MultiHandle:
             if rc:
                 raise CcgpError(rc, "ccgp_set_workspace_limit")
 
+    def debug_fill_scratch(self, byte):
+        """ccgp_debug_fill_scratch on every shard's handle; returns the shards' return values."""
+        return [lib().ccgp_debug_fill_scratch(c_void_p(lib().ccgp_multi_handle(self._m, i)), int(byte))
+                for i in range(self.count())]
+
     def loglik_batch(self, X, y, K, params, sigma2, mean_mode=MEAN_PROFILE_BETA, tau2=0.0):
         X, y = _f(X), _f(np.ravel(y))
         n, d = X.shape
@@ -379,6 +385,11 @@ class Handle:
         ws, st = c_size_t(), c_size_t()
         self._chk(lib().ccgp_workspace_bytes(self._h, ctypes.byref(ws), ctypes.byref(st)))
         return ws.value, st.value
+
+    def debug_fill_scratch(self, byte):
+        """ccgp_debug_fill_scratch: fill workspace, staging and pinned buffer with `byte` (0 .. 255) now and every buffer
+        the handle allocates from now on; -1 turns the fill on allocation off.  Returns the C return value (0 = done)."""
+        return self._chk(lib().ccgp_debug_fill_scratch(self._h, int(byte)))
 
     def synchronize(self):
         self._chk(lib().ccgp_synchronize(self._h))

@@ -82,13 +82,27 @@ struct BufferKind {
   hipError_t (*alloc)(void**, size_t);
   hipError_t (*release)(void*);
   bool slack;
+  bool host;   // host memory: ccgp_debug_fill_scratch fills it with memset
   const char* what;
 };
 const BufferKind kWorkspace{[](void** p, size_t n) { return hipMalloc(p, n); }, [](void* p) { return hipFree(p); }, false,
-                            "device workspace allocation"};
-const BufferKind kStaging{kWorkspace.alloc, kWorkspace.release, true, "device staging allocation"};
+                            false, "device workspace allocation"};
+const BufferKind kStaging{kWorkspace.alloc, kWorkspace.release, true, false, "device staging allocation"};
 const BufferKind kPinned{[](void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); },
-                         [](void* p) { return hipHostFree(p); }, true, "pinned host buffer"};
+                         [](void* p) { return hipHostFree(p); }, true, true, "pinned host buffer"};
+
+// ccgp_debug_fill_scratch: [p, p + bytes) starts as `byte` repeated.  Device memory on the handle's stream, where every
+// user of the memory is ordered behind it; host memory once that stream has drained.
+int debug_fill(ccgp_handle* h, void* p, size_t bytes, bool host, int byte) {
+  if (!p || !bytes) return CCGP_OK;
+  if (!host) {
+    CCGP_HIP(hipMemsetAsync(p, byte, bytes, h->stream));
+    return CCGP_OK;
+  }
+  CCGP_HIP(hipStreamSynchronize(h->stream));
+  std::memset(p, byte, bytes);
+  return CCGP_OK;
+}
 
 int ensure(ccgp_handle* h, Buffer& b, const BufferKind& k, size_t bytes) {
   if (bytes <= b.bytes) return CCGP_OK;
@@ -104,6 +118,7 @@ int ensure(ccgp_handle* h, Buffer& b, const BufferKind& k, size_t bytes) {
     return fail(h, CCGP_ENOMEM, std::string(k.what) + " of " + std::to_string(want) + " B failed");
   }
   b.bytes = want;
+  if (h->debug_fill >= 0) return debug_fill(h, b.ptr, b.bytes, k.host, h->debug_fill);
   return CCGP_OK;
 }
 
@@ -784,6 +799,20 @@ int ccgp_last_sched_profile(ccgp_handle* h, unsigned long long* out, int max_wor
   const int nw = std::min(max_workgroups, h->sched_prof_wgs);
   if (out_workgroups) *out_workgroups = nw;
   return pull(h, {piece(h->sched_prof_dev, out, 8 * (size_t)std::max(nw, 0))});
+} CCGP_GUARD_END(h)
+
+int ccgp_debug_fill_scratch(ccgp_handle* h, int byte) try {
+  if (!h) return CCGP_EINVAL;
+  if (byte < -1 || byte > 255) return fail(h, CCGP_EINVAL, "ccgp_debug_fill_scratch: byte must be -1 (off) or 0 .. 255");
+  h->debug_fill = byte;
+  if (byte < 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  // the scheduler's time account lies in the workspace (or in a factor set, which is not the handle's to fill: that
+  // account stays)
+  forget_sched_profile(h, h->ws.ptr, h->ws.bytes);
+  if (int rc = debug_fill(h, h->ws.ptr, h->ws.bytes, false, byte)) return rc;
+  if (int rc = debug_fill(h, h->stage.ptr, h->stage.bytes, false, byte)) return rc;
+  return debug_fill(h, h->pin.ptr, h->pin.bytes, true, byte);
 } CCGP_GUARD_END(h)
 
 int ccgp_workspace_bytes(const ccgp_handle* h, size_t* ws_bytes, size_t* stage_bytes) {
@@ -1855,6 +1884,8 @@ int ccgp_factor_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
     return fail(h, CCGP_ENOMEM, "ccgp_factor_batch: " + std::to_string(bytes) + " B for " + std::to_string(S) +
                                     " factors do not fit on the device");
   }
+  if (h->debug_fill >= 0)
+    if (int rc = debug_fill(h, fs->mem, bytes, false, h->debug_fill)) return rc;
   fs->bytes = bytes; fs->device = h->device; fs->n = n; fs->d = d; fs->K = K; fs->S = S; fs->npad = npad;
   fs->sigma2 = sigma2; fs->fam = h->fam; fs->fused = fused;
   Layout c(fs->mem);

@@ -84,6 +84,7 @@ struct ccgp_handle {
   // host buffer through which their inputs and results cross PCIe in one copy each
   ccgp::Buffer ws, stage, pin;
   size_t pin_in = 0;     // bytes of `pin` holding the inputs of the call in flight (results land behind them)
+  int debug_fill = -1;   // ccgp_debug_fill_scratch: 0..255 = every buffer allocated from now on starts filled with this byte
   hipStream_t aux_stream = nullptr;     // second stream of the kept-factor prediction (ccgp_reserve, or first use)
   hipEvent_t aux_fork = nullptr, aux_join = nullptr;
   hipEvent_t pull_ev[ccgp::kPullSlices] = {};   // one per slice of a large result on its way back (capi.hip: pull)

@@ -534,6 +534,13 @@ int ccgp_last_sched_profile(ccgp_handle* h, unsigned long long* out, int max_wor
 /* Bytes of device scratch the handle holds now: the workspace (sweep matrices, kept factors) and the staging buffer.
  * Both grow only; a figure that changed across a call means the call allocated.  Does not synchronise.  Either may be NULL. */
 int ccgp_workspace_bytes(const ccgp_handle* h, size_t* ws_bytes, size_t* stage_bytes);
+/* Tests only: make what a call finds in the handle's scratch a chosen value instead of whatever an earlier call (or a fresh
+ * allocation, usually zero pages) left there.  byte in 0 .. 255: fills the device workspace and the device staging buffer
+ * with that byte on the handle's stream and the pinned host buffer after a stream synchronise, forgets the scheduler's
+ * time account (it lies in that memory), and from now on fills every buffer the handle allocates -- a regrown workspace,
+ * staging or pinned buffer, the memory of a factor set -- right after the allocation.  byte = -1 (the default) turns the
+ * fill on allocation off; anything else is CCGP_EINVAL.  No result may depend on the byte.  May synchronise. */
+int ccgp_debug_fill_scratch(ccgp_handle* h, int byte);
 
 #ifdef __cplusplus
 }
