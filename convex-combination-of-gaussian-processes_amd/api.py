@@ -60,6 +60,10 @@ SIGNATURES = {
                                        _dp, _dp, _ip]),
     "ccgp_logpost_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, _ip, c_int, _dp, _dp, _dp, _dp,
                                   _ip]),
+    "ccgp_profile_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, c_int, _dp, _ip, c_int, _dp, _dp, _dp, _dp,
+                                        _ip]),
+    "ccgp_cgp_state_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _ip, _dp, _dp, _dp, _dp,
+                                          _ip]),
     "ccgp_grid_marginal": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, _dp, c_int, c_int,
                                    c_double, c_int, c_double, _dp, _ip, _dp]),
     "ccgp_mixed_logdet_designs": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, _dp, _ip]),
@@ -618,14 +622,14 @@ class Handle:
     @staticmethod
     def _sets(Xs, ys, sigma2s, set_of, B):
         """The C training sets of one shape as the sets calls take them: designs [C, n, d] -> C column-major blocks,
-        responses [C, n], variances [C], and the rows' set indices as int32[B]."""
+        responses [C, n], variances [C] (None where the call takes none), and the rows' set indices as int32[B]."""
         Xs = np.asarray(Xs, dtype=np.float64)
         if Xs.ndim != 3:
             raise ValueError("Xs must be [C, n, d]: the sets of one call have one shape")
         C, n, d = Xs.shape
         blocks = np.ascontiguousarray(np.transpose(Xs, (0, 2, 1)))
         ys = np.ascontiguousarray(np.asarray(ys, dtype=np.float64).reshape(C, n))
-        s2 = np.ascontiguousarray(np.asarray(sigma2s, dtype=np.float64).reshape(C))
+        s2 = None if sigma2s is None else np.ascontiguousarray(np.asarray(sigma2s, dtype=np.float64).reshape(C))
         idx = np.ascontiguousarray(np.asarray(set_of).reshape(B).astype(np.int32))
         return blocks, ys, s2, idx, C, n, d
 
@@ -656,6 +660,43 @@ class Handle:
         self._chk(lib().ccgp_logpost_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, int(prior_id), _p(theta_t), _ipt(idx), B,
                                           _p(pp), _p(val), _p(beta), _p(ll), _ipt(st)))
         return val, beta, ll, st
+
+    def profile_batch_sets(self, Xs, ys, K, params, set_of, grad=True):
+        """ccgp_profile_batch_sets: row b of params [B, K + K*d] on training set set_of[b] of the C sets Xs [C, n, d],
+        ys [C, n] in one call.  Returns what profile_batch returns -- (loglik[B], sigma2[B], beta[B], grad[B, P] or None,
+        status[B]) -- each row with the bits profile_batch gives it on its set alone."""
+        params = _f(np.atleast_2d(params))
+        B, P = params.shape
+        Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, B)
+        if P != K + K * d:
+            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
+        ll, s2, beta = np.empty(B), np.empty(B), np.empty(B)
+        g = np.empty((B, P), dtype=np.float64, order="F") if grad else None
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_profile_batch_sets(self._h, _p(Xb), n, d, _p(yb), C, K, _p(params), _ipt(idx), B, _p(ll), _p(s2),
+                                                _p(beta), _p(g), _ipt(st)))
+        return ll, s2, beta, g, st
+
+    def cgp_state_batch_sets(self, Xs, ys, params, set_of, skip=None):
+        """ccgp_cgp_state_batch_sets: the CGP state at row b of params [B, 2 d + 2] on training set set_of[b] of the C sets
+        Xs [C, n, d], ys [C, n] in one call, skip[B] as in cgp_state_batch.  Returns what cgp_state_batch returns -- (val[B],
+        beta[B], tau2[B], loo[B] or None without skip, status[B]) -- each row with the bits it has on its set alone."""
+        params = _f(np.atleast_2d(params))
+        B, P = params.shape
+        Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, B)
+        if P != 2 * d + 2:
+            raise ValueError("params must have 2 d + 2 = %d columns" % (2 * d + 2))
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(np.ravel(skip), dtype=np.int32)
+            if sk.shape[0] != B:
+                raise ValueError("skip must have one entry per row of params")
+        val, beta, tau2 = np.empty(B), np.empty(B), np.empty(B)
+        loo = np.empty(B) if sk is not None else None
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_cgp_state_batch_sets(self._h, _p(Xb), n, d, _p(yb), C, _p(params), _ipt(idx), B, _ipt(sk), _p(val),
+                                                  _p(beta), _p(tau2), _p(loo), _ipt(st)))
+        return val, beta, tau2, loo, st
 
     def grid_marginal(self, X, y, sigma2, hyper, N, tau, take_log, aniso_lambda=-1.0, want_logs=False):
         X, y = _f(X), _f(np.ravel(y))

@@ -18,6 +18,9 @@ difference with step h has truncation error h^2 f''' / 6 and rounding error 1e-1
 gradient whose entries are of order 1 to 100, where 1e-3 leaves a truncation error of 1e-6 |f'''| that moved the optimum's
 predictions by 0.01 rms on the Ground-Vibrations set (0.001 with 1e-5).  `step` is an argument.
 
+CGP_sets fits the models of many training sets of one shape in lockstep (a simulation study's comparator): the same three
+steps with the rows of every set in each device call (ccgp_cgp_state_batch_sets).
+
 The final optim run from `beststart` (GV:155-157) is not repeated: it starts where that start's refinement started, every
 evaluation depends on its own row only (not on the batch it travels in), so the lockstep run of that start IS that run.
 """
@@ -146,6 +149,119 @@ def CGP(handle, X, y, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, 
                 converged=res["converged"], jackknife_status=st, calls=count["calls"], evaluations=count["rows"],
                 refinement_calls=res["calls"],
                 seconds=dict(candidates=clock[1] - clock[0], refinement=clock[2] - clock[1], jackknife=clock[4] - clock[3]))
+
+
+def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, kappa_u=None, rngs=None, step=1e-5):
+    """CGP for C training sets of one shape in lockstep -> a list with, per set, the dict CGP(handle, Xs[c], ys[c], ...,
+    rng=rngs[c]) returns: every field bit for bit except calls, evaluations, refinement_calls and seconds.
+
+      * the candidates of all sets are ONE call of ccgp_cgp_state_batch_sets, each set's LHD from its own generator (rngs[c],
+        default seed 0 each, as CGP's);
+      * the num_starts refinements of all sets run through ONE design.minimize_starts with per-start bounds (a set's box is
+        its own: cgp.bounds), so an evaluator call is one device call for every start of every set still running;
+      * the jackknife of all sets is one call of C n rows with skip;
+      * the final state per set is ccgp_cgp_predict, unchanged.
+    A start's trajectory depends on its own evaluations only and a row's bits on its own set only, so each set's fit is the
+    fit it has alone.  calls and refinement_calls are the group's device calls (the same in every dict), evaluations the
+    rows of the set itself, seconds the group's."""
+    h = _plain(handle)
+    DDs = [np.asarray(X, dtype=np.float64) for X in Xs]
+    yobs = [np.asarray(y, dtype=np.float64).ravel() for y in ys]
+    C = len(DDs)
+    if C < 1 or len(yobs) != C:
+        raise ValueError("CGP_sets: one response per design, at least one set")
+    if any(D.ndim != 2 or D.shape != DDs[0].shape for D in DDs) or any(y.shape[0] != DDs[0].shape[0] for y in yobs):
+        raise ValueError("CGP_sets: the sets of one call have one shape (n, p)")
+    rngs = [0] * C if rngs is None else list(rngs)
+    if len(rngs) != C:
+        raise ValueError("CGP_sets takes one generator per set")
+    gens = [r if isinstance(r, np.random.Generator) else np.random.default_rng(r) for r in rngs]
+    n, p = DDs[0].shape
+    n_par = p + 3
+    std = [standardise(D) for D in DDs]
+    box = [bounds(std[c][0], nugget_l, theta_l, alpha_l, kappa_u) for c in range(C)]
+    XS, XD, Y = np.stack([s[0] for s in std]), np.stack(DDs), np.stack(yobs)
+    count = dict(calls=0, rows=np.zeros(C, dtype=np.int64))
+
+    def objective(ww, set_of):
+        """var.MLE.DK at the rows of ww, row b on set set_of[b], in one device call."""
+        val, _, _, _, st = h.cgp_state_batch_sets(XS, Y, rows_from_ww(ww), set_of)
+        count["calls"] += 1
+        np.add.at(count["rows"], set_of, 1)
+        return np.where(np.isfinite(val), val, NONFINITE), st
+
+    n_cand = N_CANDIDATE_BASE + num_starts
+    cand_pts = [box[c][0] + lhd(n_cand, n_par, gens[c]) * (box[c][1] - box[c][0]) for c in range(C)]     # GV:144-148
+    clock = [time.perf_counter()]
+    cand, _ = objective(np.concatenate(cand_pts), np.repeat(np.arange(C), n_cand))
+    clock.append(time.perf_counter())
+    Starts = []
+    for c in range(C):
+        order = np.argsort(cand[c * n_cand:(c + 1) * n_cand], kind="stable")[:num_starts]              # GV:150-151
+        Starts.append(cand_pts[c][np.sort(order)])
+    S = Starts[0].shape[0]
+    owner = np.repeat(np.arange(C), S)
+    lowers, uppers = np.stack([box[c][0] for c in owner]), np.stack([box[c][1] for c in owner])
+
+    def evaluate(W, live):
+        k = W.shape[0]
+        hi = np.minimum(W + step, uppers[live])
+        lo = np.maximum(W - step, lowers[live])
+        pts = np.repeat(W[:, None, :], 1 + 2 * n_par, axis=1)
+        for j in range(n_par):
+            pts[:, 1 + 2 * j, j] = hi[:, j]
+            pts[:, 2 + 2 * j, j] = lo[:, j]
+        f, st = objective(pts.reshape(-1, n_par), np.repeat(owner[live], 1 + 2 * n_par))
+        f = f.reshape(k, 1 + 2 * n_par)
+        g = (f[:, 1::2] - f[:, 2::2]) / (hi - lo)
+        return f[:, 0], g, st.reshape(k, -1)[:, 0]
+
+    res = minimize_starts(evaluate, np.concatenate(Starts), lowers=lowers, uppers=uppers, pass_live=True)   # GV:152-154
+    clock.append(time.perf_counter())
+    fitted = []
+    for c in range(C):
+        sl = slice(c * S, (c + 1) * S)
+        f, x = res["f"][sl], res["x"][sl]
+        if not np.isfinite(f).any():
+            raise RuntimeError("CGP_sets: the objective failed at every start of set %d" % c)
+        best = int(np.argmin(np.where(np.isfinite(f), f, np.inf)))                                     # GV:155-157
+        par = x[best]
+        lam, st_theta, kappa, bw = float(par[0]), par[1:1 + p], float(par[1 + p]), float(par[2 + p])
+        scales = std[c][1]
+        theta = st_theta / scales ** 2                                                                 # GV:164-165
+        alpha = (kappa + st_theta) / scales ** 2
+        fitted.append(dict(best=best, par=par, lam=lam, theta=theta, alpha=alpha, bw=bw,
+                           row=np.concatenate([[lam], theta, alpha, [bw]])))
+
+    clock.append(time.perf_counter())
+    rows = np.concatenate([np.repeat(ft["row"][None], n, axis=0) for ft in fitted])
+    _, _, _, loo, jst = h.cgp_state_batch_sets(XD, Y, rows, np.repeat(np.arange(C), n), skip=np.tile(np.arange(n), C))   # GV:166-198
+    clock.append(time.perf_counter())
+    count["calls"] += 1
+    count["rows"] += n
+    keeps = []
+    for c in range(C):
+        _, keep, status = h.cgp_predict(DDs[c], yobs[c], fitted[c]["row"], np.empty((0, p)))            # GV:200-221
+        count["calls"] += 1
+        count["rows"][c] += 1
+        if status:
+            raise RuntimeError("CGP_sets: the final state of set %d cannot be factorised (pivot %d)" % (c, status))
+        keeps.append(keep)
+    seconds = dict(candidates=clock[1] - clock[0], refinement=clock[2] - clock[1], jackknife=clock[4] - clock[3])
+    out = []
+    for c in range(C):
+        sl = slice(c * S, (c + 1) * S)
+        ft, keep, lo_c = fitted[c], keeps[c], loo[c * n:(c + 1) * n]
+        rmscv = float(np.sqrt(np.sum((yobs[c] - lo_c) ** 2) / n))
+        out.append(dict(X=DDs[c], yobs=yobs[c], **{"lambda": ft["lam"]}, theta=ft["theta"][None], alpha=ft["alpha"][None],
+                        bandwidth=ft["bw"], Sig_matrix=keep["s"], sf=keep["sf"], res2=keep["res2"], temp_matrix=keep["temp"],
+                        mu=keep["beta"], tau2=keep["tau2"], beststart=Starts[c][ft["best"]],
+                        objval=float(res["f"][sl][ft["best"]]), rmscv=rmscv, Yp_jackknife=lo_c, lower=box[c][0],
+                        upper=box[c][1], par=ft["par"], scales=std[c][1], starts=Starts[c], f_starts=res["f"][sl],
+                        x_starts=res["x"][sl], converged=res["converged"][sl], jackknife_status=jst[c * n:(c + 1) * n],
+                        calls=count["calls"], evaluations=int(count["rows"][c]), refinement_calls=res["calls"],
+                        seconds=seconds))
+    return out
 
 
 def param_row(est):

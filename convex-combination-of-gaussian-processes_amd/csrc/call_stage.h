@@ -294,6 +294,77 @@ inline SetsStage sets_stage(Layout& c, int n, int d, int P, int C, int B) {
   return s;
 }
 
+// ---- the sets forms of the comparator fits (ccgp_profile_batch_sets with a gradient, ccgp_cgp_state_batch_sets).  A call is
+// cut into chunks of nb rows (plan_chunk): the C training sets lie in front and go up ONCE, with the first chunk; behind them
+// a chunk's rows, its set indices and its results.  `first`: this chunk is the call's first.
+//   ccgp_profile_batch_sets: Xs | ys | set | params | grad | loglik | s2hat | beta | status
+struct ProfileSetsStage {
+  double *Xs, *ys;
+  int* set;
+  double *params, *grad, *loglik, *s2hat, *beta;
+  int* status;
+  size_t nXs, nys, P;
+  std::vector<Piece> inputs(bool first, const double* hXs, const double* hys, const int* hset, const double* hparams,
+                            int nb) const {
+    return {piece(Xs, first ? hXs : nullptr, nXs), piece(ys, first ? hys : nullptr, nys), piece(set, hset, (size_t)nb),
+            piece(params, hparams, (size_t)nb * P)};
+  }
+  // the status words follow beta (pull_status)
+  std::vector<Piece> results(double* hgrad, double* hloglik, double* hs2hat, double* hbeta, int nb) const {
+    return {piece(grad, hgrad, (size_t)nb * P), piece(loglik, hloglik, (size_t)nb), piece(s2hat, hs2hat, (size_t)nb),
+            piece(beta, hbeta, (size_t)nb)};
+  }
+};
+inline ProfileSetsStage profile_sets_stage(Layout& c, int n, int d, int P, int C, int nb) {
+  ProfileSetsStage s;
+  s.nXs = (size_t)C * n * d; s.nys = (size_t)C * n; s.P = P;
+  s.Xs = c.take<double>(s.nXs);
+  s.ys = c.take<double>(s.nys);
+  s.set = c.take<int>(nb);
+  s.params = c.take<double>((size_t)nb * P);
+  s.grad = c.take<double>((size_t)nb * P);
+  s.loglik = c.take<double>(nb);
+  s.s2hat = c.take<double>(nb);
+  s.beta = c.take<double>(nb);
+  s.status = c.take<int>(nb);
+  return s;
+}
+inline size_t profile_sets_row_bytes(int P) { return sizeof(double) * (2 * (size_t)P + 3) + 2 * sizeof(int); }
+//   ccgp_cgp_state_batch_sets: Xs | ys | set | skip | params | val | beta | tau2 | loo | status
+struct CgpSetsStage {
+  double *Xs, *ys;
+  int *set, *skip;
+  double *params, *val, *beta, *tau2, *loo;
+  int* status;
+  size_t nXs, nys, P;
+  std::vector<Piece> inputs(bool first, const double* hXs, const double* hys, const int* hset, const int* hskip,
+                            const double* hparams, int nb) const {
+    return {piece(Xs, first ? hXs : nullptr, nXs), piece(ys, first ? hys : nullptr, nys), piece(set, hset, (size_t)nb),
+            piece(skip, hskip, (size_t)nb), piece(params, hparams, (size_t)nb * P)};
+  }
+  // the status words follow loo (pull_status)
+  std::vector<Piece> results(double* hval, double* hbeta, double* htau2, double* hloo, int nb) const {
+    return {piece(val, hval, (size_t)nb), piece(beta, hbeta, (size_t)nb), piece(tau2, htau2, (size_t)nb),
+            piece(loo, hloo, (size_t)nb)};
+  }
+};
+inline CgpSetsStage cgp_sets_stage(Layout& c, int n, int d, int C, int nb) {
+  CgpSetsStage s;
+  s.nXs = (size_t)C * n * d; s.nys = (size_t)C * n; s.P = 2 * (size_t)d + 2;
+  s.Xs = c.take<double>(s.nXs);
+  s.ys = c.take<double>(s.nys);
+  s.set = c.take<int>(nb);
+  s.skip = c.take<int>(nb);
+  s.params = c.take<double>((size_t)nb * s.P);
+  s.val = c.take<double>(nb);
+  s.beta = c.take<double>(nb);
+  s.tau2 = c.take<double>(nb);
+  s.loo = c.take<double>(nb);
+  s.status = c.take<int>(nb);
+  return s;
+}
+inline size_t cgp_sets_row_bytes(int d) { return sizeof(double) * (2 * (size_t)d + 2 + 4) + 3 * sizeof(int); }
+
 // the staging ccgp_reserve(n, d, K, B, m) provides: the host-pointer likelihood and, with test sites, the prediction
 // (without its tail) and the tables of ccgp_predict_summary_dev
 inline size_t reserve_stage_bytes(int n, int d, int P, int B, int m) {

@@ -1181,6 +1181,153 @@ int ccgp_cgp_state_batch(ccgp_handle* h, const double* X, int n, int d, const do
   return failed;
 } CCGP_GUARD_END(h)
 
+// ---- the comparator fits over many training sets of one shape (ccgp.h) ------------------------------------------------------
+// what ccgp_profile_batch_sets and ccgp_cgp_state_batch_sets refuse before anything is copied or launched (B == 0 is legal)
+static bool sets_rows_ok(const double* Xs, const double* ys, int C, const int* set, int B) {
+  if (C < 1 || B < 0 || !Xs || !ys || !set) return false;
+  for (int b = 0; b < B; ++b)
+    if (set[b] < 0 || set[b] >= C) return false;
+  return true;
+}
+
+// rows b0 .. b0 + nb of a B x P column-major table as an nb x P one: `rows` where the chunk is not the whole table
+static const double* chunk_rows(const double* params, int B, int P, int b0, int nb, std::vector<double>& rows) {
+  if (nb == B) return params;
+  rows.resize((size_t)nb * P);
+  for (int j = 0; j < P; ++j) std::memcpy(&rows[(size_t)j * nb], params + b0 + (size_t)j * B, sizeof(double) * nb);
+  return rows.data();
+}
+
+// small_route_profile_grad_sets says Blocked, or no gradient is wanted: the rows of every set, in their order, through
+// ccgp_profile_batch (whatever route that call takes)
+static int profile_sets_by_group(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int K,
+                                 const double* params, const int* set, int B, double* out_loglik, double* out_sigma2,
+                                 double* out_beta, double* out_grad, int* status) {
+  const int P = K + K * d;
+  std::vector<std::vector<int>> rows_of(C);
+  for (int b = 0; b < B; ++b) rows_of[set[b]].push_back(b);
+  int failed = 0;
+  std::vector<double> rows, ll, s2, beta, grad;
+  std::vector<int> st;
+  for (int c = 0; c < C; ++c) {
+    const std::vector<int>& idx = rows_of[c];
+    const int nb = (int)idx.size();
+    if (!nb) continue;
+    rows.resize((size_t)nb * P); ll.resize(nb); s2.resize(nb); beta.resize(nb); st.resize(nb);
+    if (out_grad) grad.resize((size_t)nb * P);
+    for (int j = 0; j < P; ++j)
+      for (int i = 0; i < nb; ++i) rows[i + (size_t)j * nb] = params[idx[i] + (size_t)j * B];
+    const int rc = ccgp_profile_batch(h, Xs + (size_t)c * n * d, n, d, ys + (size_t)c * n, K, rows.data(), nb, ll.data(),
+                                      s2.data(), beta.data(), out_grad ? grad.data() : nullptr, st.data());
+    if (rc < 0) return rc;
+    failed += rc;
+    for (int i = 0; i < nb; ++i) {
+      out_loglik[idx[i]] = ll[i];
+      out_sigma2[idx[i]] = s2[i];
+      if (out_beta) out_beta[idx[i]] = beta[i];
+      if (status) status[idx[i]] = st[i];
+    }
+    if (out_grad)
+      for (int j = 0; j < P; ++j)
+        for (int i = 0; i < nb; ++i) out_grad[idx[i] + (size_t)j * B] = grad[i + (size_t)j * nb];
+  }
+  return failed;
+}
+
+int ccgp_profile_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int K,
+                            const double* params, const int* set, int B, double* out_loglik, double* out_sigma2,
+                            double* out_beta, double* out_grad, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || !params || !out_loglik || !out_sigma2 || !sets_rows_ok(Xs, ys, C, set, B))
+    return fail(h, CCGP_EINVAL, "ccgp_profile_batch_sets: bad argument");
+  if (B == 0) return CCGP_OK;
+  const bool gauss = h->fam.id == 0;
+  // ccgp_profile_batch's refusals, before the first group is launched
+  if (out_grad && !gauss)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch_sets: analytic gradient is implemented for the Gaussian family only");
+  if (out_grad && small_route(Op::Grad, gauss, n, d, K) == Route::Blocked && !blocked_grad_supported(d, K))
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch_sets: d + K too large for the contraction kernel's LDS");
+  if (!out_grad || small_route_profile_grad_sets(gauss, n, d, K) == Route::Blocked)
+    return profile_sets_by_group(h, Xs, n, d, ys, C, K, params, set, B, out_loglik, out_sigma2, out_beta, out_grad, status);
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  // A chunk is a call of its own, as in ccgp_cgp_state_batch: the planner cuts B by the workspace limit and by the grid's
+  // 65535; a row reads its own parameters and its own set only, so where the cuts fall changes no bit.
+  int nbc = 0;
+  if (int rc = plan_chunk(h, profile_sets_row_bytes(P), B, kSweepMargin,
+                          [&](int nb) { return layout_bytes([&](Layout& w) { profile_sets_stage(w, n, d, P, C, nb); }); }, &nbc))
+    return rc;
+  Layout ws(h->ws.ptr);
+  const ProfileSetsStage s = profile_sets_stage(ws, n, d, P, C, nbc);
+  std::vector<double> rows, grad;
+  int failed = 0;
+  for (int b0 = 0; b0 < B; b0 += nbc) {
+    const int nb = std::min(nbc, B - b0);
+    DrawView dv;
+    if (int frc = draw_view(h, h->fam, s.params, nb, K, d, &dv)) return frc;
+    if (int prc = push(h, s.inputs(b0 == 0, Xs, ys, set + b0, chunk_rows(params, B, P, b0, nb, rows), nb))) return prc;
+    {
+      ScopedTimer t(h, CCGP_T_FUSED);
+      launch_small_reg_profile_grad_sets(h->stream, s.Xs, n, d, s.ys, s.set, dv, nb, s.loglik, s.s2hat, s.beta, s.grad, s.status);
+    }
+    CCGP_LAUNCH_CHECK();
+    double* hgrad = out_grad;
+    if (nb != B) {
+      grad.resize((size_t)nb * P);
+      hgrad = grad.data();
+    }
+    const int rc = pull_status(h, s.results(hgrad, out_loglik + b0, out_sigma2 + b0, out_beta ? out_beta + b0 : nullptr, nb),
+                               s.status, nb, status ? status + b0 : nullptr);
+    if (rc < 0) return rc;
+    failed += rc;
+    if (nb != B)
+      for (int j = 0; j < P; ++j) std::memcpy(out_grad + b0 + (size_t)j * B, &grad[(size_t)j * nb], sizeof(double) * nb);
+  }
+  return failed;
+} CCGP_GUARD_END(h)
+
+int ccgp_cgp_state_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, const double* params,
+                              const int* set, int B, const int* skip, double* out_val, double* out_beta, double* out_tau2,
+                              double* out_loo, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (n < 1 || d < 1 || !params || !out_val || !sets_rows_ok(Xs, ys, C, set, B))
+    return fail(h, CCGP_EINVAL, "ccgp_cgp_state_batch_sets: bad argument");
+  if (skip)
+    for (int b = 0; b < B; ++b)
+      if (skip[b] < -1 || skip[b] >= n || (skip[b] >= 0 && n < 2))
+        return fail(h, CCGP_EINVAL, "ccgp_cgp_state_batch_sets: skip must be -1 or a row of a design of at least two points");
+  if (int rc = cgp_shape(h, "ccgp_cgp_state_batch_sets", n, d)) return rc;   // before any launch
+  if (B == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = 2 * d + 2;
+  int nbc = 0;
+  if (int rc = plan_chunk(h, cgp_sets_row_bytes(d), B, kSweepMargin,
+                          [&](int nb) { return layout_bytes([&](Layout& w) { cgp_sets_stage(w, n, d, C, nb); }); }, &nbc))
+    return rc;
+  Layout ws(h->ws.ptr);
+  const CgpSetsStage s = cgp_sets_stage(ws, n, d, C, nbc);
+  std::vector<double> rows;
+  int failed = 0;
+  for (int b0 = 0; b0 < B; b0 += nbc) {
+    const int nb = std::min(nbc, B - b0);
+    if (int prc = push(h, s.inputs(b0 == 0, Xs, ys, set + b0, skip ? skip + b0 : nullptr,
+                                   chunk_rows(params, B, P, b0, nb, rows), nb)))
+      return prc;
+    {
+      ScopedTimer t(h, CCGP_T_FUSED);
+      launch_cgp_state_sets(h->stream, s.Xs, n, d, s.ys, s.set, s.params, nb, nb, skip ? s.skip : nullptr, s.val, s.beta,
+                            s.tau2, out_loo ? s.loo : nullptr, s.status);
+    }
+    CCGP_LAUNCH_CHECK();
+    const int rc = pull_status(h, s.results(out_val + b0, out_beta ? out_beta + b0 : nullptr, out_tau2 ? out_tau2 + b0 : nullptr,
+                                            out_loo ? out_loo + b0 : nullptr, nb),
+                               s.status, nb, status ? status + b0 : nullptr);
+    if (rc < 0) return rc;
+    failed += rc;
+  }
+  return failed;
+} CCGP_GUARD_END(h)
+
 int ccgp_cgp_predict(ccgp_handle* h, const double* X, int n, int d, const double* y, const double* params,
                      const double* Xtest, int m, double* out, double* out_state, int* status) try {
   if (!h) return CCGP_EINVAL;

@@ -211,6 +211,11 @@ void launch_small_reg_loglik(hipStream_t s, const double* X, int n, int d, const
 void launch_small_reg_loglik_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
                                   const int* set, DrawView dv, int B, int mean_mode, double tau2, double* loglik,
                                   double* beta, int* status);
+// the sets form of launch_small_reg_profile with a gradient (ccgp_profile_batch_sets where small_route_profile_grad_sets says
+// Reg): row b on set set[b], grad B x P column-major with leading dimension B
+void launch_small_reg_profile_grad_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set,
+                                        DrawView dv, int B, double* loglik, double* s2hat, double* beta, double* grad,
+                                        int* status);
 // leave-one-out mean / variance of every training point for B draws (ccgp_loo_batch where small_route_loo says Reg): one
 // workgroup per draw on the inverse instances' scheme; mean / var are B x n column-major, sigma2 is the scalar that
 // vf.sigma2_row (indexed by draw) replaces, vf.q (may be nullptr) receives Q per draw
@@ -249,6 +254,10 @@ inline bool cgp_supported(int n, int d) { return n >= 1 && n <= kSmallMaxN && d 
 // dimension ldp; skip (nb, -1 = none) and loo may be nullptr; keep != nullptr: evaluation 0 leaves its CgpKeep(n) there
 void launch_cgp_state(hipStream_t s, const double* X, int n, int d, const double* y, const double* params, int ldp, int nb,
                       const int* skip, double* val, double* beta, double* tau2, double* loo, int* status, double* keep);
+// the sets form (ccgp_cgp_state_batch_sets): evaluation b on training set set[b] of the blocks at Xs / ys; no kept state
+void launch_cgp_state_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set,
+                           const double* params, int ldp, int nb, const int* skip, double* val, double* beta, double* tau2,
+                           double* loo, int* status);
 // predict.CGP (GV:287-307) at m sites from a kept state; row: that state's parameter row, contiguous; out m x 6 column-major
 void launch_cgp_predict(hipStream_t s, const double* X, int n, int d, const double* row, const double* Xtest, int m,
                         const double* keep, const int* status, double* out);

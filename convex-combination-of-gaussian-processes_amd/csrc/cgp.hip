@@ -44,6 +44,7 @@ struct CgpStateArgs {
   double *val, *beta, *tau2, *loo;   // nb each; loo may be nullptr
   int* status;
   double* keep;           // CgpKeep(n) of evaluation 0, or nullptr
+  const int* set;         // SETS: evaluation b belongs to training set set[b]: X + set[b] n d, y + set[b] n
 };
 
 __device__ inline double cgp_wave_sum(double v) {
@@ -69,6 +70,11 @@ __device__ __forceinline__ double cgp_dist_to(const double* xs, int ldx, int j, 
   return s;
 }
 
+// SETS: many training sets of one shape in one launch (ccgp_cgp_state_batch_sets): the evaluation's design and responses come
+// from its set, everything after the loads is the single-set instance's code, hence its bits.  A template parameter, not a
+// branch, for the reason small_reg.hip gives for PROF and SETS: the single-set instance compiles from unchanged code.  The
+// sets form keeps no state (`keep` does not exist there).
+template <bool SETS>
 __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int n0 = a.n, d = a.d;
@@ -80,6 +86,12 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
          *e2 = smem + cv.e2, *tv = smem + cv.tv, *uv = smem + cv.uv, *x0 = smem + cv.x0, *th = smem + cv.th, *al = smem + cv.al,
          *tb = smem + cv.tb, *red = smem + cv.red;
 
+  const double *X = a.X, *y = a.y;
+  if constexpr (SETS) {
+    const int st = __builtin_amdgcn_readfirstlane(a.set[b]);   // wave-uniform: the addresses stay in scalar registers
+    X += (size_t)st * n0 * d;
+    y += (size_t)st * n0;
+  }
   int skip = a.skip ? a.skip[b] : -1;
   if (skip < 0 || skip >= n0) skip = -1;
   const int n = skip >= 0 ? n0 - 1 : n0;            // points of this evaluation
@@ -91,14 +103,14 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
     th[k] = t;
     tb[k] = t * bw;
     al[k] = a.params[b + (size_t)(1 + d + k) * a.ldp];
-    x0[k] = skip >= 0 ? a.X[(size_t)k * n0 + skip] : 0.0;
+    x0[k] = skip >= 0 ? X[(size_t)k * n0 + skip] : 0.0;
   }
   for (int e = tid; e < n * d; e += 256) {
     const int k = e / n, i = e % n;
-    xs[k * n0 + i] = a.X[(size_t)k * n0 + i + (skip >= 0 && i >= skip ? 1 : 0)];
+    xs[k * n0 + i] = X[(size_t)k * n0 + i + (skip >= 0 && i >= skip ? 1 : 0)];
   }
   for (int i = tid; i < n; i += 256) {
-    yv[i] = a.y[i + (skip >= 0 && i >= skip ? 1 : 0)];
+    yv[i] = y[i + (skip >= 0 && i >= skip ? 1 : 0)];
     s[i] = 1.0;
     rs[i] = 1.0;
   }
@@ -168,7 +180,7 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
       // A[k + i ld] / d_i, i < k) carries it into the entries above
       double t0 = r0 * rd0, t1 = r1 * rd1;          // temp
       double u0 = z10 * rd0, u1 = z11 * rd1;        // Q^-1 1 (kept state only)
-      const bool want_u = last && a.keep != nullptr;
+      const bool want_u = !SETS && last && a.keep != nullptr;
       for (int k = n - 1; k > 0; --k) {
         const double xk = __shfl(k < 64 ? t0 : t1, k & 63, 64);
         const double c0 = i0 < k ? A[k + (size_t)i0 * ld] * rd0 : 0.0;
@@ -262,7 +274,7 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
       a.status[b] = bad;
     }
   }
-  if (a.keep && b == 0 && !bad) {
+  if (!SETS && a.keep && b == 0 && !bad) {
     const CgpKeep kp(n);
     double* K = a.keep;
     for (int e = tid; e < n * n; e += 256) {
@@ -376,11 +388,22 @@ __global__ __launch_bounds__(256) void cgp_predict_kernel(CgpPredictArgs a) {
 void launch_cgp_state(hipStream_t st, const double* X, int n, int d, const double* y, const double* params, int ldp, int nb,
                       const int* skip, double* val, double* beta, double* tau2, double* loo, int* status, double* keep) {
   static unsigned long long attr_mask = 0;
-  once_per_device(attr_mask, [] { raise_lds_limit((const void*)cgp_state_kernel, "cgp_state_kernel"); });
+  once_per_device(attr_mask, [] { raise_lds_limit((const void*)cgp_state_kernel<false>, "cgp_state_kernel"); });
   CgpStateArgs a{};
   a.X = X; a.y = y; a.n = n; a.d = d; a.params = params; a.ldp = ldp; a.skip = skip;
   a.val = val; a.beta = beta; a.tau2 = tau2; a.loo = loo; a.status = status; a.keep = keep;
-  hipLaunchKernelGGL(cgp_state_kernel, dim3(nb), dim3(256), sizeof(double) * CgpCarve(n, d).total, st, a);
+  hipLaunchKernelGGL(cgp_state_kernel<false>, dim3(nb), dim3(256), sizeof(double) * CgpCarve(n, d).total, st, a);
+}
+
+void launch_cgp_state_sets(hipStream_t st, const double* Xs, int n, int d, const double* ys, const int* set,
+                           const double* params, int ldp, int nb, const int* skip, double* val, double* beta, double* tau2,
+                           double* loo, int* status) {
+  static unsigned long long attr_mask = 0;
+  once_per_device(attr_mask, [] { raise_lds_limit((const void*)cgp_state_kernel<true>, "cgp_state_kernel<sets>"); });
+  CgpStateArgs a{};
+  a.X = Xs; a.y = ys; a.n = n; a.d = d; a.params = params; a.ldp = ldp; a.skip = skip; a.set = set;
+  a.val = val; a.beta = beta; a.tau2 = tau2; a.loo = loo; a.status = status;
+  hipLaunchKernelGGL(cgp_state_kernel<true>, dim3(nb), dim3(256), sizeof(double) * CgpCarve(n, d).total, st, a);
 }
 
 void launch_cgp_predict(hipStream_t st, const double* X, int n, int d, const double* row, const double* Xtest, int m,

@@ -246,5 +246,15 @@ inline bool small_reg_sets_supported(int n, int d, int K) {
 inline Route small_route_sets(bool gauss, int n, int d, int K) {
   return gauss && small_reg_sets_supported(n, d, K) ? Route::Reg : Route::Blocked;
 }
+// the sets form of the profiled gradient (ccgp_profile_batch_sets with out_grad): the INV = 2 instances on the 16 x 16 grid,
+// one matrix per workgroup with its set's design in the shared xs slot -- the carve of the single-set instance, so the sets
+// form exists exactly where ccgp_profile_batch's gradient takes the Reg route (the in-LDS and blocked routes have no sets
+// form: their rows go set by set)
+inline bool small_reg_profile_grad_sets_supported(int n, int d, int K) {
+  return small_route(Op::Grad, true, n, d, K) == Route::Reg;
+}
+inline Route small_route_profile_grad_sets(bool gauss, int n, int d, int K) {
+  return gauss && small_reg_profile_grad_sets_supported(n, d, K) ? Route::Reg : Route::Blocked;
+}
 
 }  // namespace ccgp

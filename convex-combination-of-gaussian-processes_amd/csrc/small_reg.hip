@@ -68,6 +68,7 @@ struct RegArgs {
   VarForm vf;          // prediction (NE > 1, FAC): per-draw sigma2 and Q indexed by the global draw, the variance form
   // sets form (SETS instantiations, ccgp_loglik_batch_sets): evaluation b belongs to training set set[b] and reads its design at
   // X + set[b] n d, its right-hand side at y + set[b] n and its sigma2 at sigma2_set[set[b]]; `sigma2` is not read
+  // (the profiled gradient over sets, ccgp_profile_batch_sets, reads neither: sigma2_set stays null there)
   const int* set;
   const double* sigma2_set;
 };
@@ -129,13 +130,16 @@ __device__ __forceinline__ void mat_sync() {
 // right-hand side and sigma2 come from its set, everything after the loads is the code of the single-set instances in the
 // same order, hence their bits.  A template parameter for the same reason as PROF.  G = 16 has one matrix per workgroup, so
 // the set's design goes into the shared xs slot; G = 8 keeps one copy per matrix where the per-design form keeps it.
+// INV = 2 with PROF and SETS (ccgp_profile_batch_sets): the ordinary-kriging fits of many sets in lockstep.  The gradient
+// epilogue takes its differences from xs and its right-hand side from zb, so it is the single-set instance's code as it is.
 template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
   static_assert(!FAC || (NE == 1 && !FULL && !INV), "the factor is kept by the plain likelihood instantiation");
   static_assert(!PROF || ((NE == 1 || INV == 2) && INV != 1 && INV != 3 && !FAC), "sigma2 is concentrated out of the likelihood and of its gradient only");
-  static_assert(!SETS || (NE == 1 && !INV && !FAC && !PROF), "the sets form exists for the plain likelihood only");
+  static_assert(!SETS || (!FAC && ((NE == 1 && !INV && !PROF) || (INV == 2 && PROF))),
+                "the sets form exists for the plain likelihood and for the profiled gradient only");
   constexpr int TPM = G * G;       // threads per matrix
   constexpr int MPW = 256 / TPM;   // matrices per workgroup
   constexpr int NP = G * NB;       // padded order
@@ -217,7 +221,7 @@ void small_reg_kernel(RegArgs a) {
   double sw = 0.0;
   for (int c = 0; c < K; ++c) sw += w2[c];
   double sigma2 = a.sigma2;
-  if constexpr (SETS) sigma2 = a.sigma2_set[st];
+  if constexpr (SETS && !PROF) sigma2 = a.sigma2_set[st];   // PROF forms its own
   const double cs = sigma2 * sw;
   // (p^2 R1 + (1-p)^2 R2) / (p^2 + (1-p)^2) (HX:412) as a multiplication by the reciprocal: one
   // fp64 division costs ~30 instructions and this kernel is instruction-issue bound (<= 1 ulp apart)
@@ -1091,11 +1095,11 @@ static void launch_site_solve(hipStream_t s, const SiteArgs& a, int ns) {
 }
 
 // ---- explicit inverse of ONE draw's matrix (solve(R), HX:454), gradient, design gradient: one workgroup per matrix ------
-template <int NB, int INV, bool PROF = false>
+template <int NB, int INV, bool PROF = false, bool SETS = false>
 static void launch_inv(hipStream_t s, const RegArgs& a) {
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask, [] {
-    raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF>,
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF, SETS>,
                     INV == 1 ? "small_reg_kernel<inverse>" : INV == 2 ? "small_reg_kernel<gradient>" :
                     INV == 3 ? "small_reg_kernel<design gradient>" : "small_reg_kernel<leave-one-out>");
   });
@@ -1105,12 +1109,12 @@ static void launch_inv(hipStream_t s, const RegArgs& a) {
   for (int b0 = 0; b0 < a.B; b0 += kMaxGrid) {
     c.draw0 = a.draw0 + b0;
     c.B = a.B - b0 < kMaxGrid ? a.B - b0 : kMaxGrid;
-    hipLaunchKernelGGL((small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF>), dim3(c.B, 1), dim3(256), lds, s, c);
+    hipLaunchKernelGGL((small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF, SETS>), dim3(c.B, 1), dim3(256), lds, s, c);
   }
 }
-template <int INV, bool PROF = false>
+template <int INV, bool PROF = false, bool SETS = false>
 static void dispatch_inv(hipStream_t s, const RegArgs& a) {
-  pick<1, 8>((a.n + 15) / 16, [&](auto nb) { launch_inv<decltype(nb)::value, INV, PROF>(s, a); });
+  pick<1, 8>((a.n + 15) / 16, [&](auto nb) { launch_inv<decltype(nb)::value, INV, PROF, SETS>(s, a); });
 }
 
 template <int NE = 1>
@@ -1161,6 +1165,17 @@ void launch_small_reg_loglik_sets(hipStream_t s, const double* Xs, int n, int d,
   a.B = B; a.mode = mean_mode; a.tau2 = tau2; a.set = set; a.sigma2_set = sigma2;
   a.loglik = loglik; a.beta = beta; a.status = status;
   dispatch_sets(s, a);
+}
+
+// ccgp_profile_batch_sets where small_route_profile_grad_sets says Reg: launch_small_reg_profile with a gradient, row b on
+// training set set[b]; one workgroup per row, one launch
+void launch_small_reg_profile_grad_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set,
+                                        DrawView dv, int B, double* loglik, double* s2hat, double* beta, double* grad,
+                                        int* status) {
+  RegArgs a = reg_args(Xs, n, d, ys, dv);
+  a.B = B; a.set = set;
+  a.loglik = loglik; a.beta = beta; a.status = status; a.s2hat = s2hat; a.grad = grad; a.Btot = B;
+  dispatch_inv<2, true, true>(s, a);
 }
 
 void launch_small_reg_inverse(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int draw,

@@ -180,23 +180,43 @@ class _Start:
         self._begin_iteration()
 
 
-def minimize_starts(evaluate, starts, lower=-1.0, upper=1.0, m=5, maxit=100, factr=1e7, pgtol=0.0, max_backtracks=30):
+def minimize_starts(evaluate, starts, lower=-1.0, upper=1.0, m=5, maxit=100, factr=1e7, pgtol=0.0, max_backtracks=30,
+                    lowers=None, uppers=None, pass_live=False):
     """Minimise f from every start in lockstep.
 
     evaluate(X[k, ...]) -> (f[k], grad[k, ...], status[k]) evaluates k points of the shape of one start; a status != 0
     or a non-finite value marks a point as infeasible.  starts: [S, ...].  Returns a dict with x [S, ...] (the last
     accepted iterate of each start), f [S] (inf where the start itself could not be evaluated), converged [S],
-    iterations [S], message [S] and calls (the number of evaluate calls)."""
+    iterations [S], message [S], calls (the number of evaluate calls) and calls_per_start [S] (the calls a start took
+    part in: what `calls` would be had it run alone).
+
+    lower / upper: a scalar or one array of the shape of a start, shared by all starts.  lowers / uppers ([S, ...], both or
+    neither) give every start its own box instead -- the starts of several problems in one run, each under its problem's
+    bounds.  A start's trajectory depends on its own box and its own evaluations only, so it is the trajectory of a run
+    that holds that start alone under lower = lowers[s], upper = uppers[s].  pass_live: evaluate is called as
+    evaluate(X, live) with the indices (into starts) of the k starts whose points X holds, in ascending order."""
     starts = np.asarray(starts, dtype=np.float64)
     S, shape = starts.shape[0], starts.shape[1:]
-    st = [_Start(starts[s], lower, upper, m, maxit, factr, pgtol, max_backtracks) for s in range(S)]
+    if (lowers is None) != (uppers is None):
+        raise ValueError("minimize_starts: lowers and uppers come together")
+    if lowers is not None:
+        lowers, uppers = np.asarray(lowers, dtype=np.float64), np.asarray(uppers, dtype=np.float64)
+        if lowers.shape != starts.shape or uppers.shape != starts.shape:
+            raise ValueError("minimize_starts: lowers and uppers must have the shape of starts")
+        box = [(lowers[s].ravel(), uppers[s].ravel()) for s in range(S)]
+    else:
+        box = [(lower, upper)] * S
+    st = [_Start(starts[s], box[s][0], box[s][1], m, maxit, factr, pgtol, max_backtracks) for s in range(S)]
     calls = 0
+    per_start = np.zeros(S, dtype=np.int64)
     while True:
         live = [s for s in range(S) if st[s].running]
         if not live:
             break
-        f, g, status = evaluate(np.stack([st[s].trial.reshape(shape) for s in live]))
+        X = np.stack([st[s].trial.reshape(shape) for s in live])
+        f, g, status = evaluate(X, np.array(live)) if pass_live else evaluate(X)
         calls += 1
+        per_start[live] += 1
         for k, s in enumerate(live):
             st[s].feed(f[k], np.asarray(g[k]), status[k] == 0)
     return dict(x=np.stack([st[s].x.reshape(shape) for s in range(S)]),
@@ -204,7 +224,7 @@ def minimize_starts(evaluate, starts, lower=-1.0, upper=1.0, m=5, maxit=100, fac
                 converged=np.array([st[s].converged for s in range(S)]),
                 iterations=np.array([st[s].iterations for s in range(S)]),
                 message=[st[s].message for s in range(S)],
-                calls=calls)
+                calls=calls, calls_per_start=per_start)
 
 
 def make_starts(n_starts, n, d, rng):

@@ -486,7 +486,10 @@ def factors_frame(gp, start, N, samp_size, batch_size, alpha_geweke, D_train, si
 def _add_cgp_columns(table, gp, D_test, D_train, y_train, cgp):
     """compare.GP's CGP columns (GV:654-660): CGP(D.train, y.train), then predict.CGP(cgp, D.test, PI = TRUE)."""
     from . import cgp as cgp_mod
-    est = cgp_mod.CGP(gp.h, D_train, y_train, **(cgp if isinstance(cgp, dict) else {}))
+    if isinstance(cgp, dict) and "est" in cgp:
+        est = cgp["est"]   # a fitted model (cgp.CGP's or cgp.CGP_sets' dict): nothing is fitted here
+    else:
+        est = cgp_mod.CGP(gp.h, D_train, y_train, **(cgp if isinstance(cgp, dict) else {}))
     pred = cgp_mod.predict_CGP(gp.h, est, D_test, PI=True)
     table.update(y_hat_CGP=pred["Yp"], LL_CGP=pred["Y_low"], UL_CGP=pred["Y_up"], CGP=est)
     return table
@@ -531,6 +534,8 @@ def _add_single_columns(table, gp, D_test, alpha, D_train, y_train, single):
     base = getattr(gp.h, "_handle", gp.h)
     given = dict(single) if isinstance(single, dict) else {}
     model = {k: given.pop(k) for k in ("theta", "sigma2", "beta") if k in given}
+    if "est" in given:   # a fitted model as the fit routine returned it: it goes into the table as it is
+        model = given.pop("est")
     if one_d:
         D = np.asarray(D_train, dtype=np.float64).reshape(-1, 1)
         if "theta" not in model:
@@ -557,9 +562,11 @@ def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=N
     (y.hat.Combined, Quant.Combined, LL.Combined, UL.Combined, y.true).  exact=True takes Quant and the interval from
     the exact posterior predictive on the device (gp.prediction) instead of sampling one variate per draw: rng is
     ignored, the tables stay on the device, and the keys are the same without mean / var.  cgp (default off; True, or a dict
-    of cgp.CGP's keyword arguments) adds the table's CGP model (GV:654-660): y_hat_CGP, LL_CGP, UL_CGP and the fit as CGP.
+    of cgp.CGP's keyword arguments) adds the table's CGP model (GV:654-660): y_hat_CGP, LL_CGP, UL_CGP and the fit as CGP;
+    cgp=dict(est=<a dict of cgp.CGP or cgp.CGP_sets>) takes a fitted model instead of fitting.
     single (default off) adds the ordinary-kriging model: True fits it on the device (ordinary_kriging_fit; for a 1-D gp
-    matern_MLEs), a dict(theta=..., sigma2=...) takes a given model, and further keys go to the fit.  It adds y_hat_single,
+    matern_MLEs), a dict(theta=..., sigma2=...) or dict(est=<a dict of ordinary_kriging_fit>) takes a given model, and
+    further keys go to the fit.  It adds y_hat_single,
     LL_single, UL_single = y_hat -+ qt(1 - alpha / 2, n - 1) sqrt(max(var, 0)) -- var in the plug-in form for the 2-D /
     emulator scripts, in the unbiased form (and returned as single_var) for the 1-D scripts -- and the model as single."""
     if single:
@@ -782,6 +789,63 @@ def ordinary_kriging_fit(handle, D_train, y_train, starts=8, rng=0, extra_starts
                 converged=res["converged"], calls=res["calls"] + 1, evaluations=count["points"] + 1)
 
 
+def ordinary_kriging_fit_sets(handle, D_trains, y_trains, starts=8, rng=0, extra_starts=None):
+    """ordinary_kriging_fit for C training sets of one shape in lockstep -> a list with, per set, the dict
+    ordinary_kriging_fit(handle, D_trains[c], y_trains[c], starts, rng, extra_starts) returns, bit for bit.
+
+    Every set draws its kriging_starts from its own generator (rng: one seed for every set, as C separate fits would take
+    it, or a list of C).  The starts of all sets run through ONE design.minimize_starts, and each evaluator call is ONE
+    ccgp_profile_batch_sets that carries every start of every set still running; the final value-only evaluation of the C
+    best points is one call of the value-only form.  Starts are independent of each other -- a start's trajectory depends on
+    its own evaluations only, and a row's bits on its own set only -- so a set's starts take the steps they take alone, and
+    the number of gradient calls of the group is the LARGEST per-set count, not the sum.  Each dict's calls / evaluations
+    are that set's own (the calls its starts took part in, the final one included): the group made max(calls) device
+    calls."""
+    from .design import minimize_starts
+
+    Ds = [np.asarray(D, dtype=np.float64) for D in D_trains]
+    ys = [np.asarray(y, dtype=np.float64).ravel() for y in y_trains]
+    C = len(Ds)
+    if C < 1 or len(ys) != C:
+        raise ValueError("ordinary_kriging_fit_sets: one response per design, at least one set")
+    if any(D.ndim != 2 or D.shape != Ds[0].shape for D in Ds) or any(y.shape[0] != Ds[0].shape[0] for y in ys):
+        raise ValueError("ordinary_kriging_fit_sets: the sets of one call have one shape (n, d)")
+    seeds = list(rng) if isinstance(rng, (list, tuple)) else [rng] * C
+    if len(seeds) != C:
+        raise ValueError("ordinary_kriging_fit_sets: rng is one seed, or one per set")
+    x0 = [kriging_starts(Ds[c], starts, seeds[c], extra_starts) for c in range(C)]
+    S = x0[0].shape[0]
+    owner = np.repeat(np.arange(C), S)
+    Xs, Y = np.stack(Ds), np.stack(ys)
+    points = np.zeros(C, dtype=np.int64)
+
+    def evaluate(logth, live):
+        theta = np.exp(logth)
+        rows = np.concatenate([np.ones((theta.shape[0], 1)), theta], axis=1)
+        set_of = owner[live]
+        ll, _, _, g, st = handle.profile_batch_sets(Xs, Y, 1, rows, set_of, grad=True)
+        np.add.at(points, set_of, 1)
+        return -ll, -(g[:, 1:] * theta), st
+
+    res = minimize_starts(evaluate, np.concatenate(x0), lower=-12.0, upper=12.0, pass_live=True)
+    best = []
+    for c in range(C):
+        f = res["f"][c * S:(c + 1) * S]
+        if not np.isfinite(f).any():
+            raise RuntimeError("ordinary_kriging_fit_sets: the likelihood failed at every start of set %d" % c)
+        best.append(c * S + int(np.argmin(np.where(np.isfinite(f), f, np.inf))))
+    thetas = np.exp(res["x"][best])
+    ll, s2, beta, _, _ = handle.profile_batch_sets(Xs, Y, 1, np.concatenate([np.ones((C, 1)), thetas], axis=1), np.arange(C),
+                                                   grad=False)
+    out = []
+    for c in range(C):
+        sl = slice(c * S, (c + 1) * S)
+        out.append(dict(sigma2=float(s2[c]), theta=thetas[c], beta=float(beta[c]), loglik=float(ll[c]), f=res["f"][sl],
+                        x=res["x"][sl], converged=res["converged"][sl], calls=int(res["calls_per_start"][sl].max()) + 1,
+                        evaluations=int(points[c]) + 1))
+    return out
+
+
 def matern_profile(handle, D, y, nu, thetas):
     """log.likeli of the 1-D scripts (D1:424-444) for an array of scale parameters in ONE value-only device call under the
     Matern(nu) family: log det R(theta) + n log sigma2.MLE(theta), with beta.MLE and sigma2.MLE (D1:411-415) at each theta.
@@ -884,7 +948,7 @@ def stack_tables(tables):
 
 def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size=None, start=None, sigma2s=None,
           theta1_pars=None, theta2_pars=None, rngs=None, max_proposals=None, speculate=0, laplace=None, cgp=False,
-          single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None):
+          single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None, lockstep_fits=True):
     """The reference's simulation study (GV:689-762 declares nine training sets and fits one): every set of `sets` -- a list
     of (D_train, y_train, D_test, y_test) -- fitted and compared, the sets of one shape (n, d) in lockstep.  Per group:
     sigma2 per set from ordinary_kriging_fit (or sigma2s[i] as given), then laplace_sets and Metro_sets with one generator
@@ -894,9 +958,18 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     by default, a zero appended where the script has a fourth parameter), or one per set.  out_dir: one results table per
     set through write_results_table (`results_<i>.txt`, i from 1; input_names default x1 ..).  logpost_sets_fn(group
     indices) -> evaluator and compare_fn replace the device (tests).
+    lockstep_fits (default on): the comparator fits run in lockstep across the sets of a group as well -- sigma2 from
+    ordinary_kriging_fit_sets for the sets whose sigma2 was not given; with single=True that same fitted model goes to
+    compare_GP instead of being fitted a second time (a dict of fit keywords in `single` asks for a fit of its own, also in
+    lockstep); with cgp the models come from cgp.CGP_sets (a cgp dict's keywords passed on; a seed in `rng` is every set's
+    seed, as it is cgp.CGP's per call; a Generator in `rng` is one stream advancing from set to set, so those CGP fits stay
+    in compare_GP, set after set) -- and compare_GP only predicts.  Tables, summaries, sigma2, draws and chains have the
+    same bits either way.  The per-set loop stays for a 1-D (Matern) gp, whose comparator is matern_MLEs, where compare_fn
+    or logpost_sets_fn replaces the device, and with lockstep_fits=False.
     Returns dict(tables, summaries, pooled: comparison_summary of the stacked tables, sigma2, draws, beta, chains,
-    groups: {(n, d): indices}, calls and seconds: device calls and wall time of the sigma2, laplace, metro and predict
-    parts)."""
+    groups: {(n, d): indices}, calls and seconds: device calls and wall time of the sigma2, single, cgp, laplace, metro and
+    predict parts; per set the single and cgp fits happen inside compare_GP, so their seconds are part of predict's and
+    their calls are read from the fitted models)."""
     import time
 
     sets = list(sets)
@@ -912,18 +985,67 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     if start is None:
         start = np.concatenate([[1.0, 1.0, 0.0], np.zeros(npar - 3)])
     starts = np.broadcast_to(np.asarray(start, dtype=np.float64), (C, np.shape(start)[-1]))
+    lockstep = bool(lockstep_fits) and compare_fn is None and logpost_sets_fn is None and not hasattr(gp, "nu")
     compare_fn = compare_fn or compare_GP
-    calls = dict(sigma2=0, laplace=0, metro=0, predict=0)
-    secs = dict(sigma2=0.0, laplace=0.0, metro=0.0, predict=0.0)
+    calls = dict(sigma2=0, single=0, cgp=0, laplace=0, metro=0, predict=0)
+    secs = dict(sigma2=0.0, single=0.0, cgp=0.0, laplace=0.0, metro=0.0, predict=0.0)
     s2 = [None] * C if sigma2s is None else [float(v) for v in sigma2s]
     chains, tables, summaries = [None] * C, [None] * C, [None] * C
+    single_of, cgp_of = [single] * C, [cgp] * C   # what compare_GP is told per set
+    cgp_in_compare = bool(cgp)   # compare_GP fits the CGP itself
     t0 = time.perf_counter()
-    for i in range(C):
-        if s2[i] is None:
-            okf = ordinary_kriging_fit(getattr(gp.h, "_handle", gp.h), sets[i][0], sets[i][1])
-            s2[i] = okf["sigma2"]
-            calls["sigma2"] += okf["calls"]
-    secs["sigma2"] = time.perf_counter() - t0
+    if lockstep:
+        base = getattr(gp.h, "_handle", gp.h)
+        given = dict(single) if isinstance(single, dict) else {}
+        has_model = "est" in given or ("theta" in given and "sigma2" in given)
+        fit_kw = {k: v for k, v in given.items() if k not in ("theta", "sigma2", "beta", "est")}
+        for shape, idx in groups.items():
+            # the sigma2 fit IS the single GP's fit when the latter asks for nothing of its own
+            share = bool(single) and not has_model and not fit_kw
+            todo = [i for i in idx if s2[i] is None or share]
+            if not todo:
+                continue
+            part = "sigma2" if any(s2[i] is None for i in todo) else "single"   # every sigma2 given: the single GP's fit alone
+            t0 = time.perf_counter()
+            fits = ordinary_kriging_fit_sets(base, [sets[i][0] for i in todo], [sets[i][1] for i in todo])
+            calls[part] += max(f["calls"] for f in fits)
+            for i, f in zip(todo, fits):
+                if s2[i] is None:
+                    s2[i] = f["sigma2"]
+                if share:
+                    single_of[i] = dict(est=f)
+            secs[part] += time.perf_counter() - t0   # the time goes where the calls go
+        t0 = time.perf_counter()
+        if single and not has_model and fit_kw:
+            for shape, idx in groups.items():
+                fits = ordinary_kriging_fit_sets(base, [sets[i][0] for i in idx], [sets[i][1] for i in idx], **fit_kw)
+                calls["single"] += max(f["calls"] for f in fits)
+                for i, f in zip(idx, fits):
+                    single_of[i] = dict(est=f)
+        secs["single"] += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        cgp_kw = dict(cgp) if isinstance(cgp, dict) else {}
+        # a Generator in the dict is ONE stream that cgp.CGP advances from set to set: only the per-set loop (compare_GP, in
+        # set order) reproduces it.  A seed is a fresh default_rng(seed) per CGP call, which is CGP_sets' rngs=[seed] * C.
+        cgp_lockstep = bool(cgp) and "est" not in cgp_kw and not isinstance(cgp_kw.get("rng"), np.random.Generator)
+        if cgp_lockstep:
+            from . import cgp as cgp_mod
+            seed = cgp_kw.pop("rng", 0)
+            for shape, idx in groups.items():
+                ests = cgp_mod.CGP_sets(base, [sets[i][0] for i in idx], [sets[i][1] for i in idx],
+                                        rngs=[seed] * len(idx), **cgp_kw)
+                calls["cgp"] += ests[0]["calls"]
+                for i, e in zip(idx, ests):
+                    cgp_of[i] = dict(est=e)
+        secs["cgp"] = time.perf_counter() - t0
+        cgp_in_compare = bool(cgp) and "est" not in cgp_kw and not cgp_lockstep   # the one stream, set after set
+    else:
+        for i in range(C):
+            if s2[i] is None:
+                okf = ordinary_kriging_fit(getattr(gp.h, "_handle", gp.h), sets[i][0], sets[i][1])
+                s2[i] = okf["sigma2"]
+                calls["sigma2"] += okf["calls"]
+        secs["sigma2"] = time.perf_counter() - t0
     for shape, idx in groups.items():
         D_trains = [np.asarray(sets[i][0], dtype=np.float64) for i in idx]
         ys = [np.asarray(sets[i][1], dtype=np.float64).ravel() for i in idx]
@@ -960,9 +1082,15 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     betas = [ch["beta"][keep] for ch in chains]
     t0 = time.perf_counter()
     for i, (D_train, y_train, D_test, y_test) in enumerate(sets):
-        tables[i] = compare_fn(gp, D_test, alpha, y_test, draws[i], D_train, s2[i], y_train, exact=True, cgp=cgp, single=single)
+        tables[i] = compare_fn(gp, D_test, alpha, y_test, draws[i], D_train, s2[i], y_train, exact=True, cgp=cgp_of[i],
+                               single=single_of[i])
         summaries[i] = comparison_summary(tables[i])
         calls["predict"] += 1
+        # the fits compare_GP made itself
+        if not lockstep and single and isinstance(tables[i].get("single"), dict):
+            calls["single"] += int(tables[i]["single"].get("calls", 0))
+        if cgp_in_compare and isinstance(tables[i].get("CGP"), dict):
+            calls["cgp"] += int(tables[i]["CGP"].get("calls", 0))
     secs["predict"] = time.perf_counter() - t0
     if out_dir is not None:
         import os

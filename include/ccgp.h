@@ -282,6 +282,39 @@ int ccgp_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const doub
                       int prior_id, const double* theta_t /* B x q */, const int* set, int B,
                       const double* prior_pars, double* out_val, double* out_beta, double* out_loglik, int* status);
 
+/* ---- the comparator fits over many training sets of one shape: what compare.GP's table holds beside the Combined GP -------
+ * The sets form of ccgp_profile_batch (the ordinary-kriging MLE behind sigma2 and the single-GP columns) and of
+ * ccgp_cgp_state_batch (CGP's candidates, refinement points and jackknife), so that a study's comparator fits run in lockstep
+ * across its sets as its chains do.  Xs, ys, set as in ccgp_loglik_batch_sets; params, the outputs and their NULLs as in the
+ * single-set call.
+ *   Bits.  Row b has exactly the bits ccgp_profile_batch / ccgp_cgp_state_batch returns for it on set set[b] alone -- for the
+ *     CGP call including its skip[b]: they do not depend on C, B, the row's position, the order of `set`, or where the
+ *     workspace limit or the 65535-workgroup grid cuts the call.
+ *   Failure.  status[b] is the 1-based pivot and the row's outputs are NaN, the whole gradient row included; the other rows are
+ *     untouched; the return value is the number of failed rows.  Q == 0 as in ccgp_profile_batch: sigma2 = 0, loglik = +Inf,
+ *     gradient row NaN, status 0.
+ *   Arguments.  C < 1, a set[b] outside 0 .. C-1, a NULL required pointer (everything but out_beta, out_grad, status; for the
+ *     CGP call everything but skip, out_beta, out_tau2, out_loo, status) or a skip[b] that ccgp_cgp_state_batch refuses return
+ *     CCGP_EINVAL before anything is copied or launched, outputs untouched.  B == 0 returns CCGP_OK.  A set no row refers to
+ *     is legal.  CCGP_EUNSUPPORTED exactly where the single-set call says it.
+ *   Routes.  ccgp_profile_batch_sets with out_grad, Gaussian family, n <= 128 where the register-resident gradient instance
+ *     fits (where ccgp_profile_batch's gradient runs in LDS as one workgroup per row): ONE launch per chunk for all rows.
+ *     Every other shape and family the single-set call serves (n > 128, the in-LDS fallback, Matern and spline value-only):
+ *     the rows are grouped by set and each group goes through ccgp_profile_batch.  The value-only form (out_grad == NULL)
+ *     takes that grouped route at EVERY shape: a fit calls it once, and one-launch instances for it would be 42 more kernels
+ *     (both grids, every block count, general and full) in the file whose compile time is already the build's longest; the
+ *     bits contract is the same either way.  ccgp_cgp_state_batch_sets: one launch per chunk for every supported shape.
+ * Host pointers only, blocking; the sets go up once per call, not once per chunk; ccgp_reserve does not cover the staging.
+ * Not in this version: _dev variants, a ccgp_multi wrapper, an R shim. */
+int ccgp_profile_batch_sets(ccgp_handle* h, const double* Xs /* C blocks n x d, column-major each */, int n, int d,
+                            const double* ys /* C blocks of n */, int C, int K, const double* params /* B x P */,
+                            const int* set /* B, 0 .. C-1 */, int B, double* out_loglik, double* out_sigma2,
+                            double* out_beta /* NULL ok */, double* out_grad /* B x P column-major, NULL ok */,
+                            int* status /* NULL ok */);
+int ccgp_cgp_state_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C,
+                              const double* params /* B x (2d+2) */, const int* set, int B, const int* skip /* B or NULL */,
+                              double* out_val, double* out_beta, double* out_tau2, double* out_loo, int* status);
+
 /* ---- a9: likeli.hyperpars HX:549-575 / choose.hyperpars HX:584-595, ADV:552-599 -------
  * hyper is G x 4 (alpha1 beta1 alpha2 beta2).  For each row: N base-2 Halton quantiles
  * u_j, p = u_j, theta1 = qigamma(u_j, a1, b1), theta2 = qigamma(u_j, a2, b2), mode-1

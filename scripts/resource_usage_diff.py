@@ -3,7 +3,9 @@ Input: the remark output of each build, e.g. for csrc/small_reg.hip
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c small_reg.hip -o /dev/null 2> new.txt
 (`make -C csrc resource-usage` prints the same remarks) and the same command on the other tree.  Kernels are matched by
 demangled name; a template argument the new build appended with its default value (`, false` at the end of
-small_reg_kernel's list) is dropped for the match, so an instance that existed before is compared with itself.  Prints every
+small_reg_kernel's list) is dropped for the match, so an instance that existed before is compared with itself; likewise a
+kernel the new build turned into a template over switches (cgp_state_kernel<false>) matches the parent's plain kernel where
+every switch is `false`.  Prints every
 difference, the counts, and the kernels only the new build has -- each beside the pre-existing instance with the same
 leading arguments.  Needs c++filt.  Exit status 1 when a pre-existing kernel differs.
     python scripts/resource_usage_diff.py parent.txt new.txt [--appended 1]"""
@@ -43,10 +45,14 @@ def main():
     args = ap.parse_args()
     par, new = parse(args.parent), parse(args.new)
     dp, dn = demangle(list(par)), demangle(list(new))
+    parent_names = set(dp.values())
     nargs = {len(re.match(r".*?<([^>]*)>", v).group(1).split(",")) for v in dp.values() if "small_reg_kernel<" in v}
 
     def split(name):
         """(name without the appended arguments, True when they are not all `false`)"""
+        m = re.match(r"void (.*?)<((?:true|false)(?:, (?:true|false))*)>(\(.*)", name)
+        if m and m.group(1) + m.group(3) in parent_names:   # a plain kernel of the parent that became a template over switches
+            return m.group(1) + m.group(3), "true" in m.group(2)
         m = re.match(r"(.*?<)([^>]*)(>.*)", name)
         if not m or "small_reg_kernel<" not in name:
             return name, False
@@ -75,7 +81,8 @@ def main():
     show = KEYS[:1] + KEYS[2:5]
     for name in sorted(added, key=lambda s: [int(x) for x in re.findall(r"\d+", s)] + [s]):
         base = old_form.get(name, {})
-        print("new %s: %s" % (re.search(r"<([^>]*)>", name).group(1),
+        arg = re.search(r"<([^>]*)>", name)
+        print("new %s: %s" % (arg.group(1) if arg else re.search(r"(\w+)\(", name).group(1) + "<true>",
                               " | ".join("%s %s (%s)" % (q.split(" [")[0], added[name].get(q), base.get(q, "-")) for q in show)))
     sys.exit(1 if differ else 0)
 
