@@ -805,6 +805,16 @@ MARGINAL_TOL_C = 4.0               # 32 x 0.108 = 3.46, rounded up to a power of
 GRID_NODE_Q = 2e-13
 
 
+# The max-entropy design criteria (ccgp_mixed_logdet_designs, ccgp_mixed_logdet_grad_designs) are held the same way, by
+# tests/design_exact.py: |ld_dev - ld_ref| <= C_LD unit_ld, |g_dev - g_ref| <= C_G unit_g entry by entry, units first order in
+# a relative error eps (1 + rho_ab) of every entry of R (no condition number).  The fp64 LAPACK evaluation with the exponent in
+# the expanded form (design_exact.fp64_restatement) reaches at most these many units over that module's case list
+# (tests/test_design_exact_host.py measures both on every run); C is 32 times the figure, rounded up to a power of two and
+# capped at GRAD_TOL_C (design_exact.design_constants): C_LD = 8, C_G = 16.  Nothing here was taken from a device run.
+DESIGN_LD_LAPACK_MAX = 0.245       # measured: 0.2443 at the one-point design n = 1, d = 1, K = 1 (`instances`, design 1)
+DESIGN_GRAD_LAPACK_MAX = 0.296     # measured: 0.2951 at n = 64, d = 1, K = 1 (`instances`, design 0)
+
+
 def marginal_parts(X, y, row, K, d, sigma2, tau2, dtype=np.longdouble, expanded=False, Rc=None):
     """The mode-1 counterpart of loglik_grad_parts in dtype (long double: the hand-written Cholesky of Sigma0 and the rank-one
     term in closed form; fp64: LAPACK on Sigma):

@@ -1,7 +1,8 @@
 """ccgp_mixed_logdet_grad_designs -- d log det R_mixed / d X of candidate designs (small_reg_kernel, INV = 3) -- and the
 design search built on it (CombinedGP.Entropy_optim / Batch_Entropy_optim, Batch Sequential ME Design.R:886-948) on the
 device: against a numpy fp64 reference and mpmath, batch independence, failures, limits, the stored first-batch design
-of the reference, and the R shim routine."""
+of the reference, and the R shim routine.  (tests/test_gpu_design_exact.py holds the same values component-wise to a
+long-double reference, on every instance of the kernel.)"""
 import os
 import sys
 
