@@ -150,6 +150,27 @@ def _ipt(a):
     return a.ctypes.data_as(_ip) if a is not None else None
 
 
+# what the single-set batch wrappers and their sets forms share
+def _check_columns(P, want, formula):
+    if P != want:
+        raise ValueError("params must have %s = %d columns" % (formula, want))
+
+
+def _skip_rows(skip, B):
+    """skip as int32[B], or None."""
+    if skip is None:
+        return None
+    sk = np.ascontiguousarray(np.ravel(skip), dtype=np.int32)
+    if sk.shape[0] != B:
+        raise ValueError("skip must have one entry per row of params")
+    return sk
+
+
+def _outputs(B, count):
+    """`count` double arrays of B entries and, last, the B status words."""
+    return [np.empty(B) for _ in range(count)] + [np.zeros(B, dtype=np.int32)]
+
+
 def halton_base2(N):
     out = np.empty(int(N), dtype=np.float64)
     rc = lib().ccgp_halton_base2(int(N), _p(out))
@@ -288,10 +309,8 @@ class MultiHandle:
         n, d = X.shape
         params = _f(np.atleast_2d(params))
         B, P = params.shape
-        if P != K + K * d:
-            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
-        ll, beta = np.empty(B), np.empty(B)
-        st = np.zeros(B, dtype=np.int32)
+        _check_columns(P, K + K * d, "K + K*d")
+        ll, beta, st = _outputs(B, 2)
         self._chk(lib().ccgp_multi_loglik_batch(self._m, _p(X), n, d, _p(y), K, _p(params), B, float(sigma2),
                                                 int(mean_mode), float(tau2), _p(ll), _p(beta), _ipt(st)))
         return ll, beta, st
@@ -513,10 +532,8 @@ class Handle:
         n, d = X.shape
         params = _f(np.atleast_2d(params))
         B, P = params.shape
-        if P != K + K * d:
-            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
-        ll, beta = np.empty(B), np.empty(B)
-        st = np.zeros(B, dtype=np.int32)
+        _check_columns(P, K + K * d, "K + K*d")
+        ll, beta, st = _outputs(B, 2)
         self._chk(lib().ccgp_loglik_batch(self._h, _p(X), n, d, _p(y), K, _p(params), B, float(sigma2),
                                           int(mean_mode), float(tau2), _p(ll), _p(beta), _ipt(st)))
         return ll, beta, st
@@ -541,11 +558,9 @@ class Handle:
         n, d = X.shape
         params = _f(np.atleast_2d(params))
         B, P = params.shape
-        if P != K + K * d:
-            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
-        ll, s2, beta = np.empty(B), np.empty(B), np.empty(B)
+        _check_columns(P, K + K * d, "K + K*d")
+        ll, s2, beta, st = _outputs(B, 3)
         g = np.empty((B, P), dtype=np.float64, order="F") if grad else None
-        st = np.zeros(B, dtype=np.int32)
         self._chk(lib().ccgp_profile_batch(self._h, _p(X), n, d, _p(y), K, _p(params), B, _p(ll), _p(s2), _p(beta),
                                            _p(g), _ipt(st)))
         return ll, s2, beta, g, st
@@ -558,16 +573,10 @@ class Handle:
         n, d = X.shape
         params = _f(np.atleast_2d(params))
         B, P = params.shape
-        if P != 2 * d + 2:
-            raise ValueError("params must have 2 d + 2 = %d columns" % (2 * d + 2))
-        sk = None
-        if skip is not None:
-            sk = np.ascontiguousarray(np.ravel(skip), dtype=np.int32)
-            if sk.shape[0] != B:
-                raise ValueError("skip must have one entry per row of params")
-        val, beta, tau2 = np.empty(B), np.empty(B), np.empty(B)
+        _check_columns(P, 2 * d + 2, "2 d + 2")
+        sk = _skip_rows(skip, B)
+        val, beta, tau2, st = _outputs(B, 3)
         loo = np.empty(B) if sk is not None else None
-        st = np.zeros(B, dtype=np.int32)
         self._chk(lib().ccgp_cgp_state_batch(self._h, _p(X), n, d, _p(y), _p(params), B, _ipt(sk), _p(val), _p(beta),
                                              _p(tau2), _p(loo), _ipt(st)))
         return val, beta, tau2, loo, st
@@ -613,8 +622,7 @@ class Handle:
         theta_t = _f(np.atleast_2d(theta_t))
         B = theta_t.shape[0]
         pp = _f(np.ravel(prior_pars)) if prior_pars is not None else None
-        val, beta, ll = np.empty(B), np.empty(B), np.empty(B)
-        st = np.zeros(B, dtype=np.int32)
+        val, beta, ll, st = _outputs(B, 3)
         self._chk(lib().ccgp_logpost_batch(self._h, _p(X), n, d, _p(y), float(sigma2), int(prior_id), _p(theta_t), B,
                                            _p(pp), _p(val), _p(beta), _p(ll), _ipt(st)))
         return val, beta, ll, st
@@ -640,10 +648,8 @@ class Handle:
         params = _f(np.atleast_2d(params))
         B, P = params.shape
         Xb, yb, s2, idx, C, n, d = self._sets(Xs, ys, sigma2s, set_of, B)
-        if P != K + K * d:
-            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
-        ll, beta = np.empty(B), np.empty(B)
-        st = np.zeros(B, dtype=np.int32)
+        _check_columns(P, K + K * d, "K + K*d")
+        ll, beta, st = _outputs(B, 2)
         self._chk(lib().ccgp_loglik_batch_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, K, _p(params), _ipt(idx), B,
                                                int(mean_mode), float(tau2), _p(ll), _p(beta), _ipt(st)))
         return ll, beta, st
@@ -655,8 +661,7 @@ class Handle:
         B = theta_t.shape[0]
         Xb, yb, s2, idx, C, n, d = self._sets(Xs, ys, sigma2s, set_of, B)
         pp = _f(np.ravel(prior_pars)) if prior_pars is not None else None
-        val, beta, ll = np.empty(B), np.empty(B), np.empty(B)
-        st = np.zeros(B, dtype=np.int32)
+        val, beta, ll, st = _outputs(B, 3)
         self._chk(lib().ccgp_logpost_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, int(prior_id), _p(theta_t), _ipt(idx), B,
                                           _p(pp), _p(val), _p(beta), _p(ll), _ipt(st)))
         return val, beta, ll, st
@@ -668,11 +673,9 @@ class Handle:
         params = _f(np.atleast_2d(params))
         B, P = params.shape
         Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, B)
-        if P != K + K * d:
-            raise ValueError("params must have K + K*d = %d columns" % (K + K * d))
-        ll, s2, beta = np.empty(B), np.empty(B), np.empty(B)
+        _check_columns(P, K + K * d, "K + K*d")
+        ll, s2, beta, st = _outputs(B, 3)
         g = np.empty((B, P), dtype=np.float64, order="F") if grad else None
-        st = np.zeros(B, dtype=np.int32)
         self._chk(lib().ccgp_profile_batch_sets(self._h, _p(Xb), n, d, _p(yb), C, K, _p(params), _ipt(idx), B, _p(ll), _p(s2),
                                                 _p(beta), _p(g), _ipt(st)))
         return ll, s2, beta, g, st
@@ -684,16 +687,10 @@ class Handle:
         params = _f(np.atleast_2d(params))
         B, P = params.shape
         Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, B)
-        if P != 2 * d + 2:
-            raise ValueError("params must have 2 d + 2 = %d columns" % (2 * d + 2))
-        sk = None
-        if skip is not None:
-            sk = np.ascontiguousarray(np.ravel(skip), dtype=np.int32)
-            if sk.shape[0] != B:
-                raise ValueError("skip must have one entry per row of params")
-        val, beta, tau2 = np.empty(B), np.empty(B), np.empty(B)
+        _check_columns(P, 2 * d + 2, "2 d + 2")
+        sk = _skip_rows(skip, B)
+        val, beta, tau2, st = _outputs(B, 3)
         loo = np.empty(B) if sk is not None else None
-        st = np.zeros(B, dtype=np.int32)
         self._chk(lib().ccgp_cgp_state_batch_sets(self._h, _p(Xb), n, d, _p(yb), C, _p(params), _ipt(idx), B, _ipt(sk), _p(val),
                                                   _p(beta), _p(tau2), _p(loo), _ipt(st)))
         return val, beta, tau2, loo, st

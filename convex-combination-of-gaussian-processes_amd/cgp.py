@@ -81,74 +81,14 @@ def CGP(handle, X, y, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, 
     """CGP(X, yobs, ...) of GV:58-236 -> dict with the reference's fields (lambda, theta, alpha, bandwidth, Sig_matrix: its
     diagonal, sf, res2, temp_matrix, mu, tau2, beststart, objval, rmscv, Yp_jackknife, X, yobs), the fit's bounds, and
     calls / evaluations: device calls and the parameter rows they carried (seconds: host clock around the three steps).  invQ
-    is not returned: predict_CGP solves with the factor the device keeps."""
+    is not returned: predict_CGP solves with the factor the device keeps.  It is _fit_sets' C = 1 case over
+    ccgp_cgp_state_batch."""
     h = _plain(handle)
-    DD = np.asarray(X, dtype=np.float64)
-    yobs = np.asarray(y, dtype=np.float64).ravel()
-    n, p = DD.shape
-    Xs, scales = standardise(DD)
-    lower, upper = bounds(Xs, nugget_l, theta_l, alpha_l, kappa_u)
-    n_par = p + 3
-    gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
-    count = dict(calls=0, rows=0)
 
-    def objective(ww):
-        """var.MLE.DK at the rows of ww in one device call -> (val with GV:130-131 applied, status)."""
-        val, _, _, _, st = h.cgp_state_batch(Xs, yobs, rows_from_ww(ww))
-        count["calls"] += 1
-        count["rows"] += ww.shape[0]
-        return np.where(np.isfinite(val), val, NONFINITE), st
+    def state(designs, Y, rows, set_of, skip):
+        return h.cgp_state_batch(designs[0], Y[0], rows, skip=skip)
 
-    starts = lower + lhd(N_CANDIDATE_BASE + num_starts, n_par, gen) * (upper - lower)       # GV:144-148
-    clock = [time.perf_counter()]
-    cand, _ = objective(starts)
-    clock.append(time.perf_counter())
-    order = np.argsort(cand, kind="stable")[:num_starts]                                   # GV:150-151
-    Starts = starts[np.sort(order)]
-
-    def evaluate(W):
-        k = W.shape[0]
-        hi = np.minimum(W + step, upper)
-        lo = np.maximum(W - step, lower)
-        pts = np.repeat(W[:, None, :], 1 + 2 * n_par, axis=1)
-        for j in range(n_par):
-            pts[:, 1 + 2 * j, j] = hi[:, j]
-            pts[:, 2 + 2 * j, j] = lo[:, j]
-        f, st = objective(pts.reshape(-1, n_par))
-        f = f.reshape(k, 1 + 2 * n_par)
-        g = (f[:, 1::2] - f[:, 2::2]) / (hi - lo)
-        return f[:, 0], g, st.reshape(k, -1)[:, 0]
-
-    res = minimize_starts(evaluate, Starts, lower=lower, upper=upper)                      # GV:152-154
-    clock.append(time.perf_counter())
-    if not np.isfinite(res["f"]).any():
-        raise RuntimeError("CGP: the objective failed at every start")
-    best = int(np.argmin(np.where(np.isfinite(res["f"]), res["f"], np.inf)))              # GV:155-157
-    par = res["x"][best]
-    lam, st_theta, kappa, bw = float(par[0]), par[1:1 + p], float(par[1 + p]), float(par[2 + p])
-    theta = st_theta / scales ** 2                                                         # GV:164-165
-    alpha = (kappa + st_theta) / scales ** 2
-    row = np.concatenate([[lam], theta, alpha, [bw]])
-
-    clock.append(time.perf_counter())
-    _, _, _, loo, st = h.cgp_state_batch(DD, yobs, np.repeat(row[None], n, axis=0), skip=np.arange(n))   # GV:166-198
-    clock.append(time.perf_counter())
-    count["calls"] += 1
-    count["rows"] += n
-    rmscv = float(np.sqrt(np.sum((yobs - loo) ** 2) / n))
-
-    _, keep, status = h.cgp_predict(DD, yobs, row, np.empty((0, p)))                        # GV:200-221
-    count["calls"] += 1
-    count["rows"] += 1
-    if status:
-        raise RuntimeError("CGP: the final state cannot be factorised (pivot %d)" % status)
-    return dict(X=DD, yobs=yobs, **{"lambda": lam}, theta=theta[None], alpha=alpha[None], bandwidth=bw,
-                Sig_matrix=keep["s"], sf=keep["sf"], res2=keep["res2"], temp_matrix=keep["temp"], mu=keep["beta"],
-                tau2=keep["tau2"], beststart=Starts[best], objval=float(res["f"][best]), rmscv=rmscv, Yp_jackknife=loo,
-                lower=lower, upper=upper, par=par, scales=scales, starts=Starts, f_starts=res["f"], x_starts=res["x"],
-                converged=res["converged"], jackknife_status=st, calls=count["calls"], evaluations=count["rows"],
-                refinement_calls=res["calls"],
-                seconds=dict(candidates=clock[1] - clock[0], refinement=clock[2] - clock[1], jackknife=clock[4] - clock[3]))
+    return _fit_sets("CGP", "", h, state, [X], [y], [rng], nugget_l, num_starts, theta_l, alpha_l, kappa_u, step)[0]
 
 
 def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, kappa_u=None, rngs=None, step=1e-5):
@@ -165,16 +105,28 @@ def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l
     fit it has alone.  calls and refinement_calls are the group's device calls (the same in every dict), evaluations the
     rows of the set itself, seconds the group's."""
     h = _plain(handle)
+    rngs = [0] * len(Xs) if rngs is None else list(rngs)
+
+    def state(designs, Y, rows, set_of, skip):
+        return h.cgp_state_batch_sets(designs, Y, rows, set_of, skip=skip)
+
+    return _fit_sets("CGP_sets", " of set %d", h, state, Xs, ys, rngs, nugget_l, num_starts, theta_l, alpha_l, kappa_u, step)
+
+
+def _fit_sets(who, of_set, h, state, Xs, ys, rngs, nugget_l, num_starts, theta_l, alpha_l, kappa_u, step):
+    """The fit of C sets of one shape in lockstep: candidates, refinement, jackknife, final state.  state(designs[C, n, p],
+    Y[C, n], rows, set_of, skip) -> (val, ..., loo, status) evaluates row b on set set_of[b]; skip is None except in the
+    jackknife.  who and of_set (a format of the set's index, or empty) word the errors, those about the arguments' shapes
+    included.  Returns one dict per set."""
     DDs = [np.asarray(X, dtype=np.float64) for X in Xs]
     yobs = [np.asarray(y, dtype=np.float64).ravel() for y in ys]
     C = len(DDs)
     if C < 1 or len(yobs) != C:
-        raise ValueError("CGP_sets: one response per design, at least one set")
+        raise ValueError("%s: one response per design, at least one set" % who)
     if any(D.ndim != 2 or D.shape != DDs[0].shape for D in DDs) or any(y.shape[0] != DDs[0].shape[0] for y in yobs):
-        raise ValueError("CGP_sets: the sets of one call have one shape (n, p)")
-    rngs = [0] * C if rngs is None else list(rngs)
+        raise ValueError("%s: the sets of one call have one shape (n, p)" % who)
     if len(rngs) != C:
-        raise ValueError("CGP_sets takes one generator per set")
+        raise ValueError("%s takes one generator per set" % who)
     gens = [r if isinstance(r, np.random.Generator) else np.random.default_rng(r) for r in rngs]
     n, p = DDs[0].shape
     n_par = p + 3
@@ -184,8 +136,8 @@ def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l
     count = dict(calls=0, rows=np.zeros(C, dtype=np.int64))
 
     def objective(ww, set_of):
-        """var.MLE.DK at the rows of ww, row b on set set_of[b], in one device call."""
-        val, _, _, _, st = h.cgp_state_batch_sets(XS, Y, rows_from_ww(ww), set_of)
+        """var.MLE.DK at the rows of ww, row b on set set_of[b], in one device call -> (val with GV:130-131 applied, status)."""
+        val, _, _, _, st = state(XS, Y, rows_from_ww(ww), set_of, None)
         count["calls"] += 1
         np.add.at(count["rows"], set_of, 1)
         return np.where(np.isfinite(val), val, NONFINITE), st
@@ -223,7 +175,7 @@ def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l
         sl = slice(c * S, (c + 1) * S)
         f, x = res["f"][sl], res["x"][sl]
         if not np.isfinite(f).any():
-            raise RuntimeError("CGP_sets: the objective failed at every start of set %d" % c)
+            raise RuntimeError("%s: the objective failed at every start%s" % (who, of_set and of_set % c))
         best = int(np.argmin(np.where(np.isfinite(f), f, np.inf)))                                     # GV:155-157
         par = x[best]
         lam, st_theta, kappa, bw = float(par[0]), par[1:1 + p], float(par[1 + p]), float(par[2 + p])
@@ -235,7 +187,7 @@ def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l
 
     clock.append(time.perf_counter())
     rows = np.concatenate([np.repeat(ft["row"][None], n, axis=0) for ft in fitted])
-    _, _, _, loo, jst = h.cgp_state_batch_sets(XD, Y, rows, np.repeat(np.arange(C), n), skip=np.tile(np.arange(n), C))   # GV:166-198
+    _, _, _, loo, jst = state(XD, Y, rows, np.repeat(np.arange(C), n), np.tile(np.arange(n), C))        # GV:166-198
     clock.append(time.perf_counter())
     count["calls"] += 1
     count["rows"] += n
@@ -245,7 +197,7 @@ def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l
         count["calls"] += 1
         count["rows"][c] += 1
         if status:
-            raise RuntimeError("CGP_sets: the final state of set %d cannot be factorised (pivot %d)" % (c, status))
+            raise RuntimeError("%s: the final state%s cannot be factorised (pivot %d)" % (who, of_set and of_set % c, status))
         keeps.append(keep)
     seconds = dict(candidates=clock[1] - clock[0], refinement=clock[2] - clock[1], jackknife=clock[4] - clock[3])
     out = []

@@ -294,9 +294,10 @@ inline SetsStage sets_stage(Layout& c, int n, int d, int P, int C, int B) {
   return s;
 }
 
-// ---- the sets forms of the comparator fits (ccgp_profile_batch_sets with a gradient, ccgp_cgp_state_batch_sets).  A call is
-// cut into chunks of nb rows (plan_chunk): the C training sets lie in front and go up ONCE, with the first chunk; behind them
-// a chunk's rows, its set indices and its results.  `first`: this chunk is the call's first.
+// ---- the chunked calls of the comparator fits (ccgp_profile_batch_sets with a gradient; ccgp_cgp_state_batch_sets and, as
+// its C = 1 case that names no set, ccgp_cgp_state_batch).  A call is cut into chunks of nb rows (plan_chunk): the C training
+// sets lie in front and go up ONCE, with the first chunk; behind them a chunk's rows, its set indices and its results, the
+// inputs back to back so that they go up as one span.  `first`: this chunk is the call's first.
 //   ccgp_profile_batch_sets: Xs | ys | set | params | grad | loglik | s2hat | beta | status
 struct ProfileSetsStage {
   double *Xs, *ys;
@@ -330,7 +331,7 @@ inline ProfileSetsStage profile_sets_stage(Layout& c, int n, int d, int P, int C
   return s;
 }
 inline size_t profile_sets_row_bytes(int P) { return sizeof(double) * (2 * (size_t)P + 3) + 2 * sizeof(int); }
-//   ccgp_cgp_state_batch_sets: Xs | ys | set | skip | params | val | beta | tau2 | loo | status
+//   ccgp_cgp_state_batch[_sets]: Xs | ys | set | skip | params | val | beta | tau2 | loo | status
 struct CgpSetsStage {
   double *Xs, *ys;
   int *set, *skip;

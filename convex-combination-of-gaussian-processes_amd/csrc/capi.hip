@@ -602,6 +602,135 @@ __global__ void count_bad_kernel(const int* status, int B, int* out) {
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
 }
 
+// The fallback where the sets kernel has no route: the rows of every set, in their order, through a single-set call.
+// call(c, rows, nb, idx) evaluates the nb rows of set c (column-major, leading dimension nb) and scatters its results by
+// idx, the rows' places among the B; it returns what the single-set entry point returned.
+template <class Call>
+int sets_by_group(const int* set, int B, int C, int P, const double* params, Call call) {
+  std::vector<std::vector<int>> rows_of(C);
+  for (int b = 0; b < B; ++b) rows_of[set[b]].push_back(b);
+  int failed = 0;
+  std::vector<double> rows;
+  for (int c = 0; c < C; ++c) {
+    const std::vector<int>& idx = rows_of[c];
+    const int nb = (int)idx.size();
+    if (!nb) continue;
+    rows.resize((size_t)nb * P);
+    for (int j = 0; j < P; ++j)
+      for (int i = 0; i < nb; ++i) rows[i + (size_t)j * nb] = params[idx[i] + (size_t)j * B];
+    const int rc = call(c, rows.data(), nb, idx);
+    if (rc < 0) return rc;
+    failed += rc;
+  }
+  return failed;
+}
+// out[idx[i] + j * ldo] = src[i + j * nb] for the P columns of a group's result; out == nullptr: not wanted
+template <class T>
+void scatter_by(const std::vector<int>& idx, const std::vector<T>& src, T* out, int P = 1, int ldo = 0) {
+  const size_t nb = idx.size();
+  if (!out) return;
+  for (int j = 0; j < P; ++j)
+    for (size_t i = 0; i < nb; ++i) out[idx[i] + (size_t)j * ldo] = src[i + (size_t)j * nb];
+}
+
+// row b0 of a per-row array; nullptr stays nullptr (an input the call does not take, an output the caller does not want)
+template <class T>
+T* at(T* p, int b0) {
+  return p ? p + b0 : nullptr;
+}
+
+// rows b0 .. b0 + nb of a B x P column-major table as an nb x P one: `rows` where the chunk is not the whole table
+const double* chunk_rows(const double* params, int B, int P, int b0, int nb, std::vector<double>& rows) {
+  if (nb == B) return params;
+  rows.resize((size_t)nb * P);
+  for (int j = 0; j < P; ++j) std::memcpy(&rows[(size_t)j * nb], params + b0 + (size_t)j * B, sizeof(double) * nb);
+  return rows.data();
+}
+
+// A call of B rows cut into chunks.  A chunk is a call of its own: stage(Layout&, nb) lays out, in the workspace, what the
+// whole call shares and behind it a chunk's rows and results (row_bytes each).  The planner cuts B by the workspace limit
+// and by the grid's 65535; a row reads its own parameters (and its own set) only, so where the cuts fall changes no bit.
+// body(s, b0, nb, rows, table) pushes, launches and returns pull_status's value for rows b0 .. b0 + nb: rows is their
+// nb x P column-major parameter table, table where their nb x P result table goes when the caller wants one (out_table,
+// B x P column-major) -- out_table itself for an uncut call, else a buffer this runner scatters into out_table's rows.
+template <class Stage, class Body>
+int run_chunked(ccgp_handle* h, size_t row_bytes, const double* params, int B, int P, double* out_table, Stage stage,
+                Body body) {
+  int nbc = 0;
+  if (int rc = plan_chunk(h, row_bytes, B, kSweepMargin,
+                          [&](int nb) { return layout_bytes([&](Layout& w) { stage(w, nb); }); }, &nbc))
+    return rc;
+  Layout ws(h->ws.ptr);
+  const auto s = stage(ws, nbc);
+  std::vector<double> rows, table;
+  int failed = 0;
+  for (int b0 = 0; b0 < B; b0 += nbc) {
+    const int nb = std::min(nbc, B - b0);
+    const bool cut = out_table && nb != B;
+    if (cut) table.resize((size_t)nb * P);
+    const int rc = body(s, b0, nb, chunk_rows(params, B, P, b0, nb, rows), cut ? table.data() : out_table);
+    if (rc < 0) return rc;
+    failed += rc;
+    if (cut)
+      for (int j = 0; j < P; ++j) std::memcpy(out_table + b0 + (size_t)j * B, &table[(size_t)j * nb], sizeof(double) * nb);
+  }
+  return failed;
+}
+
+// One transformed parameter vector (psi1, psi2, phi[, zeta]) = (log theta1, log theta2, logit p[, log lambda]) -> the C-ABI
+// parameter row (w_1, w_2, theta_1k.., theta_2k..), the log-Jacobian and the script's log-prior (HX:446-463, GV:450, ISO:453,
+// ANI:459-462).  theta_t / row: element j of vector b at [b + j * ld]; shared by ccgp_logpost and ccgp_logpost_batch so that a
+// value does not depend on which of the two produced it.
+void logpost_terms(int prior_id, int d, const double* theta_t, int ldt, const double* prior_pars, double* row, int ldr,
+                   double* log_jacob, double* log_prior) {
+  const double psi1 = theta_t[0], psi2 = theta_t[ldt], phi = theta_t[2 * (size_t)ldt];
+  const double theta1 = std::exp(psi1), theta2 = std::exp(psi2);
+  const double p = 1.0 / (1.0 + std::exp(-phi));
+  row[0] = p;
+  row[ldr] = 1.0 - p;
+  double lj = -phi - 2.0 * std::log(1.0 + std::exp(-phi)) + psi1 + psi2;
+  double lp = 0.0;
+  if (prior_id == CCGP_PRIOR_ANI) {
+    const double zeta = theta_t[3 * (size_t)ldt], lambda = std::exp(zeta);
+    row[2 * (size_t)ldr] = theta1; row[3 * (size_t)ldr] = theta2;
+    row[4 * (size_t)ldr] = (1.0 + lambda) * theta1; row[5 * (size_t)ldr] = (1.0 + lambda) * theta2;
+    lj += zeta;
+    lp = -psi1 - psi1 * psi1 / 2.0 - psi2 - psi2 * psi2 / 2.0 - 4.0 * zeta - 4.0 / lambda;
+  } else {
+    for (int k = 0; k < d; ++k) { row[(size_t)(2 + k) * ldr] = theta1; row[(size_t)(2 + d + k) * ldr] = theta2; }
+    if (prior_id == CCGP_PRIOR_INVGAMMA)
+      lp = -(prior_pars[0] + 1.0) * psi1 - prior_pars[1] / theta1 -
+           (prior_pars[2] + 1.0) * psi2 - prior_pars[3] / theta2;
+    else if (prior_id == CCGP_PRIOR_GV)
+      lp = -4.0 * psi1 - 1.0 / theta1 - 6.0 * psi2 - 75.0 / theta2;
+    else
+      lp = -4.0 * psi1 - 2.0 / theta1 - 6.0 * psi2 - 16.0 / theta2;
+  }
+  *log_jacob = lj;
+  *log_prior = lp;
+}
+
+// ccgp_logpost_batch and ccgp_logpost_sets behind their argument checks: logpost_terms over the B vectors of theta_t,
+// loglik(K, rows, ll, beta, st) -> the likelihood call's return value, then the sums in ccgp_logpost's order of additions
+// (NaN where the factorisation failed: the reference's NA)
+template <class Loglik>
+int logpost_rows(int prior_id, int d, const double* theta_t, int B, const double* prior_pars, double* out_val,
+                 double* out_beta, double* out_loglik, int* status, Loglik loglik) {
+  const int K = 2, P = K + K * d;
+  std::vector<double> rows((size_t)B * P), ljac(B), lpri(B), ll(B), beta(B);
+  std::vector<int> st(B);
+  for (int b = 0; b < B; ++b) logpost_terms(prior_id, d, theta_t + b, B, prior_pars, rows.data() + b, B, &ljac[b], &lpri[b]);
+  const int rc = loglik(K, rows.data(), ll.data(), beta.data(), st.data());
+  if (rc < 0) return rc;
+  for (int b = 0; b < B; ++b) {
+    out_val[b] = ll[b] + ljac[b] + lpri[b];
+    if (out_beta) out_beta[b] = beta[b];
+    if (out_loglik) out_loglik[b] = ll[b];
+    if (status) status[b] = st[b];
+  }
+  return rc;
+}
+
 }  // namespace
 
 // No C++ exception may cross the C ABI (inside R that would be std::terminate for the user's session): every entry point
@@ -1025,55 +1154,39 @@ int ccgp_loglik_batch(ccgp_handle* h, const double* X, int n, int d, const doubl
 } CCGP_GUARD_END(h)
 
 // ---- many training sets of one shape in one call (ccgp.h) -----------------------------------------------------------------
-// what ccgp_loglik_batch_sets and ccgp_logpost_sets refuse before anything is copied or launched
-static bool sets_args_ok(const double* Xs, const double* ys, const double* sigma2, int C, const int* set, int B) {
-  if (C < 1 || B < 1 || !Xs || !ys || !sigma2 || !set) return false;
+// what the sets entry points refuse before anything is copied or launched.  need_sigma2: the call reads a sigma2 per set;
+// min_B: 1, or 0 where an empty call is legal
+static bool sets_args_ok(const double* Xs, const double* ys, const double* sigma2, bool need_sigma2, int C, const int* set,
+                         int B, int min_B) {
+  if (C < 1 || B < min_B || !Xs || !ys || (need_sigma2 && !sigma2) || !set) return false;
   for (int b = 0; b < B; ++b)
     if (set[b] < 0 || set[b] >= C) return false;
   return true;
-}
-
-// small_route_sets says Blocked: the rows of every set, in their order, through the single-set call
-static int sets_by_group(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C, int K,
-                         const double* params, const int* set, int B, int mean_mode, double tau2, double* out_loglik,
-                         double* out_beta, int* status) {
-  const int P = K + K * d;
-  std::vector<std::vector<int>> rows_of(C);
-  for (int b = 0; b < B; ++b) rows_of[set[b]].push_back(b);
-  int failed = 0;
-  std::vector<double> rows, ll, beta;
-  std::vector<int> st;
-  for (int c = 0; c < C; ++c) {
-    const std::vector<int>& idx = rows_of[c];
-    const int nb = (int)idx.size();
-    if (!nb) continue;
-    rows.resize((size_t)nb * P); ll.resize(nb); beta.resize(nb); st.resize(nb);
-    for (int j = 0; j < P; ++j)
-      for (int i = 0; i < nb; ++i) rows[i + (size_t)j * nb] = params[idx[i] + (size_t)j * B];
-    const int rc = ccgp_loglik_batch(h, Xs + (size_t)c * n * d, n, d, ys + (size_t)c * n, K, rows.data(), nb, sigma2[c],
-                                     mean_mode, tau2, ll.data(), beta.data(), st.data());
-    if (rc < 0) return rc;
-    failed += rc;
-    for (int i = 0; i < nb; ++i) {
-      out_loglik[idx[i]] = ll[i];
-      if (out_beta) out_beta[idx[i]] = beta[i];
-      if (status) status[idx[i]] = st[i];
-    }
-  }
-  return failed;
 }
 
 int ccgp_loglik_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
                            int K, const double* params, const int* set, int B, int mean_mode, double tau2,
                            double* out_loglik, double* out_beta, int* status) try {
   if (!h) return CCGP_EINVAL;
-  if (bad_shape(n, d, K) || !params || !out_loglik || !sets_args_ok(Xs, ys, sigma2, C, set, B))
+  if (bad_shape(n, d, K) || !params || !out_loglik || !sets_args_ok(Xs, ys, sigma2, true, C, set, B, 1))
     return fail(h, CCGP_EINVAL, "ccgp_loglik_batch_sets: bad argument");
   if (int rc = check_mean_mode(h, mean_mode)) return rc;
-  if (small_route_sets(h->fam.id == 0, n, d, K) == Route::Blocked)
-    return sets_by_group(h, Xs, n, d, ys, sigma2, C, K, params, set, B, mean_mode, tau2, out_loglik, out_beta, status);
-  CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
+  if (small_route_sets(h->fam.id == 0, n, d, K) == Route::Blocked) {   // ccgp_loglik_batch, whatever route that call takes
+    std::vector<double> ll, beta;
+    std::vector<int> st;
+    return sets_by_group(set, B, C, P, params, [&](int c, const double* rows, int nb, const std::vector<int>& idx) -> int {
+      ll.resize(nb); beta.resize(nb); st.resize(nb);
+      const int rc = ccgp_loglik_batch(h, Xs + (size_t)c * n * d, n, d, ys + (size_t)c * n, K, rows, nb, sigma2[c], mean_mode,
+                                       tau2, ll.data(), beta.data(), st.data());
+      if (rc < 0) return rc;
+      scatter_by(idx, ll, out_loglik);
+      scatter_by(idx, beta, out_beta);
+      scatter_by(idx, st, status);
+      return rc;
+    });
+  }
+  CCGP_HIP(hipSetDevice(h->device));
   SetsStage s;
   if (int rc = stage(h, [&](Layout& c) { s = sets_stage(c, n, d, P, C, B); })) return rc;
   DrawView dv;
@@ -1116,129 +1229,56 @@ static int cgp_shape(ccgp_handle* h, const char* who, int n, int d) {
   return CCGP_OK;
 }
 
+// ccgp_cgp_state_batch (set == nullptr: the one set of C = 1, launch_cgp_state) and ccgp_cgp_state_batch_sets behind their
+// pointer checks: what both refuse before any launch, then the chunked call
+static int cgp_state_call(ccgp_handle* h, const char* who, const double* Xs, int n, int d, const double* ys, int C,
+                          const double* params, const int* set, int B, const int* skip, double* out_val, double* out_beta,
+                          double* out_tau2, double* out_loo, int* status) {
+  if (skip)
+    for (int b = 0; b < B; ++b)
+      if (skip[b] < -1 || skip[b] >= n || (skip[b] >= 0 && n < 2))
+        return fail(h, CCGP_EINVAL, std::string(who) + ": skip must be -1 or a row of a design of at least two points");
+  if (int rc = cgp_shape(h, who, n, d)) return rc;
+  if (B == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = 2 * d + 2;
+  return run_chunked(
+      h, cgp_sets_row_bytes(d), params, B, P, nullptr, [&](Layout& w, int nb) { return cgp_sets_stage(w, n, d, C, nb); },
+      [&](const CgpSetsStage& s, int b0, int nb, const double* rows, double*) -> int {
+        // without `set` (the single-set call) or `skip` their staged words go up unwritten inside the one span; no kernel
+        // reads them: launch_cgp_state takes no set array, and a null skip is passed on as null
+        if (int prc = push(h, s.inputs(b0 == 0, Xs, ys, at(set, b0), at(skip, b0), rows, nb))) return prc;
+        {
+          ScopedTimer t(h, CCGP_T_FUSED);
+          if (set)
+            launch_cgp_state_sets(h->stream, s.Xs, n, d, s.ys, s.set, s.params, nb, nb, skip ? s.skip : nullptr, s.val, s.beta,
+                                  s.tau2, out_loo ? s.loo : nullptr, s.status);
+          else
+            launch_cgp_state(h->stream, s.Xs, n, d, s.ys, s.params, nb, nb, skip ? s.skip : nullptr, s.val, s.beta, s.tau2,
+                             out_loo ? s.loo : nullptr, s.status, nullptr);
+        }
+        CCGP_LAUNCH_CHECK();
+        return pull_status(h, s.results(out_val + b0, at(out_beta, b0), at(out_tau2, b0), at(out_loo, b0), nb), s.status, nb,
+                           at(status, b0));
+      });
+}
+
 int ccgp_cgp_state_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, const double* params, int B,
                          const int* skip, double* out_val, double* out_beta, double* out_tau2, double* out_loo,
                          int* status) try {
   if (!h) return CCGP_EINVAL;
   if (n < 1 || d < 1 || B < 0 || !X || !y || !params || !out_val)
     return fail(h, CCGP_EINVAL, "ccgp_cgp_state_batch: bad argument");
-  if (skip)
-    for (int b = 0; b < B; ++b)
-      if (skip[b] < -1 || skip[b] >= n || (skip[b] >= 0 && n < 2))
-        return fail(h, CCGP_EINVAL, "ccgp_cgp_state_batch: skip must be -1 or a row of a design of at least two points");
-  if (int rc = cgp_shape(h, "ccgp_cgp_state_batch", n, d)) return rc;   // before any launch
-  if (B == 0) return CCGP_OK;
-  CCGP_HIP(hipSetDevice(h->device));
-  const int P = 2 * d + 2;
-  // A chunk is a call of its own: its parameter rows, its held-out rows and its results lie in the workspace, X and y in
-  // front of them.  The planner cuts B by the workspace limit and by the grid's 65535; an evaluation reads its own row only,
-  // so where the cuts fall changes no bit.
-  double *dX, *dy, *dp, *dval, *dbeta, *dtau2, *dloo;
-  int *dst, *dskip;
-  auto lay = [&](Layout& w, int nb) {
-    dX = w.take<double>((size_t)n * d);
-    dy = w.take<double>(n);
-    dp = w.take<double>((size_t)nb * P);
-    dval = w.take<double>(nb);
-    dbeta = w.take<double>(nb);
-    dtau2 = w.take<double>(nb);
-    dloo = w.take<double>(nb);
-    dst = w.take<int>(nb);
-    dskip = w.take<int>(nb);
-  };
-  int nbc = 0;
-  if (int rc = plan_chunk(h, sizeof(double) * (P + 4) + 2 * sizeof(int), B, kSweepMargin,
-                          [&](int nb) { return layout_bytes([&](Layout& w) { lay(w, nb); }); }, &nbc))
-    return rc;
-  Layout ws(h->ws.ptr);
-  lay(ws, nbc);
-  std::vector<double> rows;
-  int failed = 0;
-  for (int b0 = 0; b0 < B; b0 += nbc) {
-    const int nb = std::min(nbc, B - b0);
-    const double* hp = params;
-    if (nb != B) {   // the chunk's rows, column-major with leading dimension nb
-      rows.resize((size_t)nb * P);
-      for (int j = 0; j < P; ++j) std::memcpy(&rows[(size_t)j * nb], params + b0 + (size_t)j * B, sizeof(double) * nb);
-      hp = rows.data();
-    }
-    if (int prc = push(h, {piece(dX, b0 == 0 ? X : nullptr, (size_t)n * d), piece(dy, b0 == 0 ? y : nullptr, n),
-                           piece(dp, hp, (size_t)nb * P), piece(dskip, skip ? skip + b0 : nullptr, nb)}))
-      return prc;
-    {
-      ScopedTimer t(h, CCGP_T_FUSED);
-      launch_cgp_state(h->stream, dX, n, d, dy, dp, nb, nb, skip ? dskip : nullptr, dval, dbeta, dtau2,
-                       out_loo ? dloo : nullptr, dst, nullptr);
-    }
-    CCGP_LAUNCH_CHECK();
-    const int rc = pull_status(h, {piece(dval, out_val + b0, nb), piece(dbeta, out_beta ? out_beta + b0 : nullptr, nb),
-                                   piece(dtau2, out_tau2 ? out_tau2 + b0 : nullptr, nb),
-                                   piece(dloo, out_loo ? out_loo + b0 : nullptr, nb)},
-                               dst, nb, status ? status + b0 : nullptr);
-    if (rc < 0) return rc;
-    failed += rc;
-  }
-  return failed;
+  return cgp_state_call(h, "ccgp_cgp_state_batch", X, n, d, y, 1, params, nullptr, B, skip, out_val, out_beta, out_tau2, out_loo,
+                        status);
 } CCGP_GUARD_END(h)
 
 // ---- the comparator fits over many training sets of one shape (ccgp.h) ------------------------------------------------------
-// what ccgp_profile_batch_sets and ccgp_cgp_state_batch_sets refuse before anything is copied or launched (B == 0 is legal)
-static bool sets_rows_ok(const double* Xs, const double* ys, int C, const int* set, int B) {
-  if (C < 1 || B < 0 || !Xs || !ys || !set) return false;
-  for (int b = 0; b < B; ++b)
-    if (set[b] < 0 || set[b] >= C) return false;
-  return true;
-}
-
-// rows b0 .. b0 + nb of a B x P column-major table as an nb x P one: `rows` where the chunk is not the whole table
-static const double* chunk_rows(const double* params, int B, int P, int b0, int nb, std::vector<double>& rows) {
-  if (nb == B) return params;
-  rows.resize((size_t)nb * P);
-  for (int j = 0; j < P; ++j) std::memcpy(&rows[(size_t)j * nb], params + b0 + (size_t)j * B, sizeof(double) * nb);
-  return rows.data();
-}
-
-// small_route_profile_grad_sets says Blocked, or no gradient is wanted: the rows of every set, in their order, through
-// ccgp_profile_batch (whatever route that call takes)
-static int profile_sets_by_group(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int K,
-                                 const double* params, const int* set, int B, double* out_loglik, double* out_sigma2,
-                                 double* out_beta, double* out_grad, int* status) {
-  const int P = K + K * d;
-  std::vector<std::vector<int>> rows_of(C);
-  for (int b = 0; b < B; ++b) rows_of[set[b]].push_back(b);
-  int failed = 0;
-  std::vector<double> rows, ll, s2, beta, grad;
-  std::vector<int> st;
-  for (int c = 0; c < C; ++c) {
-    const std::vector<int>& idx = rows_of[c];
-    const int nb = (int)idx.size();
-    if (!nb) continue;
-    rows.resize((size_t)nb * P); ll.resize(nb); s2.resize(nb); beta.resize(nb); st.resize(nb);
-    if (out_grad) grad.resize((size_t)nb * P);
-    for (int j = 0; j < P; ++j)
-      for (int i = 0; i < nb; ++i) rows[i + (size_t)j * nb] = params[idx[i] + (size_t)j * B];
-    const int rc = ccgp_profile_batch(h, Xs + (size_t)c * n * d, n, d, ys + (size_t)c * n, K, rows.data(), nb, ll.data(),
-                                      s2.data(), beta.data(), out_grad ? grad.data() : nullptr, st.data());
-    if (rc < 0) return rc;
-    failed += rc;
-    for (int i = 0; i < nb; ++i) {
-      out_loglik[idx[i]] = ll[i];
-      out_sigma2[idx[i]] = s2[i];
-      if (out_beta) out_beta[idx[i]] = beta[i];
-      if (status) status[idx[i]] = st[i];
-    }
-    if (out_grad)
-      for (int j = 0; j < P; ++j)
-        for (int i = 0; i < nb; ++i) out_grad[idx[i] + (size_t)j * B] = grad[i + (size_t)j * nb];
-  }
-  return failed;
-}
-
 int ccgp_profile_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int K,
                             const double* params, const int* set, int B, double* out_loglik, double* out_sigma2,
                             double* out_beta, double* out_grad, int* status) try {
   if (!h) return CCGP_EINVAL;
-  if (bad_shape(n, d, K) || !params || !out_loglik || !out_sigma2 || !sets_rows_ok(Xs, ys, C, set, B))
+  if (bad_shape(n, d, K) || !params || !out_loglik || !out_sigma2 || !sets_args_ok(Xs, ys, nullptr, false, C, set, B, 0))
     return fail(h, CCGP_EINVAL, "ccgp_profile_batch_sets: bad argument");
   if (B == 0) return CCGP_OK;
   const bool gauss = h->fam.id == 0;
@@ -1247,85 +1287,52 @@ int ccgp_profile_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, cons
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch_sets: analytic gradient is implemented for the Gaussian family only");
   if (out_grad && small_route(Op::Grad, gauss, n, d, K) == Route::Blocked && !blocked_grad_supported(d, K))
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch_sets: d + K too large for the contraction kernel's LDS");
-  if (!out_grad || small_route_profile_grad_sets(gauss, n, d, K) == Route::Blocked)
-    return profile_sets_by_group(h, Xs, n, d, ys, C, K, params, set, B, out_loglik, out_sigma2, out_beta, out_grad, status);
-  CCGP_HIP(hipSetDevice(h->device));
   const int P = K + K * d;
-  // A chunk is a call of its own, as in ccgp_cgp_state_batch: the planner cuts B by the workspace limit and by the grid's
-  // 65535; a row reads its own parameters and its own set only, so where the cuts fall changes no bit.
-  int nbc = 0;
-  if (int rc = plan_chunk(h, profile_sets_row_bytes(P), B, kSweepMargin,
-                          [&](int nb) { return layout_bytes([&](Layout& w) { profile_sets_stage(w, n, d, P, C, nb); }); }, &nbc))
-    return rc;
-  Layout ws(h->ws.ptr);
-  const ProfileSetsStage s = profile_sets_stage(ws, n, d, P, C, nbc);
-  std::vector<double> rows, grad;
-  int failed = 0;
-  for (int b0 = 0; b0 < B; b0 += nbc) {
-    const int nb = std::min(nbc, B - b0);
-    DrawView dv;
-    if (int frc = draw_view(h, h->fam, s.params, nb, K, d, &dv)) return frc;
-    if (int prc = push(h, s.inputs(b0 == 0, Xs, ys, set + b0, chunk_rows(params, B, P, b0, nb, rows), nb))) return prc;
-    {
-      ScopedTimer t(h, CCGP_T_FUSED);
-      launch_small_reg_profile_grad_sets(h->stream, s.Xs, n, d, s.ys, s.set, dv, nb, s.loglik, s.s2hat, s.beta, s.grad, s.status);
-    }
-    CCGP_LAUNCH_CHECK();
-    double* hgrad = out_grad;
-    if (nb != B) {
-      grad.resize((size_t)nb * P);
-      hgrad = grad.data();
-    }
-    const int rc = pull_status(h, s.results(hgrad, out_loglik + b0, out_sigma2 + b0, out_beta ? out_beta + b0 : nullptr, nb),
-                               s.status, nb, status ? status + b0 : nullptr);
-    if (rc < 0) return rc;
-    failed += rc;
-    if (nb != B)
-      for (int j = 0; j < P; ++j) std::memcpy(out_grad + b0 + (size_t)j * B, &grad[(size_t)j * nb], sizeof(double) * nb);
+  if (!out_grad || small_route_profile_grad_sets(gauss, n, d, K) == Route::Blocked) {
+    // no sets kernel for the call: ccgp_profile_batch per set, whatever route that call takes
+    std::vector<double> ll, s2, beta, grad;
+    std::vector<int> st;
+    return sets_by_group(set, B, C, P, params, [&](int c, const double* rows, int nb, const std::vector<int>& idx) -> int {
+      ll.resize(nb); s2.resize(nb); beta.resize(nb); st.resize(nb);
+      if (out_grad) grad.resize((size_t)nb * P);
+      const int rc = ccgp_profile_batch(h, Xs + (size_t)c * n * d, n, d, ys + (size_t)c * n, K, rows, nb, ll.data(), s2.data(),
+                                        beta.data(), out_grad ? grad.data() : nullptr, st.data());
+      if (rc < 0) return rc;
+      scatter_by(idx, ll, out_loglik);
+      scatter_by(idx, s2, out_sigma2);
+      scatter_by(idx, beta, out_beta);
+      scatter_by(idx, st, status);
+      scatter_by(idx, grad, out_grad, P, B);
+      return rc;
+    });
   }
-  return failed;
+  CCGP_HIP(hipSetDevice(h->device));
+  return run_chunked(
+      h, profile_sets_row_bytes(P), params, B, P, out_grad,
+      [&](Layout& w, int nb) { return profile_sets_stage(w, n, d, P, C, nb); },
+      [&](const ProfileSetsStage& s, int b0, int nb, const double* rows, double* grad) -> int {
+        DrawView dv;
+        if (int frc = draw_view(h, h->fam, s.params, nb, K, d, &dv)) return frc;
+        if (int prc = push(h, s.inputs(b0 == 0, Xs, ys, set + b0, rows, nb))) return prc;
+        {
+          ScopedTimer t(h, CCGP_T_FUSED);
+          launch_small_reg_profile_grad_sets(h->stream, s.Xs, n, d, s.ys, s.set, dv, nb, s.loglik, s.s2hat, s.beta, s.grad,
+                                             s.status);
+        }
+        CCGP_LAUNCH_CHECK();
+        return pull_status(h, s.results(grad, out_loglik + b0, out_sigma2 + b0, at(out_beta, b0), nb), s.status, nb,
+                           at(status, b0));
+      });
 } CCGP_GUARD_END(h)
 
 int ccgp_cgp_state_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, const double* params,
                               const int* set, int B, const int* skip, double* out_val, double* out_beta, double* out_tau2,
                               double* out_loo, int* status) try {
   if (!h) return CCGP_EINVAL;
-  if (n < 1 || d < 1 || !params || !out_val || !sets_rows_ok(Xs, ys, C, set, B))
+  if (n < 1 || d < 1 || !params || !out_val || !sets_args_ok(Xs, ys, nullptr, false, C, set, B, 0))
     return fail(h, CCGP_EINVAL, "ccgp_cgp_state_batch_sets: bad argument");
-  if (skip)
-    for (int b = 0; b < B; ++b)
-      if (skip[b] < -1 || skip[b] >= n || (skip[b] >= 0 && n < 2))
-        return fail(h, CCGP_EINVAL, "ccgp_cgp_state_batch_sets: skip must be -1 or a row of a design of at least two points");
-  if (int rc = cgp_shape(h, "ccgp_cgp_state_batch_sets", n, d)) return rc;   // before any launch
-  if (B == 0) return CCGP_OK;
-  CCGP_HIP(hipSetDevice(h->device));
-  const int P = 2 * d + 2;
-  int nbc = 0;
-  if (int rc = plan_chunk(h, cgp_sets_row_bytes(d), B, kSweepMargin,
-                          [&](int nb) { return layout_bytes([&](Layout& w) { cgp_sets_stage(w, n, d, C, nb); }); }, &nbc))
-    return rc;
-  Layout ws(h->ws.ptr);
-  const CgpSetsStage s = cgp_sets_stage(ws, n, d, C, nbc);
-  std::vector<double> rows;
-  int failed = 0;
-  for (int b0 = 0; b0 < B; b0 += nbc) {
-    const int nb = std::min(nbc, B - b0);
-    if (int prc = push(h, s.inputs(b0 == 0, Xs, ys, set + b0, skip ? skip + b0 : nullptr,
-                                   chunk_rows(params, B, P, b0, nb, rows), nb)))
-      return prc;
-    {
-      ScopedTimer t(h, CCGP_T_FUSED);
-      launch_cgp_state_sets(h->stream, s.Xs, n, d, s.ys, s.set, s.params, nb, nb, skip ? s.skip : nullptr, s.val, s.beta,
-                            s.tau2, out_loo ? s.loo : nullptr, s.status);
-    }
-    CCGP_LAUNCH_CHECK();
-    const int rc = pull_status(h, s.results(out_val + b0, out_beta ? out_beta + b0 : nullptr, out_tau2 ? out_tau2 + b0 : nullptr,
-                                            out_loo ? out_loo + b0 : nullptr, nb),
-                               s.status, nb, status ? status + b0 : nullptr);
-    if (rc < 0) return rc;
-    failed += rc;
-  }
-  return failed;
+  return cgp_state_call(h, "ccgp_cgp_state_batch_sets", Xs, n, d, ys, C, params, set, B, skip, out_val, out_beta, out_tau2,
+                        out_loo, status);
 } CCGP_GUARD_END(h)
 
 int ccgp_cgp_predict(ccgp_handle* h, const double* X, int n, int d, const double* y, const double* params,
@@ -1370,39 +1377,6 @@ int ccgp_cgp_predict(ccgp_handle* h, const double* X, int n, int d, const double
 } CCGP_GUARD_END(h)
 
 // ---- a8: logpost ------------------------------------------------------------------------------
-// One transformed parameter vector (psi1, psi2, phi[, zeta]) = (log theta1, log theta2, logit p[, log lambda]) -> the C-ABI
-// parameter row (w_1, w_2, theta_1k.., theta_2k..), the log-Jacobian and the script's log-prior (HX:446-463, GV:450, ISO:453,
-// ANI:459-462).  theta_t / row: element j of vector b at [b + j * ld]; shared by ccgp_logpost and ccgp_logpost_batch so that a
-// value does not depend on which of the two produced it.
-static void logpost_terms(int prior_id, int d, const double* theta_t, int ldt, const double* prior_pars, double* row,
-                          int ldr, double* log_jacob, double* log_prior) {
-  const double psi1 = theta_t[0], psi2 = theta_t[ldt], phi = theta_t[2 * (size_t)ldt];
-  const double theta1 = std::exp(psi1), theta2 = std::exp(psi2);
-  const double p = 1.0 / (1.0 + std::exp(-phi));
-  row[0] = p;
-  row[ldr] = 1.0 - p;
-  double lj = -phi - 2.0 * std::log(1.0 + std::exp(-phi)) + psi1 + psi2;
-  double lp = 0.0;
-  if (prior_id == CCGP_PRIOR_ANI) {
-    const double zeta = theta_t[3 * (size_t)ldt], lambda = std::exp(zeta);
-    row[2 * (size_t)ldr] = theta1; row[3 * (size_t)ldr] = theta2;
-    row[4 * (size_t)ldr] = (1.0 + lambda) * theta1; row[5 * (size_t)ldr] = (1.0 + lambda) * theta2;
-    lj += zeta;
-    lp = -psi1 - psi1 * psi1 / 2.0 - psi2 - psi2 * psi2 / 2.0 - 4.0 * zeta - 4.0 / lambda;
-  } else {
-    for (int k = 0; k < d; ++k) { row[(size_t)(2 + k) * ldr] = theta1; row[(size_t)(2 + d + k) * ldr] = theta2; }
-    if (prior_id == CCGP_PRIOR_INVGAMMA)
-      lp = -(prior_pars[0] + 1.0) * psi1 - prior_pars[1] / theta1 -
-           (prior_pars[2] + 1.0) * psi2 - prior_pars[3] / theta2;
-    else if (prior_id == CCGP_PRIOR_GV)
-      lp = -4.0 * psi1 - 1.0 / theta1 - 6.0 * psi2 - 75.0 / theta2;
-    else
-      lp = -4.0 * psi1 - 2.0 / theta1 - 6.0 * psi2 - 16.0 / theta2;
-  }
-  *log_jacob = lj;
-  *log_prior = lp;
-}
-
 // the argument checks ccgp_logpost and ccgp_logpost_batch share; `who` is the name the message carries
 static int logpost_args(ccgp_handle* h, const char* who, bool shapes_ok, int d, int prior_id, const double* prior_pars) {
   auto bad = [&](const char* what) { return fail(h, CCGP_EINVAL, std::string(who) + what); };
@@ -1420,25 +1394,10 @@ int ccgp_logpost_batch(ccgp_handle* h, const double* X, int n, int d, const doub
   if (int rc = logpost_args(h, "ccgp_logpost_batch", n >= 1 && d >= 1 && d <= kMaxD && B >= 1 && X && y && theta_t && out_val,
                             d, prior_id, prior_pars))
     return rc;
-  const int K = 2, P = K + K * d;
-  std::vector<double> rows((size_t)B * P), ljac(B), lpri(B), ll(B), beta(B);
-  std::vector<int> st(B);
-  for (int b = 0; b < B; ++b) {
-    double lj = 0.0, lp = 0.0;
-    logpost_terms(prior_id, d, theta_t + b, B, prior_pars, rows.data() + b, B, &lj, &lp);
-    ljac[b] = lj;
-    lpri[b] = lp;
-  }
-  const int rc = ccgp_loglik_batch(h, X, n, d, y, K, rows.data(), B, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, ll.data(), beta.data(),
-                                   st.data());
-  if (rc < 0) return rc;
-  for (int b = 0; b < B; ++b) {
-    out_val[b] = ll[b] + ljac[b] + lpri[b];   // ccgp_logpost's order of additions; NaN where the factorisation failed: the reference's NA
-    if (out_beta) out_beta[b] = beta[b];
-    if (out_loglik) out_loglik[b] = ll[b];
-    if (status) status[b] = st[b];
-  }
-  return rc;
+  return logpost_rows(prior_id, d, theta_t, B, prior_pars, out_val, out_beta, out_loglik, status,
+                      [&](int K, const double* rows, double* ll, double* beta, int* st) {
+                        return ccgp_loglik_batch(h, X, n, d, y, K, rows, B, sigma2, CCGP_MEAN_PROFILE_BETA, 0.0, ll, beta, st);
+                      });
 } CCGP_GUARD_END(h)
 
 // ccgp_logpost_batch over many training sets: the same host arithmetic around ccgp_loglik_batch_sets
@@ -1447,28 +1406,15 @@ int ccgp_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const doub
                       double* out_beta, double* out_loglik, int* status) try {
   if (!h) return CCGP_EINVAL;
   if (int rc = logpost_args(h, "ccgp_logpost_sets",
-                            n >= 1 && d >= 1 && d <= kMaxD && theta_t && out_val && sets_args_ok(Xs, ys, sigma2, C, set, B), d,
-                            prior_id, prior_pars))
+                            n >= 1 && d >= 1 && d <= kMaxD && theta_t && out_val &&
+                                sets_args_ok(Xs, ys, sigma2, true, C, set, B, 1),
+                            d, prior_id, prior_pars))
     return rc;
-  const int K = 2, P = K + K * d;
-  std::vector<double> rows((size_t)B * P), ljac(B), lpri(B), ll(B), beta(B);
-  std::vector<int> st(B);
-  for (int b = 0; b < B; ++b) {
-    double lj = 0.0, lp = 0.0;
-    logpost_terms(prior_id, d, theta_t + b, B, prior_pars, rows.data() + b, B, &lj, &lp);
-    ljac[b] = lj;
-    lpri[b] = lp;
-  }
-  const int rc = ccgp_loglik_batch_sets(h, Xs, n, d, ys, sigma2, C, K, rows.data(), set, B, CCGP_MEAN_PROFILE_BETA, 0.0,
-                                        ll.data(), beta.data(), st.data());
-  if (rc < 0) return rc;
-  for (int b = 0; b < B; ++b) {
-    out_val[b] = ll[b] + ljac[b] + lpri[b];   // ccgp_logpost_batch's order of additions
-    if (out_beta) out_beta[b] = beta[b];
-    if (out_loglik) out_loglik[b] = ll[b];
-    if (status) status[b] = st[b];
-  }
-  return rc;
+  return logpost_rows(prior_id, d, theta_t, B, prior_pars, out_val, out_beta, out_loglik, status,
+                      [&](int K, const double* rows, double* ll, double* beta, int* st) {
+                        return ccgp_loglik_batch_sets(h, Xs, n, d, ys, sigma2, C, K, rows, set, B, CCGP_MEAN_PROFILE_BETA, 0.0,
+                                                      ll, beta, st);
+                      });
 } CCGP_GUARD_END(h)
 
 int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y, double sigma2,

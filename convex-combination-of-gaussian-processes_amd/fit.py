@@ -85,6 +85,34 @@ def logpost_batch(gp, D_train, theta_t, y, sigma2, prior_pars=None):
 
 
 # ----------------------------------------------------------------------------- LearnBayes::laplace
+def _hessian_vars(fn_sets, modes, hess_step):
+    """The covariance -H^-1 at each row of modes [C, p], H by central differences: the points of all modes go out as ONE
+    fn_sets(rows, set_of) call.  Where H is not negative definite the covariance falls back to H's diagonal."""
+    C, p = modes.shape
+    idx = [(i, j) for i in range(p) for j in range(i, p)]
+    pts = []
+    for mode in modes:
+        for i, j in idx:
+            for si, sj in ((1, 1), (1, -1), (-1, 1), (-1, -1)):
+                x = mode.copy()
+                x[i] += si * hess_step
+                x[j] += sj * hess_step
+                pts.append(x)
+    vals = np.asarray(fn_sets(np.asarray(pts), np.repeat(np.arange(C), 4 * len(idx))), dtype=np.float64).reshape(C, -1, 4)
+    out = []
+    for c in range(C):
+        H = np.zeros((p, p))
+        for (i, j), v in zip(idx, vals[c]):
+            H[i, j] = H[j, i] = (v[0] - v[1] - v[2] + v[3]) / (4.0 * hess_step ** 2)
+        try:
+            var = -np.linalg.inv(H)
+            np.linalg.cholesky(var)
+        except np.linalg.LinAlgError:
+            var = np.diag(1.0 / np.maximum(-np.diag(H), 1e-6))   # not negative definite: fall back to its diagonal
+        out.append(var)
+    return out
+
+
 def laplace(fn_batch, start, hess_step=1e-3, maxiter=2000):
     """Posterior mode by Nelder-Mead and covariance = -H^-1 from central differences
     (LearnBayes::laplace -> optim(..., hessian = TRUE); HX:493).  `fn_batch(rows) -> values`."""
@@ -98,27 +126,8 @@ def laplace(fn_batch, start, hess_step=1e-3, maxiter=2000):
 
     res = minimize(neg, start, method="Nelder-Mead",
                    options=dict(xatol=1e-6, fatol=1e-9, maxiter=maxiter, maxfev=maxiter))
-    mode = res.x
-    p = mode.size
-    pts, idx = [], []
-    for i in range(p):
-        for j in range(i, p):
-            for si, sj in ((1, 1), (1, -1), (-1, 1), (-1, -1)):
-                x = mode.copy()
-                x[i] += si * hess_step
-                x[j] += sj * hess_step
-                pts.append(x)
-            idx.append((i, j))
-    vals = np.asarray(fn_batch(np.asarray(pts)), dtype=np.float64).reshape(-1, 4)
-    H = np.zeros((p, p))
-    for (i, j), v in zip(idx, vals):
-        H[i, j] = H[j, i] = (v[0] - v[1] - v[2] + v[3]) / (4.0 * hess_step ** 2)
-    try:
-        var = -np.linalg.inv(H)
-        np.linalg.cholesky(var)
-    except np.linalg.LinAlgError:
-        var = np.diag(1.0 / np.maximum(-np.diag(H), 1e-6))   # not negative definite: fall back to its diagonal
-    return dict(mode=mode, var=var, converged=bool(res.success), value=-float(res.fun))
+    var = _hessian_vars(lambda rows, set_of: fn_batch(rows), res.x[None], hess_step)[0]
+    return dict(mode=res.x, var=var, converged=bool(res.success), value=-float(res.fun))
 
 
 # ----------------------------------------------------------------------------- coda::geweke.diag
@@ -258,6 +267,13 @@ class _Chain:
                     proposals=self.proposals, laplace=self.est, geweke_p=self.pv, device_batches=self.batches)
 
 
+def _prior_pars(gp, theta1_pars, theta2_pars):
+    """(a1, b1, a2, b2) for the scripts whose prior takes its parameters from the caller (HX, ADV); None for the others."""
+    if gp.script in ("HX", "ADV"):
+        return (*np.ravel(theta1_pars)[:2], *np.ravel(theta2_pars)[:2])
+    return None
+
+
 def Metro(gp, start, N, samp_size, batch_size, alpha, D_train, sigma2, y, theta1_pars=None,
           theta2_pars=None, rng=None, max_proposals=None, speculate=0, logpost_fn=None):
     """HX:483-540 (and its per-script copies).  Returns dict(sample[samp_size, p], beta[samp_size],
@@ -272,18 +288,13 @@ def Metro(gp, start, N, samp_size, batch_size, alpha, D_train, sigma2, y, theta1
     (the sequential caller on the batched path).  `logpost_fn(rows) -> (val, beta)`
     replaces the device evaluator (tests)."""
     rng = np.random.default_rng(rng)
-    pars = None
     if logpost_fn is None:
-        if gp.script in ("HX", "ADV"):
-            pars = (*np.ravel(theta1_pars)[:2], *np.ravel(theta2_pars)[:2])
+        pars = _prior_pars(gp, theta1_pars, theta2_pars)
 
         def logpost_fn(rows):
             return logpost_batch(gp, D_train, rows, y, sigma2, pars)
 
-    def val_batch(rows):
-        return logpost_fn(rows)[0]
-
-    est = laplace(val_batch, start)
+    est = laplace(lambda rows: logpost_fn(rows)[0], start)
     ch = _Chain(est, float(logpost_fn(est["mode"][None])[0][0]), N, samp_size, batch_size, alpha, rng, max_proposals)
     m = int(speculate)
     if m <= 1:
@@ -307,6 +318,14 @@ def logpost_sets_batch(gp, D_trains, theta_t, ys, sigma2s, set_of, prior_pars=No
     (ccgp_logpost_sets) -> (val, beta), each value with the bits logpost_batch gives it on its set alone."""
     val, beta, _, _ = gp.h.logpost_sets(D_trains, ys, sigma2s, gp.cfg["prior"], theta_t, set_of, prior_pars)
     return val, beta
+
+
+def _device_sets_evaluator(gp, D_trains, ys, sigma2s, theta1_pars, theta2_pars):
+    """`(rows, set_of) -> (val, beta)` over logpost_sets_batch with the sets stacked once."""
+    pars = _prior_pars(gp, theta1_pars, theta2_pars)
+    Xs = np.stack([np.asarray(D, dtype=np.float64) for D in D_trains])
+    Y = np.stack([np.asarray(y, dtype=np.float64).ravel() for y in ys])
+    return lambda rows, set_of: logpost_sets_batch(gp, Xs, rows, Y, sigma2s, set_of, pars)
 
 
 def laplace_sets(fn_sets, starts, hess_step=1e-3, maxiter=2000):
@@ -379,33 +398,9 @@ def laplace_sets(fn_sets, starts, hess_step=1e-3, maxiter=2000):
         for c in live:
             o = np.argsort(fsim[c], kind="stable")
             sim[c], fsim[c] = sim[c][o], fsim[c][o]
-    pts, idx = [], []
-    for c in range(C):
-        mode = sim[c, 0]
-        for i in range(p):
-            for j in range(i, p):
-                for si, sj in ((1, 1), (1, -1), (-1, 1), (-1, -1)):
-                    x = mode.copy()
-                    x[i] += si * hess_step
-                    x[j] += sj * hess_step
-                    pts.append(x)
-                if c == 0:
-                    idx.append((i, j))
-    per = 4 * len(idx)
-    vals = np.asarray(fn_sets(np.asarray(pts), np.repeat(np.arange(C), per)), dtype=np.float64).reshape(C, -1, 4)
-    out = []
-    for c in range(C):
-        H = np.zeros((p, p))
-        for (i, j), v in zip(idx, vals[c]):
-            H[i, j] = H[j, i] = (v[0] - v[1] - v[2] + v[3]) / (4.0 * hess_step ** 2)
-        try:
-            var = -np.linalg.inv(H)
-            np.linalg.cholesky(var)
-        except np.linalg.LinAlgError:
-            var = np.diag(1.0 / np.maximum(-np.diag(H), 1e-6))   # not negative definite: fall back to its diagonal
-        out.append(dict(mode=sim[c, 0].copy(), var=var, converged=bool(converged[c]), value=-float(fsim[c, 0]),
-                        iterations=int(iters[c]), evaluations=int(evals[c])))
-    return out
+    var = _hessian_vars(fn_sets, sim[:, 0], hess_step)
+    return [dict(mode=sim[c, 0].copy(), var=var[c], converged=bool(converged[c]), value=-float(fsim[c, 0]),
+                 iterations=int(iters[c]), evaluations=int(evals[c])) for c in range(C)]
 
 
 def Metro_sets(gp, starts, N, samp_size, batch_size, alpha, D_trains, sigma2s, ys, theta1_pars=None, theta2_pars=None,
@@ -421,32 +416,28 @@ def Metro_sets(gp, starts, N, samp_size, batch_size, alpha, D_trains, sigma2s, y
     rngs = [np.random.default_rng(r) for r in (rngs if rngs is not None else [None] * C)]
     if len(rngs) != C:
         raise ValueError("Metro_sets takes one generator per set")
-    calls = dict(n=0)
+    laplace_calls = 0
     if logpost_sets_fn is None:
-        pars = None
-        if gp.script in ("HX", "ADV"):
-            pars = (*np.ravel(theta1_pars)[:2], *np.ravel(theta2_pars)[:2])
-        Xs = np.stack([np.asarray(D, dtype=np.float64) for D in D_trains])
-        Y = np.stack([np.asarray(y, dtype=np.float64).ravel() for y in ys])
-
-        def logpost_sets_fn(rows, set_of):
-            return logpost_sets_batch(gp, Xs, rows, Y, sigma2s, set_of, pars)
+        logpost_sets_fn = _device_sets_evaluator(gp, D_trains, ys, sigma2s, theta1_pars, theta2_pars)
 
     def evaluate(rows, set_of):
-        calls["n"] += 1
         return logpost_sets_fn(np.asarray(rows), np.asarray(set_of, dtype=np.int64))
 
+    def counted(rows, set_of):
+        nonlocal laplace_calls
+        laplace_calls += 1
+        return evaluate(rows, set_of)[0]
+
     if laplace is None:
-        ests = laplace_sets(lambda rows, set_of: evaluate(rows, set_of)[0], starts)
+        ests = laplace_sets(counted, starts)
     else:
         ests = list(laplace)
         if len(ests) != C:
             raise ValueError("Metro_sets takes one Laplace estimate per set")
-    laplace_calls, calls["n"] = calls["n"], 0
     l0 = evaluate(np.stack([e["mode"] for e in ests]), np.arange(C))[0]
     chains = [_Chain(ests[c], float(l0[c]), N, samp_size, batch_size, alpha, rngs[c], max_proposals) for c in range(C)]
-    calls["n"] = 0
-    m = int(speculate)
+    batches, m = 0, int(speculate)
+    per = (1 << m) - 1
     while True:
         live = [c for c in range(C) if chains[c].running()]
         if not live:
@@ -454,20 +445,20 @@ def Metro_sets(gp, starts, N, samp_size, batch_size, alpha, D_trains, sigma2s, y
         if m <= 1:
             pairs = [chains[c].propose() for c in live]
             l_all, b_all = evaluate(np.stack([cand for _, cand in pairs]), live)
-            for j, c in enumerate(live):
-                chains[c].batches += 1
-                chains[c].consume(pairs[j][0], pairs[j][1], float(l_all[j]), float(b_all[j]))
         else:
             trees = [chains[c].tree(m) for c in live]
-            per = (1 << m) - 1
             l_all, b_all = evaluate(np.concatenate([np.concatenate(t, axis=0) for t in trees], axis=0), np.repeat(live, per))
-            for j, c in enumerate(live):
-                chains[c].batches += 1
+        batches += 1
+        for j, c in enumerate(live):
+            chains[c].batches += 1
+            if m <= 1:
+                chains[c].consume(pairs[j][0], pairs[j][1], float(l_all[j]), float(b_all[j]))
+            else:
                 chains[c].walk(trees[j], l_all[j * per:(j + 1) * per], b_all[j * per:(j + 1) * per])
     if m > 1:
         for ch in chains:
             ch.rewind()
-    return dict(chains=[ch.result("Metro_sets (set %d)" % c) for c, ch in enumerate(chains)], device_batches=calls["n"],
+    return dict(chains=[ch.result("Metro_sets (set %d)" % c) for c, ch in enumerate(chains)], device_batches=batches,
                 laplace_calls=laplace_calls)
 
 
@@ -526,30 +517,39 @@ def prediction_single(handle, D_train, D_new, y_train, MLE, alpha, nu=None):
     return dict(y_hat_single=mean[0].copy(), LL_single=lo, UL_single=hi, single_var=var[0].copy())
 
 
+def _single_model(gp, D_train, y_train, single):
+    """The single-GP comparator of compare_GP and leave_one_out: the model `single` gives (theta, sigma2[, beta], or est = a
+    fit routine's dict, which goes into the table as it is) or, without one, the fit on the device (matern_MLEs for a 1-D gp,
+    ordinary_kriging_fit otherwise; further keys of `single` go to it).  Returns (model, handle, D, sigma2 argument,
+    variance form): the 1-D scripts take the unbiased form under the Matern family, the others the plug-in form."""
+    base = getattr(gp.h, "_handle", gp.h)
+    given = dict(single) if isinstance(single, dict) else {}
+    model = {k: given.pop(k) for k in ("theta", "sigma2", "beta") if k in given}
+    if "est" in given:
+        model = given.pop("est")
+    if hasattr(gp, "nu"):
+        from .rsurface import _FamilyHandle
+        D = np.asarray(D_train, dtype=np.float64).reshape(-1, 1)
+        if "theta" not in model:
+            model = matern_MLEs(base, D, y_train, gp.nu, **given)
+        return model, _FamilyHandle(base, api.KERNEL_MATERN, float(gp.nu)), D, None, api.VAR_UNBIASED
+    D = np.asarray(D_train, dtype=np.float64)
+    if "theta" not in model or "sigma2" not in model:
+        model = ordinary_kriging_fit(base, D, y_train, **given)
+    return model, base, D, [model["sigma2"]], api.VAR_PLUGIN
+
+
 def _add_single_columns(table, gp, D_test, alpha, D_train, y_train, single):
     """compare.GP's single-GP columns.  The 2-D / emulator scripts: mlegp + predict.gp(se.fit = TRUE), fit -+ se.fit
     qt(1 - alpha / 2, n - 1) (GV:662-666, ANI:679-683, ISO:665-669, ADV:733-737, BSQ:664-668) -- the plug-in variance.  The
     1-D scripts: MLEs() + prediction.single (D1:548-567) -- the unbiased form, which also gives single_var."""
-    one_d = hasattr(gp, "nu")
-    base = getattr(gp.h, "_handle", gp.h)
-    given = dict(single) if isinstance(single, dict) else {}
-    model = {k: given.pop(k) for k in ("theta", "sigma2", "beta") if k in given}
-    if "est" in given:   # a fitted model as the fit routine returned it: it goes into the table as it is
-        model = given.pop("est")
-    if one_d:
-        D = np.asarray(D_train, dtype=np.float64).reshape(-1, 1)
-        if "theta" not in model:
-            model = matern_MLEs(base, D, y_train, gp.nu, **given)
-        table.update(prediction_single(base, D, np.asarray(D_test, dtype=np.float64).reshape(-1, 1), y_train, model, alpha,
-                                       nu=gp.nu))
+    model, h, D, s2, form = _single_model(gp, D_train, y_train, single)
+    if hasattr(gp, "nu"):   # h is the Matern(nu) handle already
+        table.update(prediction_single(h, D, np.asarray(D_test, dtype=np.float64).reshape(-1, 1), y_train, model, alpha))
         table["single"] = model
         return table
-    D = np.asarray(D_train, dtype=np.float64)
-    if "theta" not in model or "sigma2" not in model:
-        model = ordinary_kriging_fit(base, D, y_train, **given)
     theta = np.asarray(model["theta"], dtype=np.float64).ravel()
-    mean, var, _, _, st = base.krige_predict_batch(D, y_train, 1, np.concatenate([[1.0], theta])[None], [model["sigma2"]],
-                                                   D_test, api.VAR_PLUGIN)
+    mean, var, _, _, st = h.krige_predict_batch(D, y_train, 1, np.concatenate([[1.0], theta])[None], s2, D_test, form)
     if st[0] != 0:
         raise RuntimeError("compare_GP: the single GP's correlation matrix could not be factorised (pivot %d)" % st[0])
     lo, hi = _t_interval(mean[0], var[0], alpha, D.shape[0])
@@ -596,22 +596,8 @@ def _add_single_loo_columns(table, gp, alpha, D_train, y_train, single):
     parameters stay fixed across the folds, as for the Combined GP's draws), then one ccgp_loo_batch row with K = 1 -- the
     plug-in variance for the 2-D / emulator scripts, the unbiased form for the 1-D scripts -- and the interval
     y_hat -+ qt(1 - alpha / 2, n - 2) sqrt(max(var, 0)): a fold has n - 1 points."""
-    one_d = hasattr(gp, "nu")
-    base = getattr(gp.h, "_handle", gp.h)
-    given = dict(single) if isinstance(single, dict) else {}
-    model = {k: given.pop(k) for k in ("theta", "sigma2", "beta") if k in given}
     y = np.asarray(y_train, dtype=np.float64).ravel()
-    if one_d:
-        from .rsurface import _FamilyHandle
-        D = np.asarray(D_train, dtype=np.float64).reshape(-1, 1)
-        if "theta" not in model:
-            model = matern_MLEs(base, D, y, gp.nu, **given)
-        h, s2, form = _FamilyHandle(base, api.KERNEL_MATERN, float(gp.nu)), None, api.VAR_UNBIASED
-    else:
-        D = np.asarray(D_train, dtype=np.float64)
-        if "theta" not in model or "sigma2" not in model:
-            model = ordinary_kriging_fit(base, D, y, **given)
-        h, s2, form = base, [model["sigma2"]], api.VAR_PLUGIN
+    model, h, D, s2, form = _single_model(gp, D_train, y, single)
     theta = np.atleast_1d(np.asarray(model["theta"], dtype=np.float64)).ravel()
     if theta.size != D.shape[1]:
         raise ValueError("the single GP's theta must hold one scale per input dimension")
@@ -620,7 +606,7 @@ def _add_single_loo_columns(table, gp, alpha, D_train, y_train, single):
         raise RuntimeError("leave_one_out: the single GP's correlation matrix could not be factorised (pivot %d)" % st[0])
     lo, hi = _t_interval(mean[0], var[0], alpha, D.shape[0] - 1)
     table.update(y_hat_single=mean[0].copy(), LL_single=lo, UL_single=hi, single=model)
-    if one_d:
+    if hasattr(gp, "nu"):
         table["single_var"] = var[0].copy()
     return table
 
@@ -630,7 +616,8 @@ def leave_one_out(gp, alpha, draws, D_train, sigma2, y_train, single=False):
     predictive of y_i given the n - 1 other points under the posterior draws (gp.leave_one_out: one factorisation per draw,
     no refitting), y_true = y_train.  comparison_summary of it gives the Combined GP's leave-one-out RMSPE (what GV:199 calls
     rmscv for the CGP), interval coverage and mean quantile without a held-out set; `pit` holds F(y_i).  single as in
-    compare_GP (True fits, a dict gives the model) adds y_hat_single, LL_single, UL_single.  No CGP columns: its jackknife is
+    compare_GP (True fits; a dict(theta=..., sigma2=...) or dict(est=<a dict of ordinary_kriging_fit>) gives the model) adds
+    y_hat_single, LL_single, UL_single.  No CGP columns: its jackknife is
     cgp.CGP's Yjfp / rmscv and has no interval in the reference."""
     r = gp.leave_one_out(alpha, draws, D_train, sigma2, y_train)
     table = dict(y_hat=r["y_hat"], quant=r["Quant"], LL=r["LL"], UL=r["UL"],
@@ -638,6 +625,16 @@ def leave_one_out(gp, alpha, draws, D_train, sigma2, y_train, single=False):
     if single:
         _add_single_loo_columns(table, gp, alpha, D_train, y_train, single)
     return table
+
+
+def _q_logdet_beta(h, D, y, rows):
+    """(Q, log det R, beta, ok) per parameter row, Q = (y - beta)' R^-1 (y - beta), from two likelihood calls that differ in
+    sigma2 only: ll(s) = -(n log 2pi + n log s + logdet + Q / s) / 2 at s = 1 and s = e.  ok: the row was factorised."""
+    n = D.shape[0]
+    a, beta, st = h.loglik_batch(D, y, 1, rows, 1.0)
+    b, _, _ = h.loglik_batch(D, y, 1, rows, math.e)
+    Q = (n - 2.0 * (a - b)) / (1.0 - 1.0 / math.e)
+    return Q, -2.0 * a - n * math.log(2 * math.pi) - Q, beta, (st == 0) & np.isfinite(a)
 
 
 def ordinary_kriging_sigma2(handle, D_train, y_train, starts=8, rng=0):
@@ -657,14 +654,8 @@ def ordinary_kriging_sigma2(handle, D_train, y_train, starts=8, rng=0):
     span = np.maximum(D.max(axis=0) - D.min(axis=0), 1e-12)
 
     def parts(theta):
-        row = np.concatenate([[1.0], theta])[None]
-        a, beta, st = handle.loglik_batch(D, y, 1, row, 1.0)
-        b, _, _ = handle.loglik_batch(D, y, 1, row, math.e)
-        if st[0] != 0 or not math.isfinite(a[0]):
-            return None
-        Q = (n - 2.0 * (a[0] - b[0])) / (1.0 - 1.0 / math.e)       # (y-b)'R^-1(y-b)
-        logdet = -2.0 * a[0] - n * math.log(2 * math.pi) - Q
-        return max(Q, 1e-300), logdet, beta[0]
+        Q, logdet, beta, ok = _q_logdet_beta(handle, D, y, np.concatenate([[1.0], theta])[None])
+        return (max(Q[0], 1e-300), logdet[0], beta[0]) if ok[0] else None
 
     def f(logth):
         theta = np.exp(logth)
@@ -712,14 +703,9 @@ def matern_MLEs(handle, D, y, nu, grid=96, lo=1e-3, hi=1e2):
     span = max(float(D.max() - D.min()), 1e-12)
 
     def parts(thetas):
-        """(Q, logdet, beta) per theta from two likelihood evaluations that differ in sigma2 only:
-        ll(s) = -(n log 2pi + n log s + logdet + Q / s) / 2."""
-        P = np.stack([np.ones_like(thetas), thetas], axis=1)
-        a, beta, st = h.loglik_batch(D, y, 1, P, 1.0)
-        b, _, _ = h.loglik_batch(D, y, 1, P, math.e)
-        Q = (n - 2.0 * (a - b)) / (1.0 - 1.0 / math.e)
-        logdet = -2.0 * a - n * math.log(2 * math.pi) - Q
-        bad = (st != 0) | ~np.isfinite(a) | ~(Q > 0)
+        """(Q, logdet, beta) per theta, NaN where the row failed or Q is not positive."""
+        Q, logdet, beta, ok = _q_logdet_beta(h, D, y, np.stack([np.ones_like(thetas), thetas], axis=1))
+        bad = ~ok | ~(Q > 0)
         return np.where(bad, np.nan, Q), np.where(bad, np.nan, logdet), beta
 
     def objective(thetas):
@@ -765,28 +751,51 @@ def ordinary_kriging_fit(handle, D_train, y_train, starts=8, rng=0, extra_starts
     ordinary_kriging_sigma2, then `extra_starts` (rows of theta).  Returns dict(sigma2, theta[d], beta, loglik of the best
     start -- sigma2, beta and loglik as a final value-only call at theta gives them -- f[S], x[S, d] (log theta) and converged[S]
     per start, calls: the number of profile_batch calls, the final one included, and evaluations: the points they carried)."""
-    from .design import minimize_starts
-
     D = np.asarray(D_train, dtype=np.float64)
     y = np.asarray(y_train, dtype=np.float64).ravel()
-    x0 = kriging_starts(D, starts, rng, extra_starts)
-    count = dict(points=0)
 
-    def evaluate(logth):
+    def profile(rows, set_of, grad):
+        ll, s2, beta, g, st = handle.profile_batch(D, y, 1, rows, grad=grad)
+        return (ll, g, st) if grad else (ll, s2, beta)
+
+    return _kriging_fit_sets("ordinary_kriging_fit", "", profile, [D], [rng], starts, extra_starts)[0]
+
+
+def _kriging_fit_sets(who, of_set, profile, Ds, seeds, starts, extra_starts):
+    """The lockstep fit behind ordinary_kriging_fit (C = 1) and ordinary_kriging_fit_sets: the kriging_starts of every set
+    through ONE design.minimize_starts, then one value-only call at the C best points.  profile(rows, set_of, grad)
+    evaluates row b on set set_of[b] -> (ll, gradient, status) with grad, (ll, sigma2, beta) without.  who and of_set (a format of
+    the set's index, or empty) word the error.  Returns one dict per set."""
+    from .design import minimize_starts
+
+    C = len(Ds)
+    x0 = [kriging_starts(Ds[c], starts, seeds[c], extra_starts) for c in range(C)]
+    S = x0[0].shape[0]
+    owner = np.repeat(np.arange(C), S)
+    points = np.zeros(C, dtype=np.int64)
+
+    def evaluate(logth, live):
         theta = np.exp(logth)
-        rows = np.concatenate([np.ones((theta.shape[0], 1)), theta], axis=1)
-        ll, _, _, g, st = handle.profile_batch(D, y, 1, rows, grad=True)
-        count["points"] += theta.shape[0]
+        ll, g, st = profile(np.concatenate([np.ones((theta.shape[0], 1)), theta], axis=1), owner[live], True)
+        np.add.at(points, owner[live], 1)
         return -ll, -(g[:, 1:] * theta), st
 
-    res = minimize_starts(evaluate, x0, lower=-12.0, upper=12.0)
-    if not np.isfinite(res["f"]).any():
-        raise RuntimeError("ordinary_kriging_fit: the likelihood failed at every start")
-    best = int(np.argmin(np.where(np.isfinite(res["f"]), res["f"], np.inf)))
-    theta = np.exp(res["x"][best])
-    ll, s2, beta, _, _ = handle.profile_batch(D, y, 1, np.concatenate([[1.0], theta])[None], grad=False)
-    return dict(sigma2=float(s2[0]), theta=theta, beta=float(beta[0]), loglik=float(ll[0]), f=res["f"], x=res["x"],
-                converged=res["converged"], calls=res["calls"] + 1, evaluations=count["points"] + 1)
+    res = minimize_starts(evaluate, np.concatenate(x0), lower=-12.0, upper=12.0, pass_live=True)
+    best = []
+    for c in range(C):
+        f = res["f"][c * S:(c + 1) * S]
+        if not np.isfinite(f).any():
+            raise RuntimeError("%s: the likelihood failed at every start%s" % (who, of_set and of_set % c))
+        best.append(c * S + int(np.argmin(np.where(np.isfinite(f), f, np.inf))))
+    thetas = np.exp(res["x"][best])
+    ll, s2, beta = profile(np.concatenate([np.ones((C, 1)), thetas], axis=1), np.arange(C), False)
+    out = []
+    for c in range(C):
+        sl = slice(c * S, (c + 1) * S)
+        out.append(dict(sigma2=float(s2[c]), theta=thetas[c], beta=float(beta[c]), loglik=float(ll[c]), f=res["f"][sl],
+                        x=res["x"][sl], converged=res["converged"][sl], calls=int(res["calls_per_start"][sl].max()) + 1,
+                        evaluations=int(points[c]) + 1))
+    return out
 
 
 def ordinary_kriging_fit_sets(handle, D_trains, y_trains, starts=8, rng=0, extra_starts=None):
@@ -801,8 +810,6 @@ def ordinary_kriging_fit_sets(handle, D_trains, y_trains, starts=8, rng=0, extra
     the number of gradient calls of the group is the LARGEST per-set count, not the sum.  Each dict's calls / evaluations
     are that set's own (the calls its starts took part in, the final one included): the group made max(calls) device
     calls."""
-    from .design import minimize_starts
-
     Ds = [np.asarray(D, dtype=np.float64) for D in D_trains]
     ys = [np.asarray(y, dtype=np.float64).ravel() for y in y_trains]
     C = len(Ds)
@@ -813,37 +820,13 @@ def ordinary_kriging_fit_sets(handle, D_trains, y_trains, starts=8, rng=0, extra
     seeds = list(rng) if isinstance(rng, (list, tuple)) else [rng] * C
     if len(seeds) != C:
         raise ValueError("ordinary_kriging_fit_sets: rng is one seed, or one per set")
-    x0 = [kriging_starts(Ds[c], starts, seeds[c], extra_starts) for c in range(C)]
-    S = x0[0].shape[0]
-    owner = np.repeat(np.arange(C), S)
     Xs, Y = np.stack(Ds), np.stack(ys)
-    points = np.zeros(C, dtype=np.int64)
 
-    def evaluate(logth, live):
-        theta = np.exp(logth)
-        rows = np.concatenate([np.ones((theta.shape[0], 1)), theta], axis=1)
-        set_of = owner[live]
-        ll, _, _, g, st = handle.profile_batch_sets(Xs, Y, 1, rows, set_of, grad=True)
-        np.add.at(points, set_of, 1)
-        return -ll, -(g[:, 1:] * theta), st
+    def profile(rows, set_of, grad):
+        ll, s2, beta, g, st = handle.profile_batch_sets(Xs, Y, 1, rows, set_of, grad=grad)
+        return (ll, g, st) if grad else (ll, s2, beta)
 
-    res = minimize_starts(evaluate, np.concatenate(x0), lower=-12.0, upper=12.0, pass_live=True)
-    best = []
-    for c in range(C):
-        f = res["f"][c * S:(c + 1) * S]
-        if not np.isfinite(f).any():
-            raise RuntimeError("ordinary_kriging_fit_sets: the likelihood failed at every start of set %d" % c)
-        best.append(c * S + int(np.argmin(np.where(np.isfinite(f), f, np.inf))))
-    thetas = np.exp(res["x"][best])
-    ll, s2, beta, _, _ = handle.profile_batch_sets(Xs, Y, 1, np.concatenate([np.ones((C, 1)), thetas], axis=1), np.arange(C),
-                                                   grad=False)
-    out = []
-    for c in range(C):
-        sl = slice(c * S, (c + 1) * S)
-        out.append(dict(sigma2=float(s2[c]), theta=thetas[c], beta=float(beta[c]), loglik=float(ll[c]), f=res["f"][sl],
-                        x=res["x"][sl], converged=res["converged"][sl], calls=int(res["calls_per_start"][sl].max()) + 1,
-                        evaluations=int(points[c]) + 1))
-    return out
+    return _kriging_fit_sets("ordinary_kriging_fit_sets", " of set %d", profile, Ds, seeds, starts, extra_starts)
 
 
 def matern_profile(handle, D, y, nu, thetas):
@@ -1052,13 +1035,7 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
         g_s2 = [s2[i] for i in idx]
         fn = logpost_sets_fn(idx) if logpost_sets_fn is not None else None
         if fn is None:
-            pars = None
-            if gp.script in ("HX", "ADV"):
-                pars = (*np.ravel(theta1_pars)[:2], *np.ravel(theta2_pars)[:2])
-            Xs, Y = np.stack(D_trains), np.stack(ys)
-
-            def fn(rows, set_of, Xs=Xs, Y=Y, g_s2=g_s2, pars=pars):
-                return logpost_sets_batch(gp, Xs, rows, Y, g_s2, set_of, pars)
+            fn = _device_sets_evaluator(gp, D_trains, ys, g_s2, theta1_pars, theta2_pars)
         count = dict(n=0)
 
         def counted(rows, set_of, fn=fn, count=count):

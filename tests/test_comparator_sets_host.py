@@ -1,5 +1,5 @@
 """The comparator fits of a simulation study in lockstep across training sets (fit.ordinary_kriging_fit_sets, cgp.CGP_sets,
-fit.study(lockstep_fits=...)) without a GPU.  The handle is a host stand-in: profile_batch and cgp_state_batch / cgp_predict
+fit.study(lockstep_fits=...)) without a GPU.  The handle is a host stand-in (host_handles.SetsHandle): profile_batch and cgp_state_batch / cgp_predict
 are the fp64 restatements tests/test_profile_ref.py and tests/test_cgp_ref.py already run the fits on, and its *_sets methods
 call its own single-set methods set by set -- so what is held here is the host arithmetic around the device calls: a set's
 fit in the group is its fit alone, bit for bit, and the group makes as many evaluator calls as its slowest set.  Every
@@ -14,115 +14,12 @@ import re
 import numpy as np
 import pytest
 
-import cgp_ref
-import krige_ref
-import profile_ref
 from conftest import synthetic_design
+from host_handles import SetsHandle
 from ccgp_amd import api, cgp, design, fit
-from oracle import ccgp_oracle as orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ccgp_profile_batch_sets", "ccgp_cgp_state_batch_sets")
-
-
-class SetsHandle:
-    """profile_batch, cgp_state_batch, cgp_predict, krige_predict_batch and logpost_sets on the host; the *_sets methods go
-    set by set through the single-set ones.  calls: single-set and sets calls made by a fit, each counted once."""
-
-    def __init__(self):
-        self.profile, self.cgp = profile_ref.NumpyHandle(), cgp_ref.NumpyHandle()
-        self.memo = {}
-        self.calls = dict(profile_batch=0, profile_batch_sets=0, cgp_state_batch=0, cgp_state_batch_sets=0, cgp_predict=0)
-        self.inner = False
-
-    def _count(self, name):
-        if not self.inner:
-            self.calls[name] += 1
-
-    def _rows(self, tag, fn, X, y, rows, extra):
-        """fn(row index) per row, remembered by the bytes of (set, row, extra)."""
-        key0 = (tag, np.ascontiguousarray(X).tobytes(), np.ascontiguousarray(y).tobytes())
-        out = []
-        for b in range(len(rows)):
-            key = key0 + (rows[b].tobytes(), extra[b])
-            if key not in self.memo:
-                self.memo[key] = fn(b)
-            out.append(self.memo[key])
-        return out
-
-    # ---- single-set calls
-    def profile_batch(self, X, y, K, params, grad=False):
-        self._count("profile_batch")
-        X, y = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64).ravel()
-        P = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
-
-        def one(b):
-            ll, s2, beta, g, st = self.profile.profile_batch(X, y, K, P[b:b + 1], grad=True)
-            return ll[0], s2[0], beta[0], g[0], st[0]
-        r = self._rows("profile%d" % K, one, X, y, P, [0] * len(P))
-        g = np.stack([v[3] for v in r]) if grad else None
-        return (np.array([v[0] for v in r]), np.array([v[1] for v in r]), np.array([v[2] for v in r]), g,
-                np.array([v[4] for v in r], dtype=np.int32))
-
-    def cgp_state_batch(self, X, y, params, skip=None):
-        self._count("cgp_state_batch")
-        X, y = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64).ravel()
-        P = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
-        sk = [-1] * len(P) if skip is None else [int(s) for s in skip]
-
-        def one(b):
-            v = self.cgp.cgp_state_batch(X, y, P[b:b + 1], skip=None if skip is None else [sk[b]])
-            return v[0][0], v[1][0], v[2][0], (np.nan if v[3] is None else v[3][0]), v[4][0]
-        r = self._rows("cgp", one, X, y, P, sk)
-        cols = [np.array([v[k] for v in r]) for k in range(4)]
-        return cols[0], cols[1], cols[2], (None if skip is None else cols[3]), np.array([v[4] for v in r], dtype=np.int32)
-
-    def cgp_predict(self, X, y, row, Xtest):
-        self._count("cgp_predict")
-        return self.cgp.cgp_predict(np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64).ravel(), row, Xtest)
-
-    def krige_predict_batch(self, X, y, K, params, sigma2, Xtest, form):
-        assert form == api.VAR_PLUGIN and len(params) == 1
-        r = krige_ref.device_restatement(np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64).ravel(),
-                                         np.asarray(params[0], dtype=np.float64), K, np.asarray(Xtest, dtype=np.float64))
-        return r["mean"][None], (sigma2[0] * r["plug_unit"])[None], np.array([r["beta"]]), None, np.zeros(1, dtype=np.int32)
-
-    def logpost_sets(self, Xs, ys, sigma2s, prior, theta_t, set_of, prior_pars=None):
-        out = [orc.logpost(Xs[c], t, ys[c], sigma2s[c], "GV") for t, c in zip(np.atleast_2d(theta_t), set_of)]
-        val, beta = np.array([o["val"] for o in out]), np.array([o["beta"] for o in out])
-        return val, beta, val, np.zeros(len(out), dtype=np.int32)
-
-    # ---- the sets calls: the single-set ones, set by set
-    def _by_set(self, name, call, set_of, B, nout):
-        self._count(name)
-        set_of = np.asarray(set_of)
-        assert set_of.shape == (B,)
-        out = [None] * nout
-        self.inner = True
-        try:
-            for c in np.unique(set_of):
-                rows = np.flatnonzero(set_of == c)
-                for k, v in enumerate(call(int(c), rows)):
-                    if v is None:
-                        continue
-                    if out[k] is None:
-                        out[k] = np.empty((B,) + v.shape[1:], dtype=v.dtype)
-                    out[k][rows] = v
-        finally:
-            self.inner = False
-        return tuple(out)
-
-    def profile_batch_sets(self, Xs, ys, K, params, set_of, grad=True):
-        P = np.atleast_2d(params)
-        return self._by_set("profile_batch_sets", lambda c, rows: self.profile_batch(Xs[c], ys[c], K, P[rows], grad), set_of,
-                            len(P), 5)
-
-    def cgp_state_batch_sets(self, Xs, ys, params, set_of, skip=None):
-        P = np.atleast_2d(params)
-        sk = None if skip is None else np.asarray(skip)
-        return self._by_set("cgp_state_batch_sets",
-                            lambda c, rows: self.cgp_state_batch(Xs[c], ys[c], P[rows], None if sk is None else sk[rows]),
-                            set_of, len(P), 5)
 
 
 def _same_dict(got, want, skip=()):

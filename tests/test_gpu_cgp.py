@@ -130,7 +130,7 @@ def test_a_row_has_the_same_bits_alone_in_a_batch_and_across_a_split():
         small = h.cgp_state_batch(Xs, y, rows[:600], skip=skip[:600])
         whole = h.cgp_state_batch(Xs, y, rows, skip=skip)
         ws_whole = h.workspace_bytes()[0]
-        # a row costs 8 (2 d + 2 + 4) + 8 = 88 bytes of workspace: 1 MiB, the smallest limit, holds 11 915 of the 12 500
+        # a row costs 8 (2 d + 2 + 4) + 12 = 92 bytes of workspace: 1 MiB, the smallest limit, holds 11 397 of the 12 500
         h2 = api.Handle(0)
         try:
             h2.set_workspace_limit(1 << 20)
