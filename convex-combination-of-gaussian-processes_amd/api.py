@@ -62,6 +62,12 @@ SIGNATURES = {
                                   _ip]),
     "ccgp_profile_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, c_int, _dp, _ip, c_int, _dp, _dp, _dp, _dp,
                                         _ip]),
+    "ccgp_chain_terms": (c_int, [c_int, c_int, _dp, c_int, _dp, _dp, _dp, _dp]),
+    "ccgp_chain_logpost_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, _ip, c_int, _dp, _dp, _dp,
+                                        _dp, _ip]),
+    "ccgp_metro_segments_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, c_int, _ip, _dp, _dp, _dp,
+                                         c_int, _dp, _dp, _ip, _ip, c_int, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                         _ip, _ip]),
     "ccgp_cgp_state_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _ip, _dp, _dp, _dp, _dp,
                                           _ip]),
     "ccgp_grid_marginal": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, _dp, c_int, c_int,
@@ -186,6 +192,20 @@ def qigamma(p, alpha, beta):
     if rc:
         raise CcgpError(rc, "ccgp_qigamma")
     return out
+
+
+def chain_terms(prior_id, d, theta_t, prior_pars=None):
+    """ccgp_chain_terms: the parameter rows [B, 2 + 2 d], log-Jacobians and log-priors of the transformed vectors theta_t
+    [B, q] by the portable arithmetic the chain kernel runs (csrc/chain_terms.h) -> (rows, ljac, lprior).  No device."""
+    theta_t = _f(np.atleast_2d(theta_t))
+    B = theta_t.shape[0]
+    pp = _f(np.ravel(prior_pars)) if prior_pars is not None else None
+    rows = np.empty((B, 2 + 2 * int(d)), order="F")
+    lj, lp = np.empty(B), np.empty(B)
+    rc = lib().ccgp_chain_terms(int(prior_id), int(d), _p(theta_t), B, _p(pp), _p(rows), _p(lj), _p(lp))
+    if rc:
+        raise CcgpError(rc, "ccgp_chain_terms")
+    return rows, lj, lp
 
 
 SUMMARY_MAX_PROBS = 8
@@ -665,6 +685,55 @@ class Handle:
         self._chk(lib().ccgp_logpost_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, int(prior_id), _p(theta_t), _ipt(idx), B,
                                           _p(pp), _p(val), _p(beta), _p(ll), _ipt(st)))
         return val, beta, ll, st
+
+    def chain_logpost_sets(self, Xs, ys, sigma2s, prior_id, theta_t, set_of, prior_pars=None):
+        """ccgp_chain_logpost_sets: logpost_sets with the portable Jacobian / prior arithmetic of the device chains -- the
+        host twin of metro_segments_sets' evaluation -> (val, beta, loglik, status)."""
+        theta_t = _f(np.atleast_2d(theta_t))
+        B = theta_t.shape[0]
+        Xb, yb, s2, idx, C, n, d = self._sets(Xs, ys, sigma2s, set_of, B)
+        pp = _f(np.ravel(prior_pars)) if prior_pars is not None else None
+        val, beta, ll, st = _outputs(B, 3)
+        self._chk(lib().ccgp_chain_logpost_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, int(prior_id), _p(theta_t),
+                                                _ipt(idx), B, _p(pp), _p(val), _p(beta), _p(ll), _ipt(st)))
+        return val, beta, ll, st
+
+    def metro_segments_sets(self, Xs, ys, sigma2s, prior_id, set_of, theta0, l0, steps, logu, n_prop, stop_acc,
+                            prior_pars=None, beta0=None, trace=False):
+        """ccgp_metro_segments_sets: A chains, chain a on training set set_of[a], walked on the device through the proposals
+        theta + steps[a, t] with log-uniforms logu[a, t] (steps [A, T, q], logu [A, T]) from the state (theta0 [A, q], l0 [A],
+        beta0 [A] or None) until chain a has accepted stop_acc[a] draws or used n_prop[a] proposals.  Returns dict(used[A],
+        accepted[A], draws [A, M, q], draw_val [A, M], draw_beta [A, M] with M = max(stop_acc, 1) -- NaN beyond a chain's
+        accepted count --, theta [A, q], l [A], beta [A], failed: proposals whose factorisation failed, and with trace=True
+        trace_val, trace_beta, trace_status, trace_accept [A, T])."""
+        theta0 = _f(np.atleast_2d(theta0))
+        A, q = theta0.shape
+        Xb, yb, s2, idx, C, n, d = self._sets(Xs, ys, sigma2s, set_of, A)
+        steps = np.ascontiguousarray(np.asarray(steps, dtype=np.float64))
+        if steps.ndim != 3 or steps.shape[0] != A or steps.shape[2] != q:
+            raise ValueError("steps must be [A, T, q]")
+        T = steps.shape[1]
+        logu = np.ascontiguousarray(np.asarray(logu, dtype=np.float64).reshape(A, T))
+        l0 = np.ascontiguousarray(np.asarray(l0, dtype=np.float64).reshape(A))
+        b0 = None if beta0 is None else np.ascontiguousarray(np.asarray(beta0, dtype=np.float64).reshape(A))
+        n_prop = np.ascontiguousarray(np.asarray(n_prop).reshape(A).astype(np.int32))
+        stop_acc = np.ascontiguousarray(np.asarray(stop_acc).reshape(A).astype(np.int32))
+        M = max(int(stop_acc.max()) if A else 1, 1)
+        pp = _f(np.ravel(prior_pars)) if prior_pars is not None else None
+        used, acc = np.zeros(A, dtype=np.int32), np.zeros(A, dtype=np.int32)
+        draws, dval, dbeta = np.empty((A, M, q)), np.empty((A, M)), np.empty((A, M))
+        theta, l, beta = np.empty((A, q), order="F"), np.empty(A), np.empty(A)
+        tr = (np.empty((A, T)), np.empty((A, T)), np.zeros((A, T), dtype=np.int32), np.zeros((A, T), dtype=np.int32)) \
+            if trace else (None, None, None, None)
+        failed = self._chk(lib().ccgp_metro_segments_sets(
+            self._h, _p(Xb), n, d, _p(yb), _p(s2), C, int(prior_id), _p(pp), A, _ipt(idx), _p(theta0), _p(l0), _p(b0), T,
+            _p(steps), _p(logu), _ipt(n_prop), _ipt(stop_acc), M, _ipt(used), _ipt(acc), _p(draws), _p(dval), _p(dbeta),
+            _p(theta), _p(l), _p(beta), _p(tr[0]), _p(tr[1]), _ipt(tr[2]), _ipt(tr[3])))
+        out = dict(used=used, accepted=acc, draws=draws, draw_val=dval, draw_beta=dbeta, theta=np.ascontiguousarray(theta),
+                   l=l, beta=beta, failed=failed)
+        if trace:
+            out.update(trace_val=tr[0], trace_beta=tr[1], trace_status=tr[2], trace_accept=tr[3])
+        return out
 
     def profile_batch_sets(self, Xs, ys, K, params, set_of, grad=True):
         """ccgp_profile_batch_sets: row b of params [B, K + K*d] on training set set_of[b] of the C sets Xs [C, n, d],

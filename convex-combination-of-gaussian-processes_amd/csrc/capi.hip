@@ -15,6 +15,7 @@
 
 #include "call_stage.h"
 #include "ccgp_internal.h"
+#include "chain_terms.h"
 #include "special_math.h"
 
 using namespace ccgp;
@@ -731,6 +732,42 @@ int logpost_rows(int prior_id, int d, const double* theta_t, int B, const double
   return rc;
 }
 
+// ---- the portable terms (chain_terms.h) on the host: the twin of what the chain kernel computes ---------------------------
+struct ChainTables {
+  double hi[kChainTable], lo[kChainTable];
+  ChainTables() {
+    static const unsigned long long hb[kChainTable] = CCGP_EXP_TABLE_BITS, lb[kChainTable] = CCGP_CHAIN_EXP_LO_BITS;
+    for (int j = 0; j < kChainTable; ++j) { hi[j] = chain_from_bits(hb[j]); lo[j] = chain_from_bits(lb[j]); }
+  }
+};
+const ChainTables& chain_tables() {
+  static const ChainTables t;
+  return t;
+}
+// logpost_terms' outputs for the B vectors of theta_t (B x q column-major) by chain_terms: rows B x P column-major
+void chain_terms_rows(int prior_id, int d, const double* theta_t, int B, const double* prior_pars, double* rows, double* ljac,
+                      double* lpri) {
+  const ChainTables& tb = chain_tables();
+  const int q = prior_id == CCGP_PRIOR_ANI ? 4 : 3;
+  for (int b = 0; b < B; ++b) {
+    double th[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j = 0; j < q; ++j) th[j] = theta_t[b + (size_t)j * B];
+    const ChainTerms tm = chain_terms(prior_id, th, prior_pars, tb.hi, tb.lo);
+    rows[b] = tm.w0;
+    rows[b + (size_t)B] = tm.w1;
+    for (int c = 0; c < 2; ++c)
+      for (int k = 0; k < d; ++k) rows[b + (size_t)(2 + c * d + k) * B] = chain_rate(tm, prior_id, c, k);
+    ljac[b] = tm.lj;
+    lpri[b] = tm.lp;
+  }
+}
+// what ccgp_logpost_batch refuses about a prior, without a handle to carry the message
+bool chain_prior_ok(int prior_id, int d, const double* prior_pars) {
+  if (prior_id < CCGP_PRIOR_INVGAMMA || prior_id > CCGP_PRIOR_ANI) return false;
+  if (prior_id == CCGP_PRIOR_INVGAMMA && !prior_pars) return false;
+  return prior_id != CCGP_PRIOR_ANI || d == 2;
+}
+
 }  // namespace
 
 // No C++ exception may cross the C ABI (inside R that would be std::terminate for the user's session): every entry point
@@ -1415,6 +1452,136 @@ int ccgp_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const doub
                         return ccgp_loglik_batch_sets(h, Xs, n, d, ys, sigma2, C, K, rows, set, B, CCGP_MEAN_PROFILE_BETA, 0.0,
                                                       ll, beta, st);
                       });
+} CCGP_GUARD_END(h)
+
+// ---- Metropolis chains on the device (ccgp.h) --------------------------------------------------------------------------------
+int ccgp_chain_terms(int prior_id, int d, const double* theta_t, int B, const double* prior_pars, double* out_rows,
+                     double* out_ljac, double* out_lprior) {
+  if (d < 1 || d > kMaxD || B < 0 || !chain_prior_ok(prior_id, d, prior_pars) || !theta_t || !out_rows || !out_ljac || !out_lprior)
+    return CCGP_EINVAL;
+  try {
+    chain_terms_rows(prior_id, d, theta_t, B, prior_pars, out_rows, out_ljac, out_lprior);
+  } catch (...) {
+    return CCGP_ENOMEM;
+  }
+  return CCGP_OK;
+}
+
+// the host twin of the chain kernel's evaluation: ccgp_logpost_sets with the portable terms in place of glibc's
+int ccgp_chain_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                            int prior_id, const double* theta_t, const int* set, int B, const double* prior_pars,
+                            double* out_val, double* out_beta, double* out_loglik, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (int rc = logpost_args(h, "ccgp_chain_logpost_sets",
+                            n >= 1 && d >= 1 && d <= kMaxD && theta_t && out_val &&
+                                sets_args_ok(Xs, ys, sigma2, true, C, set, B, 1),
+                            d, prior_id, prior_pars))
+    return rc;
+  const int K = 2, P = K + K * d;
+  std::vector<double> rows((size_t)B * P), ljac(B), lpri(B), ll(B), beta(B);
+  std::vector<int> st(B);
+  chain_terms_rows(prior_id, d, theta_t, B, prior_pars, rows.data(), ljac.data(), lpri.data());
+  const int rc = ccgp_loglik_batch_sets(h, Xs, n, d, ys, sigma2, C, K, rows.data(), set, B, CCGP_MEAN_PROFILE_BETA, 0.0,
+                                        ll.data(), beta.data(), st.data());
+  if (rc < 0) return rc;
+  for (int b = 0; b < B; ++b) {
+    out_val[b] = chain_value(ll[b], ljac[b], lpri[b]);
+    if (out_beta) out_beta[b] = beta[b];
+    if (out_loglik) out_loglik[b] = ll[b];
+    if (status) status[b] = st[b];
+  }
+  return rc;
+} CCGP_GUARD_END(h)
+
+int ccgp_metro_segments_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                             int prior_id, const double* prior_pars, int A, const int* set, const double* theta0,
+                             const double* l0, const double* beta0, int T, const double* steps, const double* logu,
+                             const int* n_prop, const int* stop_acc, int M, int* out_used, int* out_accepted,
+                             double* out_draws, double* out_draw_val, double* out_draw_beta, double* out_theta, double* out_l,
+                             double* out_beta, double* trace_val, double* trace_beta, int* trace_status,
+                             int* trace_accept) try {
+  if (!h) return CCGP_EINVAL;
+  const int ntrace = (trace_val != nullptr) + (trace_beta != nullptr) + (trace_status != nullptr) + (trace_accept != nullptr);
+  bool ok = n >= 1 && d >= 1 && d <= kMaxD && A >= 0 && T >= 1 && M >= 1 && theta0 && l0 && steps && logu && n_prop &&
+            stop_acc && out_used && out_accepted && out_draws && out_draw_val && out_draw_beta && out_theta && out_l &&
+            (ntrace == 0 || ntrace == 4) && sets_args_ok(Xs, ys, sigma2, true, C, set, A, 0);
+  for (int a = 0; ok && a < A; ++a) ok = n_prop[a] >= 0 && n_prop[a] <= T && stop_acc[a] >= 0 && stop_acc[a] <= M;
+  if (int rc = logpost_args(h, "ccgp_metro_segments_sets", ok, d, prior_id, prior_pars)) return rc;
+  if (small_route_chain(h->fam.id == 0, n, d, 2) != Route::Reg)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_metro_segments_sets: chains run on the device for Gaussian sets of n <= 128 whose "
+                                      "register-resident instance fits; keep the chain on ccgp_chain_logpost_sets");
+  if (A == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  const int q = prior_id == CCGP_PRIOR_ANI ? 4 : 3;
+  const size_t sA = A, sT = (size_t)A * T, sM = (size_t)A * M;
+  double *dXs, *dys, *ds2, *dpp, *dbeta0;
+  int *dset, *dused;
+  ChainIO io{};
+  io.prior_id = prior_id; io.p = q; io.T = T; io.M = M;
+  // inputs back to back, then results back to back: each side crosses PCIe as one span
+  if (int rc = stage(h, [&](Layout& c) {
+        dXs = c.take<double>((size_t)C * n * d);
+        dys = c.take<double>((size_t)C * n);
+        ds2 = c.take<double>(C);
+        dpp = c.take<double>(4);
+        io.prior_pars = dpp;
+        io.theta0 = c.take<double>(sA * q);
+        io.l0 = c.take<double>(sA);
+        io.beta0 = dbeta0 = c.take<double>(sA);
+        io.steps = c.take<double>(sT * q);
+        io.logu = c.take<double>(sT);
+        dset = c.take<int>(sA);
+        io.n_prop = c.take<int>(sA);
+        io.stop_acc = c.take<int>(sA);
+        io.draws = c.take<double>(sM * q);
+        io.draw_val = c.take<double>(sM);
+        io.draw_beta = c.take<double>(sM);
+        io.theta_fin = c.take<double>(sA * q);
+        io.l_fin = c.take<double>(sA);
+        io.beta_fin = c.take<double>(sA);
+        io.used = dused = c.take<int>(3 * sA);   // used | accepted | failed
+        io.nacc = dused ? dused + sA : nullptr;
+        io.nfail = dused ? dused + 2 * sA : nullptr;
+        io.tr_val = ntrace ? c.take<double>(sT) : nullptr;
+        io.tr_beta = ntrace ? c.take<double>(sT) : nullptr;
+        io.tr_status = ntrace ? c.take<int>(sT) : nullptr;
+        io.tr_acc = ntrace ? c.take<int>(sT) : nullptr;
+      }))
+    return rc;
+  const double kNaN = std::nan("");
+  std::vector<double> b0(sA, kNaN);
+  const double pp0[4] = {0.0, 0.0, 0.0, 0.0};
+  if (int prc = push(h, {piece(dXs, Xs, (size_t)C * n * d), piece(dys, ys, (size_t)C * n), piece(ds2, sigma2, C),
+                         piece(dpp, prior_pars ? prior_pars : pp0, 4), piece(const_cast<double*>(io.theta0), theta0, sA * q),
+                         piece(const_cast<double*>(io.l0), l0, sA), piece(dbeta0, beta0 ? beta0 : b0.data(), sA),
+                         piece(const_cast<double*>(io.steps), steps, sT * q), piece(const_cast<double*>(io.logu), logu, sT),
+                         piece(dset, set, sA), piece(const_cast<int*>(io.n_prop), n_prop, sA),
+                         piece(const_cast<int*>(io.stop_acc), stop_acc, sA)}))
+    return prc;
+  if (ntrace) {   // a chain that stops early leaves the rest of its trace as it is: NaN / -1, not what the buffer held
+    CCGP_HIP(hipMemsetAsync(io.tr_val, 0xFF, Layout::al(sT * sizeof(double)) * 2 + Layout::al(sT * sizeof(int)) * 2, h->stream));
+  }
+  CCGP_HIP(hipMemsetAsync(io.draws, 0xFF, (size_t)((char*)io.theta_fin - (char*)io.draws), h->stream));
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    launch_small_reg_chain_sets(h->stream, dXs, n, d, dys, ds2, dset, A, io);
+    CCGP_LAUNCH_CHECK();
+  }
+  std::vector<int> cnt(3 * sA);
+  if (int rc = pull(h, {piece(io.draws, out_draws, sM * q), piece(io.draw_val, out_draw_val, sM),
+                        piece(io.draw_beta, out_draw_beta, sM), piece(io.theta_fin, out_theta, sA * q),
+                        piece(io.l_fin, out_l, sA), piece(io.beta_fin, out_beta, out_beta ? sA : 0),
+                        piece(dused, cnt.data(), 3 * sA), piece(io.tr_val, trace_val, ntrace ? sT : 0),
+                        piece(io.tr_beta, trace_beta, ntrace ? sT : 0), piece(io.tr_status, trace_status, ntrace ? sT : 0),
+                        piece(io.tr_acc, trace_accept, ntrace ? sT : 0)}))
+    return rc;
+  int failed = 0;
+  for (int a = 0; a < A; ++a) {
+    out_used[a] = cnt[a];
+    out_accepted[a] = cnt[sA + a];
+    failed += cnt[2 * sA + a];
+  }
+  return failed;
 } CCGP_GUARD_END(h)
 
 int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y, double sigma2,

@@ -216,6 +216,24 @@ void launch_small_reg_loglik_sets(hipStream_t s, const double* Xs, int n, int d,
 void launch_small_reg_profile_grad_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set,
                                         DrawView dv, int B, double* loglik, double* s2hat, double* beta, double* grad,
                                         int* status);
+// Metropolis chains on the device (ccgp_metro_segments_sets where small_route_chain says Reg): what chain a = workgroup a of
+// A reads and leaves, every pointer a device pointer.  theta0 / theta_fin: A x p column-major (element j of chain a at
+// [a + j A]); steps [A][T][p], logu [A][T]; the accepted draws [A][M][p] with their values and betas [A][M]; the trace
+// [A][T], all four or none
+struct ChainIO {
+  int prior_id, p, T, M;
+  const double* prior_pars;   // 4 values where the prior reads them
+  const double *theta0, *l0, *beta0;
+  const double *steps, *logu;
+  const int *n_prop, *stop_acc;
+  int *used, *nacc, *nfail;
+  double *draws, *draw_val, *draw_beta;
+  double *theta_fin, *l_fin, *beta_fin;
+  double *tr_val, *tr_beta;
+  int *tr_status, *tr_acc;
+};
+void launch_small_reg_chain_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
+                                 const int* set, int A, const ChainIO& io);
 // leave-one-out mean / variance of every training point for B draws (ccgp_loo_batch where small_route_loo says Reg): one
 // workgroup per draw on the inverse instances' scheme; mean / var are B x n column-major, sigma2 is the scalar that
 // vf.sigma2_row (indexed by draw) replaces, vf.q (may be nullptr) receives Q per draw

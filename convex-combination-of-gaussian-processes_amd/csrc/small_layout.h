@@ -246,6 +246,20 @@ inline bool small_reg_sets_supported(int n, int d, int K) {
 inline Route small_route_sets(bool gauss, int n, int d, int K) {
   return gauss && small_reg_sets_supported(n, d, K) ? Route::Reg : Route::Blocked;
 }
+// Metropolis chains on the device (ccgp_metro_segments_sets): the CHAIN instances are the sets likelihood instances of the
+// 16 x 16 grid, one workgroup per chain, with the chain's own words behind the instance's carve: the two 256-entry tables
+// of the portable exp (chain_terms.h), state, candidate, l / ljac / lprior / beta, and the two words of the decision (go on, accepted)
+// that the whole workgroup reads after its barrier
+constexpr int kChainLdsDoubles = 2 * 256 + 4 + 4 + 4 + 2;
+inline size_t reg_chain_lds_doubles(int NB, int n, int d, int K) {
+  return reg_lds_doubles(16, NB, 1, false, false, n, d, K) + kChainLdsDoubles;
+}
+// Reg exactly where the sets likelihood has its one-launch route and the chain's words fit beside the carve; Unsupported
+// otherwise (n > 128, Matern and spline, a carve that does not fit): the caller keeps the chain on the host there
+inline Route small_route_chain(bool gauss, int n, int d, int K) {
+  if (small_route_sets(gauss, n, d, K) != Route::Reg) return Route::Unsupported;
+  return lds_fits(reg_chain_lds_doubles((n + 15) / 16, n, d, K)) ? Route::Reg : Route::Unsupported;
+}
 // the sets form of the profiled gradient (ccgp_profile_batch_sets with out_grad): the INV = 2 instances on the 16 x 16 grid,
 // one matrix per workgroup with its set's design in the shared xs slot -- the carve of the single-set instance, so the sets
 // form exists exactly where ccgp_profile_batch's gradient takes the Reg route (the in-LDS and blocked routes have no sets

@@ -28,10 +28,30 @@
 #include <type_traits>
 
 #include "ccgp_internal.h"
+#include "chain_terms.h"
 
 namespace ccgp {
 
 namespace {
+
+// the two tables of chain_exp (chain_terms.h) for the chain instances, which copy them to LDS once
+static __device__ const unsigned long long kChainExpLoBits[kChainTable] = CCGP_CHAIN_EXP_LO_BITS;
+
+// the chain's words behind the instance's carve: hi[256] | lo[256] | theta[4] | cand[4] | l, ljac, lprior, beta | go | accepted
+// (the last two are the decision thread 0 publishes, 0.0 or 1.0: every word of the block is a double)
+enum { kChainHi = 0, kChainLo = kChainTable, kChainTheta = 2 * kChainTable, kChainCand = kChainTheta + 4,
+       kChainL = kChainCand + 4, kChainLj, kChainLp, kChainBeta, kChainGo, kChainAcc };
+static_assert(kChainAcc + 1 == kChainLdsDoubles, "small_layout.h sizes the chain's words");
+
+// The mode-0 log-likelihood of the CHAIN instances with its operations spelled out.  In the other instances the compiler
+// contracts `n * kLog2Pi + n * log(cs)` to fma(log 2 pi, n, n log cs); inside the proposal loop the loop-invariant product
+// n log 2 pi is hoisted out of the loop and the OTHER product would be fused -- one rounding elsewhere, 1 - 4 ulp of the value
+// for every n that is no power of two.  A chain's likelihood must have the sets instance's bits, so: that instance's operations.
+__device__ __forceinline__ double chain_loglik(int n, double log2pi, double log_cs, double logdet, double q_over_cs) {
+#pragma clang fp contract(off)
+  const double nl = n * log_cs;
+  return -0.5 * ((__builtin_fma(log2pi, (double)n, nl) + logdet) + q_over_cs);
+}
 
 struct RegArgs {
   const double* X;
@@ -71,6 +91,7 @@ struct RegArgs {
   // (the profiled gradient over sets, ccgp_profile_batch_sets, reads neither: sigma2_set stays null there)
   const int* set;
   const double* sigma2_set;
+  ChainIO ch;          // CHAIN instantiations only
 };
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
@@ -132,7 +153,14 @@ __device__ __forceinline__ void mat_sync() {
 // the set's design goes into the shared xs slot; G = 8 keeps one copy per matrix where the per-design form keeps it.
 // INV = 2 with PROF and SETS (ccgp_profile_batch_sets): the ordinary-kriging fits of many sets in lockstep.  The gradient
 // epilogue takes its differences from xs and its right-hand side from zb, so it is the single-set instance's code as it is.
-template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false>
+// CHAIN: a Metropolis chain per workgroup (ccgp_metro_segments_sets): the sets likelihood instance evaluating again and
+// again.  The set's design is loaded once; then, per proposal, wave 0 forms the candidate theta + e_t and its portable terms
+// (chain_terms.h) into th[] / w2[], the evaluation below runs as it is -- same operations in the same order as the sets
+// instance, hence the likelihood bits ccgp_loglik_batch_sets gives that row -- and thread 0 decides, publishes the decision
+// through LDS and, after one barrier, every thread reads the same word: go on with the next proposal or leave.  The trip
+// count is bounded by n_prop[a]; no path waits on another workgroup.  A template parameter, as PROF and SETS are.
+template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false,
+          bool CHAIN = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
@@ -140,6 +168,7 @@ void small_reg_kernel(RegArgs a) {
   static_assert(!PROF || ((NE == 1 || INV == 2) && INV != 1 && INV != 3 && !FAC), "sigma2 is concentrated out of the likelihood and of its gradient only");
   static_assert(!SETS || (!FAC && ((NE == 1 && !INV && !PROF) || (INV == 2 && PROF))),
                 "the sets form exists for the plain likelihood and for the profiled gradient only");
+  static_assert(!CHAIN || (SETS && G == 16 && NE == 1 && !INV && !PROF && !FAC), "a chain is the sets likelihood instance on the 16 x 16 grid");
   constexpr int TPM = G * G;       // threads per matrix
   constexpr int MPW = 256 / TPM;   // matrices per workgroup
   constexpr int NP = G * NB;       // padded order
@@ -175,6 +204,28 @@ void small_reg_kernel(RegArgs a) {
 
   const int pb = a.shared_params ? 0 : b;
   if (CCGP_SMALL_EXP_TABLE) exp_table_load(etab, tid, 256);
+  // CHAIN: proposals used, draws accepted and factorisations failed so far (uniform over the workgroup), the chain's words
+  double* cst = nullptr;
+  int ct = 0, cacc = 0, cfail = 0;
+  if constexpr (CHAIN) {
+    cst = smem + cv.total;
+    const ChainIO& ch = a.ch;
+    if (ch.n_prop[b] <= 0 || ch.stop_acc[b] <= 0) {   // nothing to do: the state as it came (every thread reads the same words)
+      if (tid == 0) {
+        ch.used[b] = 0; ch.nacc[b] = 0; ch.nfail[b] = 0;
+        for (int j = 0; j < ch.p; ++j) ch.theta_fin[b + (size_t)j * a.B] = ch.theta0[b + (size_t)j * a.B];
+        ch.l_fin[b] = ch.l0[b];
+        ch.beta_fin[b] = ch.beta0[b];
+      }
+      return;
+    }
+    for (int e = tid; e < kChainTable; e += 256) {
+      cst[kChainHi + e] = __longlong_as_double((long long)kExpTableBits[e]);
+      cst[kChainLo + e] = __longlong_as_double((long long)kChainExpLoBits[e]);
+    }
+    if (tid < ch.p) cst[kChainTheta + tid] = ch.theta0[b + (size_t)tid * a.B];
+    if (tid == 0) { cst[kChainL] = ch.l0[b]; cst[kChainBeta] = ch.beta0[b]; }
+  }
   int st = 0;   // SETS: this evaluation's training set
   if constexpr (SETS) {
     // a matrix's threads are whole waves on both grids: the set index is wave-uniform, and saying so keeps it -- and the
@@ -190,10 +241,35 @@ void small_reg_kernel(RegArgs a) {
     xs = smem + cv.xs_own + (size_t)sub * d * n;
     for (int e = lt; e < n * d; e += TPM) xs[e] = a.X[(size_t)b * a.x_stride + e];
   }
-  for (int e = lt; e < K * d; e += TPM) th[e] = a.params[pb + (size_t)(K + e) * a.ldp];
-  if (lt < K) {
-    const double w = a.params[pb + (size_t)lt * a.ldp];
-    w2[lt] = w * w;
+  if constexpr (!CHAIN) {
+    for (int e = lt; e < K * d; e += TPM) th[e] = a.params[pb + (size_t)(K + e) * a.ldp];
+    if (lt < K) {
+      const double w = a.params[pb + (size_t)lt * a.ldp];
+      w2[lt] = w * w;
+    }
+  } else {
+    __syncthreads();   // the tables, the start state and the design are in LDS
+  }
+chain_next:
+  if constexpr (CHAIN) {
+    if (tid < 64) {   // wave 0, every lane the same arithmetic; lane 0 writes
+      const ChainIO& ch = a.ch;
+      const double* e = ch.steps + ((size_t)b * ch.T + ct) * ch.p;
+      double cand[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cand[j] = j < ch.p ? cst[kChainTheta + j] + e[j] : 0.0;
+      const ChainTerms tm = chain_terms(ch.prior_id, cand, ch.prior_pars, cst + kChainHi, cst + kChainLo);
+      if (tid == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cst[kChainCand + j] = cand[j];
+        w2[0] = tm.w0 * tm.w0;
+        w2[1] = tm.w1 * tm.w1;
+        cst[kChainLj] = tm.lj;
+        cst[kChainLp] = tm.lp;
+      }
+      // the 2 d rates: every lane holds tm, so lane e stores rate e (d <= 64: two passes at the most)
+      for (int e = tid; e < 2 * d; e += 64) th[e] = chain_rate(tm, ch.prior_id, e / d, e % d);
+    }
   }
   if constexpr (NE > 1 && !INV) {
     for (int e = tid; e < d * XR; e += 256) {
@@ -446,6 +522,8 @@ void small_reg_kernel(RegArgs a) {
         ll = -0.5 * (n * kLog2Pi + n * log(csh) + logdet + n);
         if (lt == 0) slack[2] = csh;   // for the gradient epilogue
         if (lt == 0 && valid && blockIdx.y == 0) a.s2hat[b] = bad ? kNaN : csh / sw;
+      } else if constexpr (CHAIN) {
+        ll = chain_loglik(n, kLog2Pi, log(cs), logdet, q / cs);
       } else {
         ll = -0.5 * (n * kLog2Pi + n * log(cs) + logdet + q / cs);
       }
@@ -481,6 +559,45 @@ void small_reg_kernel(RegArgs a) {
         if (a.vf.q) a.vf.q[b] = bad ? kNaN : q;
       }
     }
+    if constexpr (CHAIN) {
+      if (lt == 0) {   // the accept / reject step of HX:505-535 on this proposal's value
+        const ChainIO& ch = a.ch;
+        const size_t at = (size_t)b * ch.T + ct;
+        const double val = chain_value(ll, cst[kChainLj], cst[kChainLp]);
+        const int acc = __builtin_isfinite(val) && (val - cst[kChainL]) > ch.logu[at];
+        if (ch.tr_val) { ch.tr_val[at] = val; ch.tr_beta[at] = beta; ch.tr_status[at] = bad; ch.tr_acc[at] = acc; }
+        if (acc) {
+          const size_t k = (size_t)b * ch.M + cacc;
+          for (int j = 0; j < ch.p; ++j) {
+            ch.draws[k * ch.p + j] = cst[kChainCand + j];
+            cst[kChainTheta + j] = cst[kChainCand + j];
+          }
+          ch.draw_val[k] = val;
+          ch.draw_beta[k] = beta;
+          cst[kChainL] = val;
+          cst[kChainBeta] = beta;
+        }
+        const int used = ct + 1, nacc = cacc + acc;
+        const int go = nacc < ch.stop_acc[b] && used < ch.n_prop[b];
+        cst[kChainGo] = go ? 1.0 : 0.0;
+        cst[kChainAcc] = acc ? 1.0 : 0.0;
+        if (!go) {
+          ch.used[b] = used; ch.nacc[b] = nacc; ch.nfail[b] = cfail + (bad != 0);
+          for (int j = 0; j < ch.p; ++j) ch.theta_fin[b + (size_t)j * a.B] = cst[kChainTheta + j];
+          ch.l_fin[b] = cst[kChainL];
+          ch.beta_fin[b] = cst[kChainBeta];
+        }
+      }
+    }
+  }
+  if constexpr (CHAIN) {
+    __syncthreads();
+    const int go = __builtin_amdgcn_readfirstlane(cst[kChainGo] != 0.0);
+    cacc += __builtin_amdgcn_readfirstlane(cst[kChainAcc] != 0.0);
+    ct += 1;
+    cfail += bad != 0;
+    if (go) goto chain_next;
+    return;
   }
   if constexpr (INV) {
     // R^-1 = Z' D^-1 Z with Z[t][c] = (L'^-1)[c][t] (zero for c < t).  Round 4: the columns are scaled by d_c^-1/2 on the
@@ -1154,7 +1271,32 @@ static void dispatch_sets(hipStream_t s, const RegArgs& a) {
   pick<1, 8>((n + 15) / 16, [&](auto nb) { launch_one<16, decltype(nb)::value, 1>(s, a); });
 }
 
+// the chain instances: the sets likelihood instance of the 16 x 16 grid (general, FULL) compiled with CHAIN, one workgroup
+// per chain, the chain's words behind the instance's carve
+template <int NB>
+static void launch_chain(hipStream_t s, const RegArgs& a) {
+  static unsigned long long attr_mask = 0;
+  once_per_device(attr_mask, [] {
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, 1, false, 0, false, false, true, true>, "small_reg_kernel<chain>");
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, 1, true, 0, false, false, true, true>, "small_reg_kernel<full, chain>");
+  });
+  const size_t lds = sizeof(double) * reg_chain_lds_doubles(NB, a.n, a.d, a.K);
+  void (*kernel)(RegArgs) = small_reg_kernel<16, NB, 1, false, 0, false, false, true, true>;
+  if (a.n == 16 * NB) kernel = small_reg_kernel<16, NB, 1, true, 0, false, false, true, true>;
+  hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
+}
+
 }  // namespace
+
+// ccgp_metro_segments_sets where small_route_chain says Reg: A chains, chain a on training set set[a]; arrays as ChainIO
+// lays them out (theta0 / theta_fin A x p column-major); every pointer a device pointer
+void launch_small_reg_chain_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
+                                 const int* set, int A, const ChainIO& io) {
+  DrawView dv{nullptr, A, 2, d, KernelFamily{}};
+  RegArgs a = reg_args(Xs, n, d, ys, dv);
+  a.B = A; a.set = set; a.sigma2_set = sigma2; a.ch = io;
+  pick<1, 8>((n + 15) / 16, [&](auto nb) { launch_chain<decltype(nb)::value>(s, a); });
+}
 
 // ccgp_loglik_batch_sets where small_route_sets says Reg: the B rows of dv, row b on training set set[b] of the C sets at
 // Xs (C blocks of n x d, column-major each), ys (C blocks of n) and sigma2 (C values)

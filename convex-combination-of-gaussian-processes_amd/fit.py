@@ -462,6 +462,210 @@ def Metro_sets(gp, starts, N, samp_size, batch_size, alpha, D_trains, sigma2s, y
                 laplace_calls=laplace_calls)
 
 
+# ----------------------------------------------------------------------------- chains on the device
+class _BlockChain(_Chain):
+    """_Chain with the random numbers of its proposals drawn ahead in blocks, which is what lets the accept / reject walk run
+    where the evaluator is.  Stream contract: proposals t = 0, 1, ... use, block after block, u = rng.random(block) and then
+    z = rng.standard_normal((block, p)); the increment is e_t = L z_t with L the Cholesky factor of sqrt(2) V (computed
+    once), each component summed left to right with elementwise numpy operations (no BLAS), and log u_t is math.log on the
+    host.  Numbers a segment did not use stay pending for the next one."""
+
+    def __init__(self, est, l0, b0, N, samp_size, batch_size, alpha, rng, max_proposals, block):
+        super().__init__(est, l0, N, samp_size, batch_size, alpha, rng, max_proposals)
+        self.beta = b0
+        self.block = int(block)
+        self.L = np.linalg.cholesky(self.cov)
+        p = self.zero.size
+        self.pend_e, self.pend_logu, self.blocks = np.zeros((0, p)), np.zeros(0), 0
+
+    def fill(self, m):
+        """At least m pending proposals, where the chain may still use that many."""
+        p = self.zero.size
+        while self.pend_logu.size < m:
+            u = self.rng.random(self.block)
+            z = self.rng.standard_normal((self.block, p))
+            e = np.empty((self.block, p))
+            for i in range(p):
+                acc = self.L[i, 0] * z[:, 0]
+                for j in range(1, i + 1):
+                    acc = acc + self.L[i, j] * z[:, j]
+                e[:, i] = acc
+            logu = np.array([math.log(v) if v > 0.0 else -math.inf for v in u])
+            self.pend_e, self.pend_logu = np.concatenate([self.pend_e, e]), np.concatenate([self.pend_logu, logu])
+            self.blocks += 1
+
+    def rewind(self):
+        """Leave the generator where the contract says: after exactly ceil(proposals / block) blocks."""
+        self.rng.bit_generator.state = self.state0
+        for _ in range(-(-self.proposals // self.block)):
+            self.rng.random(self.block)
+            self.rng.standard_normal((self.block, self.zero.size))
+
+    def request(self, seg):
+        """(proposals, acceptances) the next segment may use: up to seg proposals, stopping at the next acceptance count
+        consume() would look at -- k >= samp_size and k % batch_size == 0 -- or at N."""
+        n_prop = min(int(seg), self.max_proposals - self.proposals)
+        nxt = max(self.samp_size, self.k + 1)
+        stop_k = min(self.N, -(-nxt // self.batch_size) * self.batch_size)
+        self.fill(n_prop)
+        return n_prop, stop_k - self.k
+
+    def absorb(self, used, draws, vals, betas):
+        """What a segment did: `used` proposals, the accepted draws in order.  Then the Geweke rule as consume() applies it."""
+        from scipy.stats import norm
+
+        a = len(vals)
+        self.samp[self.k:self.k + a] = draws
+        self.betas[self.k:self.k + a] = betas
+        self.proposals += int(used)
+        self.pend_e, self.pend_logu = self.pend_e[used:], self.pend_logu[used:]
+        if not a:
+            return
+        self.theta, self.l, self.beta, self.k = np.array(draws[-1], dtype=np.float64), float(vals[-1]), float(betas[-1]), self.k + a
+        k = self.k
+        if k >= self.samp_size and k % self.batch_size == 0:
+            try:
+                z = geweke_z(geweke_window(self.samp, k, self.samp_size))
+                self.pv = float(2.0 * (1.0 - norm.cdf(abs(z))))
+            except Exception:
+                self.pv = 0.0
+
+
+def _twin_sets_evaluator(gp, D_trains, ys, sigma2s, theta1_pars, theta2_pars):
+    """`(rows, set_of) -> (val, beta)` over ccgp_chain_logpost_sets: the evaluation a device chain makes, on the host side."""
+    pars = _prior_pars(gp, theta1_pars, theta2_pars)
+    Xs = np.stack([np.asarray(D, dtype=np.float64) for D in D_trains])
+    Y = np.stack([np.asarray(y, dtype=np.float64).ravel() for y in ys])
+
+    def fn(rows, set_of):
+        val, beta, _, _ = gp.h.chain_logpost_sets(Xs, Y, sigma2s, gp.cfg["prior"], rows, set_of, pars)
+        return val, beta
+
+    return fn
+
+
+def _host_segments(chains, live, reqs, evaluate):
+    """The segments of the live chains one proposal at a time: one evaluator call per step for every chain still inside its
+    segment.  Same decisions as the kernel, in Python: isfinite(val) and val - l > log u."""
+    state = {c: dict(theta=np.array(chains[c].theta, dtype=np.float64), l=chains[c].l, t=0, draws=[], vals=[], betas=[]) for c in live}
+    calls = 0
+    while True:
+        go = [c for c in live if state[c]["t"] < reqs[c][0] and len(state[c]["vals"]) < reqs[c][1]]
+        if not go:
+            break
+        cands = [state[c]["theta"] + chains[c].pend_e[state[c]["t"]] for c in go]
+        val, beta = evaluate(np.stack(cands), go)
+        calls += 1
+        for j, c in enumerate(go):
+            s = state[c]
+            v = float(val[j])
+            if math.isfinite(v) and (v - s["l"]) > chains[c].pend_logu[s["t"]]:
+                s["theta"], s["l"] = cands[j], v
+                s["draws"].append(cands[j]); s["vals"].append(v); s["betas"].append(float(beta[j]))
+            s["t"] += 1
+    for c in live:
+        s = state[c]
+        chains[c].absorb(s["t"], np.array(s["draws"]).reshape(len(s["vals"]), chains[c].zero.size), s["vals"], s["betas"])
+    return calls
+
+
+def Metro_device_sets(gp, starts, N, samp_size, batch_size, alpha, D_trains, sigma2s, ys, theta1_pars=None, theta2_pars=None,
+                      rngs=None, max_proposals=None, laplace=None, block=256, seg=2048, on_device=True,
+                      logpost_sets_fn=None):
+    """Metro for C training sets of one shape with the chains RESIDENT ON THE DEVICE: one launch (ccgp_metro_segments_sets)
+    carries every live chain through up to `seg` proposals -- candidate, Jacobian and prior, likelihood and the accept /
+    reject step all in the kernel, one workgroup per chain -- and comes back only where the Geweke rule looks at the chain.
+    Stream contract (not Metro's: the proposals are drawn in vectorised blocks, so these are different chains with the same
+    law).  Chain c owns rngs[c]; its proposals t = 0, 1, ... use numbers drawn in blocks of `block`: u = rng.random(block),
+    then z = rng.standard_normal((block, p)); e_t = L z_t with L the Cholesky factor of sqrt(2) V computed once, L z_t by
+    elementwise numpy operations in a fixed order; log u on the host.  Unused numbers stay pending for the next segment, so
+    a chain depends on `block` and on nothing else about how it is cut into launches (seg, the other chains), and leaves its
+    generator after exactly ceil(proposals / block) blocks.
+    Stop logic is Metro's: a segment stops at the next acceptance count k with k >= samp_size and k % batch_size == 0, at N,
+    or at max_proposals; the host then applies the Geweke rule exactly as Metro does.  The Laplace stage and the starting
+    values go through ccgp_chain_logpost_sets, the host twin of the kernel's evaluation.
+    on_device=False runs the same driver one proposal at a time through that twin (or through logpost_sets_fn(rows, set_of)
+    -> (val, beta)): the exact reference for the device chain, bit for bit, and what the driver falls back to where the
+    device refuses the shape (n > 128, the 1-D families).  Returns Metro_sets' dict: chains (one Metro result per set),
+    device_batches (the calls made for the chains), laplace_calls."""
+    C = len(D_trains)
+    rngs = [np.random.default_rng(r) for r in (rngs if rngs is not None else [None] * C)]
+    if len(rngs) != C:
+        raise ValueError("Metro_device_sets takes one generator per set")
+    if logpost_sets_fn is not None:
+        on_device = False
+    else:
+        logpost_sets_fn = _twin_sets_evaluator(gp, D_trains, ys, sigma2s, theta1_pars, theta2_pars)
+    laplace_calls = 0
+
+    def evaluate(rows, set_of):
+        return logpost_sets_fn(np.asarray(rows), np.asarray(set_of, dtype=np.int64))
+
+    def counted(rows, set_of):
+        nonlocal laplace_calls
+        laplace_calls += 1
+        return evaluate(rows, set_of)[0]
+
+    if laplace is None:
+        ests = laplace_sets(counted, starts)
+    else:
+        ests = list(laplace)
+        if len(ests) != C:
+            raise ValueError("Metro_device_sets takes one Laplace estimate per set")
+    l0, b0 = evaluate(np.stack([e["mode"] for e in ests]), np.arange(C))
+    chains = [_BlockChain(ests[c], float(l0[c]), float(b0[c]), N, samp_size, batch_size, alpha, rngs[c], max_proposals, block)
+              for c in range(C)]
+    if on_device:
+        pars = _prior_pars(gp, theta1_pars, theta2_pars)
+        Xs = np.stack([np.asarray(D, dtype=np.float64) for D in D_trains])
+        Y = np.stack([np.asarray(y, dtype=np.float64).ravel() for y in ys])
+    batches = 0
+    while True:
+        live = [c for c in range(C) if chains[c].running()]
+        if not live:
+            break
+        reqs = {c: chains[c].request(seg) for c in live}
+        if on_device:
+            T = max(r[0] for r in reqs.values())
+            p = chains[live[0]].zero.size
+            steps, logu = np.zeros((len(live), T, p)), np.zeros((len(live), T))
+            for j, c in enumerate(live):
+                steps[j, :reqs[c][0]], logu[j, :reqs[c][0]] = chains[c].pend_e[:reqs[c][0]], chains[c].pend_logu[:reqs[c][0]]
+            try:
+                r = gp.h.metro_segments_sets(Xs, Y, sigma2s, gp.cfg["prior"], live, np.stack([chains[c].theta for c in live]),
+                                             [chains[c].l for c in live], steps, logu, [reqs[c][0] for c in live],
+                                             [reqs[c][1] for c in live], pars, [chains[c].beta for c in live])
+            except api.CcgpError as e:
+                if e.code != -4:   # CCGP_EUNSUPPORTED: this shape has no device chain; the twin carries it
+                    raise
+                on_device = False
+                continue
+            batches += 1
+            for j, c in enumerate(live):
+                a = int(r["accepted"][j])
+                chains[c].batches += 1
+                chains[c].absorb(int(r["used"][j]), r["draws"][j, :a], r["draw_val"][j, :a], r["draw_beta"][j, :a])
+        else:
+            for c in live:
+                chains[c].batches += 1
+            batches += _host_segments(chains, live, reqs, evaluate)
+    for ch in chains:
+        ch.rewind()
+    return dict(chains=[ch.result("Metro_device_sets (set %d)" % c) for c, ch in enumerate(chains)], device_batches=batches,
+                laplace_calls=laplace_calls)
+
+
+def Metro_device(gp, start, N, samp_size, batch_size, alpha, D_train, sigma2, y, theta1_pars=None, theta2_pars=None, rng=None,
+                 max_proposals=None, laplace=None, block=256, seg=2048, on_device=True, logpost_fn=None):
+    """Metro_device_sets' C = 1 case: one chain on one training set -> Metro's result dict.  `logpost_fn(rows) -> (val, beta)`
+    replaces the device evaluator (and keeps the chain on the host)."""
+    fn = None if logpost_fn is None else (lambda rows, set_of: logpost_fn(rows))
+    r = Metro_device_sets(gp, None if start is None else np.asarray(start, dtype=np.float64)[None], N, samp_size, batch_size,
+                          alpha, [D_train], [sigma2], [y], theta1_pars, theta2_pars, [rng], max_proposals,
+                          None if laplace is None else [laplace], block, seg, on_device, fn)
+    return r["chains"][0]
+
+
 def factors_frame(gp, start, N, samp_size, batch_size, alpha_geweke, D_train, sigma2, y_train,
                   net_samp_size, theta1_pars=None, theta2_pars=None, rng=None, speculate=0):
     """HX:625-644 without materialising R.Inv per draw: returns the retained posterior draws
@@ -931,7 +1135,8 @@ def stack_tables(tables):
 
 def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size=None, start=None, sigma2s=None,
           theta1_pars=None, theta2_pars=None, rngs=None, max_proposals=None, speculate=0, laplace=None, cgp=False,
-          single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None, lockstep_fits=True):
+          single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None, lockstep_fits=True,
+          device_chains=False):
     """The reference's simulation study (GV:689-762 declares nine training sets and fits one): every set of `sets` -- a list
     of (D_train, y_train, D_test, y_test) -- fitted and compared, the sets of one shape (n, d) in lockstep.  Per group:
     sigma2 per set from ordinary_kriging_fit (or sigma2s[i] as given), then laplace_sets and Metro_sets with one generator
@@ -949,6 +1154,9 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     in compare_GP, set after set) -- and compare_GP only predicts.  Tables, summaries, sigma2, draws and chains have the
     same bits either way.  The per-set loop stays for a 1-D (Matern) gp, whose comparator is matern_MLEs, where compare_fn
     or logpost_sets_fn replaces the device, and with lockstep_fits=False.
+    device_chains (default off): the Metro part of each group goes through Metro_device_sets -- chains resident on the
+    device, many proposals per launch, with that function's own stream contract (so other chains than Metro_sets', same
+    law); the Laplace stage then runs on its twin evaluator, and speculate is not used.
     Returns dict(tables, summaries, pooled: comparison_summary of the stacked tables, sigma2, draws, beta, chains,
     groups: {(n, d): indices}, calls and seconds: device calls and wall time of the sigma2, single, cgp, laplace, metro and
     predict parts; per set the single and cgp fits happen inside compare_GP, so their seconds are part of predict's and
@@ -1035,7 +1243,8 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
         g_s2 = [s2[i] for i in idx]
         fn = logpost_sets_fn(idx) if logpost_sets_fn is not None else None
         if fn is None:
-            fn = _device_sets_evaluator(gp, D_trains, ys, g_s2, theta1_pars, theta2_pars)
+            make = _twin_sets_evaluator if device_chains else _device_sets_evaluator
+            fn = make(gp, D_trains, ys, g_s2, theta1_pars, theta2_pars)
         count = dict(n=0)
 
         def counted(rows, set_of, fn=fn, count=count):
@@ -1048,8 +1257,13 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
         secs["laplace"] += time.perf_counter() - t0
         calls["laplace"] += count["n"]
         t0 = time.perf_counter()
-        r = Metro_sets(gp, None, N, samp_size, batch_size, alpha_geweke, D_trains, g_s2, ys, theta1_pars, theta2_pars,
-                       [rngs[i] for i in idx], max_proposals, speculate, laplace=ests, logpost_sets_fn=fn)
+        if device_chains:
+            r = Metro_device_sets(gp, None, N, samp_size, batch_size, alpha_geweke, D_trains, g_s2, ys, theta1_pars, theta2_pars,
+                                  [rngs[i] for i in idx], max_proposals, laplace=ests,
+                                  logpost_sets_fn=fn if logpost_sets_fn is not None else None)
+        else:
+            r = Metro_sets(gp, None, N, samp_size, batch_size, alpha_geweke, D_trains, g_s2, ys, theta1_pars, theta2_pars,
+                           [rngs[i] for i in idx], max_proposals, speculate, laplace=ests, logpost_sets_fn=fn)
         secs["metro"] += time.perf_counter() - t0
         calls["metro"] += r["device_batches"] + 1   # the chains' starting values are one call
         for j, i in enumerate(idx):

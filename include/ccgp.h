@@ -282,6 +282,49 @@ int ccgp_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const doub
                       int prior_id, const double* theta_t /* B x q */, const int* set, int B,
                       const double* prior_pars, double* out_val, double* out_beta, double* out_loglik, int* status);
 
+/* ---- Metropolis chains on the device: many proposals per launch (Metro, HX:483-540) ------------------------------------------
+ * The random numbers of a proposal do not depend on the chain's state: the candidate is theta + e_t and the rule is
+ * isfinite(l_cand) && l_cand - l > log u_t.  ccgp_metro_segments_sets takes A chains, chain a on training set set[a], each
+ * with its start state (theta0 A x q column-major as theta_t; l0; beta0, may be NULL: NaN) and a block of pre-drawn
+ * increments steps[a][t][j] and log-uniforms logu[a][t] (leading dimension T), and walks chain a through its proposals
+ * t = 0, 1, .. on the device until it has accepted stop_acc[a] draws in this call or used n_prop[a] <= T proposals.  One
+ * workgroup per chain; no chain waits for another.
+ *   Values.  The likelihood of a proposal has the bits ccgp_loglik_batch_sets gives that parameter row.  Jacobian, prior and
+ *     the parameter row come from a restatement of ccgp_logpost's host arithmetic whose exp and log are built from exactly
+ *     rounded operations, so that host and device agree bit for bit: ccgp_chain_terms is that arithmetic on the host (rows
+ *     B x P column-major as ccgp_loglik_batch takes them; needs no handle), ccgp_chain_logpost_sets the whole evaluation
+ *     (arguments, checks and routes of ccgp_logpost_sets) -- the chain's host twin.  A chain driven proposal by proposal
+ *     through ccgp_chain_logpost_sets makes the same decisions and leaves the same bits.  val is NaN (one quiet NaN) where
+ *     the factorisation fails or a term is NaN.
+ *   Outputs per chain.  out_used[a], out_accepted[a]; the accepted draws in order, out_draws[(a M + k) q + j] with their
+ *     values out_draw_val[a M + k] and betas out_draw_beta[a M + k], k < out_accepted[a] <= stop_acc[a] <= M (entries beyond
+ *     are NaN); the final state out_theta (A x q column-major), out_l, out_beta (may be NULL).  The trace (all four or none,
+ *     [a T + t]): val, beta, pivot status and accept flag of every proposal used; NaN / -1 beyond.
+ *   Bits.  A chain depends on its own inputs only: not on A, its position, the other chains' sets, what the handle ran before,
+ *     or how its proposals are cut into calls (the state a call leaves is the next call's start).
+ *   Failure.  A failed factorisation is a rejected proposal (status = 1-based pivot in the trace, val and beta NaN); the chain
+ *     goes on.  The return value is the number of such proposals over all chains.
+ *   Arguments.  CCGP_EINVAL before anything is copied or launched, outputs untouched: bad shapes, a NULL required pointer,
+ *     an unknown prior (prior_pars as ccgp_logpost_batch), C < 1, A < 0, T < 1, M < 1, set[a] outside 0 .. C-1, n_prop[a]
+ *     outside 0 .. T, stop_acc[a] outside 0 .. M, a partial trace.  CCGP_EUNSUPPORTED, outputs untouched, where the sets
+ *     likelihood has no one-launch route: n > 128, the Matern and spline families, a shape whose instance does not fit.
+ *     A == 0 returns CCGP_OK.
+ * Host pointers only, blocking; ccgp_reserve does not cover the staging. */
+int ccgp_chain_terms(int prior_id, int d, const double* theta_t /* B x q */, int B, const double* prior_pars,
+                     double* out_rows /* B x (2 + 2 d) column-major */, double* out_ljac, double* out_lprior);
+int ccgp_chain_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                            int prior_id, const double* theta_t /* B x q */, const int* set, int B,
+                            const double* prior_pars, double* out_val, double* out_beta, double* out_loglik, int* status);
+int ccgp_metro_segments_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                             int prior_id, const double* prior_pars, int A, const int* set /* A */,
+                             const double* theta0 /* A x q */, const double* l0 /* A */, const double* beta0 /* A or NULL */,
+                             int T, const double* steps /* A x T x q */, const double* logu /* A x T */,
+                             const int* n_prop /* A */, const int* stop_acc /* A */, int M, int* out_used,
+                             int* out_accepted, double* out_draws /* A x M x q */, double* out_draw_val /* A x M */,
+                             double* out_draw_beta /* A x M */, double* out_theta /* A x q */, double* out_l,
+                             double* out_beta, double* trace_val /* A x T */, double* trace_beta, int* trace_status,
+                             int* trace_accept);
+
 /* ---- the comparator fits over many training sets of one shape: what compare.GP's table holds beside the Combined GP -------
  * The sets form of ccgp_profile_batch (the ordinary-kriging MLE behind sigma2 and the single-GP columns) and of
  * ccgp_cgp_state_batch (CGP's candidates, refinement points and jackknife), so that a study's comparator fits run in lockstep
