@@ -68,6 +68,12 @@ SIGNATURES = {
     "ccgp_metro_segments_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, c_int, _ip, _dp, _dp, _dp,
                                          c_int, _dp, _dp, _ip, _ip, c_int, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                          _ip, _ip]),
+    "ccgp_fit_state_doubles": (c_int, [c_int]),
+    "ccgp_fit_begin": (c_int, [_dp, c_int, _dp, _dp, _dp, c_int, c_double, c_double, c_int]),
+    "ccgp_fit_feed": (c_int, [_dp, c_int, c_double, _dp, c_int]),
+    "ccgp_profile_fit_eval_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _dp, _dp, _dp, _dp, _dp,
+                                           _ip]),
+    "ccgp_profile_fit_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, c_int, _ip, _dp, _ip, _ip, _dp, _ip, c_int]),
     "ccgp_cgp_state_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _ip, _dp, _dp, _dp, _dp,
                                           _ip]),
     "ccgp_grid_marginal": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, _dp, c_int, c_int,
@@ -206,6 +212,63 @@ def chain_terms(prior_id, d, theta_t, prior_pars=None):
     if rc:
         raise CcgpError(rc, "ccgp_chain_terms")
     return rows, lj, lp
+
+
+# the codes of a start's state (csrc/fit_logic.h) and where its words lie
+FIT_RUNNING, FIT_CONV_REDUCTION, FIT_CONV_PROJ_GRAD, FIT_MAXIT, FIT_LINE_SEARCH, FIT_NOT_EVALUABLE = range(6)
+FIT_CODE, FIT_F, FIT_ITERATIONS, FIT_EVALS, FIT_HEADER = 1, 2, 5, 12, 16
+FIT_MAX_EVALS = 4096
+
+
+def fit_state_doubles(d):
+    """ccgp_fit_state_doubles: the doubles of one start's state, 16 + 16 d."""
+    W = lib().ccgp_fit_state_doubles(int(d))
+    if W < 0:
+        raise CcgpError(W, "ccgp_fit_state_doubles")
+    return W
+
+
+def fit_begin(x0, lower, upper, maxit=100, factr=1e7, pgtol=0.0, max_backtracks=30):
+    """ccgp_fit_begin: the state of a start at x0 [d] under the box [lower, upper] (scalars or [d]) with design.minimize_starts'
+    defaults -> float64[W].  state[FIT_HEADER + 3 d:][:d] is the point to evaluate first.  No device."""
+    x0 = np.ascontiguousarray(np.ravel(np.asarray(x0, dtype=np.float64)))
+    d = x0.shape[0]
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (d,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (d,)))
+    state = np.empty(fit_state_doubles(d))
+    rc = lib().ccgp_fit_begin(_p(state), d, _p(x0), _p(lo), _p(hi), int(maxit), float(factr), float(pgtol), int(max_backtracks))
+    if rc:
+        raise CcgpError(rc, "ccgp_fit_begin")
+    return state
+
+
+def fit_feed(state, f, g, ok=True):
+    """ccgp_fit_feed: hand the state (float64[W], C-contiguous, changed in place) the value and gradient at its trial point
+    -> the new code.  No device."""
+    if not (isinstance(state, np.ndarray) and state.dtype == np.float64 and state.flags.c_contiguous and state.ndim == 1):
+        raise ValueError("state must be a contiguous float64 vector")
+    d = (state.shape[0] - FIT_HEADER) // 16
+    g = np.ascontiguousarray(np.ravel(np.asarray(g, dtype=np.float64)))
+    if g.shape[0] != d or fit_state_doubles(d) != state.shape[0]:
+        raise ValueError("state and gradient disagree about d")
+    rc = lib().ccgp_fit_feed(_p(state), d, float(f), _p(g), int(bool(ok)))
+    if rc < 0:
+        raise CcgpError(rc, "ccgp_fit_feed")
+    return rc
+
+
+def fit_trial(state):
+    """The point a running start wants evaluated next: a copy of the `trial` words of its state (or of each row of [A, W])."""
+    state = np.asarray(state)
+    d = (state.shape[-1] - FIT_HEADER) // 16
+    return np.array(state[..., FIT_HEADER + 3 * d:FIT_HEADER + 4 * d])
+
+
+def fit_x(state):
+    """The last accepted iterate of a start: a copy of the `x` words of its state (or of each row of [A, W])."""
+    state = np.asarray(state)
+    d = (state.shape[-1] - FIT_HEADER) // 16
+    return np.array(state[..., FIT_HEADER:FIT_HEADER + d])
 
 
 SUMMARY_MAX_PROBS = 8
@@ -748,6 +811,42 @@ class Handle:
         self._chk(lib().ccgp_profile_batch_sets(self._h, _p(Xb), n, d, _p(yb), C, K, _p(params), _ipt(idx), B, _p(ll), _p(s2),
                                                 _p(beta), _p(g), _ipt(st)))
         return ll, s2, beta, g, st
+
+    def profile_fit_eval_sets(self, Xs, ys, logtheta, set_of, grad=True):
+        """ccgp_profile_fit_eval_sets: the ordinary-kriging objective at the rows of logtheta [B, d], row b on training set
+        set_of[b] -- theta = exp(logtheta) by the portable exp, f = -loglik, g = -(d loglik / d theta) theta -- the host twin
+        of profile_fit_sets' evaluation.  Returns (f[B], g[B, d] or None, theta[B, d], sigma2[B], beta[B], status[B])."""
+        logtheta = _f(np.atleast_2d(logtheta))
+        B, dd = logtheta.shape
+        Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, B)
+        _check_columns(dd, d, "d")
+        f, s2, beta, st = _outputs(B, 3)
+        g = np.empty((B, d), order="F") if grad else None
+        theta = np.empty((B, d), order="F")
+        self._chk(lib().ccgp_profile_fit_eval_sets(self._h, _p(Xb), n, d, _p(yb), C, _p(logtheta), _ipt(idx), B, _p(f), _p(g),
+                                                   _p(theta), _p(s2), _p(beta), _ipt(st)))
+        return f, g, theta, s2, beta, st
+
+    def profile_fit_sets(self, Xs, ys, set_of, state, max_evals, trace=False, T=None):
+        """ccgp_profile_fit_sets: A starts, start a on training set set_of[a], stepped on the device from state [A, W]
+        (api.fit_begin) through up to max_evals[a] evaluations each.  Returns dict(state [A, W], evals[A], failed: evaluations
+        whose factorisation failed, and with trace=True trace_f, trace_status [A, T], T = max(max_evals) unless given)."""
+        state = np.ascontiguousarray(np.atleast_2d(np.asarray(state, dtype=np.float64))).copy()
+        A = state.shape[0]
+        Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, A)
+        max_evals = np.ascontiguousarray(np.broadcast_to(np.asarray(max_evals), (A,)).astype(np.int32))
+        if T is None:
+            T = int(max_evals.max()) if A else 0
+        if state.shape[1] != fit_state_doubles(d):
+            raise ValueError("state must be [A, %d] for d = %d" % (fit_state_doubles(d), d))
+        evals = np.zeros(A, dtype=np.int32)
+        tr_f, tr_st = (np.full((A, T), np.nan), np.full((A, T), -1, dtype=np.int32)) if trace else (None, None)
+        failed = self._chk(lib().ccgp_profile_fit_sets(self._h, _p(Xb), n, d, _p(yb), C, A, _ipt(idx), _p(state),
+                                                       _ipt(max_evals), _ipt(evals), _p(tr_f), _ipt(tr_st), int(T)))
+        out = dict(state=state, evals=evals, failed=failed)
+        if trace:
+            out.update(trace_f=tr_f, trace_status=tr_st)
+        return out
 
     def cgp_state_batch_sets(self, Xs, ys, params, set_of, skip=None):
         """ccgp_cgp_state_batch_sets: the CGP state at row b of params [B, 2 d + 2] on training set set_of[b] of the C sets

@@ -16,6 +16,7 @@
 #include "call_stage.h"
 #include "ccgp_internal.h"
 #include "chain_terms.h"
+#include "fit_logic.h"
 #include "special_math.h"
 
 using namespace ccgp;
@@ -1580,6 +1581,123 @@ int ccgp_metro_segments_sets(ccgp_handle* h, const double* Xs, int n, int d, con
     out_used[a] = cnt[a];
     out_accepted[a] = cnt[sA + a];
     failed += cnt[2 * sA + a];
+  }
+  return failed;
+} CCGP_GUARD_END(h)
+
+// ---- the ordinary-kriging fits on the device (ccgp.h) --------------------------------------------------------------------------
+int ccgp_fit_state_doubles(int d) { return d >= 1 && d <= kMaxD ? fit_state_doubles(d) : CCGP_EINVAL; }
+
+// what a state must say before anything steps it: the d it was begun with, a code and a pair count inside their ranges
+static bool fit_state_ok(const double* st, int d) {
+  return st[kFitD] == (double)d && st[kFitCode] >= 0.0 && st[kFitCode] <= (double)kFitNotEvaluable &&
+         st[kFitCode] == (double)(int)st[kFitCode] && st[kFitPairs] >= 0.0 && st[kFitPairs] <= (double)kFitMemory &&
+         st[kFitPairs] == (double)(int)st[kFitPairs];
+}
+
+int ccgp_fit_begin(double* state, int d, const double* x0, const double* lo, const double* hi, int maxit, double factr,
+                   double pgtol, int max_backtracks) {
+  if (d < 1 || d > kMaxD || !state || !x0 || !lo || !hi || maxit < 0 || max_backtracks < 0) return CCGP_EINVAL;
+  fit_begin(state, d, x0, lo, hi, FitOpts{maxit, factr, pgtol, max_backtracks});
+  return CCGP_OK;
+}
+
+int ccgp_fit_feed(double* state, int d, double f, const double* g, int ok) {
+  if (d < 1 || d > kMaxD || !state || !g || !fit_state_ok(state, d)) return CCGP_EINVAL;
+  fit_feed(state, f, g, ok != 0);
+  return (int)state[kFitCode];
+}
+
+// the host twin of the fit kernel's evaluation: ccgp_profile_batch_sets on the rows (1, exp(logtheta)) with the portable exp
+int ccgp_profile_fit_eval_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, const double* logtheta,
+                               const int* set, int B, double* out_f, double* out_g, double* out_theta, double* out_sigma2,
+                               double* out_beta, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, 1) || !logtheta || !out_f || !sets_args_ok(Xs, ys, nullptr, false, C, set, B, 0))
+    return fail(h, CCGP_EINVAL, "ccgp_profile_fit_eval_sets: bad argument");
+  if (B == 0) return CCGP_OK;
+  const ChainTables& tb = chain_tables();
+  const int P = 1 + d;
+  const size_t sB = B;
+  std::vector<double> rows(sB * P), ll(sB), s2(sB), beta(sB), grad(out_g ? sB * P : 0);
+  std::vector<int> st(sB);
+  for (int b = 0; b < B; ++b) {
+    rows[b] = 1.0;
+    for (int k = 0; k < d; ++k) rows[b + (size_t)(1 + k) * sB] = fit_theta(logtheta[b + (size_t)k * sB], tb.hi, tb.lo);
+  }
+  const int rc = ccgp_profile_batch_sets(h, Xs, n, d, ys, C, 1, rows.data(), set, B, ll.data(), s2.data(), beta.data(),
+                                         out_g ? grad.data() : nullptr, st.data());
+  if (rc < 0) return rc;
+  for (int b = 0; b < B; ++b) {
+    out_f[b] = fit_value(ll[b]);
+    if (out_sigma2) out_sigma2[b] = s2[b];
+    if (out_beta) out_beta[b] = beta[b];
+    if (status) status[b] = st[b];
+    for (int k = 0; k < d; ++k) {
+      const double th = rows[b + (size_t)(1 + k) * sB];
+      if (out_theta) out_theta[b + (size_t)k * sB] = th;
+      if (out_g) out_g[b + (size_t)k * sB] = fit_grad(grad[b + (size_t)(1 + k) * sB], th);
+    }
+  }
+  return rc;
+} CCGP_GUARD_END(h)
+
+int ccgp_profile_fit_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int A, const int* set,
+                          double* state, const int* max_evals, int* out_evals, double* trace_f, int* trace_status,
+                          int T) try {
+  if (!h) return CCGP_EINVAL;
+  bool ok = !bad_shape(n, d, 1) && A >= 0 && T >= 0 && state && max_evals && out_evals &&
+            (trace_f != nullptr) == (trace_status != nullptr) && sets_args_ok(Xs, ys, nullptr, false, C, set, A, 0);
+  const int W = ok ? fit_state_doubles(d) : 0;
+  const int cap = T < 4096 ? T : 4096;
+  for (int a = 0; ok && a < A; ++a)
+    ok = max_evals[a] >= 0 && max_evals[a] <= cap && fit_state_ok(state + (size_t)a * W, d);
+  if (!ok) return fail(h, CCGP_EINVAL, "ccgp_profile_fit_sets: bad argument");
+  if (small_route_fit(h->fam.id == 0, n, d, 1) != Route::Reg)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_fit_sets: fits run on the device for Gaussian sets of n <= 128 whose "
+                                      "register-resident gradient instance fits; keep the fit on ccgp_profile_fit_eval_sets");
+  if (A == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  const size_t sA = A, sT = (size_t)A * T;
+  const bool tr = trace_f != nullptr && T > 0;
+  double *dXs, *dys;
+  int *dset, *dmax, *dcnt;
+  FitIO io{};
+  io.W = W; io.T = T;
+  // inputs back to back, then results back to back: each side crosses PCIe as one span (the state is both)
+  if (int rc = stage(h, [&](Layout& c) {
+        dXs = c.take<double>((size_t)C * n * d);
+        dys = c.take<double>((size_t)C * n);
+        dset = c.take<int>(sA);
+        dmax = c.take<int>(sA);
+        io.state = c.take<double>(sA * W);
+        dcnt = c.take<int>(2 * sA);   // evaluations | failed
+        io.tr_f = tr ? c.take<double>(sT) : nullptr;
+        io.tr_status = tr ? c.take<int>(sT) : nullptr;
+      }))
+    return rc;
+  io.max_evals = dmax;
+  io.evals = dcnt;
+  io.nfail = dcnt ? dcnt + sA : nullptr;
+  if (int prc = push(h, {piece(dXs, Xs, (size_t)C * n * d), piece(dys, ys, (size_t)C * n), piece(dset, set, sA),
+                         piece(dmax, max_evals, sA), piece(io.state, state, sA * W)}))
+    return prc;
+  if (tr) {   // a start that stops early leaves the rest of its trace as it is: NaN / -1, not what the buffer held
+    CCGP_HIP(hipMemsetAsync(io.tr_f, 0xFF, Layout::al(sT * sizeof(double)) + Layout::al(sT * sizeof(int)), h->stream));
+  }
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    launch_small_reg_fit_sets(h->stream, dXs, n, d, dys, dset, A, io);
+    CCGP_LAUNCH_CHECK();
+  }
+  std::vector<int> cnt(2 * sA);
+  if (int rc = pull(h, {piece(io.state, state, sA * W), piece(dcnt, cnt.data(), 2 * sA), piece(io.tr_f, trace_f, tr ? sT : 0),
+                        piece(io.tr_status, trace_status, tr ? sT : 0)}))
+    return rc;
+  int failed = 0;
+  for (int a = 0; a < A; ++a) {
+    out_evals[a] = cnt[a];
+    failed += cnt[sA + a];
   }
   return failed;
 } CCGP_GUARD_END(h)

@@ -234,6 +234,19 @@ struct ChainIO {
 };
 void launch_small_reg_chain_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
                                  const int* set, int A, const ChainIO& io);
+// the ordinary-kriging fits on the device (ccgp_profile_fit_sets where small_route_fit says Reg): what start a = workgroup a
+// of A reads and leaves, every pointer a device pointer.  state [A][W] in and out (fit_logic.h), max_evals / evals / nfail
+// [A], the trace [A][T], both or none
+struct FitIO {
+  double* state;
+  int W, T;
+  const int* max_evals;
+  int *evals, *nfail;
+  double* tr_f;
+  int* tr_status;
+};
+void launch_small_reg_fit_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set, int A,
+                               const FitIO& io);
 // leave-one-out mean / variance of every training point for B draws (ccgp_loo_batch where small_route_loo says Reg): one
 // workgroup per draw on the inverse instances' scheme; mean / var are B x n column-major, sigma2 is the scalar that
 // vf.sigma2_row (indexed by draw) replaces, vf.q (may be nullptr) receives Q per draw

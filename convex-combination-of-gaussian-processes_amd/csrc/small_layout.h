@@ -270,5 +270,21 @@ inline bool small_reg_profile_grad_sets_supported(int n, int d, int K) {
 inline Route small_route_profile_grad_sets(bool gauss, int n, int d, int K) {
   return gauss && small_reg_profile_grad_sets_supported(n, d, K) ? Route::Reg : Route::Blocked;
 }
+// the ordinary-kriging fits on the device (ccgp_profile_fit_sets): the FIT instances are the profiled-gradient sets instances,
+// one workgroup per start, K = 1, with the start's own words behind the instance's carve: the two 256-entry tables of the
+// portable exp (chain_terms.h), the word the whole workgroup reads after its barrier (go on / leave), the likelihood, the
+// gradient row (kMaxD words) and the start's state (fit_logic.h: 16 + 16 d doubles)
+constexpr int kFitLdsHead = 2 * 256 + 2 + kMaxD;
+CCGP_HD constexpr int fit_state_words(int d) { return 16 + 16 * d; }
+inline size_t reg_fit_lds_doubles(int NB, int n, int d) {
+  return reg_lds_doubles(16, NB, NB + 1, true, false, n, d, 1) + kFitLdsHead + fit_state_words(d);
+}
+// Reg exactly where the sets form of the profiled gradient has its one-launch route and the start's words fit beside the
+// carve; Unsupported otherwise (n > 128, Matern and spline, K != 1, a carve that does not fit): the caller keeps the fit on
+// the host twin there
+inline Route small_route_fit(bool gauss, int n, int d, int K) {
+  if (K != 1 || small_route_profile_grad_sets(gauss, n, d, K) != Route::Reg) return Route::Unsupported;
+  return lds_fits(reg_fit_lds_doubles((n + 15) / 16, n, d)) ? Route::Reg : Route::Unsupported;
+}
 
 }  // namespace ccgp

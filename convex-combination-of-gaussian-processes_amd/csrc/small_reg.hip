@@ -29,6 +29,7 @@
 
 #include "ccgp_internal.h"
 #include "chain_terms.h"
+#include "fit_logic.h"
 
 namespace ccgp {
 
@@ -51,6 +52,22 @@ __device__ __forceinline__ double chain_loglik(int n, double log2pi, double log_
 #pragma clang fp contract(off)
   const double nl = n * log_cs;
   return -0.5 * ((__builtin_fma(log2pi, (double)n, nl) + logdet) + q_over_cs);
+}
+
+// the start's words of the FIT instances behind the instance's carve: hi[256] | lo[256] | go | ll | grad[kMaxD] | state[W]
+// (go is the decision thread 0 publishes, 0.0 or 1.0: every word of the block is a double)
+enum { kFitHi = 0, kFitLo = kChainTable, kFitGo = 2 * kChainTable, kFitLl, kFitGrad, kFitState = kFitGrad + kMaxD };
+static_assert(kFitState == kFitLdsHead && fit_state_doubles(kMaxD) == fit_state_words(kMaxD) && fit_state_doubles(1) == fit_state_words(1),
+              "small_layout.h sizes the start's words");
+constexpr int kFitMaxEvals = 4096;   // evaluations of one start in one call (ccgp.h)
+
+// The profiled log-likelihood of the FIT instances with its operations spelled out, for chain_loglik's reason: inside the
+// evaluation loop the loop-invariant product n log 2 pi would be hoisted and the other product fused.  The operations are the
+// ones the profiled instances compile to: fma(log 2 pi, n, n log cs_hat), then + log det, then + n.
+__device__ __forceinline__ double fit_loglik(int n, double log2pi, double log_csh, double logdet) {
+#pragma clang fp contract(off)
+  const double nl = n * log_csh;
+  return -0.5 * ((__builtin_fma(log2pi, (double)n, nl) + logdet) + (double)n);
 }
 
 struct RegArgs {
@@ -92,6 +109,7 @@ struct RegArgs {
   const int* set;
   const double* sigma2_set;
   ChainIO ch;          // CHAIN instantiations only
+  FitIO fit;           // FIT instantiations only
 };
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
@@ -159,8 +177,15 @@ __device__ __forceinline__ void mat_sync() {
 // instance, hence the likelihood bits ccgp_loglik_batch_sets gives that row -- and thread 0 decides, publishes the decision
 // through LDS and, after one barrier, every thread reads the same word: go on with the next proposal or leave.  The trip
 // count is bounded by n_prop[a]; no path waits on another workgroup.  A template parameter, as PROF and SETS are.
+// FIT: an ordinary-kriging start per workgroup (ccgp_profile_fit_sets): the profiled-gradient sets instance (INV = 2, K = 1)
+// evaluating again and again.  The set's design and the start's state (fit_logic.h) are loaded once; then, per evaluation,
+// wave 0 forms theta = exp(trial) by the portable exp into th[] (w^2 = 1), generation, sweep with identity rows and gradient
+// epilogue run as they are -- the operations of the sets instance in its order, hence the bits ccgp_profile_batch_sets gives
+// that row -- with the likelihood and the gradient row left in LDS; thread 0 runs fit_feed on them, writes the trace and
+// publishes one word, and after one barrier every thread reads it: go on with the next trial or leave.  The trip count is
+// bounded by max_evals[a] <= 4096; no path waits on another workgroup.  On exit the state goes back to HBM.
 template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false,
-          bool CHAIN = false>
+          bool CHAIN = false, bool FIT = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
@@ -169,6 +194,7 @@ void small_reg_kernel(RegArgs a) {
   static_assert(!SETS || (!FAC && ((NE == 1 && !INV && !PROF) || (INV == 2 && PROF))),
                 "the sets form exists for the plain likelihood and for the profiled gradient only");
   static_assert(!CHAIN || (SETS && G == 16 && NE == 1 && !INV && !PROF && !FAC), "a chain is the sets likelihood instance on the 16 x 16 grid");
+  static_assert(!FIT || (SETS && PROF && INV == 2 && !CHAIN), "a fit is the profiled-gradient sets instance");
   constexpr int TPM = G * G;       // threads per matrix
   constexpr int MPW = 256 / TPM;   // matrices per workgroup
   constexpr int NP = G * NB;       // padded order
@@ -226,6 +252,24 @@ void small_reg_kernel(RegArgs a) {
     if (tid < ch.p) cst[kChainTheta + tid] = ch.theta0[b + (size_t)tid * a.B];
     if (tid == 0) { cst[kChainL] = ch.l0[b]; cst[kChainBeta] = ch.beta0[b]; }
   }
+  // FIT: evaluations made and factorisations failed so far in this call (uniform over the workgroup), the start's words
+  double* fst = nullptr;
+  int ft = 0, ffail = 0;
+  if constexpr (FIT) {
+    fst = smem + cv.total;
+    const FitIO& fi = a.fit;
+    const double* sg = fi.state + (size_t)b * fi.W;
+    // a start that is not running, or has no evaluations to make, stays as it came (every thread reads the same words)
+    if (fi.max_evals[b] <= 0 || sg[kFitCode] != (double)kFitRunning) {
+      if (tid == 0) { fi.evals[b] = 0; fi.nfail[b] = 0; }
+      return;
+    }
+    for (int e = tid; e < kChainTable; e += 256) {
+      fst[kFitHi + e] = __longlong_as_double((long long)kExpTableBits[e]);
+      fst[kFitLo + e] = __longlong_as_double((long long)kChainExpLoBits[e]);
+    }
+    for (int e = tid; e < fi.W; e += 256) fst[kFitState + e] = sg[e];
+  }
   int st = 0;   // SETS: this evaluation's training set
   if constexpr (SETS) {
     // a matrix's threads are whole waves on both grids: the set index is wave-uniform, and saying so keeps it -- and the
@@ -241,7 +285,7 @@ void small_reg_kernel(RegArgs a) {
     xs = smem + cv.xs_own + (size_t)sub * d * n;
     for (int e = lt; e < n * d; e += TPM) xs[e] = a.X[(size_t)b * a.x_stride + e];
   }
-  if constexpr (!CHAIN) {
+  if constexpr (!CHAIN && !FIT) {
     for (int e = lt; e < K * d; e += TPM) th[e] = a.params[pb + (size_t)(K + e) * a.ldp];
     if (lt < K) {
       const double w = a.params[pb + (size_t)lt * a.ldp];
@@ -269,6 +313,13 @@ chain_next:
       }
       // the 2 d rates: every lane holds tm, so lane e stores rate e (d <= 64: two passes at the most)
       for (int e = tid; e < 2 * d; e += 64) th[e] = chain_rate(tm, ch.prior_id, e / d, e % d);
+    }
+  }
+  if constexpr (FIT) {
+    if (tid < 64) {   // wave 0: the parameter row (1, theta) of the trial point, theta_k = exp(trial_k)
+      const double* trial = fit_trial(fst + kFitState, d);
+      for (int e = tid; e < d; e += 64) th[e] = fit_theta(trial[e], fst + kFitHi, fst + kFitLo);
+      if (tid == 0) w2[0] = 1.0;
     }
   }
   if constexpr (NE > 1 && !INV) {
@@ -519,9 +570,12 @@ chain_next:
       if constexpr (PROF) {
         // q / cs = n at cs = q / n: l_p = -(n log 2 pi + n log cs_hat + log det R + n) / 2; q = 0 (a constant y): +Inf
         const double csh = q / n;
-        ll = -0.5 * (n * kLog2Pi + n * log(csh) + logdet + n);
+        if constexpr (FIT) ll = fit_loglik(n, kLog2Pi, log(csh), logdet);
+        else ll = -0.5 * (n * kLog2Pi + n * log(csh) + logdet + n);
         if (lt == 0) slack[2] = csh;   // for the gradient epilogue
-        if (lt == 0 && valid && blockIdx.y == 0) a.s2hat[b] = bad ? kNaN : csh / sw;
+        if constexpr (!FIT) {
+          if (lt == 0 && valid && blockIdx.y == 0) a.s2hat[b] = bad ? kNaN : csh / sw;
+        }
       } else if constexpr (CHAIN) {
         ll = chain_loglik(n, kLog2Pi, log(cs), logdet, q / cs);
       } else {
@@ -531,6 +585,9 @@ chain_next:
       ll = -0.5 * (n * kLog2Pi + logdet + syy);
     }
     if (bad) { ll = kNaN; beta = kNaN; }
+    if constexpr (FIT) {
+      if (lt == 0) fst[kFitLl] = ll;
+    }
     if (lt == 0) {
       slack[0] = beta;      // for the epilogues
       slack[1] = s11;
@@ -724,7 +781,10 @@ chain_next:
             if (lt < QG * (1 + KG) && valid) {
               const int qq = lt / (1 + KG), slot = lt % (1 + KG), q = q0 + qq;
               const double tot = (part[lt] + part[kGradSlots + lt]) + (part[2 * kGradSlots + lt] + part[3 * kGradSlots + lt]);
-              if (q < K) {
+              if constexpr (FIT) {
+                // the row (1, theta): w = 1, and only the theta columns are wanted; they stay in LDS for thread 0
+                if (q < K && slot != 0 && k0 + slot - 1 < d) fst[kFitGrad + k0 + slot - 1] = nograd ? kNaN : -s2g * tot;
+              } else if (q < K) {
                 const double wq = a.params[pb + (size_t)q * a.ldp];
                 if (slot == 0) {
                   if (k0 == 0) a.grad[b + (size_t)q * a.Btot] = nograd ? kNaN : 2.0 * s2g * wq * tot;
@@ -827,6 +887,33 @@ chain_next:
             if (k0 + k < d) g[(i - nf) + (size_t)(k0 + k) * nfree] = bad ? kNaN : -4.0 * rsw * acc[k];
         }
       }
+    }
+    if constexpr (FIT) {
+      // the epilogue's last barrier has made ll and the gradient row visible: thread 0 takes the step of design._Start.feed
+      const FitIO& fi = a.fit;
+      if (tid == 0) {
+        double* sw_ = fst + kFitState;
+        const double* th_ = th;
+        double gx[kMaxD];
+        for (int k = 0; k < d; ++k) gx[k] = fit_grad(fst[kFitGrad + k], th_[k]);
+        const double f = fit_value(fst[kFitLl]);
+        if (fi.tr_f) {
+          const size_t at = (size_t)b * fi.T + ft;
+          fi.tr_f[at] = f;
+          fi.tr_status[at] = bad;
+        }
+        fit_feed(sw_, f, gx, bad == 0);
+        const int go = sw_[kFitCode] == (double)kFitRunning && ft + 1 < fi.max_evals[b] && ft + 1 < kFitMaxEvals;
+        fst[kFitGo] = go ? 1.0 : 0.0;
+      }
+      __syncthreads();
+      const int go = __builtin_amdgcn_readfirstlane(fst[kFitGo] != 0.0);
+      ft += 1;
+      ffail += bad != 0;
+      if (go) goto chain_next;
+      double* sg = fi.state + (size_t)b * fi.W;
+      for (int e = tid; e < fi.W; e += 256) sg[e] = fst[kFitState + e];
+      if (tid == 0) { fi.evals[b] = ft; fi.nfail[b] = ffail; }
     }
     return;
   }
@@ -1286,7 +1373,30 @@ static void launch_chain(hipStream_t s, const RegArgs& a) {
   hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
 }
 
+// the fit instances: the profiled-gradient sets instance compiled with FIT, one workgroup per start, the start's words behind
+// the instance's carve
+template <int NB>
+static void launch_fit(hipStream_t s, const RegArgs& a) {
+  static unsigned long long attr_mask = 0;
+  void (*kernel)(RegArgs) = small_reg_kernel<16, NB, NB + 1, false, 2, false, true, true, false, true>;
+  once_per_device(attr_mask, [] {
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, 2, false, true, true, false, true>, "small_reg_kernel<fit>");
+  });
+  const size_t lds = sizeof(double) * reg_fit_lds_doubles(NB, a.n, a.d);
+  hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
+}
+
 }  // namespace
+
+// ccgp_profile_fit_sets where small_route_fit says Reg: A starts, start a on training set set[a]; arrays as FitIO lays them
+// out; every pointer a device pointer
+void launch_small_reg_fit_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set, int A,
+                               const FitIO& io) {
+  DrawView dv{nullptr, A, 1, d, KernelFamily{}};
+  RegArgs a = reg_args(Xs, n, d, ys, dv);
+  a.B = A; a.set = set; a.Btot = A; a.fit = io;
+  pick<1, 8>((n + 15) / 16, [&](auto nb) { launch_fit<decltype(nb)::value>(s, a); });
+}
 
 // ccgp_metro_segments_sets where small_route_chain says Reg: A chains, chain a on training set set[a]; arrays as ChainIO
 // lays them out (theta0 / theta_fin A x p column-major); every pointer a device pointer

@@ -1033,6 +1033,109 @@ def ordinary_kriging_fit_sets(handle, D_trains, y_trains, starts=8, rng=0, extra
     return _kriging_fit_sets("ordinary_kriging_fit_sets", " of set %d", profile, Ds, seeds, starts, extra_starts)
 
 
+def _twin_fit_segment(handle, Xs, Y, owner, state, seg):
+    """What one launch of profile_fit_sets does, on the host twin: every start of `state` [A, W] (changed in place) takes up to
+    `seg` evaluations, all running starts' trial points in one profile_fit_eval_sets call per step.  A start depends on its
+    own evaluations only, so the cut into steps changes no bit.  Returns evals[A]."""
+    from . import api
+
+    A = state.shape[0]
+    evals = np.zeros(A, dtype=np.int64)
+    for _ in range(int(seg)):
+        live = np.flatnonzero(state[:, api.FIT_CODE] == api.FIT_RUNNING)
+        if live.size == 0:
+            break
+        f, g, _, _, _, st = handle.profile_fit_eval_sets(Xs, Y, api.fit_trial(state[live]), owner[live])
+        for k, a in enumerate(live):
+            api.fit_feed(state[a], f[k], g[k], st[k] == 0)
+        evals[live] += 1
+    return evals
+
+
+def ordinary_kriging_fit_device_sets(handle, D_trains, y_trains, starts=8, rng=0, extra_starts=None, on_device=True, seg=512):
+    """ordinary_kriging_fit_sets with the quasi-Newton iteration itself on the device: one launch of ccgp_profile_fit_sets
+    carries every running start of every set through up to `seg` evaluations (one workgroup per start: the profiled-gradient
+    instance, the step of design._Start restated in csrc/fit_logic.h), until none is running; then one value-only
+    ccgp_profile_fit_eval_sets at the C best points.  Starts: kriging_starts under the bounds [-12, 12], as
+    ordinary_kriging_fit_sets draws them (rng: one seed for every set, or a list of C).
+
+    The fit has a contract of its own: theta = exp(log theta) comes from the portable exp the kernel runs, not numpy's, so
+    it is the same method and the same optimum as ordinary_kriging_fit, not its bits.  What it keeps bit for bit is its host
+    twin: on_device=False runs the same driver with every evaluation through ccgp_profile_fit_eval_sets and every step
+    through ccgp_fit_feed, and leaves the same states.  The driver falls back to the twin by itself where the device call
+    says CCGP_EUNSUPPORTED (n > 128, the Matern and spline families).
+
+    Returns one dict per set with ordinary_kriging_fit_sets' keys: sigma2, theta[d], beta, loglik of the best start (as the
+    final value-only call gives them), f[S], x[S, d], converged[S], calls = launches + 1 (on the twin: the evaluator calls
+    the set's starts took part in, + 1), evaluations = the points evaluated on the set, the final one included."""
+    from . import api
+
+    Ds = [np.asarray(D, dtype=np.float64) for D in D_trains]
+    ys = [np.asarray(y, dtype=np.float64).ravel() for y in y_trains]
+    C = len(Ds)
+    if C < 1 or len(ys) != C:
+        raise ValueError("ordinary_kriging_fit_device_sets: one response per design, at least one set")
+    if any(D.ndim != 2 or D.shape != Ds[0].shape for D in Ds) or any(y.shape[0] != Ds[0].shape[0] for y in ys):
+        raise ValueError("ordinary_kriging_fit_device_sets: the sets of one call have one shape (n, d)")
+    seeds = list(rng) if isinstance(rng, (list, tuple)) else [rng] * C
+    if len(seeds) != C:
+        raise ValueError("ordinary_kriging_fit_device_sets: rng is one seed, or one per set")
+    seg = int(seg)
+    if seg < 1 or seg > api.FIT_MAX_EVALS:
+        raise ValueError("ordinary_kriging_fit_device_sets: seg must lie in 1 .. %d" % api.FIT_MAX_EVALS)
+    Xs, Y = np.stack(Ds), np.stack(ys)
+    x0 = np.concatenate([kriging_starts(Ds[c], starts, seeds[c], extra_starts) for c in range(C)])
+    S = x0.shape[0] // C
+    owner = np.repeat(np.arange(C), S)
+    state = np.stack([api.fit_begin(x, -12.0, 12.0) for x in x0])
+    evals = np.zeros(C * S, dtype=np.int64)
+    calls = np.zeros(C, dtype=np.int64)
+    device = bool(on_device)
+    while True:
+        live = np.flatnonzero(state[:, api.FIT_CODE] == api.FIT_RUNNING)
+        if live.size == 0:
+            break
+        if device:
+            try:
+                r = handle.profile_fit_sets(Xs, Y, owner[live], state[live], seg)
+            except api.CcgpError as e:
+                if e.code != -4:   # CCGP_EUNSUPPORTED: this shape has no device fit; the twin carries it
+                    raise
+                device = False
+                continue
+            state[live] = r["state"]
+            evals[live] += r["evals"]
+            calls[np.unique(owner[live])] += 1
+        else:
+            sub = state[live]
+            took = _twin_fit_segment(handle, Xs, Y, owner[live], sub, seg)
+            state[live] = sub
+            evals[live] += took
+            for c in np.unique(owner[live]):   # every step carried every running start: a set's calls are its longest start's
+                calls[c] += int(took[owner[live] == c].max())
+    f_all, x_all = state[:, api.FIT_F].copy(), api.fit_x(state)
+    code = state[:, api.FIT_CODE].astype(np.int64)
+    best = []
+    for c in range(C):
+        f = f_all[c * S:(c + 1) * S]
+        if not np.isfinite(f).any():
+            raise RuntimeError("ordinary_kriging_fit_device_sets: the likelihood failed at every start of set %d" % c)
+        best.append(c * S + int(np.argmin(np.where(np.isfinite(f), f, np.inf))))
+    fb, _, thetas, s2, beta, _ = handle.profile_fit_eval_sets(Xs, Y, x_all[best], np.arange(C), grad=False)
+    out = []
+    for c in range(C):
+        sl = slice(c * S, (c + 1) * S)
+        out.append(dict(sigma2=float(s2[c]), theta=np.array(thetas[c]), beta=float(beta[c]), loglik=float(-fb[c]), f=f_all[sl],
+                        x=x_all[sl], converged=(code[sl] == api.FIT_CONV_REDUCTION) | (code[sl] == api.FIT_CONV_PROJ_GRAD),
+                        calls=int(calls[c]) + 1, evaluations=int(evals[sl].sum()) + 1))
+    return out
+
+
+def ordinary_kriging_fit_device(handle, D_train, y_train, starts=8, rng=0, extra_starts=None, on_device=True, seg=512):
+    """ordinary_kriging_fit_device_sets for one training set: its C = 1 case, field for field."""
+    return ordinary_kriging_fit_device_sets(handle, [D_train], [y_train], starts, rng, extra_starts, on_device, seg)[0]
+
+
 def matern_profile(handle, D, y, nu, thetas):
     """log.likeli of the 1-D scripts (D1:424-444) for an array of scale parameters in ONE value-only device call under the
     Matern(nu) family: log det R(theta) + n log sigma2.MLE(theta), with beta.MLE and sigma2.MLE (D1:411-415) at each theta.
@@ -1136,7 +1239,7 @@ def stack_tables(tables):
 def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size=None, start=None, sigma2s=None,
           theta1_pars=None, theta2_pars=None, rngs=None, max_proposals=None, speculate=0, laplace=None, cgp=False,
           single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None, lockstep_fits=True,
-          device_chains=False):
+          device_chains=False, device_fits=False):
     """The reference's simulation study (GV:689-762 declares nine training sets and fits one): every set of `sets` -- a list
     of (D_train, y_train, D_test, y_test) -- fitted and compared, the sets of one shape (n, d) in lockstep.  Per group:
     sigma2 per set from ordinary_kriging_fit (or sigma2s[i] as given), then laplace_sets and Metro_sets with one generator
@@ -1157,6 +1260,9 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     device_chains (default off): the Metro part of each group goes through Metro_device_sets -- chains resident on the
     device, many proposals per launch, with that function's own stream contract (so other chains than Metro_sets', same
     law); the Laplace stage then runs on its twin evaluator, and speculate is not used.
+    device_fits (default off): the sigma2 / single-GP fits of each group go through ordinary_kriging_fit_device_sets -- the
+    quasi-Newton iteration resident on the device, every start of every set in one launch -- with that function's own
+    contract (the same method and optimum as ordinary_kriging_fit_sets, not its bits).
     Returns dict(tables, summaries, pooled: comparison_summary of the stacked tables, sigma2, draws, beta, chains,
     groups: {(n, d): indices}, calls and seconds: device calls and wall time of the sigma2, single, cgp, laplace, metro and
     predict parts; per set the single and cgp fits happen inside compare_GP, so their seconds are part of predict's and
@@ -1178,6 +1284,8 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     starts = np.broadcast_to(np.asarray(start, dtype=np.float64), (C, np.shape(start)[-1]))
     lockstep = bool(lockstep_fits) and compare_fn is None and logpost_sets_fn is None and not hasattr(gp, "nu")
     compare_fn = compare_fn or compare_GP
+    fit_sets = ordinary_kriging_fit_device_sets if device_fits else ordinary_kriging_fit_sets
+    fit_one = ordinary_kriging_fit_device if device_fits else ordinary_kriging_fit
     calls = dict(sigma2=0, single=0, cgp=0, laplace=0, metro=0, predict=0)
     secs = dict(sigma2=0.0, single=0.0, cgp=0.0, laplace=0.0, metro=0.0, predict=0.0)
     s2 = [None] * C if sigma2s is None else [float(v) for v in sigma2s]
@@ -1198,7 +1306,7 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
                 continue
             part = "sigma2" if any(s2[i] is None for i in todo) else "single"   # every sigma2 given: the single GP's fit alone
             t0 = time.perf_counter()
-            fits = ordinary_kriging_fit_sets(base, [sets[i][0] for i in todo], [sets[i][1] for i in todo])
+            fits = fit_sets(base, [sets[i][0] for i in todo], [sets[i][1] for i in todo])
             calls[part] += max(f["calls"] for f in fits)
             for i, f in zip(todo, fits):
                 if s2[i] is None:
@@ -1209,7 +1317,7 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
         t0 = time.perf_counter()
         if single and not has_model and fit_kw:
             for shape, idx in groups.items():
-                fits = ordinary_kriging_fit_sets(base, [sets[i][0] for i in idx], [sets[i][1] for i in idx], **fit_kw)
+                fits = fit_sets(base, [sets[i][0] for i in idx], [sets[i][1] for i in idx], **fit_kw)
                 calls["single"] += max(f["calls"] for f in fits)
                 for i, f in zip(idx, fits):
                     single_of[i] = dict(est=f)
@@ -1233,7 +1341,7 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     else:
         for i in range(C):
             if s2[i] is None:
-                okf = ordinary_kriging_fit(getattr(gp.h, "_handle", gp.h), sets[i][0], sets[i][1])
+                okf = fit_one(getattr(gp.h, "_handle", gp.h), sets[i][0], sets[i][1])
                 s2[i] = okf["sigma2"]
                 calls["sigma2"] += okf["calls"]
         secs["sigma2"] = time.perf_counter() - t0

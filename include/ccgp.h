@@ -358,6 +358,57 @@ int ccgp_cgp_state_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, co
                               const double* params /* B x (2d+2) */, const int* set, int B, const int* skip /* B or NULL */,
                               double* out_val, double* out_beta, double* out_tau2, double* out_loo, int* status);
 
+/* ---- the ordinary-kriging fits on the device: every start in one launch (mlegp(...)$sig2, HX:759-760) ----------------------------
+ * The quasi-Newton iteration of a start (box-constrained L-BFGS, memory 5, projected Armijo search: design._Start of the
+ * Python package) restated from exactly rounded operations (csrc/fit_logic.h), so that host and device step a start to the
+ * same bits.  One start's state is a flat array of W = ccgp_fit_state_doubles(d) = 16 + 16 d doubles:
+ *   [0] d  [1] code  [2] f  [3] t  [4] backtracks  [5] iterations  [6] first  [7] pairs kept  [8] maxit  [9] factr  [10] pgtol
+ *   [11] max_backtracks  [12] evaluations fed  [13 .. 15] 0, then x | g | p | trial | lo | hi (d each) and the five (s, y)
+ *   pairs, s_0 .. s_4 | y_0 .. y_4, oldest first.
+ *   code: 0 running, 1 converged by relative reduction, 2 converged by projected gradient, 3 maxit, 4 line-search failure,
+ *   5 the start itself cannot be evaluated.  While the code is 0, `trial` is the next point to evaluate.
+ * ccgp_fit_begin fills a state from a start x0 (clipped into [lo, hi]) and the options (R's optim defaults are maxit = 100,
+ * factr = 1e7, pgtol = 0; max_backtracks = 30); ccgp_fit_feed hands it the value f and gradient g (d values) at `trial`, ok != 0
+ * where the evaluator reported no failure, and returns the new code.  Host only, no handle; CCGP_EINVAL for d outside 1 .. 64, a
+ * NULL pointer, maxit < 0, max_backtracks < 0, or (feed) a state whose recorded d is not d.
+ * The objective.  x = log theta; theta_k = exp(x_k) by the portable exp of the device chains (ccgp_chain_terms), the parameter
+ * row is (1, theta), f = -loglik and g_k = -(d loglik / d theta_k) theta_k.  ccgp_profile_fit_eval_sets is that evaluation of
+ * B points (logtheta, out_g, out_theta: B x d column-major) on the host side of ccgp_profile_batch_sets: it forms the rows,
+ * calls ccgp_profile_batch_sets with that call's arguments, checks and routes -- so it serves every shape and family that call
+ * serves, value-only (out_g == NULL) included -- and transforms the results.  A failed row has f = NaN (the one quiet NaN), a
+ * NaN gradient row and its 1-based pivot in status; the return value is the number of failed rows.  NULL ok: out_g, out_theta,
+ * out_sigma2, out_beta, status.
+ * ccgp_profile_fit_sets runs A starts, start a on training set set[a] (Xs, ys, C as in ccgp_profile_batch_sets, K = 1), on the
+ * device: one workgroup carries one start from its state through up to max_evals[a] evaluations -- theta from `trial`, the
+ * profiled likelihood and its gradient from one factorisation, the step of ccgp_fit_feed -- and writes the state back, so the
+ * next call continues it.  out_evals[a] is the number of evaluations made.  The trace (both or neither, [a T + t]): f and the
+ * pivot status of evaluation t of this call; NaN / -1 beyond out_evals[a].
+ *   Bits.  Every evaluation inside a fit has the bits ccgp_profile_batch_sets gives that row on that set.  A start driven
+ *     evaluation by evaluation through ccgp_profile_fit_eval_sets and ccgp_fit_feed leaves the same state and trace, bit for bit.
+ *   Independence.  A start depends on its own inputs only: not on A, its position, the other starts' sets, what the handle ran
+ *     before, or how its evaluations are cut into calls by max_evals.
+ *   Failure.  A failed factorisation is an infeasible trial: the line search backs off and the start goes on.  A start whose
+ *     first point fails ends with code 5, its neighbours untouched.  The return value is the number of evaluations whose
+ *     factorisation failed, over all starts.
+ *   Arguments.  CCGP_EINVAL before anything is copied or launched, outputs untouched: bad shapes, C < 1, A < 0, T < 0, set[a]
+ *     outside 0 .. C-1, max_evals[a] outside 0 .. min(T, 4096), a partial trace, a NULL required pointer (everything but the
+ *     trace), a state whose recorded d is not d.  CCGP_EUNSUPPORTED, outputs untouched, where ccgp_profile_batch_sets has no
+ *     one-launch gradient route or the start's words do not fit beside its carve: n > 128, the Matern and spline families.
+ *     A == 0 returns CCGP_OK.  A start that is not running, or whose max_evals is 0, is returned as it came.
+ * Host pointers only, blocking; ccgp_reserve does not cover the staging.  Not in this version: _dev variants, a ccgp_multi
+ * wrapper, an R shim. */
+int ccgp_fit_state_doubles(int d);
+int ccgp_fit_begin(double* state, int d, const double* x0, const double* lo, const double* hi, int maxit, double factr,
+                   double pgtol, int max_backtracks);
+int ccgp_fit_feed(double* state, int d, double f, const double* g, int ok);
+int ccgp_profile_fit_eval_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C,
+                               const double* logtheta /* B x d */, const int* set, int B, double* out_f,
+                               double* out_g /* B x d, NULL: value-only */, double* out_theta, double* out_sigma2,
+                               double* out_beta, int* status);
+int ccgp_profile_fit_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int A,
+                          const int* set /* A */, double* state /* A x W, in and out */, const int* max_evals /* A */,
+                          int* out_evals /* A */, double* trace_f, int* trace_status /* A x T, both or neither */, int T);
+
 /* ---- a9: likeli.hyperpars HX:549-575 / choose.hyperpars HX:584-595, ADV:552-599 -------
  * hyper is G x 4 (alpha1 beta1 alpha2 beta2).  For each row: N base-2 Halton quantiles
  * u_j, p = u_j, theta1 = qigamma(u_j, a1, b1), theta2 = qigamma(u_j, a2, b2), mode-1
