@@ -74,6 +74,11 @@ SIGNATURES = {
     "ccgp_profile_fit_eval_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _dp, _dp, _dp, _dp, _dp,
                                            _ip]),
     "ccgp_profile_fit_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, c_int, _ip, _dp, _ip, _ip, _dp, _ip, c_int]),
+    "ccgp_nm_state_doubles": (c_int, [c_int]),
+    "ccgp_nm_begin": (c_int, [_dp, c_int, _dp, c_double, c_double, c_int]),
+    "ccgp_nm_feed": (c_int, [_dp, c_int, c_double]),
+    "ccgp_laplace_search_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, c_int, _ip, _dp, _ip, _ip,
+                                         _dp, _ip, c_int]),
     "ccgp_cgp_state_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _ip, _dp, _dp, _dp, _dp,
                                           _ip]),
     "ccgp_grid_marginal": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, _dp, c_int, c_int,
@@ -269,6 +274,67 @@ def fit_x(state):
     state = np.asarray(state)
     d = (state.shape[-1] - FIT_HEADER) // 16
     return np.array(state[..., FIT_HEADER:FIT_HEADER + d])
+
+
+# the codes of a Nelder-Mead search's state (csrc/nm_logic.h) and where its words lie
+NM_RUNNING, NM_CONVERGED, NM_MAXITER = range(3)
+NM_Q, NM_CODE, NM_PHASE, NM_ITERATIONS, NM_CHARGED, NM_FED, NM_HEADER = 0, 1, 2, 4, 5, 6, 16
+NM_COUNTERS = dict(expansion_taken=10, expansion_refused=11, reflection=12, outside_contraction=13, inside_contraction=14,
+                   shrink=15)
+NM_MAX_EVALS = 4096
+
+
+def nm_state_doubles(q):
+    """ccgp_nm_state_doubles: the doubles of one search's state, q^2 + 5 q + 18."""
+    W = lib().ccgp_nm_state_doubles(int(q))
+    if W < 0:
+        raise CcgpError(W, "ccgp_nm_state_doubles")
+    return W
+
+
+def _nm_q(state):
+    q = int(np.asarray(state)[..., NM_Q].flat[0])
+    if q < 1 or q > 8 or np.asarray(state).shape[-1] != q * q + 5 * q + 18:
+        raise ValueError("not the state of a search: %d words for q = %d" % (np.asarray(state).shape[-1], q))
+    return q
+
+
+def nm_begin(x0, xatol=1e-6, fatol=1e-9, maxiter=2000):
+    """ccgp_nm_begin: the state of fit.laplace_sets' Nelder-Mead search from x0 [q] -> float64[W]; nm_trial(state) is the
+    point to evaluate first.  No device."""
+    x0 = np.ascontiguousarray(np.ravel(np.asarray(x0, dtype=np.float64)))
+    q = x0.shape[0]
+    state = np.empty(nm_state_doubles(q))
+    rc = lib().ccgp_nm_begin(_p(state), q, _p(x0), float(xatol), float(fatol), int(maxiter))
+    if rc:
+        raise CcgpError(rc, "ccgp_nm_begin")
+    return state
+
+
+def nm_feed(state, val):
+    """ccgp_nm_feed: hand the state (float64[W], C-contiguous, changed in place) the log-posterior at its trial point -> the
+    new code.  No device."""
+    if not (isinstance(state, np.ndarray) and state.dtype == np.float64 and state.flags.c_contiguous and state.ndim == 1):
+        raise ValueError("state must be a contiguous float64 vector")
+    rc = lib().ccgp_nm_feed(_p(state), _nm_q(state), float(val))
+    if rc < 0:
+        raise CcgpError(rc, "ccgp_nm_feed")
+    return rc
+
+
+def nm_trial(state):
+    """The point a running search wants evaluated next: a copy of the `trial` words of its state (or of each row of [A, W])."""
+    state = np.asarray(state)
+    return np.array(state[..., state.shape[-1] - _nm_q(state):])
+
+
+def nm_simplex(state):
+    """(simplex [q + 1, q], values [q + 1]) of a search's state, best vertex first once sorted; the values are the
+    log-posterior's (the state keeps them negated), -1e300 where it was not finite."""
+    state = np.asarray(state)
+    q = _nm_q(state)
+    sim = np.array(state[NM_HEADER:NM_HEADER + (q + 1) * q]).reshape(q + 1, q)
+    return sim, -np.array(state[NM_HEADER + (q + 1) * q:NM_HEADER + (q + 1) * q + q + 1])
 
 
 SUMMARY_MAX_PROBS = 8
@@ -846,6 +912,31 @@ class Handle:
         out = dict(state=state, evals=evals, failed=failed)
         if trace:
             out.update(trace_f=tr_f, trace_status=tr_st)
+        return out
+
+    def laplace_search_sets(self, Xs, ys, sigma2s, prior_id, set_of, state, max_evals, prior_pars=None, trace=False, T=None):
+        """ccgp_laplace_search_sets: A Nelder-Mead searches, search a on training set set_of[a], stepped on the device from
+        state [A, W] (api.nm_begin) through up to max_evals[a] evaluations each.  Returns dict(state [A, W], evals[A], failed:
+        evaluations whose factorisation failed, and with trace=True trace_val, trace_status [A, T], T = max(max_evals) unless
+        given)."""
+        state = np.ascontiguousarray(np.atleast_2d(np.asarray(state, dtype=np.float64))).copy()
+        A = state.shape[0]
+        Xb, yb, s2, idx, C, n, d = self._sets(Xs, ys, sigma2s, set_of, A)
+        max_evals = np.ascontiguousarray(np.broadcast_to(np.asarray(max_evals), (A,)).astype(np.int32))
+        if T is None:
+            T = int(max_evals.max()) if A else 0
+        pp = _f(np.ravel(prior_pars)) if prior_pars is not None else None
+        q = 4 if int(prior_id) == PRIOR_ANI else 3
+        if state.shape[1] != nm_state_doubles(q):
+            raise ValueError("state must be [A, %d] for this prior (q = %d)" % (nm_state_doubles(q), q))
+        evals = np.zeros(A, dtype=np.int32)
+        tr_v, tr_st = (np.full((A, T), np.nan), np.full((A, T), -1, dtype=np.int32)) if trace else (None, None)
+        failed = self._chk(lib().ccgp_laplace_search_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, int(prior_id), _p(pp), A,
+                                                          _ipt(idx), _p(state), _ipt(max_evals), _ipt(evals), _p(tr_v),
+                                                          _ipt(tr_st), int(T)))
+        out = dict(state=state, evals=evals, failed=failed)
+        if trace:
+            out.update(trace_val=tr_v, trace_status=tr_st)
         return out
 
     def cgp_state_batch_sets(self, Xs, ys, params, set_of, skip=None):

@@ -17,6 +17,7 @@
 #include "ccgp_internal.h"
 #include "chain_terms.h"
 #include "fit_logic.h"
+#include "nm_logic.h"
 #include "special_math.h"
 
 using namespace ccgp;
@@ -1692,6 +1693,94 @@ int ccgp_profile_fit_sets(ccgp_handle* h, const double* Xs, int n, int d, const 
   }
   std::vector<int> cnt(2 * sA);
   if (int rc = pull(h, {piece(io.state, state, sA * W), piece(dcnt, cnt.data(), 2 * sA), piece(io.tr_f, trace_f, tr ? sT : 0),
+                        piece(io.tr_status, trace_status, tr ? sT : 0)}))
+    return rc;
+  int failed = 0;
+  for (int a = 0; a < A; ++a) {
+    out_evals[a] = cnt[a];
+    failed += cnt[sA + a];
+  }
+  return failed;
+} CCGP_GUARD_END(h)
+
+// ---- the Laplace search on the device (ccgp.h) ----------------------------------------------------------------------------------
+int ccgp_nm_state_doubles(int q) { return q >= 1 && q <= kNmMaxQ ? nm_state_doubles(q) : CCGP_EINVAL; }
+
+// what a state must say before anything steps it: the q it was begun with, a code, a phase and a vertex inside their ranges
+static bool nm_state_ok(const double* st, int q) {
+  auto whole = [](double v, int lo, int hi) { return v >= (double)lo && v <= (double)hi && v == (double)(int)v; };
+  return st[kNmQ] == (double)q && whole(st[kNmCode], kNmRunning, kNmMaxiter) &&
+         whole(st[kNmPhase], kNmPhaseInit, kNmPhaseShrink) && whole(st[kNmVertex], 0, q);
+}
+
+int ccgp_nm_begin(double* state, int q, const double* x0, double xatol, double fatol, int maxiter) {
+  if (q < 1 || q > kNmMaxQ || !state || !x0 || maxiter < 0) return CCGP_EINVAL;
+  nm_begin(state, q, x0, xatol, fatol, maxiter);
+  return CCGP_OK;
+}
+
+int ccgp_nm_feed(double* state, int q, double val) {
+  if (q < 1 || q > kNmMaxQ || !state || !nm_state_ok(state, q)) return CCGP_EINVAL;
+  nm_feed(state, val);
+  return (int)state[kNmCode];
+}
+
+int ccgp_laplace_search_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                             int prior_id, const double* prior_pars, int A, const int* set, double* state,
+                             const int* max_evals, int* out_evals, double* trace_val, int* trace_status, int T) try {
+  if (!h) return CCGP_EINVAL;
+  bool ok = n >= 1 && d >= 1 && d <= kMaxD && A >= 0 && T >= 0 && state && max_evals && out_evals &&
+            (trace_val != nullptr) == (trace_status != nullptr) && sets_args_ok(Xs, ys, sigma2, true, C, set, A, 0);
+  if (int rc = logpost_args(h, "ccgp_laplace_search_sets", ok, d, prior_id, prior_pars)) return rc;
+  const int q = prior_id == CCGP_PRIOR_ANI ? 4 : 3, W = nm_state_doubles(q);
+  const int cap = T < 4096 ? T : 4096;
+  for (int a = 0; ok && a < A; ++a)
+    ok = max_evals[a] >= 0 && max_evals[a] <= cap && nm_state_ok(state + (size_t)a * W, q);
+  if (!ok) return fail(h, CCGP_EINVAL, "ccgp_laplace_search_sets: bad argument");
+  if (small_route_nm(h->fam.id == 0, n, d, 2) != Route::Reg)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_laplace_search_sets: searches run on the device for Gaussian sets of n <= 128 whose "
+                                      "register-resident instance fits; keep the search on ccgp_chain_logpost_sets and ccgp_nm_feed");
+  if (A == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  const size_t sA = A, sT = (size_t)A * T;
+  const bool tr = trace_val != nullptr && T > 0;
+  double *dXs, *dys, *ds2, *dpp;
+  int *dset, *dmax, *dcnt;
+  NmIO io{};
+  io.prior_id = prior_id; io.q = q; io.W = W; io.T = T;
+  // inputs back to back, then results back to back: each side crosses PCIe as one span (the state is both)
+  if (int rc = stage(h, [&](Layout& c) {
+        dXs = c.take<double>((size_t)C * n * d);
+        dys = c.take<double>((size_t)C * n);
+        ds2 = c.take<double>(C);
+        dpp = c.take<double>(4);
+        dset = c.take<int>(sA);
+        dmax = c.take<int>(sA);
+        io.state = c.take<double>(sA * W);
+        dcnt = c.take<int>(2 * sA);   // evaluations | failed
+        io.tr_val = tr ? c.take<double>(sT) : nullptr;
+        io.tr_status = tr ? c.take<int>(sT) : nullptr;
+      }))
+    return rc;
+  io.prior_pars = dpp;
+  io.max_evals = dmax;
+  io.evals = dcnt;
+  io.nfail = dcnt ? dcnt + sA : nullptr;
+  const double pp0[4] = {0.0, 0.0, 0.0, 0.0};
+  if (int prc = push(h, {piece(dXs, Xs, (size_t)C * n * d), piece(dys, ys, (size_t)C * n), piece(ds2, sigma2, C),
+                         piece(dpp, prior_pars ? prior_pars : pp0, 4), piece(dset, set, sA), piece(dmax, max_evals, sA),
+                         piece(io.state, state, sA * W)}))
+    return prc;
+  if (tr) {   // a search that stops early leaves the rest of its trace as it is: NaN / -1, not what the buffer held
+    CCGP_HIP(hipMemsetAsync(io.tr_val, 0xFF, Layout::al(sT * sizeof(double)) + Layout::al(sT * sizeof(int)), h->stream));
+  }
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    launch_small_reg_nm_sets(h->stream, dXs, n, d, dys, ds2, dset, A, io);
+    CCGP_LAUNCH_CHECK();
+  }
+  std::vector<int> cnt(2 * sA);
+  if (int rc = pull(h, {piece(io.state, state, sA * W), piece(dcnt, cnt.data(), 2 * sA), piece(io.tr_val, trace_val, tr ? sT : 0),
                         piece(io.tr_status, trace_status, tr ? sT : 0)}))
     return rc;
   int failed = 0;

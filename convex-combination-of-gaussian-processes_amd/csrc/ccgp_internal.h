@@ -247,6 +247,21 @@ struct FitIO {
 };
 void launch_small_reg_fit_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set, int A,
                                const FitIO& io);
+// the Laplace search on the device (ccgp_laplace_search_sets where small_route_nm says Reg): what search a = workgroup a of A
+// reads and leaves, every pointer a device pointer.  state [A][W] in and out (nm_logic.h), max_evals / evals / nfail [A], the
+// trace [A][T], both or none
+struct NmIO {
+  int prior_id, q;
+  const double* prior_pars;   // 4 values where the prior reads them
+  double* state;
+  int W, T;
+  const int* max_evals;
+  int *evals, *nfail;
+  double* tr_val;
+  int* tr_status;
+};
+void launch_small_reg_nm_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
+                              const int* set, int A, const NmIO& io);
 // leave-one-out mean / variance of every training point for B draws (ccgp_loo_batch where small_route_loo says Reg): one
 // workgroup per draw on the inverse instances' scheme; mean / var are B x n column-major, sigma2 is the scalar that
 // vf.sigma2_row (indexed by draw) replaces, vf.q (may be nullptr) receives Q per draw

@@ -286,5 +286,20 @@ inline Route small_route_fit(bool gauss, int n, int d, int K) {
   if (K != 1 || small_route_profile_grad_sets(gauss, n, d, K) != Route::Reg) return Route::Unsupported;
   return lds_fits(reg_fit_lds_doubles((n + 15) / 16, n, d)) ? Route::Reg : Route::Unsupported;
 }
+// the Laplace search on the device (ccgp_laplace_search_sets): the NM instances are the CHAIN instances with a Nelder-Mead
+// search in place of the Metropolis walk, one workgroup per search.  The search's state (nm_logic.h: q^2 + 5 q + 18 doubles,
+// q = 3 or 4 for the priors a chain has) lies behind the chain's words, of which the search uses the tables, ljac / lprior
+// and the decision word
+constexpr int kNmLdsQ = 4;
+CCGP_HD constexpr int nm_state_words(int q) { return q * q + 5 * q + 18; }
+inline size_t reg_nm_lds_doubles(int NB, int n, int d, int K) {
+  return reg_chain_lds_doubles(NB, n, d, K) + nm_state_words(kNmLdsQ);
+}
+// Reg exactly where small_route_chain says Reg and the search's words fit behind the chain's; Unsupported otherwise: the
+// caller keeps the search on the host twin there
+inline Route small_route_nm(bool gauss, int n, int d, int K) {
+  if (small_route_chain(gauss, n, d, K) != Route::Reg) return Route::Unsupported;
+  return lds_fits(reg_nm_lds_doubles((n + 15) / 16, n, d, K)) ? Route::Reg : Route::Unsupported;
+}
 
 }  // namespace ccgp

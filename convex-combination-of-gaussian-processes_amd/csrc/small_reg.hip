@@ -30,6 +30,7 @@
 #include "ccgp_internal.h"
 #include "chain_terms.h"
 #include "fit_logic.h"
+#include "nm_logic.h"
 
 namespace ccgp {
 
@@ -69,6 +70,12 @@ __device__ __forceinline__ double fit_loglik(int n, double log2pi, double log_cs
   const double nl = n * log_csh;
   return -0.5 * ((__builtin_fma(log2pi, (double)n, nl) + logdet) + (double)n);
 }
+
+// the search's state of the NM instances lies behind the chain's words (of which a search uses the tables, ljac, lprior and go)
+enum { kNmState = kChainLdsDoubles };
+static_assert(nm_state_doubles(kNmLdsQ) == nm_state_words(kNmLdsQ) && nm_state_doubles(3) == nm_state_words(3),
+              "small_layout.h sizes the search's words");
+constexpr int kNmMaxEvals = 4096;   // evaluations of one search in one call (ccgp.h)
 
 struct RegArgs {
   const double* X;
@@ -110,6 +117,7 @@ struct RegArgs {
   const double* sigma2_set;
   ChainIO ch;          // CHAIN instantiations only
   FitIO fit;           // FIT instantiations only
+  NmIO nm;             // NM instantiations only
 };
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
@@ -184,8 +192,15 @@ __device__ __forceinline__ void mat_sync() {
 // that row -- with the likelihood and the gradient row left in LDS; thread 0 runs fit_feed on them, writes the trace and
 // publishes one word, and after one barrier every thread reads it: go on with the next trial or leave.  The trip count is
 // bounded by max_evals[a] <= 4096; no path waits on another workgroup.  On exit the state goes back to HBM.
+// NM (with CHAIN): a Nelder-Mead search per workgroup (ccgp_laplace_search_sets): the chain instance with the search of
+// nm_logic.h in place of the walk.  The set's design, the two tables and the search's state are loaded once; then, per
+// evaluation, wave 0 forms the portable terms of the state's `trial` -- the chain's code with trial in place of theta + e_t --,
+// the evaluation runs as it is, thread 0 forms val in logpost_rows' order, runs nm_feed on the LDS state, writes the trace and
+// publishes one word, and after one barrier every thread reads it.  The trip count is bounded by max_evals[a] <= 4096; no
+// path waits on another workgroup.  A failed factorisation is a non-finite value: the search goes on.  On exit the state
+// goes back to HBM.
 template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false,
-          bool CHAIN = false, bool FIT = false>
+          bool CHAIN = false, bool FIT = false, bool NM = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
@@ -195,6 +210,7 @@ void small_reg_kernel(RegArgs a) {
                 "the sets form exists for the plain likelihood and for the profiled gradient only");
   static_assert(!CHAIN || (SETS && G == 16 && NE == 1 && !INV && !PROF && !FAC), "a chain is the sets likelihood instance on the 16 x 16 grid");
   static_assert(!FIT || (SETS && PROF && INV == 2 && !CHAIN), "a fit is the profiled-gradient sets instance");
+  static_assert(!NM || CHAIN, "a Laplace search is a chain instance with another step");
   constexpr int TPM = G * G;       // threads per matrix
   constexpr int MPW = 256 / TPM;   // matrices per workgroup
   constexpr int NP = G * NB;       // padded order
@@ -233,7 +249,21 @@ void small_reg_kernel(RegArgs a) {
   // CHAIN: proposals used, draws accepted and factorisations failed so far (uniform over the workgroup), the chain's words
   double* cst = nullptr;
   int ct = 0, cacc = 0, cfail = 0;
-  if constexpr (CHAIN) {
+  if constexpr (NM) {
+    cst = smem + cv.total;
+    const NmIO& nm = a.nm;
+    const double* sg = nm.state + (size_t)b * nm.W;
+    // a search that is not running, or has no evaluations to make, stays as it came (every thread reads the same words)
+    if (nm.max_evals[b] <= 0 || sg[kNmCode] != (double)kNmRunning) {
+      if (tid == 0) { nm.evals[b] = 0; nm.nfail[b] = 0; }
+      return;
+    }
+    for (int e = tid; e < kChainTable; e += 256) {
+      cst[kChainHi + e] = __longlong_as_double((long long)kExpTableBits[e]);
+      cst[kChainLo + e] = __longlong_as_double((long long)kChainExpLoBits[e]);
+    }
+    for (int e = tid; e < nm.W; e += 256) cst[kNmState + e] = sg[e];
+  } else if constexpr (CHAIN) {
     cst = smem + cv.total;
     const ChainIO& ch = a.ch;
     if (ch.n_prop[b] <= 0 || ch.stop_acc[b] <= 0) {   // nothing to do: the state as it came (every thread reads the same words)
@@ -295,7 +325,23 @@ void small_reg_kernel(RegArgs a) {
     __syncthreads();   // the tables, the start state and the design are in LDS
   }
 chain_next:
-  if constexpr (CHAIN) {
+  if constexpr (NM) {
+    if (tid < 64) {   // wave 0, every lane the same arithmetic; lane 0 writes
+      const NmIO& nm = a.nm;
+      const double* trial = nm_trial(cst + kNmState, nm.q);
+      double cand[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cand[j] = j < nm.q ? trial[j] : 0.0;
+      const ChainTerms tm = chain_terms(nm.prior_id, cand, nm.prior_pars, cst + kChainHi, cst + kChainLo);
+      if (tid == 0) {
+        w2[0] = tm.w0 * tm.w0;
+        w2[1] = tm.w1 * tm.w1;
+        cst[kChainLj] = tm.lj;
+        cst[kChainLp] = tm.lp;
+      }
+      for (int e = tid; e < 2 * d; e += 64) th[e] = chain_rate(tm, nm.prior_id, e / d, e % d);
+    }
+  } else if constexpr (CHAIN) {
     if (tid < 64) {   // wave 0, every lane the same arithmetic; lane 0 writes
       const ChainIO& ch = a.ch;
       const double* e = ch.steps + ((size_t)b * ch.T + ct) * ch.p;
@@ -616,7 +662,20 @@ chain_next:
         if (a.vf.q) a.vf.q[b] = bad ? kNaN : q;
       }
     }
-    if constexpr (CHAIN) {
+    if constexpr (NM) {
+      if (lt == 0) {   // the step of laplace_sets' search on this evaluation's value
+        const NmIO& nm = a.nm;
+        const double val = chain_value(ll, cst[kChainLj], cst[kChainLp]);
+        if (nm.tr_val) {
+          const size_t at = (size_t)b * nm.T + ct;
+          nm.tr_val[at] = val;
+          nm.tr_status[at] = bad;
+        }
+        nm_feed(cst + kNmState, val);
+        const int go = cst[kNmState + kNmCode] == (double)kNmRunning && ct + 1 < nm.max_evals[b] && ct + 1 < kNmMaxEvals;
+        cst[kChainGo] = go ? 1.0 : 0.0;
+      }
+    } else if constexpr (CHAIN) {
       if (lt == 0) {   // the accept / reject step of HX:505-535 on this proposal's value
         const ChainIO& ch = a.ch;
         const size_t at = (size_t)b * ch.T + ct;
@@ -647,7 +706,18 @@ chain_next:
       }
     }
   }
-  if constexpr (CHAIN) {
+  if constexpr (NM) {
+    __syncthreads();
+    const int go = __builtin_amdgcn_readfirstlane(cst[kChainGo] != 0.0);
+    ct += 1;
+    cfail += bad != 0;
+    if (go) goto chain_next;
+    const NmIO& nm = a.nm;
+    double* sg = nm.state + (size_t)b * nm.W;
+    for (int e = tid; e < nm.W; e += 256) sg[e] = cst[kNmState + e];
+    if (tid == 0) { nm.evals[b] = ct; nm.nfail[b] = cfail; }
+    return;
+  } else if constexpr (CHAIN) {
     __syncthreads();
     const int go = __builtin_amdgcn_readfirstlane(cst[kChainGo] != 0.0);
     cacc += __builtin_amdgcn_readfirstlane(cst[kChainAcc] != 0.0);
@@ -1373,6 +1443,20 @@ static void launch_chain(hipStream_t s, const RegArgs& a) {
   hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
 }
 
+// the search instances: the chain instances compiled with NM, one workgroup per search, the search's words behind the chain's
+template <int NB>
+static void launch_nm(hipStream_t s, const RegArgs& a) {
+  static unsigned long long attr_mask = 0;
+  once_per_device(attr_mask, [] {
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, 1, false, 0, false, false, true, true, false, true>, "small_reg_kernel<nm>");
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, 1, true, 0, false, false, true, true, false, true>, "small_reg_kernel<full, nm>");
+  });
+  const size_t lds = sizeof(double) * reg_nm_lds_doubles(NB, a.n, a.d, a.K);
+  void (*kernel)(RegArgs) = small_reg_kernel<16, NB, 1, false, 0, false, false, true, true, false, true>;
+  if (a.n == 16 * NB) kernel = small_reg_kernel<16, NB, 1, true, 0, false, false, true, true, false, true>;
+  hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
+}
+
 // the fit instances: the profiled-gradient sets instance compiled with FIT, one workgroup per start, the start's words behind
 // the instance's carve
 template <int NB>
@@ -1387,6 +1471,16 @@ static void launch_fit(hipStream_t s, const RegArgs& a) {
 }
 
 }  // namespace
+
+// ccgp_laplace_search_sets where small_route_nm says Reg: A searches, search a on training set set[a]; arrays as NmIO lays
+// them out; every pointer a device pointer
+void launch_small_reg_nm_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
+                              const int* set, int A, const NmIO& io) {
+  DrawView dv{nullptr, A, 2, d, KernelFamily{}};
+  RegArgs a = reg_args(Xs, n, d, ys, dv);
+  a.B = A; a.set = set; a.sigma2_set = sigma2; a.nm = io;
+  pick<1, 8>((n + 15) / 16, [&](auto nb) { launch_nm<decltype(nb)::value>(s, a); });
+}
 
 // ccgp_profile_fit_sets where small_route_fit says Reg: A starts, start a on training set set[a]; arrays as FitIO lays them
 // out; every pointer a device pointer

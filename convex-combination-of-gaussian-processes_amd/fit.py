@@ -666,6 +666,100 @@ def Metro_device(gp, start, N, samp_size, batch_size, alpha, D_train, sigma2, y,
     return r["chains"][0]
 
 
+def _twin_nm_segment(evaluate, owner, state, seg):
+    """What one launch of laplace_search_sets does, on the host twin: every search of `state` [A, W] (changed in place) takes
+    up to `seg` evaluations, all running searches' trial points in one evaluator call per step.  A search depends on its own
+    evaluations only, so the cut into steps changes no bit.  Returns evals[A]."""
+    A = state.shape[0]
+    evals = np.zeros(A, dtype=np.int64)
+    for _ in range(int(seg)):
+        live = np.flatnonzero(state[:, api.NM_CODE] == api.NM_RUNNING)
+        if live.size == 0:
+            break
+        val = np.asarray(evaluate(api.nm_trial(state[live]), owner[live])[0], dtype=np.float64)
+        for k, a in enumerate(live):
+            api.nm_feed(state[a], val[k])
+        evals[live] += 1
+    return evals
+
+
+def laplace_device_sets(gp, D_trains, ys, sigma2s, starts, theta1_pars=None, theta2_pars=None, hess_step=1e-3, maxiter=2000,
+                        on_device=True, seg=512, logpost_sets_fn=None):
+    """laplace_sets over the twin evaluator (ccgp_chain_logpost_sets) with the Nelder-Mead search itself on the device: one
+    launch of ccgp_laplace_search_sets carries every running search through up to `seg` evaluations (one workgroup per search:
+    the chain instance's evaluation, the step of laplace_sets restated in csrc/nm_logic.h), until none is running; then the
+    central-difference Hessian points of all sets go out as ONE ccgp_chain_logpost_sets call, as laplace_sets sends them.
+    The search asks for one value at a time -- the reflection, then what the reflected value calls for -- where laplace_sets
+    sends all four trial points of an iteration; its decisions are laplace_sets' decisions on the same values, so mode, var,
+    converged, value and iterations are laplace_sets' bits, and `evaluations` is the count laplace_sets charges (p + 1, + 4
+    per iteration, + p per shrink), which its maxiter rule reads.  starts is [C, p].
+    on_device=False runs the same driver with every evaluation through the twin and every step through ccgp_nm_feed: the
+    exact reference for the device search, and what the driver falls back to by itself where the device call says
+    CCGP_EUNSUPPORTED (n > 128, the Matern and spline families).  `logpost_sets_fn(rows, set_of) -> (val, beta)` replaces the
+    twin evaluator and keeps the search on the host.
+    Returns one dict per set with laplace_sets' keys, plus fed: the evaluations the search made, and calls: the launches the
+    set took part in + 1 (on the twin: its evaluator calls + 1)."""
+    starts = np.atleast_2d(np.asarray(starts, dtype=np.float64))
+    C, p = starts.shape
+    if C < 1 or len(D_trains) != C or len(ys) != C or len(sigma2s) != C:
+        raise ValueError("laplace_device_sets: one design, response, sigma2 and start per set, at least one set")
+    seg = int(seg)
+    if seg < 1 or seg > api.NM_MAX_EVALS:
+        raise ValueError("laplace_device_sets: seg must lie in 1 .. %d" % api.NM_MAX_EVALS)
+    if int(maxiter) < 0:
+        raise ValueError("laplace_device_sets: maxiter must not be negative")
+    device = bool(on_device) and logpost_sets_fn is None
+    if logpost_sets_fn is None:
+        logpost_sets_fn = _twin_sets_evaluator(gp, D_trains, ys, sigma2s, theta1_pars, theta2_pars)
+        q = 4 if gp.cfg["prior"] == api.PRIOR_ANI else 3
+        if p != q:
+            raise ValueError("laplace_device_sets: starts must be [C, %d] for this script" % q)
+
+    def evaluate(rows, set_of):
+        return logpost_sets_fn(np.asarray(rows), np.asarray(set_of, dtype=np.int64))
+
+    if device:
+        pars = _prior_pars(gp, theta1_pars, theta2_pars)
+        Xs = np.stack([np.asarray(D, dtype=np.float64) for D in D_trains])
+        Y = np.stack([np.asarray(y, dtype=np.float64).ravel() for y in ys])
+    owner = np.arange(C)
+    state = np.stack([api.nm_begin(x, 1e-6, 1e-9, maxiter) for x in starts])
+    calls = np.zeros(C, dtype=np.int64)
+    while True:
+        live = np.flatnonzero(state[:, api.NM_CODE] == api.NM_RUNNING)
+        if live.size == 0:
+            break
+        if device:
+            try:
+                r = gp.h.laplace_search_sets(Xs, Y, sigma2s, gp.cfg["prior"], owner[live], state[live], seg, pars)
+            except api.CcgpError as e:
+                if e.code != -4:   # CCGP_EUNSUPPORTED: this shape has no device search; the twin carries it
+                    raise
+                device = False
+                continue
+            state[live] = r["state"]
+            calls[live] += 1
+        else:
+            sub = state[live]
+            calls[live] += _twin_nm_segment(evaluate, owner[live], sub, seg)
+            state[live] = sub
+    modes = np.stack([api.nm_simplex(s)[0][0] for s in state])
+    var = _hessian_vars(lambda rows, set_of: evaluate(rows, set_of)[0], modes, hess_step)
+    return [dict(mode=modes[c].copy(), var=var[c], converged=bool(state[c, api.NM_CODE] == api.NM_CONVERGED),
+                 value=float(api.nm_simplex(state[c])[1][0]), iterations=int(state[c, api.NM_ITERATIONS]),
+                 evaluations=int(state[c, api.NM_CHARGED]), fed=int(state[c, api.NM_FED]), calls=int(calls[c]) + 1)
+            for c in range(C)]
+
+
+def laplace_device(gp, D_train, y, sigma2, start, theta1_pars=None, theta2_pars=None, hess_step=1e-3, maxiter=2000,
+                   on_device=True, seg=512, logpost_fn=None):
+    """laplace_device_sets' C = 1 case: one search on one training set -> its dict.  `logpost_fn(rows) -> (val, beta)`
+    replaces the twin evaluator (and keeps the search on the host)."""
+    fn = None if logpost_fn is None else (lambda rows, set_of: logpost_fn(rows))
+    return laplace_device_sets(gp, [D_train], [y], [sigma2], np.asarray(start, dtype=np.float64)[None], theta1_pars,
+                               theta2_pars, hess_step, maxiter, on_device, seg, fn)[0]
+
+
 def factors_frame(gp, start, N, samp_size, batch_size, alpha_geweke, D_train, sigma2, y_train,
                   net_samp_size, theta1_pars=None, theta2_pars=None, rng=None, speculate=0):
     """HX:625-644 without materialising R.Inv per draw: returns the retained posterior draws
@@ -1239,7 +1333,7 @@ def stack_tables(tables):
 def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size=None, start=None, sigma2s=None,
           theta1_pars=None, theta2_pars=None, rngs=None, max_proposals=None, speculate=0, laplace=None, cgp=False,
           single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None, lockstep_fits=True,
-          device_chains=False, device_fits=False):
+          device_chains=False, device_fits=False, device_laplace=False):
     """The reference's simulation study (GV:689-762 declares nine training sets and fits one): every set of `sets` -- a list
     of (D_train, y_train, D_test, y_test) -- fitted and compared, the sets of one shape (n, d) in lockstep.  Per group:
     sigma2 per set from ordinary_kriging_fit (or sigma2s[i] as given), then laplace_sets and Metro_sets with one generator
@@ -1263,6 +1357,9 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     device_fits (default off): the sigma2 / single-GP fits of each group go through ordinary_kriging_fit_device_sets -- the
     quasi-Newton iteration resident on the device, every start of every set in one launch -- with that function's own
     contract (the same method and optimum as ordinary_kriging_fit_sets, not its bits).
+    device_laplace (default off): the Laplace stage of each group goes through laplace_device_sets -- the Nelder-Mead search
+    resident on the device, every set's search in one launch, over the twin evaluator.  Its estimates are laplace_sets' over
+    that evaluator bit for bit, so with device_chains=True the tables are those of device_chains=True alone.
     Returns dict(tables, summaries, pooled: comparison_summary of the stacked tables, sigma2, draws, beta, chains,
     groups: {(n, d): indices}, calls and seconds: device calls and wall time of the sigma2, single, cgp, laplace, metro and
     predict parts; per set the single and cgp fits happen inside compare_GP, so their seconds are part of predict's and
@@ -1360,8 +1457,14 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
             return fn(rows, set_of)
 
         t0 = time.perf_counter()
-        ests = [laplace[i] for i in idx] if laplace is not None else \
-            laplace_sets(lambda rows, set_of: counted(rows, set_of)[0], starts[idx])
+        if laplace is not None:
+            ests = [laplace[i] for i in idx]
+        elif device_laplace:
+            ests = laplace_device_sets(gp, D_trains, ys, g_s2, starts[idx], theta1_pars, theta2_pars,
+                                       logpost_sets_fn=fn if logpost_sets_fn is not None else None)
+            count["n"] = max(e["calls"] for e in ests)
+        else:
+            ests = laplace_sets(lambda rows, set_of: counted(rows, set_of)[0], starts[idx])
         secs["laplace"] += time.perf_counter() - t0
         calls["laplace"] += count["n"]
         t0 = time.perf_counter()

@@ -409,6 +409,54 @@ int ccgp_profile_fit_sets(ccgp_handle* h, const double* Xs, int n, int d, const 
                           const int* set /* A */, double* state /* A x W, in and out */, const int* max_evals /* A */,
                           int* out_evals /* A */, double* trace_f, int* trace_status /* A x T, both or neither */, int T);
 
+/* ---- the Laplace search on the device: every set's Nelder-Mead in one launch (LearnBayes::laplace, HX:493) -----------------------
+ * The Nelder-Mead search of the Python package's fit.laplace_sets for one set (coefficients 1, 2, 1/2, 1/2; the initial simplex
+ * x[k] -> (1.0 + 0.05) x[k], or 0.00025 where x[k] is zero; converged where every |x_v - x_0| <= xatol and every
+ * |f_0 - f_v| <= fatol; a non-finite value counts as -1e300) restated from exactly rounded operations (csrc/nm_logic.h), so
+ * that host and device step a search to the same bits, and advanced ONE evaluation at a time: reflection first, then the
+ * expansion or the contraction the reflected value calls for, the shrink points only where the contraction fails.  One
+ * search's state is a flat array of W = ccgp_nm_state_doubles(q) = q^2 + 5 q + 18 doubles:
+ *   [0] q  [1] code  [2] phase  [3] vertex (of the initial-simplex and shrink phases)  [4] iterations
+ *   [5] charged: the evaluations laplace_sets counts for this search (q + 1, + 4 per iteration, + q per shrink); the maxiter
+ *       rule reads it  [6] fed: the evaluations actually made  [7] maxiter  [8] xatol  [9] fatol
+ *   [10] expansions taken  [11] expansions refused  [12] plain reflections  [13] outside contractions taken
+ *   [14] inside contractions taken  [15] shrinks
+ *   then the simplex ((q + 1) x q, vertex-major, best first once sorted) | the negated values (q + 1) | xbar (q) | the
+ *   reflected point (q) | its negated value (1) | trial (q).
+ *   code: 0 running, 1 converged, 2 maxiter (iterations >= maxiter or charged >= maxiter, tested after the convergence test,
+ *   once the initial simplex is sorted and after every iteration's sort).  phase: 0 initial simplex, 1 reflection, 2 expansion,
+ *   3 outside contraction, 4 inside contraction, 5 shrink.  While the code is 0, `trial` is the next point to evaluate; the
+ *   mode is simplex vertex 0 and its value minus negated value 0.
+ * ccgp_nm_begin fills a state from a start x0 (laplace_sets uses xatol = 1e-6, fatol = 1e-9) with `trial` = x0;
+ * ccgp_nm_feed hands it the log-posterior at `trial` and returns the new code.  Host only, no handle; CCGP_EINVAL for q outside
+ * 1 .. 8, a NULL pointer, maxiter < 0, or (feed) a state whose recorded q is not q.
+ * ccgp_laplace_search_sets runs A searches, search a on training set set[a] (Xs, ys, sigma2, C, prior_id, prior_pars as in
+ * ccgp_chain_logpost_sets; q = 3, or 4 for CCGP_PRIOR_ANI), on the device: one workgroup carries one search from its state
+ * through up to max_evals[a] evaluations -- the portable terms of `trial`, the likelihood, val = ll + ljac + lprior, the step of
+ * ccgp_nm_feed -- and writes the state back, so the next call continues it.  out_evals[a] is the number of evaluations made.
+ * The trace (both or neither, [a T + t]): val and the pivot status of evaluation t of this call; NaN / -1 beyond out_evals[a].
+ *   Bits.  Every evaluation has the bits ccgp_chain_logpost_sets gives that point on that set.  A search driven evaluation by
+ *     evaluation through ccgp_chain_logpost_sets and ccgp_nm_feed leaves the same state and trace, bit for bit.
+ *   Independence.  A search depends on its own inputs only: not on A, its position, the other searches' sets, what the handle
+ *     ran before, or how its evaluations are cut into calls by max_evals.
+ *   Failure.  A failed factorisation is a non-finite value (NaN in the trace, its 1-based pivot in the status): the search
+ *     goes on.  The return value is the number of evaluations whose factorisation failed, over all searches.
+ *   Arguments.  CCGP_EINVAL before anything is copied or launched, outputs untouched: bad shapes, an unknown prior (prior_pars
+ *     as ccgp_logpost_batch), C < 1, A < 0, T < 0, set[a] outside 0 .. C-1, max_evals[a] outside 0 .. min(T, 4096), a partial
+ *     trace, a NULL required pointer (everything but the trace and prior_pars), a state whose recorded q is not the prior's.
+ *     CCGP_EUNSUPPORTED, outputs untouched, where ccgp_metro_segments_sets has no route or the search's words do not fit
+ *     behind its carve: n > 128, the Matern and spline families.  A == 0 returns CCGP_OK.  A search that is not running, or
+ *     whose max_evals is 0, is returned as it came.
+ * Host pointers only, blocking; ccgp_reserve does not cover the staging.  Not in this version: the Hessian points inside the
+ * launch, _dev variants, a ccgp_multi wrapper, an R shim. */
+int ccgp_nm_state_doubles(int q);
+int ccgp_nm_begin(double* state, int q, const double* x0, double xatol, double fatol, int maxiter);
+int ccgp_nm_feed(double* state, int q, double val);
+int ccgp_laplace_search_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                             int prior_id, const double* prior_pars, int A, const int* set /* A */,
+                             double* state /* A x W, in and out */, const int* max_evals /* A */, int* out_evals /* A */,
+                             double* trace_val, int* trace_status /* A x T, both or neither */, int T);
+
 /* ---- a9: likeli.hyperpars HX:549-575 / choose.hyperpars HX:584-595, ADV:552-599 -------
  * hyper is G x 4 (alpha1 beta1 alpha2 beta2).  For each row: N base-2 Halton quantiles
  * u_j, p = u_j, theta1 = qigamma(u_j, a1, b1), theta2 = qigamma(u_j, a2, b2), mode-1
