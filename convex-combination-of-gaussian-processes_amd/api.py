@@ -85,6 +85,8 @@ SIGNATURES = {
                                    c_double, c_int, c_double, _dp, _ip, _dp]),
     "ccgp_mixed_logdet_designs": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, _dp, _ip]),
     "ccgp_mixed_logdet_grad_designs": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, c_int, _dp, _dp, _ip]),
+    "ccgp_design_fit_eval": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, c_double, _dp, c_int, _dp, _dp, _ip]),
+    "ccgp_design_fit": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, c_double, c_int, _dp, _ip, _ip, _dp, _ip, c_int]),
     "ccgp_halton_base2": (c_int, [c_int, _dp]),
     "ccgp_qigamma": (c_int, [_dp, c_int, c_double, c_double, _dp]),
     "ccgp_predict_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, _dp, c_int,
@@ -994,6 +996,55 @@ class Handle:
         st = np.zeros(B, dtype=np.int32)
         self._chk(lib().ccgp_mixed_logdet_grad_designs(self._h, _p(Xs), n, d, B, K, _p(row), nf, _p(out), _p(g), _ipt(st)))
         return out, g.reshape(B, d, n - nf).transpose(0, 2, 1), st
+
+    @staticmethod
+    def _design_fit_shared(D_old, d, K, params_row):
+        """The inputs every start of a design search shares: D_old [n_fixed, d] or None -> (column-major copy or None, n_fixed,
+        the parameter row)."""
+        old = None if D_old is None else np.asarray(D_old, dtype=np.float64).reshape(-1, d)
+        nf = 0 if old is None else old.shape[0]
+        if nf == 0:
+            old = None
+        else:
+            old = np.ascontiguousarray(np.asfortranarray(old).ravel(order="F"))
+        return old, nf, _f(params_row, (K + K * d,))
+
+    def design_fit_eval(self, x, K, params_row, D_old=None, ld_offset=0.0):
+        """ccgp_design_fit_eval: the design search's objective at the points x [B, n_free, d] (the free rows of B designs;
+        D_old [n_fixed, d] or None is the fixed batch on top of each) -- f = -(log det R - ld_offset), g = -(d log det R / d x)
+        -- the host twin of design_fit's evaluation.  Returns (f[B], g[B, n_free, d], status[B])."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+        B, nfree, d = x.shape
+        old, nf, row = self._design_fit_shared(D_old, d, K, params_row)
+        f = np.empty(B)
+        g = np.empty((B, nfree, d))
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_design_fit_eval(self._h, _p(old), nf, nf + nfree, d, K, _p(row), float(ld_offset), _p(x), B, _p(f),
+                                             _p(g), _ipt(st)))
+        return f, g, st
+
+    def design_fit(self, n_free, d, K, params_row, state, max_evals, D_old=None, ld_offset=0.0, trace=False, T=None):
+        """ccgp_design_fit: A starts of the design search (n_free free rows of d dimensions each under D_old [n_fixed, d] or
+        None), stepped on the device from state [A, W] (api.fit_begin at the raveled start) through up to max_evals[a]
+        evaluations each.  Returns dict(state [A, W], evals[A], failed: evaluations whose elimination failed, and with
+        trace=True trace_f, trace_status [A, T], T = max(max_evals) unless given)."""
+        state = np.ascontiguousarray(np.atleast_2d(np.asarray(state, dtype=np.float64))).copy()
+        A = state.shape[0]
+        nfree, d = int(n_free), int(d)
+        old, nf, row = self._design_fit_shared(D_old, d, K, params_row)
+        max_evals = np.ascontiguousarray(np.broadcast_to(np.asarray(max_evals), (A,)).astype(np.int32))
+        if T is None:
+            T = int(max_evals.max()) if A else 0
+        if state.shape[1] != FIT_HEADER + 16 * nfree * d:
+            raise ValueError("state must be [A, %d] for %d free rows of %d dimensions" % (FIT_HEADER + 16 * nfree * d, nfree, d))
+        evals = np.zeros(A, dtype=np.int32)
+        tr_f, tr_st = (np.full((A, T), np.nan), np.full((A, T), -1, dtype=np.int32)) if trace else (None, None)
+        failed = self._chk(lib().ccgp_design_fit(self._h, _p(old), nf, nf + nfree, d, K, _p(row), float(ld_offset), A, _p(state),
+                                                 _ipt(max_evals), _ipt(evals), _p(tr_f), _ipt(tr_st), int(T)))
+        out = dict(state=state, evals=evals, failed=failed)
+        if trace:
+            out.update(trace_f=tr_f, trace_status=tr_st)
+        return out
 
     # -- a10 + a11 -------------------------------------------------------------------------
     def predict_batch(self, X, y, K, params, Xtest, sigma2):

@@ -1703,6 +1703,102 @@ int ccgp_profile_fit_sets(ccgp_handle* h, const double* Xs, int n, int d, const 
   return failed;
 } CCGP_GUARD_END(h)
 
+// ---- the maximum-entropy design search on the device (ccgp.h) ----------------------------------------------------------------------
+// the host twin of the design-search kernel's evaluation: ccgp_mixed_logdet_grad_designs on the designs (D_old on top of the
+// free rows of block b of x), then f = -(ld - ld_offset), g = -grad in variable order
+int ccgp_design_fit_eval(ccgp_handle* h, const double* D_old, int n_fixed, int n, int d, int K, const double* params,
+                         double ld_offset, const double* x, int B, double* out_f, double* out_g, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || n_fixed < 0 || n_fixed >= n || (n_fixed > 0 && !D_old) || !params || B < 0 || !x || !out_f || !out_g)
+    return fail(h, CCGP_EINVAL, "ccgp_design_fit_eval: bad argument");
+  if (B == 0) return CCGP_OK;
+  const int nfree = n - n_fixed;
+  const size_t sB = B, nd = (size_t)n * d, nv = (size_t)nfree * d;
+  std::vector<double> Xs(sB * nd), ld(sB), grad(sB * nv);
+  std::vector<int> st(sB);
+  for (size_t b = 0; b < sB; ++b)
+    for (int k = 0; k < d; ++k) {
+      double* col = Xs.data() + b * nd + (size_t)k * n;
+      for (int i = 0; i < n_fixed; ++i) col[i] = D_old[i + (size_t)k * n_fixed];
+      for (int i = 0; i < nfree; ++i) col[n_fixed + i] = x[b * nv + (size_t)i * d + k];
+    }
+  const int rc = ccgp_mixed_logdet_grad_designs(h, Xs.data(), n, d, B, K, params, n_fixed, ld.data(), grad.data(), st.data());
+  if (rc < 0) return rc;
+  for (size_t b = 0; b < sB; ++b) {
+    out_f[b] = design_fit_value(ld[b], ld_offset);
+    if (status) status[b] = st[b];
+    for (int i = 0; i < nfree; ++i)
+      for (int k = 0; k < d; ++k) out_g[b * nv + (size_t)i * d + k] = design_fit_grad(grad[b * nv + i + (size_t)k * nfree]);
+  }
+  return rc;
+} CCGP_GUARD_END(h)
+
+int ccgp_design_fit(ccgp_handle* h, const double* D_old, int n_fixed, int n, int d, int K, const double* params,
+                    double ld_offset, int A, double* state, const int* max_evals, int* out_evals, double* trace_f,
+                    int* trace_status, int T) try {
+  if (!h) return CCGP_EINVAL;
+  bool ok = !bad_shape(n, d, K) && n_fixed >= 0 && n_fixed < n && (n_fixed == 0 || D_old) && params && A >= 0 && T >= 0 &&
+            state && max_evals && out_evals && (trace_f != nullptr) == (trace_status != nullptr);
+  const long long nvl = ok ? (long long)(n - n_fixed) * d : 0;
+  const bool steppable = nvl >= 1 && nvl <= kMaxD;   // beyond it no state exists to check: the route refuses below
+  const int nv = steppable ? (int)nvl : 0, W = steppable ? fit_state_doubles(nv) : 0;
+  const int cap = T < 4096 ? T : 4096;
+  for (int a = 0; ok && a < A; ++a)
+    ok = max_evals[a] >= 0 && max_evals[a] <= cap && (!steppable || fit_state_ok(state + (size_t)a * W, nv));
+  if (!ok) return fail(h, CCGP_EINVAL, "ccgp_design_fit: bad argument");
+  if (small_route_design_fit(h->fam.id == 0, n, d, K, n_fixed) != Route::Reg)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_design_fit: the search runs on the device for Gaussian designs of n <= 128 with at "
+                                      "most 64 free coordinates whose design-gradient instance fits; keep it on "
+                                      "ccgp_design_fit_eval");
+  if (A == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  const size_t sA = A, sT = (size_t)A * T, nold = (size_t)n_fixed * d;
+  const bool tr = trace_f != nullptr && T > 0;
+  double *dold = nullptr, *dp;
+  int *dmax, *dcnt;
+  DesignFitIO io{};
+  io.W = W; io.T = T; io.ld_offset = ld_offset;
+  // inputs back to back, then results back to back: each side crosses PCIe as one span (the state is both)
+  if (int rc = stage(h, [&](Layout& c) {
+        dold = nold ? c.take<double>(nold) : nullptr;
+        dp = c.take<double>(P);
+        dmax = c.take<int>(sA);
+        io.state = c.take<double>(sA * W);
+        dcnt = c.take<int>(2 * sA);   // evaluations | failed
+        io.tr_f = tr ? c.take<double>(sT) : nullptr;
+        io.tr_status = tr ? c.take<int>(sT) : nullptr;
+      }))
+    return rc;
+  io.D_old = dold;
+  io.max_evals = dmax;
+  io.evals = dcnt;
+  io.nfail = dcnt ? dcnt + sA : nullptr;
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, dp, 1, K, d, &dv)) return frc;
+  if (int prc = push(h, {piece(dold, D_old, nold), piece(dp, params, P), piece(dmax, max_evals, sA),
+                         piece(io.state, state, sA * W)}))
+    return prc;
+  if (tr) {   // a start that stops early leaves the rest of its trace as it is: NaN / -1, not what the buffer held
+    CCGP_HIP(hipMemsetAsync(io.tr_f, 0xFF, Layout::al(sT * sizeof(double)) + Layout::al(sT * sizeof(int)), h->stream));
+  }
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    launch_small_reg_design_fit(h->stream, n, d, dv, n_fixed, A, io);
+    CCGP_LAUNCH_CHECK();
+  }
+  std::vector<int> cnt(2 * sA);
+  if (int rc = pull(h, {piece(io.state, state, sA * W), piece(dcnt, cnt.data(), 2 * sA), piece(io.tr_f, trace_f, tr ? sT : 0),
+                        piece(io.tr_status, trace_status, tr ? sT : 0)}))
+    return rc;
+  int failed = 0;
+  for (int a = 0; a < A; ++a) {
+    out_evals[a] = cnt[a];
+    failed += cnt[sA + a];
+  }
+  return failed;
+} CCGP_GUARD_END(h)
+
 // ---- the Laplace search on the device (ccgp.h) ----------------------------------------------------------------------------------
 int ccgp_nm_state_doubles(int q) { return q >= 1 && q <= kNmMaxQ ? nm_state_doubles(q) : CCGP_EINVAL; }
 

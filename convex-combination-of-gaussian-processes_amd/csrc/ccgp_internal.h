@@ -247,6 +247,21 @@ struct FitIO {
 };
 void launch_small_reg_fit_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set, int A,
                                const FitIO& io);
+// the maximum-entropy design search on the device (ccgp_design_fit where small_route_design_fit says Reg): what start a =
+// workgroup a of A reads and leaves, every pointer a device pointer.  D_old: the n_fixed fixed rows every start shares
+// (n_fixed x d column-major, not read where n_fixed == 0); state [A][W] in and out (fit_logic.h with d = nv), max_evals /
+// evals / nfail [A], the trace [A][T], both or none
+struct DesignFitIO {
+  const double* D_old;
+  double ld_offset;
+  double* state;
+  int W, T;
+  const int* max_evals;
+  int *evals, *nfail;
+  double* tr_f;
+  int* tr_status;
+};
+void launch_small_reg_design_fit(hipStream_t s, int n, int d, DrawView dv, int n_fixed, int A, const DesignFitIO& io);
 // the Laplace search on the device (ccgp_laplace_search_sets where small_route_nm says Reg): what search a = workgroup a of A
 // reads and leaves, every pointer a device pointer.  state [A][W] in and out (nm_logic.h), max_evals / evals / nfail [A], the
 // trace [A][T], both or none

@@ -308,4 +308,18 @@ CCGP_CHAIN_HD inline double fit_grad(double g_theta, double theta) {
   return v == v ? v : chain_from_bits(0x7ff8000000000000ULL);
 }
 
+// ---- the objective of the maximum-entropy design search (rsurface.Entropy_optim / Batch_Entropy_optim) ----------------------
+// The iterate is the design itself, so nothing is transformed: f = -(ld - ld_offset) (ld_offset = log det R(D.old) of the
+// batch form, 0 otherwise) and g_v = -(d ld / d x_v), each one exactly rounded operation and a sign; a failed elimination's
+// NaN is the one quiet NaN on both sides
+CCGP_CHAIN_HD inline double design_fit_value(double ld, double ld_offset) {
+#pragma clang fp contract(off)
+  const double v = -(ld - ld_offset);
+  return v == v ? v : chain_from_bits(0x7ff8000000000000ULL);
+}
+CCGP_CHAIN_HD inline double design_fit_grad(double g_x) {
+  const double v = -g_x;
+  return v == v ? v : chain_from_bits(0x7ff8000000000000ULL);
+}
+
 }  // namespace ccgp

@@ -301,5 +301,22 @@ inline Route small_route_nm(bool gauss, int n, int d, int K) {
   if (small_route_chain(gauss, n, d, K) != Route::Reg) return Route::Unsupported;
   return lds_fits(reg_nm_lds_doubles((n + 15) / 16, n, d, K)) ? Route::Reg : Route::Unsupported;
 }
+// the maximum-entropy design search on the device (ccgp_design_fit): the DFIT instances are the design-gradient instances
+// (INV = 3, per-design carve), one workgroup per start.  A start's variables are the free rows of its design in the order
+// numpy ravels [n - n_fixed, d]: nv = (n - n_fixed) d, variable v = i d + k is free row i, dimension k.  Nothing is
+// transformed between the iterate and the design, so there are no exp tables: the start's words behind the carve are
+//   go | ld | grad[nv] | state[fit_state_words(nv)]
+// (go: the word the whole workgroup reads after its barrier), sized from the actual nv
+inline size_t reg_design_fit_lds_doubles(int NB, int n, int d, int K, int nv) {
+  return reg_lds_doubles(16, NB, NB + 1, true, true, n, d, K) + 2 + nv + fit_state_words(nv);
+}
+// Reg exactly where the design gradient has its route, the start is one the stepper takes (1 <= nv <= kMaxD: its state and
+// fit_sum's stated order end there) and the words fit; Unsupported otherwise: the caller keeps the search on the host twin
+inline Route small_route_design_fit(bool gauss, int n, int d, int K, int n_fixed) {
+  if (!gauss || n_fixed < 0 || n_fixed >= n || small_route(Op::DesignGrad, gauss, n, d, K) != Route::Reg) return Route::Unsupported;
+  const long long nv = (long long)(n - n_fixed) * d;
+  if (nv < 1 || nv > kMaxD) return Route::Unsupported;
+  return lds_fits(reg_design_fit_lds_doubles((n + 15) / 16, n, d, K, (int)nv)) ? Route::Reg : Route::Unsupported;
+}
 
 }  // namespace ccgp

@@ -77,6 +77,11 @@ static_assert(nm_state_doubles(kNmLdsQ) == nm_state_words(kNmLdsQ) && nm_state_d
               "small_layout.h sizes the search's words");
 constexpr int kNmMaxEvals = 4096;   // evaluations of one search in one call (ccgp.h)
 
+// the start's words of the DFIT instances behind the instance's per-design carve: go | ld | grad[nv] | state[W(nv)]
+// (small_layout.h: reg_design_fit_lds_doubles; go is the decision thread 0 publishes, 0.0 or 1.0)
+enum { kDfGo = 0, kDfLd, kDfGrad };
+constexpr int kDfMaxEvals = 4096;   // evaluations of one start in one call (ccgp.h)
+
 struct RegArgs {
   const double* X;
   const double* y;
@@ -118,6 +123,7 @@ struct RegArgs {
   ChainIO ch;          // CHAIN instantiations only
   FitIO fit;           // FIT instantiations only
   NmIO nm;             // NM instantiations only
+  DesignFitIO dfit;    // DFIT instantiations only
 };
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
@@ -199,8 +205,16 @@ __device__ __forceinline__ void mat_sync() {
 // publishes one word, and after one barrier every thread reads it.  The trip count is bounded by max_evals[a] <= 4096; no
 // path waits on another workgroup.  A failed factorisation is a non-finite value: the search goes on.  On exit the state
 // goes back to HBM.
+// DFIT: a start of the maximum-entropy design search per workgroup (ccgp_design_fit): the design-gradient instance (INV = 3)
+// evaluating again and again.  The shared parameter row, the fixed rows D.old and the start's state (fit_logic.h, d = nv) are
+// loaded once; then, per evaluation, all threads scatter the state's `trial` into the free rows of xs, generation, sweep with
+// identity rows, reductions and the two-pass gradient epilogue run as they are -- the operations of the single call in its
+// order, hence the bits ccgp_mixed_logdet_grad_designs gives that design -- with log det and the gradient (in variable order)
+// left in LDS; thread 0 forms f = -(ld - ld_offset) and g = -grad, runs fit_feed, writes the trace and publishes one word,
+// and after one barrier every thread reads it.  The trip count is bounded by max_evals[a] <= 4096; no path waits on another
+// workgroup.  On exit the state goes back to HBM.
 template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false,
-          bool CHAIN = false, bool FIT = false, bool NM = false>
+          bool CHAIN = false, bool FIT = false, bool NM = false, bool DFIT = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
@@ -211,6 +225,7 @@ void small_reg_kernel(RegArgs a) {
   static_assert(!CHAIN || (SETS && G == 16 && NE == 1 && !INV && !PROF && !FAC), "a chain is the sets likelihood instance on the 16 x 16 grid");
   static_assert(!FIT || (SETS && PROF && INV == 2 && !CHAIN), "a fit is the profiled-gradient sets instance");
   static_assert(!NM || CHAIN, "a Laplace search is a chain instance with another step");
+  static_assert(!DFIT || (INV == 3 && G == 16 && !PROF && !SETS && !CHAIN && !FIT), "a design search is the design-gradient instance, one workgroup per start");
   constexpr int TPM = G * G;       // threads per matrix
   constexpr int MPW = 256 / TPM;   // matrices per workgroup
   constexpr int NP = G * NB;       // padded order
@@ -300,8 +315,27 @@ void small_reg_kernel(RegArgs a) {
     }
     for (int e = tid; e < fi.W; e += 256) fst[kFitState + e] = sg[e];
   }
+  // DFIT: evaluations made and eliminations failed so far in this call (uniform over the workgroup), the start's words
+  double* dfs = nullptr;
+  int dft = 0, dffail = 0;
+  if constexpr (DFIT) {
+    dfs = smem + cv.xs_own + (size_t)d * n;   // behind the per-design carve
+    const DesignFitIO& df = a.dfit;
+    const double* sg = df.state + (size_t)b * df.W;
+    // a start that is not running, or has no evaluations to make, stays as it came (every thread reads the same words)
+    if (df.max_evals[b] <= 0 || sg[kFitCode] != (double)kFitRunning) {
+      if (tid == 0) { df.evals[b] = 0; df.nfail[b] = 0; }
+      return;
+    }
+    for (int e = tid; e < df.W; e += 256) dfs[kDfGrad + (n - a.n_fixed) * d + e] = sg[e];
+  }
   int st = 0;   // SETS: this evaluation's training set
-  if constexpr (SETS) {
+  if constexpr (DFIT) {
+    // the fixed rows every start shares; the free rows come from the state's trial point, evaluation by evaluation
+    xs = smem + cv.xs_own;
+    const int nf = a.n_fixed;
+    for (int e = tid; e < nf * d; e += 256) xs[(e / nf) * n + e % nf] = a.dfit.D_old[e];
+  } else if constexpr (SETS) {
     // a matrix's threads are whole waves on both grids: the set index is wave-uniform, and saying so keeps it -- and the
     // addresses formed from it -- in scalar registers across the generation phase
     st = __builtin_amdgcn_readfirstlane(a.set[b]);
@@ -324,7 +358,14 @@ void small_reg_kernel(RegArgs a) {
   } else {
     __syncthreads();   // the tables, the start state and the design are in LDS
   }
+  if constexpr (DFIT) __syncthreads();   // the start's state is in LDS
 chain_next:
+  if constexpr (DFIT) {
+    // variable v = i d + k of the trial point is free row i, dimension k
+    const int nf = a.n_fixed, nv = (n - nf) * d;
+    const double* trial = fit_trial(dfs + kDfGrad + nv, nv);
+    for (int e = tid; e < nv; e += 256) xs[(e % d) * n + nf + e / d] = trial[e];
+  }
   if constexpr (NM) {
     if (tid < 64) {   // wave 0, every lane the same arithmetic; lane 0 writes
       const NmIO& nm = a.nm;
@@ -484,7 +525,7 @@ chain_next:
       const int ridx = ty + G * e;
       double v = 0.0;
       if (FULL || c < n) {
-        if (ridx == 0) v = SETS ? a.y[(size_t)st * n + c] : a.y[c];
+        if (ridx == 0) v = DFIT ? 0.0 : SETS ? a.y[(size_t)st * n + c] : a.y[c];   // (a design search has no response)
         else if (ridx == 1) v = 1.0;
         else if (INV) v = (ridx - 2 == c) ? 1.0 : 0.0;   // identity rows: row 2 + t = e_t'
         else if (NE > 1 && t0 + ridx - 2 < a.m) {
@@ -506,7 +547,7 @@ chain_next:
   // ---- L' D L'^T on registers; one column broadcast through LDS per step ------------------------
   int bad = 0, cur = 0;
   // a bare log-determinant (entropy criteria, BSQ:856-877: the reference calls det(), nothing can "fail") keeps 0
-  const double ptol = a.logdet ? 0.0 : pivot_tolerance(a.mode, n);
+  const double ptol = (DFIT || a.logdet) ? 0.0 : pivot_tolerance(a.mode, n);
 #pragma unroll
   for (int kb = 0; kb < NB; ++kb) {
 #pragma unroll 1
@@ -633,6 +674,9 @@ chain_next:
     if (bad) { ll = kNaN; beta = kNaN; }
     if constexpr (FIT) {
       if (lt == 0) fst[kFitLl] = ll;
+    }
+    if constexpr (DFIT) {
+      if (lt == 0) dfs[kDfLd] = bad ? kNaN : logdet;
     }
     if (lt == 0) {
       slack[0] = beta;      // for the epilogues
@@ -950,12 +994,44 @@ chain_next:
               }
             }
           }
-        if (valid) {
+        if constexpr (DFIT) {
+          // the same values, in variable order, for thread 0
+#pragma unroll
+          for (int k = 0; k < KC; ++k)
+            if (k0 + k < d) dfs[kDfGrad + (i - nf) * d + k0 + k] = bad ? kNaN : -4.0 * rsw * acc[k];
+        } else if (valid) {
           double* g = a.dgrad + (size_t)b * nfree * d;
 #pragma unroll
           for (int k = 0; k < KC; ++k)
             if (k0 + k < d) g[(i - nf) + (size_t)(k0 + k) * nfree] = bad ? kNaN : -4.0 * rsw * acc[k];
         }
+      }
+      if constexpr (DFIT) {
+        __syncthreads();   // log det and the gradient row are in LDS: thread 0 takes the step of design._Start.feed
+        const DesignFitIO& df = a.dfit;
+        const int nv = nfree * d;
+        if (tid == 0) {
+          double* sw_ = dfs + kDfGrad + nv;
+          double* gx = dfs + kDfGrad;
+          const double f = design_fit_value(dfs[kDfLd], df.ld_offset);
+          for (int v = 0; v < nv; ++v) gx[v] = design_fit_grad(gx[v]);
+          if (df.tr_f) {
+            const size_t at = (size_t)b * df.T + dft;
+            df.tr_f[at] = f;
+            df.tr_status[at] = bad;
+          }
+          fit_feed(sw_, f, gx, bad == 0);
+          const int go = sw_[kFitCode] == (double)kFitRunning && dft + 1 < df.max_evals[b] && dft + 1 < kDfMaxEvals;
+          dfs[kDfGo] = go ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        const int go = __builtin_amdgcn_readfirstlane(dfs[kDfGo] != 0.0);
+        dft += 1;
+        dffail += bad != 0;
+        if (go) goto chain_next;
+        double* sg = df.state + (size_t)b * df.W;
+        for (int e = tid; e < df.W; e += 256) sg[e] = dfs[kDfGrad + nv + e];
+        if (tid == 0) { df.evals[b] = dft; df.nfail[b] = dffail; }
       }
     }
     if constexpr (FIT) {
@@ -1470,7 +1546,29 @@ static void launch_fit(hipStream_t s, const RegArgs& a) {
   hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
 }
 
+// the design-search instances: the design-gradient instance compiled with DFIT, one workgroup per start, the start's words
+// behind the instance's per-design carve
+template <int NB>
+static void launch_dfit(hipStream_t s, const RegArgs& a) {
+  static unsigned long long attr_mask = 0;
+  void (*kernel)(RegArgs) = small_reg_kernel<16, NB, NB + 1, false, 3, false, false, false, false, false, false, true>;
+  once_per_device(attr_mask, [] {
+    raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, 3, false, false, false, false, false, false, true>,
+                    "small_reg_kernel<design fit>");
+  });
+  const size_t lds = sizeof(double) * reg_design_fit_lds_doubles(NB, a.n, a.d, a.K, (a.n - a.n_fixed) * a.d);
+  hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
+}
+
 }  // namespace
+
+// ccgp_design_fit where small_route_design_fit says Reg: A starts sharing the parameter row of dv and the fixed rows of io;
+// arrays as DesignFitIO lays them out; every pointer a device pointer
+void launch_small_reg_design_fit(hipStream_t s, int n, int d, DrawView dv, int n_fixed, int A, const DesignFitIO& io) {
+  RegArgs a = reg_args(nullptr, n, d, nullptr, dv);   // no design array: the free rows come from the states
+  a.B = A; a.x_stride = (size_t)n * d; a.shared_params = 1; a.n_fixed = n_fixed; a.dfit = io;
+  pick<1, 8>((n + 15) / 16, [&](auto nb) { launch_dfit<decltype(nb)::value>(s, a); });
+}
 
 // ccgp_laplace_search_sets where small_route_nm says Reg: A searches, search a on training set set[a]; arrays as NmIO lays
 // them out; every pointer a device pointer

@@ -227,6 +227,79 @@ def minimize_starts(evaluate, starts, lower=-1.0, upper=1.0, m=5, maxit=100, fac
                 calls=calls, calls_per_start=per_start)
 
 
+_FIT_MESSAGES = ("", "CONVERGENCE: REL_REDUCTION_OF_F <= FACTR*EPSMCH", "CONVERGENCE: NORM OF PROJECTED GRADIENT <= PGTOL",
+                 "NEW_X: maxit reached", "ABNORMAL_TERMINATION_IN_LNSRCH", "the start itself cannot be evaluated")
+
+
+def minimize_starts_device(handle, starts, K, params_row, D_old=None, ld_offset=0.0, lower=-1.0, upper=1.0, maxit=100,
+                           factr=1e7, pgtol=0.0, max_backtracks=30, on_device=True, seg=512, evaluate=None):
+    """minimize_starts for the design criterion with the iteration itself on the device: the objective is
+    f = -(log det R(D_old U x) - ld_offset) under the parameter row params_row (K components), and one launch of
+    ccgp_design_fit carries every running start through up to `seg` evaluations (one workgroup per start: the design-gradient
+    instance, the step of _Start restated in csrc/fit_logic.h with memory 5) until none is running.  starts: [S, n_free, d];
+    lower / upper: a scalar or one array of the shape of a start.
+
+    The iterate is the design, so nothing lies between the stepper and the evaluator: x, f, converged, iterations, message
+    and calls_per_start are, bit for bit, what minimize_starts returns over handle.mixed_logdet_grad_designs with
+    f = -(ld - ld_offset), g = -grad.  `calls` counts device calls: launches, or on the twin the evaluator calls.
+
+    on_device=False drives the same states through the host twin -- every evaluation through ccgp_design_fit_eval (or through
+    `evaluate`, minimize_starts' evaluator, where one is given), every step through ccgp_fit_feed -- and leaves the same
+    states; the driver falls back to it by itself where the device call says CCGP_EUNSUPPORTED and the evaluator still serves
+    the shape (a design-gradient carve that has no room for the start's words).  Beyond 64 free coordinates no such state
+    exists: minimize_starts runs over the same evaluator.  Where the evaluator itself refuses (n > 128, the Matern and spline
+    families) its error is the caller's."""
+    from . import api
+
+    starts = np.asarray(starts, dtype=np.float64)
+    if starts.ndim != 3:
+        raise ValueError("minimize_starts_device: starts must be [S, n_free, d]")
+    S, nfree, d = starts.shape
+    nv = nfree * d
+    seg = int(seg)
+    if seg < 1 or seg > api.FIT_MAX_EVALS:
+        raise ValueError("minimize_starts_device: seg must lie in 1 .. %d" % api.FIT_MAX_EVALS)
+    lo = np.broadcast_to(np.asarray(lower, dtype=np.float64), (nfree, d)).ravel()
+    hi = np.broadcast_to(np.asarray(upper, dtype=np.float64), (nfree, d)).ravel()
+    if evaluate is None:
+        def evaluate(X):
+            return handle.design_fit_eval(X, K, params_row, D_old, ld_offset)
+    device = bool(on_device)
+    if nv > 64:   # the stepper's state ends at 64 variables (csrc/fit_logic.h): minimize_starts itself over the twin's evaluator
+        return minimize_starts(evaluate, starts, lower, upper, 5, maxit, factr, pgtol, max_backtracks)
+    state = np.stack([api.fit_begin(s.ravel(), lo, hi, maxit, factr, pgtol, max_backtracks) for s in starts]) if S else \
+        np.zeros((0, api.FIT_HEADER + 16 * nv))
+    calls = 0
+    while True:
+        live = np.flatnonzero(state[:, api.FIT_CODE] == api.FIT_RUNNING)
+        if live.size == 0:
+            break
+        if device:
+            try:
+                r = handle.design_fit(nfree, d, K, params_row, state[live], seg, D_old, ld_offset)
+            except api.CcgpError as e:
+                if e.code != -4:   # CCGP_EUNSUPPORTED: this shape has no device search; the twin carries it
+                    raise
+                device = False
+                continue
+            state[live] = r["state"]
+            calls += 1
+        else:
+            for _ in range(seg):
+                run = live[state[live, api.FIT_CODE] == api.FIT_RUNNING]
+                if run.size == 0:
+                    break
+                f, g, st = evaluate(api.fit_trial(state[run]).reshape(run.size, nfree, d))
+                calls += 1
+                for k, a in enumerate(run):
+                    api.fit_feed(state[a], f[k], np.asarray(g[k]).ravel(), st[k] == 0)
+    code = state[:, api.FIT_CODE].astype(np.int64)
+    return dict(x=api.fit_x(state).reshape(S, nfree, d), f=state[:, api.FIT_F].copy(),
+                converged=(code == api.FIT_CONV_REDUCTION) | (code == api.FIT_CONV_PROJ_GRAD),
+                iterations=state[:, api.FIT_ITERATIONS].astype(np.int64), message=[_FIT_MESSAGES[c] for c in code],
+                calls=calls, calls_per_start=state[:, api.FIT_EVALS].astype(np.int64))
+
+
 def make_starts(n_starts, n, d, rng):
     """-1 + 2 LHS(n, d) per start (BSQ:899, BSQ:935), from a seeded numpy generator."""
     if not isinstance(rng, np.random.Generator):

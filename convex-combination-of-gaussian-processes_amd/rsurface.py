@@ -239,9 +239,23 @@ class CombinedGP:
                     designs=res["x"], values=vals, logdets=logdets, converged=res["converged"],
                     iterations=res["iterations"], best=best, device_calls=res["calls"])
 
-    def Entropy_optim(self, n, d, p, theta1, theta2, n_starts, starts=None, rng=None, **opts):
+    _DEVICE_SEARCH_OPTS = frozenset(("m", "lower", "upper", "maxit", "factr", "pgtol", "max_backtracks"))
+
+    def _design_search(self, evaluate, S, row, D_old, ld_offset, on_device, opts):
+        """The search of Entropy_optim / Batch_Entropy_optim: design.minimize_starts over `evaluate`, or with on_device the
+        same search stepped inside the kernel (design.minimize_starts_device: the same dict, bit for bit, but for `calls`).
+        The device stepper has memory 5 and at most 64 variables; any other request keeps the host path."""
+        from . import design
+        if on_device and opts.get("m", 5) == 5 and S[0].size <= 64 and set(opts) <= self._DEVICE_SEARCH_OPTS:
+            dev = {k: v for k, v in opts.items() if k != "m"}
+            return design.minimize_starts_device(self.h, S, 2, row, D_old, ld_offset, **dev)
+        return design.minimize_starts(evaluate, S, **opts)
+
+    def Entropy_optim(self, n, d, p, theta1, theta2, n_starts, starts=None, rng=None, on_device=False, **opts):
         """Entropy.optim(n, d, p, theta1, theta2, n.starts), BSQ:886-912: the n-point maximum-entropy design from
         n.starts starts, all of them searched side by side (design.minimize_starts; opts: m, maxit, factr, pgtol).
+        on_device=True runs the search itself on the device, every start in one launch: the same result in every key but
+        device_calls.
         starts: [n_starts, n, d] or None for -1 + 2 LHS(n, d) from numpy's generator seeded with rng (the reference's
         lhs::optimumLHS cannot be reproduced without R).  Returns dict(Design, log_entropy = det R of the best design, as
         the reference returns it, logdet, designs, values = -det per start, logdets, converged, iterations, best,
@@ -255,13 +269,14 @@ class CombinedGP:
             ld, g, st = self.h.mixed_logdet_grad_designs(X, 2, row, 0)
             return -ld, -g, st
 
-        res = design.minimize_starts(evaluate, S, **opts)
+        res = self._design_search(evaluate, S, row, None, 0.0, on_device, opts)
         return self._design_result(res, -res["f"])
 
-    def Batch_Entropy_optim(self, D_old, n_new, d, p, theta1, theta2, n_starts, starts=None, rng=None, **opts):
+    def Batch_Entropy_optim(self, D_old, n_new, d, p, theta1, theta2, n_starts, starts=None, rng=None, on_device=False,
+                            **opts):
         """Batch.Entropy.optim(D.old, n.new, d, p, theta1, theta2, n.starts), BSQ:920-948: the n.new points to add to
         D.old that maximise det(R.new - R.cross R.old^-1 R.cross') = det R(D.old U D.new) / det R(D.old) (Schur
-        complement; its log is what is searched).  Starts, options and the returned dict as in Entropy_optim; logdet,
+        complement; its log is what is searched).  Starts, options, on_device and the returned dict as in Entropy_optim; logdet,
         logdets and log_entropy refer to the Schur determinant."""
         from . import design
         D_old = np.asarray(D_old, dtype=np.float64)
@@ -277,7 +292,7 @@ class CombinedGP:
             ld, g, st = self.h.mixed_logdet_grad_designs(full, 2, row, n_old)
             return -(ld - ld_old[0]), -g, st
 
-        res = design.minimize_starts(evaluate, S, **opts)
+        res = self._design_search(evaluate, S, row, D_old, float(ld_old[0]), on_device, opts)
         out = self._design_result(res, -res["f"])
         out["device_calls"] += 1   # log det R(D.old)
         return out

@@ -658,6 +658,45 @@ int ccgp_mixed_logdet_grad_designs(ccgp_handle* h, const double* Xs, int n, int 
                                    const double* params, int n_fixed, double* out_logdet, double* out_grad,
                                    int* status);
 
+/* ---- the maximum-entropy design search on the device: every start in one launch (Entropy.optim / Batch.Entropy.optim, -------------
+ * Batch Sequential ME Design.R:886-948).  A start's variables are the free rows of its design in row-major order: nv =
+ * (n - n_fixed) d, variable v = i d + k is free row i, dimension k.  The iterate IS the design -- nothing is transformed --, the
+ * objective is f = -(log det R - ld_offset) (ld_offset = log det R(D.old) for the batch form, 0 otherwise) and g_v = -(d log det
+ * R / d x_v), each one exactly rounded operation on what ccgp_mixed_logdet_grad_designs returns.  The state of a start is
+ * ccgp_fit_begin's with d = nv (W = ccgp_fit_state_doubles(nv)); ccgp_fit_feed steps it on the host.  All starts share D_old
+ * (n_fixed x d column-major, NULL iff n_fixed == 0) and one parameter row (K + K d values).
+ * ccgp_design_fit_eval is the evaluation of B points (x, out_g: B blocks of nv in variable order) on the host side of
+ * ccgp_mixed_logdet_grad_designs: it forms the B designs (D_old on top of block b's rows), calls ccgp_mixed_logdet_grad_designs
+ * with that call's checks and routes -- so it serves every shape that call serves, nv > 64 included -- and transforms the
+ * results.  ccgp_design_fit runs A starts on the device: one workgroup carries one start from its state through up to
+ * max_evals[a] evaluations -- the design from `trial`, log det and its gradient from one factorisation, the step of
+ * ccgp_fit_feed -- and writes the state back, so the next call continues it.  out_evals[a] is the number of evaluations made.
+ * The trace (both or neither, [a T + t]): f and the pivot status of evaluation t of this call; NaN / -1 beyond out_evals[a].
+ *   Bits.  Every evaluation inside ccgp_design_fit has the bits ccgp_mixed_logdet_grad_designs gives that design with that
+ *     n_fixed.  A start driven evaluation by evaluation through ccgp_design_fit_eval and ccgp_fit_feed leaves the same state and
+ *     trace, bit for bit.
+ *   Independence.  A start depends on its own state and the shared inputs only: not on A, its position, what the handle ran
+ *     before, or how its evaluations are cut into calls by max_evals.
+ *   Failure.  A failed elimination (coincident rows) is an infeasible trial: f is the one quiet NaN, the gradient row is NaN,
+ *     status is the 1-based pivot, and the line search backs off.  A start whose first point fails ends with code 5, its
+ *     neighbours untouched.  The return value is the number of failed evaluations (ccgp_design_fit: over all starts).
+ *   Arguments.  CCGP_EINVAL before anything is copied or launched, outputs and ccgp_workspace_bytes unchanged: bad shapes,
+ *     n_fixed outside [0, n), D_old NULL with n_fixed > 0, A < 0 (B < 0), T < 0, max_evals[a] outside 0 .. min(T, 4096), a
+ *     partial trace, a NULL required pointer (everything but D_old at n_fixed == 0, the trace and ccgp_design_fit_eval's
+ *     status), a state whose recorded d is not nv.  CCGP_EUNSUPPORTED, outputs untouched: ccgp_design_fit for a family other
+ *     than the Gaussian, n > 128, nv > 64 (the stepper's state ends there) or a design-gradient instance whose carve does not
+ *     fit with the start's words behind it; ccgp_design_fit_eval where ccgp_mixed_logdet_grad_designs refuses.  A == 0 (B == 0)
+ *     returns CCGP_OK.  A start that is not running, or whose max_evals is 0, is returned as it came.
+ * Host pointers only, blocking; ccgp_reserve does not cover the staging.  Not in this version: nv > 64, per-start parameter rows
+ * or D_old, _dev variants, a ccgp_multi wrapper, an R shim. */
+int ccgp_design_fit_eval(ccgp_handle* h, const double* D_old /* n_fixed x d column-major, NULL iff n_fixed == 0 */,
+                         int n_fixed, int n, int d, int K, const double* params /* one row */, double ld_offset,
+                         const double* x /* B blocks of nv, variable order */, int B,
+                         double* out_f, double* out_g /* B blocks of nv */, int* status /* NULL ok */);
+int ccgp_design_fit(ccgp_handle* h, const double* D_old, int n_fixed, int n, int d, int K, const double* params,
+                    double ld_offset, int A, double* state /* A x W(nv), in and out */, const int* max_evals,
+                    int* out_evals, double* trace_f, int* trace_status /* A x T, both or neither */, int T);
+
 /* ---- several GPUs behind ONE host process (csrc/multi.cpp) ------------------------------
  * The drop-in host is R: one single-threaded process.  A ccgp_multi owns one handle per device; the three
  * batched entry points below take the same arguments as their single-device forms, cut the batch into
