@@ -213,6 +213,12 @@ int pull(ccgp_handle* h, Pieces ps, size_t pin_max = kPinMax) {
   return CCGP_OK;
 }
 
+// the `gauss` flag of the four route decisions the fused family evaluators serve (CCGP_OPT_FAMILY_FUSED: Op::Loglik,
+// small_route_sets, small_route_chain, small_route_nm); every other decision asks `fam.id == 0`
+bool gauss_or_fused(const ccgp_handle* h, int n, int d, int K) {
+  return h->fam.id == 0 || (h->opt_family_fused != 0 && small_family_fused_supported(h->fam.id, n, d, K));
+}
+
 bool bad_shape(int n, int d, int K) {
   return n < 1 || d < 1 || d > kMaxD || K < 1 || K > kMaxK;
 }
@@ -291,7 +297,7 @@ int check_mean_mode(ccgp_handle* h, int mean_mode) {
 int loglik_run(ccgp_handle* h, const double* dX, int n, int d, const double* dy, const DrawView& dv, double sigma2,
                int mean_mode, double tau2, double* d_loglik, double* d_beta, int* d_status) {
   const int K = dv.K, B = dv.ldp;
-  if (small_route(Op::Loglik, dv.fam.id == 0, n, d, K) == Route::Blocked)
+  if (small_route(Op::Loglik, gauss_or_fused(h, n, d, K), n, d, K) == Route::Blocked)
     return run_sweep(h, dX, n, d, dy, dv, B, 0, sigma2, mean_mode, tau2, {d_loglik, d_beta, d_status}, nullptr, 0, no_scratch);
   ScopedTimer t(h, CCGP_T_FUSED);
   launch_small_reg_loglik(h->stream, dX, n, d, dy, dv, B, sigma2, mean_mode, tau2, d_loglik, d_beta,
@@ -900,6 +906,10 @@ int ccgp_set_option(ccgp_handle* h, int option, int value) try {
     h->opt_sched_policy = value;
     return CCGP_OK;
   }
+  if (option == CCGP_OPT_FAMILY_FUSED && (value == 0 || value == 1)) {
+    h->opt_family_fused = value;
+    return CCGP_OK;
+  }
   return fail(h, CCGP_EINVAL, "ccgp_set_option: unknown option or value");
 } CCGP_GUARD_END(h)
 
@@ -916,7 +926,7 @@ int ccgp_reserve(ccgp_handle* h, int n, int d, int K, int B, int m) try {
   // prediction on the register-resident evaluator implies the likelihood there: its instance is the larger one)
   const bool gauss = h->fam.id == 0;
   const bool sweep_predict = m > 0 && small_route(Op::Predict, gauss, n, d, K) == Route::Blocked;
-  if (sweep_predict || small_route(Op::Loglik, gauss, n, d, K) == Route::Blocked) {
+  if (sweep_predict || small_route(Op::Loglik, gauss_or_fused(h, n, d, K), n, d, K) == Route::Blocked) {
     int nbc = 0;
     if (int rc = sweep_plan(h, round_up(n, kTile), sweep_predict ? (m + kTile - 1) / kTile : 0, B, 0,
                             [&](Layout& t, int) { if (sweep_predict) predict_tail(t, B, nullptr, nullptr); }, &nbc))
@@ -1211,7 +1221,7 @@ int ccgp_loglik_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const
     return fail(h, CCGP_EINVAL, "ccgp_loglik_batch_sets: bad argument");
   if (int rc = check_mean_mode(h, mean_mode)) return rc;
   const int P = K + K * d;
-  if (small_route_sets(h->fam.id == 0, n, d, K) == Route::Blocked) {   // ccgp_loglik_batch, whatever route that call takes
+  if (small_route_sets(gauss_or_fused(h, n, d, K), n, d, K) == Route::Blocked) {   // ccgp_loglik_batch, whatever route that call takes
     std::vector<double> ll, beta;
     std::vector<int> st;
     return sets_by_group(set, B, C, P, params, [&](int c, const double* rows, int nb, const std::vector<int>& idx) -> int {
@@ -1509,9 +1519,10 @@ int ccgp_metro_segments_sets(ccgp_handle* h, const double* Xs, int n, int d, con
             (ntrace == 0 || ntrace == 4) && sets_args_ok(Xs, ys, sigma2, true, C, set, A, 0);
   for (int a = 0; ok && a < A; ++a) ok = n_prop[a] >= 0 && n_prop[a] <= T && stop_acc[a] >= 0 && stop_acc[a] <= M;
   if (int rc = logpost_args(h, "ccgp_metro_segments_sets", ok, d, prior_id, prior_pars)) return rc;
-  if (small_route_chain(h->fam.id == 0, n, d, 2) != Route::Reg)
+  if (small_route_chain(gauss_or_fused(h, n, d, 2), n, d, 2) != Route::Reg)
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_metro_segments_sets: chains run on the device for Gaussian sets of n <= 128 whose "
-                                      "register-resident instance fits; keep the chain on ccgp_chain_logpost_sets");
+                                      "register-resident instance fits (the 1-D families: n <= 32 under CCGP_OPT_FAMILY_FUSED); "
+                                      "keep the chain on ccgp_chain_logpost_sets");
   if (A == 0) return CCGP_OK;
   CCGP_HIP(hipSetDevice(h->device));
   const int q = prior_id == CCGP_PRIOR_ANI ? 4 : 3;
@@ -1566,7 +1577,7 @@ int ccgp_metro_segments_sets(ccgp_handle* h, const double* Xs, int n, int d, con
   CCGP_HIP(hipMemsetAsync(io.draws, 0xFF, (size_t)((char*)io.theta_fin - (char*)io.draws), h->stream));
   {
     ScopedTimer t(h, CCGP_T_FUSED);
-    launch_small_reg_chain_sets(h->stream, dXs, n, d, dys, ds2, dset, A, io);
+    launch_small_reg_chain_sets(h->stream, dXs, n, d, dys, ds2, dset, A, io, h->fam);
     CCGP_LAUNCH_CHECK();
   }
   std::vector<int> cnt(3 * sA);
@@ -1833,9 +1844,10 @@ int ccgp_laplace_search_sets(ccgp_handle* h, const double* Xs, int n, int d, con
   for (int a = 0; ok && a < A; ++a)
     ok = max_evals[a] >= 0 && max_evals[a] <= cap && nm_state_ok(state + (size_t)a * W, q);
   if (!ok) return fail(h, CCGP_EINVAL, "ccgp_laplace_search_sets: bad argument");
-  if (small_route_nm(h->fam.id == 0, n, d, 2) != Route::Reg)
+  if (small_route_nm(gauss_or_fused(h, n, d, 2), n, d, 2) != Route::Reg)
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_laplace_search_sets: searches run on the device for Gaussian sets of n <= 128 whose "
-                                      "register-resident instance fits; keep the search on ccgp_chain_logpost_sets and ccgp_nm_feed");
+                                      "register-resident instance fits (the 1-D families: n <= 32 under CCGP_OPT_FAMILY_FUSED); "
+                                      "keep the search on ccgp_chain_logpost_sets and ccgp_nm_feed");
   if (A == 0) return CCGP_OK;
   CCGP_HIP(hipSetDevice(h->device));
   const size_t sA = A, sT = (size_t)A * T;
@@ -1872,7 +1884,7 @@ int ccgp_laplace_search_sets(ccgp_handle* h, const double* Xs, int n, int d, con
   }
   {
     ScopedTimer t(h, CCGP_T_FUSED);
-    launch_small_reg_nm_sets(h->stream, dXs, n, d, dys, ds2, dset, A, io);
+    launch_small_reg_nm_sets(h->stream, dXs, n, d, dys, ds2, dset, A, io, h->fam);
     CCGP_LAUNCH_CHECK();
   }
   std::vector<int> cnt(2 * sA);
@@ -1905,7 +1917,7 @@ int ccgp_logpost(ccgp_handle* h, const double* X, int n, int d, const double* y,
   int st = 0;
   CCGP_HIP(hipSetDevice(h->device));
   const bool gauss = h->fam.id == 0;
-  Route route = small_route(out_Rinv ? Op::Inverse : Op::Loglik, gauss, n, d, K);
+  Route route = out_Rinv ? small_route(Op::Inverse, gauss, n, d, K) : small_route(Op::Loglik, gauss_or_fused(h, n, d, K), n, d, K);
   const size_t in_d = (size_t)n * d + n + P;                       // X | y | row
   const size_t out_d = 3 + (out_Rinv ? (size_t)n * n : 0);         // ll, beta, status (as one double slot) | R^-1
   if (route == Route::Reg && ensure(h, h->pin, kPinned, sizeof(double) * (in_d + out_d)) == CCGP_OK) {

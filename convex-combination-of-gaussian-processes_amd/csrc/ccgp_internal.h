@@ -73,6 +73,7 @@ struct ccgp_handle {
   int opt_tail_strips = 1;              // CCGP_OPT_TAIL_STRIPS
   int opt_wide_offsets = 0;             // CCGP_OPT_WIDE_OFFSETS
   int opt_fused_solve = 1;              // CCGP_OPT_FUSED_SOLVE: 0 = update + trsm launches, 1 = diagonal launch + tiles solved in the update workgroup where the batch fills whole steps, 2 = wherever possible
+  int opt_family_fused = 0;             // CCGP_OPT_FAMILY_FUSED: 1 = the 1-D families take the register-resident evaluator where small_family_fused_supported says so
   int opt_sched = 3;                    // CCGP_OPT_SCHED: 0 = one launch per phase and block column, 1 = dataflow scheduler with two workgroups per CU, 2 = with one, 3 = by chunk size
   int opt_sched_policy = 11;            // CCGP_OPT_SCHED_POLICY bit 0: a CU's second workgroup only takes work while a backlog exists; bit 1: XCD-local synchronisation
   int sched_timeout_ms = 30000;         // a scheduler wait longer than this aborts the sweep (CCGP_SCHED_TIMEOUT_MS)
@@ -232,8 +233,9 @@ struct ChainIO {
   double *tr_val, *tr_beta;
   int *tr_status, *tr_acc;
 };
+// (fam: the handle's family -- other than Gaussian where CCGP_OPT_FAMILY_FUSED routes a 1-D family here: the FAM instances)
 void launch_small_reg_chain_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
-                                 const int* set, int A, const ChainIO& io);
+                                 const int* set, int A, const ChainIO& io, KernelFamily fam = KernelFamily{});
 // the ordinary-kriging fits on the device (ccgp_profile_fit_sets where small_route_fit says Reg): what start a = workgroup a
 // of A reads and leaves, every pointer a device pointer.  state [A][W] in and out (fit_logic.h), max_evals / evals / nfail
 // [A], the trace [A][T], both or none
@@ -276,7 +278,7 @@ struct NmIO {
   int* tr_status;
 };
 void launch_small_reg_nm_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
-                              const int* set, int A, const NmIO& io);
+                              const int* set, int A, const NmIO& io, KernelFamily fam = KernelFamily{});
 // leave-one-out mean / variance of every training point for B draws (ccgp_loo_batch where small_route_loo says Reg): one
 // workgroup per draw on the inverse instances' scheme; mean / var are B x n column-major, sigma2 is the scalar that
 // vf.sigma2_row (indexed by draw) replaces, vf.q (may be nullptr) receives Q per draw

@@ -182,7 +182,8 @@ inline bool small_reg_design_grad_supported(int n, int d, int K) { return small_
 //   Reg      the register-resident evaluator (small_reg.hip)
 //   Lds      the in-LDS evaluator (small.hip): the gradient and solve(R) of shapes whose INV instance does not fit
 //   Blocked  the blocked sweep over materialised matrices (cov.hip + blocked.hip): any n, any kernel family
-// `gauss`: the Gaussian family; the others exist on the blocked sweep only.  Grad, LogdetDesigns and DesignGrad refuse them
+// `gauss`: the Gaussian family; the others exist on the blocked sweep only (but see small_family_fused_supported at the foot of
+// this file: under CCGP_OPT_FAMILY_FUSED the caller sets the flag for a 1-D family too).  Grad, LogdetDesigns and DesignGrad refuse them
 // before they ask, so their routes do not look at it.  For Grad the caller turns Blocked into a refusal when the
 // contraction kernel cannot take (d, K) (blocked_grad_supported, blocked.hip).
 // What is decided after the route, from more than the shape, stays with its owner: kept-factor or extra-row prediction
@@ -301,6 +302,20 @@ inline Route small_route_nm(bool gauss, int n, int d, int K) {
   if (small_route_chain(gauss, n, d, K) != Route::Reg) return Route::Unsupported;
   return lds_fits(reg_nm_lds_doubles((n + 15) / 16, n, d, K)) ? Route::Reg : Route::Unsupported;
 }
+// the 1-D families on the register-resident evaluator (CCGP_OPT_FAMILY_FUSED, ccgp.h): the FAM instances of small_reg.hip
+// generate a Matern (family 1) or Matern + spline (family 2: K = 2, as ccgp_set_kernel's callers enforce) matrix from the one
+// coordinate in xs, for the plain likelihood with or without SETS / CHAIN / NM.  They are compiled for the reference's own
+// shapes, d = 1 and n <= 32 (its designs have 8 points): two blocks of the 16 x 16 grid, four of the 8 x 8.  The four route
+// functions above keep their `gauss` flag; where the option is on, capi.hip passes `gauss || small_family_fused_supported(..)`
+// for Op::Loglik, small_route_sets, small_route_chain and small_route_nm, and nothing else.  The carves asked for are those
+// of all four, so a shape inside this domain is Reg on each (tests/host_small/family_fused_layout_check.cpp).
+constexpr int kFamilyFusedMaxN = 32;
+inline bool small_family_fused_supported(int family, int n, int d, int K) {
+  if ((family != 1 && family != 2) || d != 1 || n < 1 || n > kFamilyFusedMaxN) return false;
+  if (K < 1 || K > kMaxK || (family == 2 && K != 2)) return false;
+  return small_reg_supported(n, d, K) && small_reg_sets_supported(n, d, K) && lds_fits(reg_nm_lds_doubles((n + 15) / 16, n, d, K));
+}
+
 // the maximum-entropy design search on the device (ccgp_design_fit): the DFIT instances are the design-gradient instances
 // (INV = 3, per-design carve), one workgroup per start.  A start's variables are the free rows of its design in the order
 // numpy ravels [n - n_fixed, d]: nv = (n - n_fixed) d, variable v = i d + k is free row i, dimension k.  Nothing is

@@ -124,7 +124,19 @@ struct RegArgs {
   FitIO fit;           // FIT instantiations only
   NmIO nm;             // NM instantiations only
   DesignFitIO dfit;    // DFIT instantiations only
+  KernelFamily fam;    // FAM instantiations only: the handle's 1-D family (id, nu, norm); Gaussian in every other launch
 };
+
+// The 1-D families' correlation of one scaled squared distance -- corr_of_dist's family branch (ccgp_internal.h) -- as ONE
+// compiled body for every FAM instance.  Inlined, matern_corr's quadrature is contracted by the compiler in each instantiation on
+// its own, and a chain's or a search's likelihood must have the bits the sets instance gives that row, on either grid.  The call
+// costs nothing beside ~150 terms of three exp each; every loop inside is bounded (matern_corr's 6000-term cap).
+__device__ __noinline__ double family_corr(int id, double nu, double norm, double dist, int component) {
+  if (id == CCGP_KERNEL_MATERN_SPLINE && component == 1) return spline_corr(dist);
+  KernelFamily f;
+  f.id = id; f.nu = nu; f.norm = norm;
+  return matern_corr(f, dist);
+}
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
 // Rounds 2 - 4 predicted by carrying the cross-correlation rows of a CHUNK of test sites (30 at n <= 64, 62 above) through the
@@ -213,10 +225,21 @@ __device__ __forceinline__ void mat_sync() {
 // left in LDS; thread 0 forms f = -(ld - ld_offset) and g = -grad, runs fit_feed, writes the trace and publishes one word,
 // and after one barrier every thread reads it.  The trip count is bounded by max_evals[a] <= 4096; no path waits on another
 // workgroup.  On exit the state goes back to HBM.
+// FAM (CCGP_OPT_FAMILY_FUSED): the plain likelihood instance, with or without SETS / CHAIN / NM, generating the matrix of a 1-D
+// family (d = 1: Matern for every component, or Matern + spline -- a run-time branch on a.fam.id inside family_corr) in place
+// of the Gaussian one: per component q and entry (r, c), r >= c, what cov_kernel<1> forms -- rate = theta_to_rate(theta_q),
+// h = x_r - x_c from the one coordinate in xs, the family's correlation of rate h^2, accumulated with fma(w_q^2, ., acc) --
+// then the instance's own post_scale / post_shift.  The diagonal is an entry like any other (h = 0: exactly 1 per component),
+// two coincident points give two equal rows and a zero pivot, a NaN coordinate a NaN matrix.  th[] keeps holding theta (under
+// CHAIN / NM: what chain_rate writes); us[] and the expanded distance are not formed.  Everything after the generation phase
+// is the instance's code unchanged.  Compiled for n <= 32 only (small_family_fused_supported): NB <= 2 on the 16 x 16 grid,
+// NB <= 4 on the 8 x 8, general (non-FULL) instances.
 template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false,
-          bool CHAIN = false, bool FIT = false, bool NM = false, bool DFIT = false>
+          bool CHAIN = false, bool FIT = false, bool NM = false, bool DFIT = false, bool FAM = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
+  static_assert(!FAM || (NE == 1 && !INV && !PROF && !FAC && !FULL && !FIT && !DFIT && G * NB <= kFamilyFusedMaxN),
+                "a 1-D family is generated by the general plain-likelihood instance (with or without SETS / CHAIN / NM) at n <= 32");
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
   static_assert(!FAC || (NE == 1 && !FULL && !INV), "the factor is kept by the plain likelihood instantiation");
   static_assert(!PROF || ((NE == 1 || INV == 2) && INV != 1 && INV != 3 && !FAC), "sigma2 is concentrated out of the likelihood and of its gradient only");
@@ -416,7 +439,7 @@ chain_next:
     }
   }
   __syncthreads();
-  for (int e = lt; e < K * n; e += TPM) {
+  for (int e = lt; e < (FAM ? 0 : K * n); e += TPM) {   // (a 1-D family takes its distance from the direct difference: no us[])
     const int c = e / n, i = e % n;
     double s = 0.0;
     for (int k = 0; k < d; ++k) { const double v = xs[k * n + i]; s += v * v * th[c * d + k]; }
@@ -456,7 +479,26 @@ chain_next:
   int rowi[NB];   // clamped row of every row block (padding rows repeat row n-1; they are overwritten below)
 #pragma unroll
   for (int aa = 0; aa < NB; ++aa) rowi[aa] = FULL ? ty + G * aa : min(ty + G * aa, n - 1);
-  for (int q = 0; q < K; ++q) {
+  if constexpr (FAM) {
+    // a 1-D family's entries as cov_kernel<1> forms them (cov.hip), component by component in its order
+    for (int q = 0; q < K; ++q) {
+      const double wq = w2[q], rate = theta_to_rate(a.fam, th[q], q);
+#pragma unroll
+      for (int bb = 0; bb < NB; ++bb) {
+        const int c = tx + G * bb;
+#pragma unroll
+        for (int aa = 0; aa < NB; ++aa) {
+          if (aa < bb) continue;
+          const int r = ty + G * aa;
+          if (r < n && c < n && r >= c) {
+            const double h = xs[r] - xs[c];
+            M[aa][bb] = fma(wq, family_corr(a.fam.id, a.fam.nu, a.fam.norm, rate * (h * h), q), M[aa][bb]);
+          }
+        }
+      }
+    }
+  }
+  for (int q = 0; q < (FAM ? 0 : K); ++q) {
     const double wq = w2[q];
 #pragma unroll
     for (int bb0 = 0; bb0 < NB; bb0 += 2) {
@@ -1123,6 +1165,19 @@ void pick(int v, F&& f) {
   else pick<Lo + 1, Hi>(v, f);
 }
 
+// A launcher was handed a 1-D family at a shape no FAM instance is compiled for.  The routes never say so
+// (small_family_fused_supported, small_layout.h); should one, nothing is launched and the call fails at its launch check --
+// as a refused kernel attribute does -- instead of running the Gaussian kernel in the family's place.
+void no_family_instance() {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> guard(attr_mutex());
+  std::string& slot = attr_errors()[dev & 63];
+  if (!slot.empty()) return;
+  slot = "small_reg.hip: no instance generates this kernel family at this shape";
+  attr_error_mask().fetch_or(1ull << (dev & 63));
+}
+
 // the arguments every launcher shares: one design, profile-beta likelihood of draw 0 unless the launcher says otherwise
 RegArgs reg_args(const double* X, int n, int d, const double* y, DrawView dv) {
   RegArgs a{};
@@ -1166,6 +1221,20 @@ void launch_one(hipStream_t s, const RegArgs& a) {
       else kernel = small_reg_kernel<G, NB, NE, false, 0, false, true>;
     } else if (a.n == G * NB && a.x_stride == 0) {
       kernel = small_reg_kernel<G, NB, NE, true>;
+    }
+  }
+  if (a.fam.id != 0) {   // a 1-D family (CCGP_OPT_FAMILY_FUSED): the general instance compiled with FAM, single-set or sets form
+    if constexpr (NE == 1 && G * NB <= kFamilyFusedMaxN) {
+      static unsigned long long fam_mask = 0;
+      once_per_device(fam_mask, [] {
+        raise_lds_limit((const void*)small_reg_kernel<G, NB, 1, false, 0, false, false, false, false, false, false, false, true>, "small_reg_kernel<family>");
+        raise_lds_limit((const void*)small_reg_kernel<G, NB, 1, false, 0, false, false, true, false, false, false, false, true>, "small_reg_kernel<family, sets>");
+      });
+      if (a.set) kernel = small_reg_kernel<G, NB, 1, false, 0, false, false, true, false, false, false, false, true>;
+      else kernel = small_reg_kernel<G, NB, 1, false, 0, false, false, false, false, false, false, false, true>;
+    } else {
+      no_family_instance();
+      return;
     }
   }
   const int chunks = NE > 1 ? (a.m + (G * NE - 2) - 1) / (G * NE - 2) : 1;
@@ -1516,6 +1585,18 @@ static void launch_chain(hipStream_t s, const RegArgs& a) {
   const size_t lds = sizeof(double) * reg_chain_lds_doubles(NB, a.n, a.d, a.K);
   void (*kernel)(RegArgs) = small_reg_kernel<16, NB, 1, false, 0, false, false, true, true>;
   if (a.n == 16 * NB) kernel = small_reg_kernel<16, NB, 1, true, 0, false, false, true, true>;
+  if (a.fam.id != 0) {   // a 1-D family: the general chain instance compiled with FAM
+    if constexpr (16 * NB <= kFamilyFusedMaxN) {
+      static unsigned long long fam_mask = 0;
+      once_per_device(fam_mask, [] {
+        raise_lds_limit((const void*)small_reg_kernel<16, NB, 1, false, 0, false, false, true, true, false, false, false, true>, "small_reg_kernel<family, chain>");
+      });
+      kernel = small_reg_kernel<16, NB, 1, false, 0, false, false, true, true, false, false, false, true>;
+    } else {
+      no_family_instance();
+      return;
+    }
+  }
   hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
 }
 
@@ -1530,6 +1611,18 @@ static void launch_nm(hipStream_t s, const RegArgs& a) {
   const size_t lds = sizeof(double) * reg_nm_lds_doubles(NB, a.n, a.d, a.K);
   void (*kernel)(RegArgs) = small_reg_kernel<16, NB, 1, false, 0, false, false, true, true, false, true>;
   if (a.n == 16 * NB) kernel = small_reg_kernel<16, NB, 1, true, 0, false, false, true, true, false, true>;
+  if (a.fam.id != 0) {   // a 1-D family: the general search instance compiled with FAM
+    if constexpr (16 * NB <= kFamilyFusedMaxN) {
+      static unsigned long long fam_mask = 0;
+      once_per_device(fam_mask, [] {
+        raise_lds_limit((const void*)small_reg_kernel<16, NB, 1, false, 0, false, false, true, true, false, true, false, true>, "small_reg_kernel<family, nm>");
+      });
+      kernel = small_reg_kernel<16, NB, 1, false, 0, false, false, true, true, false, true, false, true>;
+    } else {
+      no_family_instance();
+      return;
+    }
+  }
   hipLaunchKernelGGL(kernel, dim3(a.B, 1), dim3(256), lds, s, a);
 }
 
@@ -1573,10 +1666,10 @@ void launch_small_reg_design_fit(hipStream_t s, int n, int d, DrawView dv, int n
 // ccgp_laplace_search_sets where small_route_nm says Reg: A searches, search a on training set set[a]; arrays as NmIO lays
 // them out; every pointer a device pointer
 void launch_small_reg_nm_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
-                              const int* set, int A, const NmIO& io) {
-  DrawView dv{nullptr, A, 2, d, KernelFamily{}};
+                              const int* set, int A, const NmIO& io, KernelFamily fam) {
+  DrawView dv{nullptr, A, 2, d, fam};
   RegArgs a = reg_args(Xs, n, d, ys, dv);
-  a.B = A; a.set = set; a.sigma2_set = sigma2; a.nm = io;
+  a.B = A; a.set = set; a.sigma2_set = sigma2; a.nm = io; a.fam = fam;
   pick<1, 8>((n + 15) / 16, [&](auto nb) { launch_nm<decltype(nb)::value>(s, a); });
 }
 
@@ -1593,10 +1686,10 @@ void launch_small_reg_fit_sets(hipStream_t s, const double* Xs, int n, int d, co
 // ccgp_metro_segments_sets where small_route_chain says Reg: A chains, chain a on training set set[a]; arrays as ChainIO
 // lays them out (theta0 / theta_fin A x p column-major); every pointer a device pointer
 void launch_small_reg_chain_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2,
-                                 const int* set, int A, const ChainIO& io) {
-  DrawView dv{nullptr, A, 2, d, KernelFamily{}};
+                                 const int* set, int A, const ChainIO& io, KernelFamily fam) {
+  DrawView dv{nullptr, A, 2, d, fam};
   RegArgs a = reg_args(Xs, n, d, ys, dv);
-  a.B = A; a.set = set; a.sigma2_set = sigma2; a.ch = io;
+  a.B = A; a.set = set; a.sigma2_set = sigma2; a.ch = io; a.fam = fam;
   pick<1, 8>((n + 15) / 16, [&](auto nb) { launch_chain<decltype(nb)::value>(s, a); });
 }
 
@@ -1607,7 +1700,7 @@ void launch_small_reg_loglik_sets(hipStream_t s, const double* Xs, int n, int d,
                                   double* beta, int* status) {
   RegArgs a = reg_args(Xs, n, d, ys, dv);
   a.B = B; a.mode = mean_mode; a.tau2 = tau2; a.set = set; a.sigma2_set = sigma2;
-  a.loglik = loglik; a.beta = beta; a.status = status;
+  a.loglik = loglik; a.beta = beta; a.status = status; a.fam = dv.fam;
   dispatch_sets(s, a);
 }
 
@@ -1684,7 +1777,7 @@ void launch_small_reg_loglik(hipStream_t s, const double* X, int n, int d, const
                              double* beta, int* status, bool grid16) {
   RegArgs a = reg_args(X, n, d, y, dv);
   a.B = B; a.sigma2 = sigma2; a.mode = mean_mode; a.tau2 = tau2;
-  a.loglik = loglik; a.beta = beta; a.status = status; a.grid16 = grid16;
+  a.loglik = loglik; a.beta = beta; a.status = status; a.grid16 = grid16; a.fam = dv.fam;
   dispatch(s, a);
 }
 

@@ -586,7 +586,8 @@ def Metro_device_sets(gp, starts, N, samp_size, batch_size, alpha, D_trains, sig
     values go through ccgp_chain_logpost_sets, the host twin of the kernel's evaluation.
     on_device=False runs the same driver one proposal at a time through that twin (or through logpost_sets_fn(rows, set_of)
     -> (val, beta)): the exact reference for the device chain, bit for bit, and what the driver falls back to where the
-    device refuses the shape (n > 128, the 1-D families).  Returns Metro_sets' dict: chains (one Metro result per set),
+    device refuses the shape (n > 128; the 1-D families, unless gp was made with fused=True and n <= 32: then the kernel takes
+    them and the chains stay on the device).  Returns Metro_sets' dict: chains (one Metro result per set),
     device_batches (the calls made for the chains), laplace_calls."""
     C = len(D_trains)
     rngs = [np.random.default_rng(r) for r in (rngs if rngs is not None else [None] * C)]
@@ -695,7 +696,8 @@ def laplace_device_sets(gp, D_trains, ys, sigma2s, starts, theta1_pars=None, the
     per iteration, + p per shrink), which its maxiter rule reads.  starts is [C, p].
     on_device=False runs the same driver with every evaluation through the twin and every step through ccgp_nm_feed: the
     exact reference for the device search, and what the driver falls back to by itself where the device call says
-    CCGP_EUNSUPPORTED (n > 128, the Matern and spline families).  `logpost_sets_fn(rows, set_of) -> (val, beta)` replaces the
+    CCGP_EUNSUPPORTED (n > 128; the Matern and spline families, unless gp was made with fused=True and n <= 32).
+    `logpost_sets_fn(rows, set_of) -> (val, beta)` replaces the
     twin evaluator and keeps the search on the host.
     Returns one dict per set with laplace_sets' keys, plus fed: the evaluations the search made, and calls: the launches the
     set took part in + 1 (on the twin: its evaluator calls + 1)."""
@@ -980,7 +982,7 @@ def ordinary_kriging_sigma2(handle, D_train, y_train, starts=8, rng=0):
     return Q / n, theta, beta
 
 
-def matern_MLEs(handle, D, y, nu, grid=96, lo=1e-3, hi=1e2):
+def matern_MLEs(handle, D, y, nu, grid=96, lo=1e-3, hi=1e2, fused=False):
     """MLEs(D, y, nu) of the 1-D scripts (D1:455-471 = D1F:547-566): ordinary kriging with ONE Matern(nu) component;
     theta minimises log.likeli = log det R(theta) + n log sigma2.MLE(theta) (D1:424-444), then beta.MLE and sigma2.MLE
     at that theta (D1:467-468).  Combined.GP.fit feeds this sigma2 to the Combined-GP path (D1:994-995).
@@ -988,7 +990,8 @@ def matern_MLEs(handle, D, y, nu, grid=96, lo=1e-3, hi=1e2):
     The reference starts nlminb at runif(1) and retries until solve() succeeds; the optimiser's path is not
     reproducible (R's RNG), its optimum is.  Here the batched device likelihood (ccgp_loglik_batch, K = 1, Matern
     family) evaluates a log-spaced grid of `grid` scale parameters (scaled by the design's range) in two calls, which
-    brackets the global minimum; a bounded scalar search refines it inside the bracket.
+    brackets the global minimum; a bounded scalar search refines it inside the bracket.  fused=True: the calls run with
+    OPT_FAMILY_FUSED on (n <= 32: the register-resident evaluator in place of the blocked sweep, equal to rounding).
     Returns dict(beta, sigma2, theta)."""
     from scipy.optimize import minimize_scalar
     from . import api
@@ -997,7 +1000,7 @@ def matern_MLEs(handle, D, y, nu, grid=96, lo=1e-3, hi=1e2):
     D = np.asarray(D, dtype=np.float64).reshape(-1, 1)
     y = np.asarray(y, dtype=np.float64).ravel()
     n = D.shape[0]
-    h = _FamilyHandle(handle, api.KERNEL_MATERN, float(nu))
+    h = _FamilyHandle(handle, api.KERNEL_MATERN, float(nu), fused)
     span = max(float(D.max() - D.min()), 1e-12)
 
     def parts(thetas):

@@ -138,9 +138,24 @@ int ccgp_set_workspace_limit(ccgp_handle* h, size_t bytes);
  *                           (whole steps of the chip), there are no extra tile rows (likelihood and factor jobs), CCGP_OPT_FUSE_DIAG is
  *                           1 and 32-bit panel offsets fit; 2 = the same route whatever the number of matrices.  Block column
  *                           0 and everything else keep the update / trsm launches.  Same summation order: same bits.  Both
- *                           launches are timed under CCGP_T_UPDATE; CCGP_T_TRSM is then block column 0 alone. */
+ *                           launches are timed under CCGP_T_UPDATE; CCGP_T_TRSM is then block column 0 alone.
+ *   CCGP_OPT_FAMILY_FUSED   NOT a same-bits switch.  0 (default) = CCGP_KERNEL_MATERN and CCGP_KERNEL_MATERN_SPLINE exist on the
+ *                           blocked sweep only, and the chain and search entry points refuse them; 1 = at d = 1, 1 <= n <= 32
+ *                           (K <= 8; K = 2 for the two-family kernel) the register-resident evaluator generates the family's
+ *                           matrix itself -- the entries cov_kernel forms, from the direct difference x_i - x_j -- and serves
+ *                           ccgp_loglik_batch(_dev) in both mean modes, the value-only ccgp_logpost and ccgp_logpost_batch,
+ *                           ccgp_grid_marginal, ccgp_loglik_batch_sets, ccgp_logpost_sets, ccgp_chain_logpost_sets (one launch
+ *                           for all sets instead of a sweep per set), ccgp_metro_segments_sets and ccgp_laplace_search_sets
+ *                           (CCGP_OK instead of CCGP_EUNSUPPORTED: a chain or a search runs to its end inside one launch).  The
+ *                           elimination is another one than the sweep's, so the values agree with the option off to rounding,
+ *                           not in their bits; a pivot at or below the tolerance gives the 1-based pivot index and NaN as on
+ *                           the Gaussian route.  Everything else keeps its route and its refusals whatever the option says:
+ *                           prediction and kept factors, ccgp_logpost with R.Inv, the gradient, ccgp_profile_batch(_sets),
+ *                           leave-one-out, the device fits, kriging, designs, CGP, and every n > 32.  No effect under
+ *                           CCGP_KERNEL_GAUSS. */
 enum { CCGP_OPT_FUSE_DIAG = 2, CCGP_OPT_TAIL_STRIPS = 3, CCGP_OPT_WIDE_OFFSETS = 4, CCGP_OPT_SMALL_GRID16 = 5,
-       CCGP_OPT_SCHED = 7, CCGP_OPT_SCHED_POLICY = 8, CCGP_OPT_PREDICT_FACTOR = 9, CCGP_OPT_FUSED_SOLVE = 10 };
+       CCGP_OPT_SCHED = 7, CCGP_OPT_SCHED_POLICY = 8, CCGP_OPT_PREDICT_FACTOR = 9, CCGP_OPT_FUSED_SOLVE = 10,
+       CCGP_OPT_FAMILY_FUSED = 11 };
 int ccgp_set_option(ccgp_handle* h, int option, int value);
 /* pre-size scratch so that later _dev calls of this shape (or of fewer draws B or test sites m), under the kernel family,
  * options and workspace limit in force now, never allocate, synchronise or create a stream or an event.  Covers: the
@@ -307,7 +322,8 @@ int ccgp_logpost_sets(ccgp_handle* h, const double* Xs, int n, int d, const doub
  *   Arguments.  CCGP_EINVAL before anything is copied or launched, outputs untouched: bad shapes, a NULL required pointer,
  *     an unknown prior (prior_pars as ccgp_logpost_batch), C < 1, A < 0, T < 1, M < 1, set[a] outside 0 .. C-1, n_prop[a]
  *     outside 0 .. T, stop_acc[a] outside 0 .. M, a partial trace.  CCGP_EUNSUPPORTED, outputs untouched, where the sets
- *     likelihood has no one-launch route: n > 128, the Matern and spline families, a shape whose instance does not fit.
+ *     likelihood has no one-launch route: n > 128, the Matern and spline families (served at d = 1, n <= 32 under
+ *     CCGP_OPT_FAMILY_FUSED), a shape whose instance does not fit.
  *     A == 0 returns CCGP_OK.
  * Host pointers only, blocking; ccgp_reserve does not cover the staging. */
 int ccgp_chain_terms(int prior_id, int d, const double* theta_t /* B x q */, int B, const double* prior_pars,
@@ -445,7 +461,8 @@ int ccgp_profile_fit_sets(ccgp_handle* h, const double* Xs, int n, int d, const 
  *     as ccgp_logpost_batch), C < 1, A < 0, T < 0, set[a] outside 0 .. C-1, max_evals[a] outside 0 .. min(T, 4096), a partial
  *     trace, a NULL required pointer (everything but the trace and prior_pars), a state whose recorded q is not the prior's.
  *     CCGP_EUNSUPPORTED, outputs untouched, where ccgp_metro_segments_sets has no route or the search's words do not fit
- *     behind its carve: n > 128, the Matern and spline families.  A == 0 returns CCGP_OK.  A search that is not running, or
+ *     behind its carve: n > 128, the Matern and spline families (served at d = 1, n <= 32 under CCGP_OPT_FAMILY_FUSED).
+ *     A == 0 returns CCGP_OK.  A search that is not running, or
  *     whose max_evals is 0, is returned as it came.
  * Host pointers only, blocking; ccgp_reserve does not cover the staging.  Not in this version: the Hessian points inside the
  * launch, _dev variants, a ccgp_multi wrapper, an R shim. */
