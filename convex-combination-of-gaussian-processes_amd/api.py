@@ -21,6 +21,7 @@ KERNEL_GAUSS, KERNEL_MATERN, KERNEL_MATERN_SPLINE = 0, 1, 2
 OPT_FUSE_DIAG, OPT_TAIL_STRIPS, OPT_WIDE_OFFSETS, OPT_SMALL_GRID16 = 2, 3, 4, 5
 OPT_SCHED, OPT_SCHED_POLICY, OPT_PREDICT_FACTOR, OPT_FUSED_SOLVE = 7, 8, 9, 10
 OPT_FAMILY_FUSED = 11   # the 1-D families on the register-resident evaluator at n <= 32 (default 0: the blocked sweep)
+OPT_FAMILY_FUSED_PREDICT = 12   # their prediction and leave-one-out on that evaluator (default 0; independent of option 11)
 VAR_ORDINARY, VAR_PLUGIN, VAR_UNBIASED = 0, 1, 2   # ccgp_krige_predict_batch's var_form
 TIMING_NAMES = ("cov", "update", "diag", "trsm", "solve", "fused", "sweep")
 

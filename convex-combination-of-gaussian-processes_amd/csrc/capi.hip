@@ -214,9 +214,22 @@ int pull(ccgp_handle* h, Pieces ps, size_t pin_max = kPinMax) {
 }
 
 // the `gauss` flag of the four route decisions the fused family evaluators serve (CCGP_OPT_FAMILY_FUSED: Op::Loglik,
-// small_route_sets, small_route_chain, small_route_nm); every other decision asks `fam.id == 0`
+// small_route_sets, small_route_chain, small_route_nm); every other decision asks `fam.id == 0`, but for prediction and
+// leave-one-out under their own option (gauss_or_fused_predict, gauss_or_fused_loo below)
 bool gauss_or_fused(const ccgp_handle* h, int n, int d, int K) {
   return h->fam.id == 0 || (h->opt_family_fused != 0 && small_family_fused_supported(h->fam.id, n, d, K));
+}
+
+// the `gauss` flags of a prediction and of leave-one-out (CCGP_OPT_FAMILY_FUSED_PREDICT): what predict_run and loo_run pass
+// to small_route(Op::Predict) / kept_factor_ws_bytes and to small_route_loo, and what ccgp_reserve asks.  `fam` is the
+// call's family (a factor set keeps its own).  A family has the kept-factor scheme only, so without
+// CCGP_OPT_PREDICT_FACTOR its prediction stays on the sweep.
+bool gauss_or_fused_predict(const ccgp_handle* h, const KernelFamily& fam, int n, int d, int K) {
+  return fam.id == 0 || (h->opt_family_fused_predict != 0 && h->opt_predict_factor != 0 &&
+                         small_family_fused_predict_supported(fam.id, n, d, K));
+}
+bool gauss_or_fused_loo(const ccgp_handle* h, const KernelFamily& fam, int n, int d, int K) {
+  return fam.id == 0 || (h->opt_family_fused_predict != 0 && small_family_fused_loo_supported(fam.id, n, d, K));
 }
 
 bool bad_shape(int n, int d, int K) {
@@ -910,6 +923,10 @@ int ccgp_set_option(ccgp_handle* h, int option, int value) try {
     h->opt_family_fused = value;
     return CCGP_OK;
   }
+  if (option == CCGP_OPT_FAMILY_FUSED_PREDICT && (value == 0 || value == 1)) {
+    h->opt_family_fused_predict = value;
+    return CCGP_OK;
+  }
   return fail(h, CCGP_EINVAL, "ccgp_set_option: unknown option or value");
 } CCGP_GUARD_END(h)
 
@@ -924,7 +941,8 @@ int ccgp_reserve(ccgp_handle* h, int n, int d, int K, int B, int m) try {
   CCGP_HIP(hipSetDevice(h->device));
   // the sweep's workspace where the likelihood or, with test sites, the prediction of this shape takes the sweep (a
   // prediction on the register-resident evaluator implies the likelihood there: its instance is the larger one)
-  const bool gauss = h->fam.id == 0;
+  // (a 1-D family under CCGP_OPT_FAMILY_FUSED_PREDICT: the flag predict_run passes)
+  const bool gauss = gauss_or_fused_predict(h, h->fam, n, d, K);
   const bool sweep_predict = m > 0 && small_route(Op::Predict, gauss, n, d, K) == Route::Blocked;
   if (sweep_predict || small_route(Op::Loglik, gauss_or_fused(h, n, d, K), n, d, K) == Route::Blocked) {
     int nbc = 0;
@@ -2195,7 +2213,21 @@ static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const dou
                        const double* dXtest, int m, double sigma2, double* d_mean, double* d_var, double* d_beta,
                        int* d_status, VarForm vf = VarForm{}) {
   const int K = dv.K, S = dv.ldp;
-  if (small_route(Op::Predict, dv.fam.id == 0, n, d, K) == Route::Blocked) {
+  // a 1-D family under CCGP_OPT_FAMILY_FUSED_PREDICT has the kept-factor scheme and nothing else (no FAM instance carries
+  // extra rows): its scratch is secured BEFORE the route is taken, and without it the call is the sweep's
+  const bool family = dv.fam.id != 0;
+  bool gauss = gauss_or_fused_predict(h, dv.fam, n, d, K);
+  void* scratch = nullptr;
+  size_t sbytes = 0;
+  if (family && gauss) {
+    const size_t want = kept_factor_ws_bytes(h, gauss, n, d, K, S, m);
+    if (want && ensure(h, h->ws, kWorkspace, want) == CCGP_OK && h->ws.bytes >= small_reg_sites_scratch(n, d, K, m)) {
+      scratch = h->ws.ptr; sbytes = h->ws.bytes;
+    } else {
+      gauss = false;
+    }
+  }
+  if (small_route(Op::Predict, gauss, n, d, K) == Route::Blocked) {
     // the m cross-correlation rows ride along as extra tile rows of the sweep; scratch for the outputs the caller did not
     // ask for lives behind the matrices
     SweepOut sc{};
@@ -2208,12 +2240,11 @@ static int predict_run(ccgp_handle* h, const double* dX, int n, int d, const dou
     ScopedTimer t(h, CCGP_T_FUSED);
     // kept-factor scheme where it applies (n <= 104, K <= 3) and its scratch fits the workspace.  After ccgp_reserve of
     // this shape both steps find what they need; a caller that never reserved pays for them here, once.
-    void* scratch = nullptr;
-    size_t sbytes = 0;
-    if (const size_t want = kept_factor_ws_bytes(h, dv.fam.id == 0, n, d, K, S, m)) {
-      if (ensure(h, h->ws, kWorkspace, want) == CCGP_OK) { scratch = h->ws.ptr; sbytes = h->ws.bytes; }
-      if (scratch) (void)ensure_aux(h);
+    if (!family) {
+      if (const size_t want = kept_factor_ws_bytes(h, true, n, d, K, S, m))
+        if (ensure(h, h->ws, kWorkspace, want) == CCGP_OK) { scratch = h->ws.ptr; sbytes = h->ws.bytes; }
     }
+    if (scratch) (void)ensure_aux(h);
     launch_small_reg_predict(h->stream, dX, n, d, dy, dv, S, dXtest, m, sigma2, d_mean, d_var, d_beta,
                              d_status, scratch, sbytes, h->aux_stream, h->aux_fork, h->aux_join, vf);
   }
@@ -2334,7 +2365,7 @@ int ccgp_predict_summary(ccgp_handle* h, const double* X, int n, int d, const do
 static int loo_run(ccgp_handle* h, const double* dX, int n, int d, const double* dy, const DrawView& dv, double sigma2,
                    VarForm vf, double* d_mean, double* d_var, double* d_beta, int* d_status) {
   const int K = dv.K, B = dv.ldp;
-  if (small_route_loo(dv.fam.id == 0, n, d, K) == Route::Blocked) {
+  if (small_route_loo(gauss_or_fused_loo(h, dv.fam, n, d, K), n, d, K) == Route::Blocked) {
     const int npad = round_up(n, kTile);
     SweepOut sc{};
     BlockedJob job{};

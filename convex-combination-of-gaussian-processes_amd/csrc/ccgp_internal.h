@@ -74,6 +74,7 @@ struct ccgp_handle {
   int opt_wide_offsets = 0;             // CCGP_OPT_WIDE_OFFSETS
   int opt_fused_solve = 1;              // CCGP_OPT_FUSED_SOLVE: 0 = update + trsm launches, 1 = diagonal launch + tiles solved in the update workgroup where the batch fills whole steps, 2 = wherever possible
   int opt_family_fused = 0;             // CCGP_OPT_FAMILY_FUSED: 1 = the 1-D families take the register-resident evaluator where small_family_fused_supported says so
+  int opt_family_fused_predict = 0;     // CCGP_OPT_FAMILY_FUSED_PREDICT: 1 = their prediction and leave-one-out too (small_family_fused_predict_supported / _loo_supported)
   int opt_sched = 3;                    // CCGP_OPT_SCHED: 0 = one launch per phase and block column, 1 = dataflow scheduler with two workgroups per CU, 2 = with one, 3 = by chunk size
   int opt_sched_policy = 11;            // CCGP_OPT_SCHED_POLICY bit 0: a CU's second workgroup only takes work while a backlog exists; bit 1: XCD-local synchronisation
   int sched_timeout_ms = 30000;         // a scheduler wait longer than this aborts the sweep (CCGP_SCHED_TIMEOUT_MS)

@@ -315,6 +315,20 @@ inline bool small_family_fused_supported(int family, int n, int d, int K) {
   if (K < 1 || K > kMaxK || (family == 2 && K != 2)) return false;
   return small_reg_supported(n, d, K) && small_reg_sets_supported(n, d, K) && lds_fits(reg_nm_lds_doubles((n + 15) / 16, n, d, K));
 }
+// prediction and leave-one-out of the 1-D families on the same evaluator (CCGP_OPT_FAMILY_FUSED_PREDICT, an option of its
+// own: option 11 keeps moving exactly what it moved).  Prediction has the kept-factor scheme only -- the FAM instances that
+// keep their factor (FAC), site_corr_family_kernel for the test sites' correlation vectors and site_solve_kernel as it is --
+// so its domain is the likelihood's cut by small_reg_sites_supported (K <= 3); no FAM instance carries extra rows.
+// Leave-one-out is the fourth inverse instance (INV = 4) compiled with FAM, on the carve of the other inverse instances; a
+// fold needs another point.  capi.hip passes `gauss || (option && these)` to small_route(Op::Predict) -- together with
+// CCGP_OPT_PREDICT_FACTOR, without which a family stays on the sweep -- and to small_route_loo, and nothing else: both are Reg
+// there (tests/host_small/family_fused_predict_layout_check.cpp).
+inline bool small_family_fused_predict_supported(int family, int n, int d, int K) {
+  return small_family_fused_supported(family, n, d, K) && small_reg_sites_supported(n, d, K);
+}
+inline bool small_family_fused_loo_supported(int family, int n, int d, int K) {
+  return small_family_fused_supported(family, n, d, K) && small_reg_inverse_supported(n, d, K) && n >= 2;
+}
 
 // the maximum-entropy design search on the device (ccgp_design_fit): the DFIT instances are the design-gradient instances
 // (INV = 3, per-design carve), one workgroup per start.  A start's variables are the free rows of its design in the order

@@ -234,12 +234,17 @@ __device__ __forceinline__ void mat_sync() {
 // CHAIN / NM: what chain_rate writes); us[] and the expanded distance are not formed.  Everything after the generation phase
 // is the instance's code unchanged.  Compiled for n <= 32 only (small_family_fused_supported): NB <= 2 on the 16 x 16 grid,
 // NB <= 4 on the 8 x 8, general (non-FULL) instances.
+// FAM with FAC, and FAM with INV = 4 (CCGP_OPT_FAMILY_FUSED_PREDICT): the same generation phase in front of the instance that
+// keeps its factor for a prediction (both grids; the test sites' correlation vectors come from site_corr_family_kernel) and of
+// the leave-one-out instance (16 x 16 grid).  Neither epilogue reads us[] or th[], so both run as they are.  No FAM instance
+// carries extra rows (NE > 1 without INV): a family's prediction is the kept-factor scheme or the blocked sweep.
 template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false,
           bool CHAIN = false, bool FIT = false, bool NM = false, bool DFIT = false, bool FAM = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
-  static_assert(!FAM || (NE == 1 && !INV && !PROF && !FAC && !FULL && !FIT && !DFIT && G * NB <= kFamilyFusedMaxN),
-                "a 1-D family is generated by the general plain-likelihood instance (with or without SETS / CHAIN / NM) at n <= 32");
+  static_assert(!FAM || (((NE == 1 && !INV) || INV == 4) && !PROF && !FULL && !FIT && !DFIT && G * NB <= kFamilyFusedMaxN),
+                "a 1-D family is generated by the general plain-likelihood instance (with or without SETS / CHAIN / NM, or keeping "
+                "its factor) and by the leave-one-out instance, at n <= 32");
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
   static_assert(!FAC || (NE == 1 && !FULL && !INV), "the factor is kept by the plain likelihood instantiation");
   static_assert(!PROF || ((NE == 1 || INV == 2) && INV != 1 && INV != 3 && !FAC), "sigma2 is concentrated out of the likelihood and of its gradient only");
@@ -1232,6 +1237,13 @@ void launch_one(hipStream_t s, const RegArgs& a) {
       });
       if (a.set) kernel = small_reg_kernel<G, NB, 1, false, 0, false, false, true, false, false, false, false, true>;
       else kernel = small_reg_kernel<G, NB, 1, false, 0, false, false, false, false, false, false, false, true>;
+      if (a.fac && !a.set) {   // CCGP_OPT_FAMILY_FUSED_PREDICT: the instance that keeps its factor for site_solve_kernel
+        static unsigned long long fam_fac_mask = 0;
+        once_per_device(fam_fac_mask, [] {
+          raise_lds_limit((const void*)small_reg_kernel<G, NB, 1, false, 0, true, false, false, false, false, false, false, true>, "small_reg_kernel<family, fac>");
+        });
+        kernel = small_reg_kernel<G, NB, 1, false, 0, true, false, false, false, false, false, false, true>;
+      }
     } else {
       no_family_instance();
       return;
@@ -1346,6 +1358,42 @@ __global__ __launch_bounds__(256, 4) void site_corr_kernel(SiteArgs a) {
       }
     }
   }
+}
+
+// The 1-D families' counterpart (CCGP_OPT_FAMILY_FUSED_PREDICT; d = 1): the same rs layout -- per (draw, batch of 64 sites)
+// npf x 64 doubles, row i at stride 64, lane = site -- with the entries cov_kernel<1> forms for a cross block: per component q
+// ascending, rate_q = theta_to_rate(theta_q), h = x_t - x_i from the direct difference, fma(w_q^2, corr(rate_q (h h)), acc);
+// then acc / sum w^2 as site_corr_kernel divides, or, under the two-family kernel, acc as it is (corr.vec.combined never
+// divides, D1F:479: cov.hip's raw_mix).  An entry costs the Matern quadrature (130 - 190 terms of three exp each), so the
+// mapping spreads ENTRIES, not sites: one wave = one (draw, site batch, training row i), four rows per workgroup, grid
+// (nbatch ceil(n / 4), draws) -- all n rows on one wave would leave a single-model call (S = 1, m = 50) as one wave running
+// n K quadratures in sequence.  The parameters are wave-uniform reads of the draw's row.  family_corr is the body the matrix
+// entries call: cross entries and matrix entries share one compiled quadrature.  Lanes with t >= m compute a valid site that
+// nobody reads; rows n .. npf - 1 are not written (site_solve_kernel masks them).  No LDS, no barrier; every loop is bounded
+// (K <= 3 components, matern_corr's 6000-term cap).  Needs nothing from the factorisation: runs beside it.
+__global__ __launch_bounds__(256) void site_corr_family_kernel(SiteArgs a, KernelFamily fam) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int n = a.n, m = a.m, K = a.K, nbatch = a.nbatch, npf = a.npf;
+  const int nrb = (n + 3) / 4;                       // groups of four training rows
+  const int batch = blockIdx.x / nrb, i = (blockIdx.x % nrb) * 4 + wave;
+  const int b = blockIdx.y, gb = a.draw0 + b;
+  if (i >= n || batch >= nbatch) return;             // (wave-uniform; nothing below waits for another wave)
+  const int t = batch * 64 + lane;
+  const int tc = t < m ? t : m - 1;
+  const double h = a.Xt[tc] - a.X[i];
+  const double h2 = h * h;
+  double sw = 0.0, acc = 0.0;
+  for (int q = 0; q < K; ++q) {
+    const double w = a.params[gb + (size_t)q * a.ldp];
+    sw += w * w;
+  }
+  for (int q = 0; q < K; ++q) {
+    const double w = a.params[gb + (size_t)q * a.ldp];
+    const double rate = theta_to_rate(fam, a.params[gb + (size_t)(K + q) * a.ldp], q);
+    acc = fma(w * w, family_corr(fam.id, fam.nu, fam.norm, rate * h2, q), acc);
+  }
+  a.rs[(((size_t)b * nbatch + batch) * npf + i) * 64 + lane] = fam.id == CCGP_KERNEL_MATERN_SPLINE ? acc : acc / sw;
 }
 
 // One workgroup per (draw, group of up to four batches of 64 test sites), one wave per batch.  The draw's factor block comes
@@ -1488,7 +1536,11 @@ static dim3 site_grid(int nbatch, int ns, int* wpb) {
   *wpb = nbatch < 4 ? nbatch : 4;                                  // waves (site batches) per workgroup
   return dim3((nbatch + *wpb - 1) / *wpb, ns);
 }
-static void launch_site_corr(hipStream_t s, const SiteArgs& a, int ns) {
+static void launch_site_corr(hipStream_t s, const SiteArgs& a, int ns, const KernelFamily& fam) {
+  if (fam.id != 0) {   // a 1-D family: one wave per (draw, site batch, training row)
+    hipLaunchKernelGGL(site_corr_family_kernel, dim3((unsigned)a.nbatch * (unsigned)((a.n + 3) / 4), ns), dim3(256), 0, s, a, fam);
+    return;
+  }
   int wpb;
   const dim3 grid = site_grid(a.nbatch, ns, &wpb), block(64 * wpb);
   const size_t lds = sizeof(double) * SiteCorrCarve(a.npf, a.d, a.K, wpb).total;
@@ -1523,12 +1575,26 @@ static void launch_inv(hipStream_t s, const RegArgs& a) {
                     INV == 3 ? "small_reg_kernel<design gradient>" : "small_reg_kernel<leave-one-out>");
   });
   const size_t lds = sizeof(double) * reg_lds_doubles(16, NB, NB + 1, true, a.x_stride != 0, a.n, a.d, a.K);
+  void (*kernel)(RegArgs) = small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF, SETS>;
+  if (a.fam.id != 0) {   // a 1-D family (CCGP_OPT_FAMILY_FUSED_PREDICT): the leave-one-out instance compiled with FAM
+    if constexpr (INV == 4 && !PROF && !SETS && 16 * NB <= kFamilyFusedMaxN) {
+      static unsigned long long fam_mask = 0;
+      once_per_device(fam_mask, [] {
+        raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, 4, false, false, false, false, false, false, false, true>,
+                        "small_reg_kernel<family, leave-one-out>");
+      });
+      kernel = small_reg_kernel<16, NB, NB + 1, false, 4, false, false, false, false, false, false, false, true>;
+    } else {
+      no_family_instance();
+      return;
+    }
+  }
   const int kMaxGrid = 1 << 20;
   RegArgs c = a;
   for (int b0 = 0; b0 < a.B; b0 += kMaxGrid) {
     c.draw0 = a.draw0 + b0;
     c.B = a.B - b0 < kMaxGrid ? a.B - b0 : kMaxGrid;
-    hipLaunchKernelGGL((small_reg_kernel<16, NB, NB + 1, false, INV, false, PROF, SETS>), dim3(c.B, 1), dim3(256), lds, s, c);
+    hipLaunchKernelGGL(kernel, dim3(c.B, 1), dim3(256), lds, s, c);
   }
 }
 template <int INV, bool PROF = false, bool SETS = false>
@@ -1737,7 +1803,7 @@ void launch_small_reg_loo(hipStream_t s, const double* X, int n, int d, const do
                           VarForm vf, double* mean, double* var, double* beta, int* status) {
   RegArgs a = reg_args(X, n, d, y, dv);
   a.B = B; a.sigma2 = sigma2; a.vf = vf;
-  a.beta = beta; a.status = status; a.mean = mean; a.var = var; a.S = B;
+  a.beta = beta; a.status = status; a.mean = mean; a.var = var; a.S = B; a.fam = dv.fam;
   dispatch_inv<4>(s, a);
 }
 
@@ -1796,7 +1862,7 @@ void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, cons
                               hipEvent_t ev_fork, hipEvent_t ev_join, VarForm vf) {
   RegArgs a = reg_args(X, n, d, y, dv);
   a.B = S; a.sigma2 = sigma2; a.vf = vf;
-  a.beta = beta; a.status = status; a.Xt = Xtest; a.m = m; a.S = S; a.mean = mean; a.var = var;
+  a.beta = beta; a.status = status; a.Xt = Xtest; a.m = m; a.S = S; a.mean = mean; a.var = var; a.fam = dv.fam;
   const size_t per = small_reg_sites_scratch(n, d, dv.K, m);
   if (scratch && small_reg_sites_supported(n, d, dv.K) && scratch_bytes >= per) {
     const FacLayout fl(n);
@@ -1812,10 +1878,10 @@ void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, cons
       if (aux && ev_fork && ev_join) {
         (void)hipEventRecord(ev_fork, s);
         (void)hipStreamWaitEvent(aux, ev_fork, 0);
-        launch_site_corr(aux, sa, ns);
+        launch_site_corr(aux, sa, ns, dv.fam);
         (void)hipEventRecord(ev_join, aux);
       } else {
-        launch_site_corr(s, sa, ns);
+        launch_site_corr(s, sa, ns, dv.fam);
       }
       RegArgs f = a;
       f.Xt = nullptr; f.m = 0; f.mean = f.var = nullptr;
@@ -1828,6 +1894,8 @@ void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, cons
     }
     return;
   }
+  // (a 1-D family never comes here: predict_run secures the scratch before it takes this route, and launch_one has no
+  // extra-row instance to give it)
   dispatch<kPredictNE>(s, a);
 }
 

@@ -793,12 +793,14 @@ def _t_interval(y_hat, var, alpha, n):
     return y_hat - delta, y_hat + delta
 
 
-def prediction_single(handle, D_train, D_new, y_train, MLE, alpha, nu=None):
+def prediction_single(handle, D_train, D_new, y_train, MLE, alpha, nu=None, fused_predict=False):
     """prediction.single of the 1-D scripts (D1:548-567 = D1F:872-889) on the device: y.hat.single, and LL / UL.Single with
     single.var from CIs.single (D1:527-539), whose post.stdev.single^2 = Q / (n - 1) post.var.single / sigma2 (D1:504-516) is
     ccgp_krige_predict_batch's VAR_UNBIASED.  With nu: one Matern(nu) component at the scalar MLE["theta"] (what matern_MLEs
     returns).  Without: a Gaussian single GP whose MLE["theta"] holds d scales (ordinary_kriging_fit's).  beta is the
-    profile beta at theta, as MLEs() forms it (D1:467).  Returns dict(y_hat_single, LL_single, UL_single, single_var)."""
+    profile beta at theta, as MLEs() forms it (D1:467).  fused_predict=True (with nu): the call runs with
+    OPT_FAMILY_FUSED_PREDICT on (n <= 32: the register-resident evaluator in place of the blocked sweep, equal to rounding).
+    Returns dict(y_hat_single, LL_single, UL_single, single_var)."""
     D = np.asarray(D_train, dtype=np.float64)
     D = D.reshape(-1, 1) if D.ndim == 1 else D
     Dn = np.asarray(D_new, dtype=np.float64).reshape(-1, D.shape[1])
@@ -809,7 +811,7 @@ def prediction_single(handle, D_train, D_new, y_train, MLE, alpha, nu=None):
     h = handle
     if nu is not None:
         from .rsurface import _FamilyHandle
-        h = _FamilyHandle(getattr(handle, "_handle", handle), api.KERNEL_MATERN, float(nu))
+        h = _FamilyHandle(getattr(handle, "_handle", handle), api.KERNEL_MATERN, float(nu), fused_predict=fused_predict)
     mean, var, _, _, st = h.krige_predict_batch(D, y, 1, np.concatenate([[1.0], theta])[None], None, Dn, api.VAR_UNBIASED)
     if st[0] != 0:
         raise RuntimeError("prediction_single: the correlation matrix could not be factorised (pivot %d)" % st[0])
@@ -821,7 +823,8 @@ def _single_model(gp, D_train, y_train, single):
     """The single-GP comparator of compare_GP and leave_one_out: the model `single` gives (theta, sigma2[, beta], or est = a
     fit routine's dict, which goes into the table as it is) or, without one, the fit on the device (matern_MLEs for a 1-D gp,
     ordinary_kriging_fit otherwise; further keys of `single` go to it).  Returns (model, handle, D, sigma2 argument,
-    variance form): the 1-D scripts take the unbiased form under the Matern family, the others the plug-in form."""
+    variance form): the 1-D scripts take the unbiased form under the Matern family, the others the plug-in form.  A 1-D gp
+    made with fused_predict=True hands that on to the single GP's handle."""
     base = getattr(gp.h, "_handle", gp.h)
     given = dict(single) if isinstance(single, dict) else {}
     model = {k: given.pop(k) for k in ("theta", "sigma2", "beta") if k in given}
@@ -832,7 +835,8 @@ def _single_model(gp, D_train, y_train, single):
         D = np.asarray(D_train, dtype=np.float64).reshape(-1, 1)
         if "theta" not in model:
             model = matern_MLEs(base, D, y_train, gp.nu, **given)
-        return model, _FamilyHandle(base, api.KERNEL_MATERN, float(gp.nu)), D, None, api.VAR_UNBIASED
+        h = _FamilyHandle(base, api.KERNEL_MATERN, float(gp.nu), fused_predict=getattr(gp, "fused_predict", False))
+        return model, h, D, None, api.VAR_UNBIASED
     D = np.asarray(D_train, dtype=np.float64)
     if "theta" not in model or "sigma2" not in model:
         model = ordinary_kriging_fit(base, D, y_train, **given)

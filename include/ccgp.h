@@ -152,10 +152,24 @@ int ccgp_set_workspace_limit(ccgp_handle* h, size_t bytes);
  *                           the Gaussian route.  Everything else keeps its route and its refusals whatever the option says:
  *                           prediction and kept factors, ccgp_logpost with R.Inv, the gradient, ccgp_profile_batch(_sets),
  *                           leave-one-out, the device fits, kriging, designs, CGP, and every n > 32.  No effect under
- *                           CCGP_KERNEL_GAUSS. */
+ *                           CCGP_KERNEL_GAUSS.  (Prediction and leave-one-out have an option of their own, below.)
+ *   CCGP_OPT_FAMILY_FUSED_PREDICT  NOT a same-bits switch, and independent of CCGP_OPT_FAMILY_FUSED.  0 (default) = prediction
+ *                           and leave-one-out of the two 1-D families run on the blocked sweep; 1 = inside the domain of
+ *                           CCGP_OPT_FAMILY_FUSED (d = 1, n <= 32; K = 2 for the two-family kernel) the register-resident
+ *                           evaluator serves ccgp_predict_batch(_dev), ccgp_predict_summary(_dev) and ccgp_krige_predict_batch
+ *                           in its three variance forms at K <= 3 by the kept-factor scheme -- one factorisation per draw, the
+ *                           test sites' correlation vectors from the direct difference x_t - x_i (under the two-family kernel
+ *                           NOT divided by sum w^2, as corr.vec.combined is written), one lane per site -- and
+ *                           ccgp_loo_batch and ccgp_loo_summary at n >= 2 from one factorisation per draw.  A family has no
+ *                           extra-row scheme: with CCGP_OPT_PREDICT_FACTOR = 0, or where the kept factor's scratch cannot be
+ *                           had, a prediction stays on the sweep with the sweep's bits.  Values agree with the option off to
+ *                           rounding; a site's column does not depend on the other sites, a draw's row not on the other
+ *                           draws; a failed pivot gives the 1-based index and NaN rows as on the Gaussian route.  Nothing else
+ *                           moves: ccgp_factor_batch and factor sets, R.Inv, the gradient, the profiled mode, the device fits,
+ *                           n > 32 and K > 3 keep their routes.  No effect under CCGP_KERNEL_GAUSS. */
 enum { CCGP_OPT_FUSE_DIAG = 2, CCGP_OPT_TAIL_STRIPS = 3, CCGP_OPT_WIDE_OFFSETS = 4, CCGP_OPT_SMALL_GRID16 = 5,
        CCGP_OPT_SCHED = 7, CCGP_OPT_SCHED_POLICY = 8, CCGP_OPT_PREDICT_FACTOR = 9, CCGP_OPT_FUSED_SOLVE = 10,
-       CCGP_OPT_FAMILY_FUSED = 11 };
+       CCGP_OPT_FAMILY_FUSED = 11, CCGP_OPT_FAMILY_FUSED_PREDICT = 12 };
 int ccgp_set_option(ccgp_handle* h, int option, int value);
 /* pre-size scratch so that later _dev calls of this shape (or of fewer draws B or test sites m), under the kernel family,
  * options and workspace limit in force now, never allocate, synchronise or create a stream or an event.  Covers: the
