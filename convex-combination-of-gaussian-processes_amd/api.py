@@ -22,6 +22,7 @@ OPT_FUSE_DIAG, OPT_TAIL_STRIPS, OPT_WIDE_OFFSETS, OPT_SMALL_GRID16 = 2, 3, 4, 5
 OPT_SCHED, OPT_SCHED_POLICY, OPT_PREDICT_FACTOR, OPT_FUSED_SOLVE = 7, 8, 9, 10
 OPT_FAMILY_FUSED = 11   # the 1-D families on the register-resident evaluator at n <= 32 (default 0: the blocked sweep)
 OPT_FAMILY_FUSED_PREDICT = 12   # their prediction and leave-one-out on that evaluator (default 0; independent of option 11)
+OPT_FAMILY_FUSED_GRAD = 13   # their analytic gradient and profiled mode on that evaluator (default 0; independent of 11 and 12)
 VAR_ORDINARY, VAR_PLUGIN, VAR_UNBIASED = 0, 1, 2   # ccgp_krige_predict_batch's var_form
 TIMING_NAMES = ("cov", "update", "diag", "trsm", "solve", "fused", "sweep")
 
@@ -44,6 +45,7 @@ SIGNATURES = {
     "ccgp_corr_cross": (c_int, [c_void_p, _dp, c_int, _dp, c_int, c_int, _dp, _dp]),
     "ccgp_mixed_corr_matrix": (c_int, [c_void_p, _dp, c_int, c_int, c_int, _dp, _dp]),
     "ccgp_mixed_corr_cross": (c_int, [c_void_p, _dp, c_int, _dp, c_int, c_int, c_int, _dp, _dp]),
+    "ccgp_family_corr_dtheta": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp]),
     "ccgp_beta_mle": (c_int, [c_void_p, _dp, _dp, c_int, _dp]),
     "ccgp_sigma2_mle": (c_int, [c_void_p, _dp, _dp, c_int, c_double, _dp]),
     "ccgp_loglik_batch": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, c_int, c_double,
@@ -634,6 +636,17 @@ class Handle:
         self._chk(lib().ccgp_mixed_corr_cross(self._h, _p(Xnew), m, _p(X), n, d, K, _p(row), _p(out)))
         return out
 
+    def family_corr_dtheta(self, X, K, params_row, q):
+        """ccgp_family_corr_dtheta: d R_q / d theta_q of component q (0-based) under the 1-D family in force, entry by
+        entry -- the derivative the gradient under OPT_FAMILY_FUSED_GRAD sums.  X: n coordinates; params_row: the 2 K
+        doubles (weights, thetas).  Returns the n x n table."""
+        x = _f(np.ravel(X))
+        n = x.size
+        row = _f(params_row, (2 * K,))
+        out = np.empty((n, n), dtype=np.float64, order="F")
+        self._chk(lib().ccgp_family_corr_dtheta(self._h, _p(x), n, K, _p(row), int(q), _p(out)))
+        return out
+
     # -- a6, a7, a10, a11 (explicit R.Inv forms) ---------------------------------------
     def beta_mle(self, R_inv, y):
         R_inv, y = _f(R_inv), _f(np.ravel(y))
@@ -706,7 +719,8 @@ class Handle:
     def profile_batch(self, X, y, K, params, grad=False):
         """ccgp_profile_batch: the likelihood with sigma2 concentrated out (ordinary kriging), one factorisation per
         draw.  params: [B, K + K*d].  Returns (loglik[B], sigma2[B], beta[B], grad[B, P] or None, status[B]); grad is
-        d loglik / d params at each draw's own (beta, sigma2) and needs the Gaussian family."""
+        d loglik / d params at each draw's own (beta, sigma2) and needs the Gaussian family, or a 1-D family at n <= 32
+        with OPT_FAMILY_FUSED_GRAD on."""
         X, y = _f(X), _f(np.ravel(y))
         n, d = X.shape
         params = _f(np.atleast_2d(params))

@@ -231,6 +231,14 @@ bool gauss_or_fused_predict(const ccgp_handle* h, const KernelFamily& fam, int n
 bool gauss_or_fused_loo(const ccgp_handle* h, const KernelFamily& fam, int n, int d, int K) {
   return fam.id == 0 || (h->opt_family_fused_predict != 0 && small_family_fused_loo_supported(fam.id, n, d, K));
 }
+// the `gauss` flag of ccgp_loglik_grad_batch, ccgp_profile_batch and ccgp_profile_batch_sets (CCGP_OPT_FAMILY_FUSED_GRAD): what
+// grad_call and grad_run pass to small_route(Op::Grad) with a gradient and to small_route(Op::Loglik) for the value-only
+// profiled call, and what ccgp_profile_batch_sets passes to small_route_profile_grad_sets.  With a gradient, false is a refusal.
+bool gauss_or_fused_grad(const ccgp_handle* h, const KernelFamily& fam, int n, int d, int K, bool grad) {
+  if (fam.id == 0) return true;
+  if (h->opt_family_fused_grad == 0) return false;
+  return grad ? small_family_fused_grad_supported(fam.id, n, d, K) : small_family_fused_profile_supported(fam.id, n, d, K);
+}
 
 bool bad_shape(int n, int d, int K) {
   return n < 1 || d < 1 || d > kMaxD || K < 1 || K > kMaxK;
@@ -334,12 +342,13 @@ int loglik_dev(ccgp_handle* h, const double* dX, int n, int d, const double* dy,
 // The value and gradient of the B >= 1 draws of dv on resident inputs, the counterpart of loglik_run.  o.s2hat set: the
 // profiled mode -- sigma2 is not read, the evaluation runs at 1.0 and leaves each draw's sigma2_hat there.  o.grad ==
 // nullptr (profiled mode only): value alone, which is a likelihood call and takes the likelihood's route.  `who` names
-// the entry point in a refusal; the callers have refused a gradient outside the Gaussian family.
+// the entry point in a refusal; the callers have refused a gradient outside the Gaussian family and outside what
+// CCGP_OPT_FAMILY_FUSED_GRAD serves.
 int grad_run(ccgp_handle* h, const char* who, const double* dX, int n, int d, const double* dy, const DrawView& dv,
              double sigma2, const GradOut& o) {
   const int K = dv.K, B = dv.ldp, P = K + K * d;
   if (o.s2hat) sigma2 = 1.0;
-  const Route route = small_route(o.grad ? Op::Grad : Op::Loglik, dv.fam.id == 0, n, d, K);
+  const Route route = small_route(o.grad ? Op::Grad : Op::Loglik, gauss_or_fused_grad(h, dv.fam, n, d, K, o.grad != nullptr), n, d, K);
   if (o.grad && route == Route::Blocked && !blocked_grad_supported(d, K))
     return fail(h, CCGP_EUNSUPPORTED, std::string(who) + ": d + K too large for the contraction kernel's LDS");
   if (route == Route::Blocked) {
@@ -399,7 +408,8 @@ int pull_status(ccgp_handle* h, Pieces ps, int* dst, int B, int* status, size_t 
 // ccgp_loglik_grad_batch and, with out_sigma2, ccgp_profile_batch behind their argument checks: stage, push, grad_run, pull
 int grad_call(ccgp_handle* h, const char* who, const double* X, int n, int d, const double* y, int K, const double* params,
               int B, double sigma2, double* out_loglik, double* out_sigma2, double* out_beta, double* out_grad, int* status) {
-  const bool gauss = h->fam.id == 0;
+  // (a 1-D family under CCGP_OPT_FAMILY_FUSED_GRAD: the flag grad_run passes)
+  const bool gauss = gauss_or_fused_grad(h, h->fam, n, d, K, out_grad != nullptr);
   if (out_grad && !gauss)
     return fail(h, CCGP_EUNSUPPORTED, std::string(who) + ": analytic gradient is implemented for the Gaussian family only");
   CCGP_HIP(hipSetDevice(h->device));
@@ -927,6 +937,10 @@ int ccgp_set_option(ccgp_handle* h, int option, int value) try {
     h->opt_family_fused_predict = value;
     return CCGP_OK;
   }
+  if (option == CCGP_OPT_FAMILY_FUSED_GRAD && (value == 0 || value == 1)) {
+    h->opt_family_fused_grad = value;
+    return CCGP_OK;
+  }
   return fail(h, CCGP_EINVAL, "ccgp_set_option: unknown option or value");
 } CCGP_GUARD_END(h)
 
@@ -1061,6 +1075,31 @@ int ccgp_corr_cross(ccgp_handle* h, const double* Xnew, int m, const double* X, 
   row[0] = 1.0;
   for (int k = 0; k < d; ++k) row[1 + k] = theta[k];
   return corr_common(h, Xnew, m, X, n, d, 1, row.data(), out, false);
+} CCGP_GUARD_END(h)
+
+int ccgp_family_corr_dtheta(ccgp_handle* h, const double* X, int n, int K, const double* params, int q, double* out) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, 1, K) || !X || !params || !out || q < 0 || q >= K)
+    return fail(h, CCGP_EINVAL, "ccgp_family_corr_dtheta: bad argument");
+  if (h->fam.id == 0)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_family_corr_dtheta: the derivative table exists for CCGP_KERNEL_MATERN and CCGP_KERNEL_MATERN_SPLINE only");
+  CCGP_HIP(hipSetDevice(h->device));
+  double *dX, *dp, *dout;
+  if (int rc = stage(h, [&](Layout& c) {
+        dX = c.take<double>(n);
+        dp = c.take<double>(2 * K);
+        dout = c.take<double>((size_t)n * n);
+      }))
+    return rc;
+  DrawView dv;   // the family's own refusals (K = 2 under the two-family kernel), before anything is copied
+  if (int frc = draw_view(h, h->fam, dp, 1, K, 1, &dv)) return frc;
+  if (int prc = push(h, {piece(dX, X, n), piece(dp, params, 2 * K)})) return prc;
+  {
+    ScopedTimer t(h, CCGP_T_COV);
+    launch_family_dcorr(h->stream, dX, n, params[K + q], q, dv.fam, dout);
+  }
+  CCGP_LAUNCH_CHECK();
+  return pull(h, {piece(dout, out, (size_t)n * n)});
 } CCGP_GUARD_END(h)
 
 int ccgp_mixed_corr_matrix(ccgp_handle* h, const double* X, int n, int d, int K,
@@ -1348,7 +1387,8 @@ int ccgp_profile_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, cons
   if (bad_shape(n, d, K) || !params || !out_loglik || !out_sigma2 || !sets_args_ok(Xs, ys, nullptr, false, C, set, B, 0))
     return fail(h, CCGP_EINVAL, "ccgp_profile_batch_sets: bad argument");
   if (B == 0) return CCGP_OK;
-  const bool gauss = h->fam.id == 0;
+  // (a 1-D family under CCGP_OPT_FAMILY_FUSED_GRAD counts as served, as in ccgp_profile_batch)
+  const bool gauss = gauss_or_fused_grad(h, h->fam, n, d, K, out_grad != nullptr);
   // ccgp_profile_batch's refusals, before the first group is launched
   if (out_grad && !gauss)
     return fail(h, CCGP_EUNSUPPORTED, "ccgp_profile_batch_sets: analytic gradient is implemented for the Gaussian family only");

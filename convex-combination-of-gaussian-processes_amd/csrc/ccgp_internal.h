@@ -75,6 +75,7 @@ struct ccgp_handle {
   int opt_fused_solve = 1;              // CCGP_OPT_FUSED_SOLVE: 0 = update + trsm launches, 1 = diagonal launch + tiles solved in the update workgroup where the batch fills whole steps, 2 = wherever possible
   int opt_family_fused = 0;             // CCGP_OPT_FAMILY_FUSED: 1 = the 1-D families take the register-resident evaluator where small_family_fused_supported says so
   int opt_family_fused_predict = 0;     // CCGP_OPT_FAMILY_FUSED_PREDICT: 1 = their prediction and leave-one-out too (small_family_fused_predict_supported / _loo_supported)
+  int opt_family_fused_grad = 0;        // CCGP_OPT_FAMILY_FUSED_GRAD: 1 = their analytic gradient and profiled mode too (small_family_fused_grad_supported / _profile_supported)
   int opt_sched = 3;                    // CCGP_OPT_SCHED: 0 = one launch per phase and block column, 1 = dataflow scheduler with two workgroups per CU, 2 = with one, 3 = by chunk size
   int opt_sched_policy = 11;            // CCGP_OPT_SCHED_POLICY bit 0: a CU's second workgroup only takes work while a backlog exists; bit 1: XCD-local synchronisation
   int sched_timeout_ms = 30000;         // a scheduler wait longer than this aborts the sweep (CCGP_SCHED_TIMEOUT_MS)
@@ -218,6 +219,9 @@ void launch_small_reg_loglik_sets(hipStream_t s, const double* Xs, int n, int d,
 void launch_small_reg_profile_grad_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set,
                                         DrawView dv, int B, double* loglik, double* s2hat, double* beta, double* grad,
                                         int* status);
+// ccgp_family_corr_dtheta: d R_q / d theta_q of component q under the 1-D family `fam`, entry by entry (any n; x: n
+// coordinates, out: n x n), from the device function the gradient epilogue of the FAM instances calls
+void launch_family_dcorr(hipStream_t s, const double* x, int n, double theta, int q, KernelFamily fam, double* out);
 // Metropolis chains on the device (ccgp_metro_segments_sets where small_route_chain says Reg): what chain a = workgroup a of
 // A reads and leaves, every pointer a device pointer.  theta0 / theta_fin: A x p column-major (element j of chain a at
 // [a + j A]); steps [A][T][p], logu [A][T]; the accepted draws [A][M][p] with their values and betas [A][M]; the trace
@@ -592,6 +596,59 @@ __device__ inline double matern_corr(const KernelFamily& f, double z2) {
     if (g < 1e-17 * s && f.nu * t < z * c1) break;
   }
   return exp(f.nu * log(z) - z) * (hs * s * f.norm);
+}
+// ---- d corr / d theta of the two families (build-defined extension: the reference differentiates numerically) ----------
+// Spline, u = |h| / theta: d f / d theta = -u f'(u) / theta = (12 u^2 - 18 u^3) / theta (u <= 1/2), 6 u (1 - u)^2 / theta
+// (u <= 1), 0 beyond; non-negative everywhere, exactly 0 where the points coincide, NaN where a coordinate is.
+// Returns the value as spline_corr forms it and writes the derivative.
+__device__ __forceinline__ double spline_corr_grad(double u2, double theta, double* dth) {
+  const double u = sqrt(u2);
+  if (u <= 0.5) { *dth = (12.0 * u * u - 18.0 * u * u * u) / theta; return 1.0 - 6.0 * u * u + 6.0 * u * u * u; }
+  if (u <= 1.0) { const double v = 1.0 - u; *dth = 6.0 * u * v * v / theta; return 2.0 * v * v * v; }
+  *dth = u > 1.0 ? 0.0 : u;
+  return u > 1.0 ? 0.0 : u;
+}
+// Matern, z = 2 sqrt(nu) |h| / theta:  d f / d theta = z^(nu+1) K_(nu-1)(z) / (Gamma(nu) 2^(nu-1) theta), from
+// d/dz [z^nu K_nu] = -z^nu K_(nu-1) and dz / d theta = -z / theta: positive, no cancellation.  K_(nu-1) by matern_corr's
+// own trapezoidal rule with order nu - 1 -- the same step, the same 6000-term cap, the same stopping test with nu - 1 in
+// place of nu -- in ONE loop with the value's sum: exp(t) and cosh t - 1 are shared, and each sum stops adding where
+// its own test says so, so the value is what matern_corr's operations give.  The exponent (nu + 1) log z - z is formed
+// before exponentiating.  The rule serves every z^2 > 9e-20: the two-term series' derivative, z^2 / (2 (nu - 1) theta),
+// is off by a relative z at nu = 1.5, so where matern_corr takes the series for the value the loop runs for the
+// derivative alone.  At z^2 <= 9e-20 the derivative is exactly 0 (its true value is below 2.1e-18 / theta); a NaN goes
+// through.  Held by tests/test_family_grad_host.py (the same rule in libm arithmetic) and
+// tests/test_gpu_family_fused_grad.py (this code) against a 40-digit evaluation.
+__device__ inline double matern_corr_grad(const KernelFamily& f, double z2, double theta, double* dth) {
+  if (!(z2 > 9e-20)) { *dth = z2 == z2 ? 0.0 : z2; return z2 == z2 ? 1.0 : z2; }
+  const bool series = z2 <= 1e-10 && f.nu >= 1.5;
+  const double z = sqrt(z2);
+  const double hs = 0.15 / fmax(1.0, sqrt(z));
+  const double num = f.nu - 1.0;
+  double s = 0.5, sd = 0.5;
+  bool run = !series, rund = true;
+  for (int k = 1; k < 6000; ++k) {
+    const double t = k * hs;
+    const double et = exp(t);
+    const double c1 = 0.5 * (et + 1.0 / et) - 1.0;        // cosh t - 1
+    if (run) {
+      const double g = 0.5 * (exp(f.nu * t - z * c1) + exp(-f.nu * t - z * c1));
+      s += g;
+      if (g < 1e-17 * s && f.nu * t < z * c1) run = false;
+    }
+    if (rund) {
+      const double g = 0.5 * (exp(num * t - z * c1) + exp(-num * t - z * c1));
+      sd += g;
+      if (g < 1e-17 * sd && num * t < z * c1) rund = false;
+    }
+    if (!run && !rund) break;
+  }
+  const double lz = log(z);
+  // The factor may exceed 1 (1 / theta), which would multiply the quantum a subnormal exp() is rounded to: below e = -700
+  // the exponent is raised by 64 (exact: e and 64 are multiples of ulp(e)) and exp(-64) goes into the factor, so that the
+  // one product is the only operation that rounds to a subnormal.
+  const double e = (f.nu + 1.0) * lz - z, fac = (hs * sd * f.norm) / theta;
+  *dth = e < -700.0 ? exp(e + 64.0) * (fac * 1.6038108905486378e-28) : exp(e) * fac;
+  return series ? 1.0 - z2 / (4.0 * (f.nu - 1.0)) : exp(f.nu * lz - z) * (hs * s * f.norm);
 }
 __device__ __forceinline__ double corr_of_dist(const KernelFamily& f, double dist, const double* tab, int component = 0) {
   if (f.id == 0) return exp_cov(dist, tab);

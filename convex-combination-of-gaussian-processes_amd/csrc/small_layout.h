@@ -184,7 +184,8 @@ inline bool small_reg_design_grad_supported(int n, int d, int K) { return small_
 //   Blocked  the blocked sweep over materialised matrices (cov.hip + blocked.hip): any n, any kernel family
 // `gauss`: the Gaussian family; the others exist on the blocked sweep only (but see small_family_fused_supported at the foot of
 // this file: under CCGP_OPT_FAMILY_FUSED the caller sets the flag for a 1-D family too).  Grad, LogdetDesigns and DesignGrad refuse them
-// before they ask, so their routes do not look at it.  For Grad the caller turns Blocked into a refusal when the
+// before they ask (Grad: but for a 1-D family under CCGP_OPT_FAMILY_FUSED_GRAD, small_family_fused_grad_supported at the foot of
+// this file, whose domain lies inside Grad's Reg cell), so their routes do not look at it.  For Grad the caller turns Blocked into a refusal when the
 // contraction kernel cannot take (d, K) (blocked_grad_supported, blocked.hip).
 // What is decided after the route, from more than the shape, stays with its owner: kept-factor or extra-row prediction
 // (capi.hip: option, small_reg_sites_supported, scratch), the grid of an instance (small_reg.hip: dispatch), the sweep's
@@ -328,6 +329,19 @@ inline bool small_family_fused_predict_supported(int family, int n, int d, int K
 }
 inline bool small_family_fused_loo_supported(int family, int n, int d, int K) {
   return small_family_fused_supported(family, n, d, K) && small_reg_inverse_supported(n, d, K) && n >= 2;
+}
+// the profiled mode and the analytic gradient of the 1-D families on the same evaluator (CCGP_OPT_FAMILY_FUSED_GRAD, an option
+// of its own: options 11 and 12 keep moving exactly what they moved).  The value-only profiled call is the likelihood
+// instance compiled with FAM + PROF, so its domain is the likelihood's; the gradient -- plain, profiled, profiled over sets --
+// is the INV = 2 instance compiled with FAM on the carve of the other inverse instances.  capi.hip passes
+// `gauss || (option && these)` where grad_call and grad_run decide Op::Grad / Op::Loglik for ccgp_loglik_grad_batch and
+// ccgp_profile_batch and to small_route_profile_grad_sets, and nothing else: all three are Reg there
+// (tests/host_small/family_fused_grad_layout_check.cpp).
+inline bool small_family_fused_profile_supported(int family, int n, int d, int K) {
+  return small_family_fused_supported(family, n, d, K);
+}
+inline bool small_family_fused_grad_supported(int family, int n, int d, int K) {
+  return small_family_fused_supported(family, n, d, K) && small_reg_inverse_supported(n, 1, K);
 }
 
 // the maximum-entropy design search on the device (ccgp_design_fit): the DFIT instances are the design-gradient instances

@@ -137,6 +137,33 @@ __device__ __noinline__ double family_corr(int id, double nu, double norm, doubl
   f.id = id; f.nu = nu; f.norm = norm;
   return matern_corr(f, dist);
 }
+// The component's correlation AND its derivative with respect to its own theta from one pass (spline_corr_grad /
+// matern_corr_grad, ccgp_internal.h; CCGP_OPT_FAMILY_FUSED_GRAD): the body the gradient epilogue of every FAM + INV = 2 instance
+// and family_dcorr_kernel call.  Not inlined for family_corr's reason: a sets row must have the single-set row's bits, and
+// the entries ccgp_family_corr_dtheta returns are the ones the gradient sums.  Bounded by the 6000-term cap.
+// Both come back by value (registers): a pointer to a caller's local would put the derivative through scratch.
+struct CorrGrad { double r, dtheta; };
+__device__ __noinline__ CorrGrad family_corr_grad(int id, double nu, double norm, double dist, double theta, int component) {
+  CorrGrad o;
+  if (id == CCGP_KERNEL_MATERN_SPLINE && component == 1) {
+    o.r = spline_corr_grad(dist, theta, &o.dtheta);
+    return o;
+  }
+  KernelFamily f;
+  f.id = id; f.nu = nu; f.norm = norm;
+  o.r = matern_corr_grad(f, dist, theta, &o.dtheta);
+  return o;
+}
+
+// ccgp_family_corr_dtheta: one thread per entry (i, j) of the n x n table, no LDS, no barrier
+__global__ __launch_bounds__(256) void family_dcorr_kernel(const double* x, int n, double theta, int q, KernelFamily fam,
+                                                           double* out) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)n * n) return;
+  const int i = (int)(e % n), j = (int)(e / n);
+  const double h = x[i] - x[j];
+  out[e] = family_corr_grad(fam.id, fam.nu, fam.norm, theta_to_rate(fam, theta, q) * (h * h), theta, q).dtheta;
+}
 
 // ---- the factor a prediction keeps (round 5) ------------------------------------------------------------------------
 // Rounds 2 - 4 predicted by carrying the cross-correlation rows of a CHUNK of test sites (30 at n <= 64, 62 above) through the
@@ -238,13 +265,21 @@ __device__ __forceinline__ void mat_sync() {
 // keeps its factor for a prediction (both grids; the test sites' correlation vectors come from site_corr_family_kernel) and of
 // the leave-one-out instance (16 x 16 grid).  Neither epilogue reads us[] or th[], so both run as they are.  No FAM instance
 // carries extra rows (NE > 1 without INV): a family's prediction is the kept-factor scheme or the blocked sweep.
+// FAM with PROF (value only) and FAM with INV = 2 -- plain, PROF, PROF + SETS -- (CCGP_OPT_FAMILY_FUSED_GRAD): the same
+// generation phase in front of the profiled likelihood and of the gradient instance.  In the gradient epilogue a FAM branch
+// stands in for the Gaussian regeneration: per pair (i >= j) and component q, family_corr_grad gives (R_q, D_q = d R_q /
+// d theta_q) of rate_q (h h), h = x_i - x_j from xs; gs[q] += m R_q, hk[q] += m D_q; the weight column is 2 sigma2 w_q sum as
+// ever, the theta column + sigma2 w_q^2 sum m D_q.  us[] and the expanded distance are not read; the diagonal gives D = 0.
 template <int G, int NB, int NE, bool FULL = false, int INV = 0, bool FAC = false, bool PROF = false, bool SETS = false,
           bool CHAIN = false, bool FIT = false, bool NM = false, bool DFIT = false, bool FAM = false>
 __global__ __launch_bounds__(256, INV ? 1 : (NE > 1 ? CCGP_SMALL_OCC_PRED : (G == 8 ? (NB > 8 ? 2 : CCGP_SMALL_OCC_G8) : CCGP_SMALL_OCC_G16)))
 void small_reg_kernel(RegArgs a) {
-  static_assert(!FAM || (((NE == 1 && !INV) || INV == 4) && !PROF && !FULL && !FIT && !DFIT && G * NB <= kFamilyFusedMaxN),
+  static_assert(!FAM || (!FULL && !FIT && !DFIT && G * NB <= kFamilyFusedMaxN &&
+                         ((NE == 1 && !INV && !PROF) || (INV == 4 && !PROF) ||
+                          (NE == 1 && !INV && PROF && !SETS && !CHAIN && !FAC) || (INV == 2 && (PROF || !SETS)))),
                 "a 1-D family is generated by the general plain-likelihood instance (with or without SETS / CHAIN / NM, or keeping "
-                "its factor) and by the leave-one-out instance, at n <= 32");
+                "its factor), by the leave-one-out instance, by the value-only profiled instance and by the gradient instance "
+                "(plain, profiled, profiled over sets), at n <= 32");
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
   static_assert(!FAC || (NE == 1 && !FULL && !INV), "the factor is kept by the plain likelihood instantiation");
   static_assert(!PROF || ((NE == 1 || INV == 2) && INV != 1 && INV != 3 && !FAC), "sigma2 is concentrated out of the likelihood and of its gradient only");
@@ -916,6 +951,15 @@ chain_next:
                 for (int qq = 0; qq < QG; ++qq) {
                   const int q = q0 + qq;
                   if (q >= K) break;
+                  if constexpr (FAM) {
+                    // a 1-D family: value and d / d theta_q of the component's correlation from the direct difference, as
+                    // the generation phase forms its distance; the diagonal gives (1, 0)
+                    const double h = xs[i] - xs[j];
+                    const CorrGrad cg = family_corr_grad(a.fam.id, a.fam.nu, a.fam.norm, theta_to_rate(a.fam, th[q], q) * (h * h), th[q], q);
+                    gs[qq] += m * cg.r;
+                    hk[qq][0] += m * cg.dtheta;
+                    continue;
+                  }
                   double sd = 0.0;
                   for (int k = 0; k < d; ++k) sd = fma(xs[k * n + i] * th[q * d + k], xs[k * n + j], sd);
                   const double dist = (us[q * NP + i] + us[q * NP + j]) + (-2.0 * sd);
@@ -950,7 +994,8 @@ chain_next:
                 if (slot == 0) {
                   if (k0 == 0) a.grad[b + (size_t)q * a.Btot] = nograd ? kNaN : 2.0 * s2g * wq * tot;
                 } else if (k0 + slot - 1 < d) {
-                  a.grad[b + (size_t)(K + q * d + k0 + slot - 1) * a.Btot] = nograd ? kNaN : -s2g * wq * wq * tot;
+                  // (a 1-D family's sum carries m d R_q / d theta_q itself: no minus sign)
+                  a.grad[b + (size_t)(K + q * d + k0 + slot - 1) * a.Btot] = nograd ? kNaN : (FAM ? s2g : -s2g) * wq * wq * tot;
                 }
               }
             }
@@ -958,7 +1003,8 @@ chain_next:
           }
         }
       };
-      if (d <= 8) contract(std::integral_constant<int, 3>{}, std::integral_constant<int, 8>{});
+      if constexpr (FAM) contract(std::integral_constant<int, 3>{}, std::integral_constant<int, 1>{});   // d = 1
+      else if (d <= 8) contract(std::integral_constant<int, 3>{}, std::integral_constant<int, 8>{});
       else contract(std::integral_constant<int, 1>{}, std::integral_constant<int, 16>{});
     } else if constexpr (INV == 4) {
       // ---- leave-one-out tables (ccgp_loo_batch; Dubrule 1983) ----------------------------------------------------------
@@ -1243,6 +1289,13 @@ void launch_one(hipStream_t s, const RegArgs& a) {
           raise_lds_limit((const void*)small_reg_kernel<G, NB, 1, false, 0, true, false, false, false, false, false, false, true>, "small_reg_kernel<family, fac>");
         });
         kernel = small_reg_kernel<G, NB, 1, false, 0, true, false, false, false, false, false, false, true>;
+      }
+      if (a.s2hat && !a.set && !a.fac) {   // CCGP_OPT_FAMILY_FUSED_GRAD: sigma2 concentrated out, value only
+        static unsigned long long fam_prof_mask = 0;
+        once_per_device(fam_prof_mask, [] {
+          raise_lds_limit((const void*)small_reg_kernel<G, NB, 1, false, 0, false, true, false, false, false, false, false, true>, "small_reg_kernel<family, profiled>");
+        });
+        kernel = small_reg_kernel<G, NB, 1, false, 0, false, true, false, false, false, false, false, true>;
       }
     } else {
       no_family_instance();
@@ -1584,6 +1637,14 @@ static void launch_inv(hipStream_t s, const RegArgs& a) {
                         "small_reg_kernel<family, leave-one-out>");
       });
       kernel = small_reg_kernel<16, NB, NB + 1, false, 4, false, false, false, false, false, false, false, true>;
+    } else if constexpr (INV == 2 && (PROF || !SETS) && 16 * NB <= kFamilyFusedMaxN) {
+      // CCGP_OPT_FAMILY_FUSED_GRAD: the gradient instance (plain, profiled, profiled over sets) compiled with FAM
+      static unsigned long long fam_mask = 0;
+      once_per_device(fam_mask, [] {
+        raise_lds_limit((const void*)small_reg_kernel<16, NB, NB + 1, false, 2, false, PROF, SETS, false, false, false, false, true>,
+                        "small_reg_kernel<family, gradient>");
+      });
+      kernel = small_reg_kernel<16, NB, NB + 1, false, 2, false, PROF, SETS, false, false, false, false, true>;
     } else {
       no_family_instance();
       return;
@@ -1777,7 +1838,7 @@ void launch_small_reg_profile_grad_sets(hipStream_t s, const double* Xs, int n, 
                                         int* status) {
   RegArgs a = reg_args(Xs, n, d, ys, dv);
   a.B = B; a.set = set;
-  a.loglik = loglik; a.beta = beta; a.status = status; a.s2hat = s2hat; a.grad = grad; a.Btot = B;
+  a.loglik = loglik; a.beta = beta; a.status = status; a.s2hat = s2hat; a.grad = grad; a.Btot = B; a.fam = dv.fam;
   dispatch_inv<2, true, true>(s, a);
 }
 
@@ -1794,7 +1855,7 @@ void launch_small_reg_grad(hipStream_t s, const double* X, int n, int d, const d
                            double sigma2, double* loglik, double* beta, double* grad, int* status) {
   RegArgs a = reg_args(X, n, d, y, dv);
   a.B = B; a.sigma2 = sigma2;
-  a.loglik = loglik; a.beta = beta; a.status = status; a.grad = grad; a.Btot = B;
+  a.loglik = loglik; a.beta = beta; a.status = status; a.grad = grad; a.Btot = B; a.fam = dv.fam;
   dispatch_inv<2>(s, a);
 }
 
@@ -1812,7 +1873,7 @@ void launch_small_reg_loo(hipStream_t s, const double* X, int n, int d, const do
 void launch_small_reg_profile(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B,
                               double* loglik, double* s2hat, double* beta, double* grad, int* status, bool grid16) {
   RegArgs a = reg_args(X, n, d, y, dv);
-  a.B = B; a.loglik = loglik; a.beta = beta; a.status = status; a.s2hat = s2hat;
+  a.B = B; a.loglik = loglik; a.beta = beta; a.status = status; a.s2hat = s2hat; a.fam = dv.fam;
   if (grad) {
     a.grad = grad; a.Btot = B;
     dispatch_inv<2, true>(s, a);
@@ -1820,6 +1881,12 @@ void launch_small_reg_profile(hipStream_t s, const double* X, int n, int d, cons
     a.grid16 = grid16;
     dispatch(s, a);
   }
+}
+
+// ccgp_family_corr_dtheta: the n x n table of d R_q / d theta_q, one thread per entry
+void launch_family_dcorr(hipStream_t s, const double* x, int n, double theta, int q, KernelFamily fam, double* out) {
+  const size_t entries = (size_t)n * n;
+  hipLaunchKernelGGL(family_dcorr_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, x, n, theta, q, fam, out);
 }
 
 // log det R_mixed for B candidate designs (Xs = B blocks of n x d, column-major each) under ONE parameter row

@@ -1032,6 +1032,73 @@ def matern_MLEs(handle, D, y, nu, grid=96, lo=1e-3, hi=1e2, fused=False):
     return dict(beta=float(beta[0]), sigma2=float(Q[0] / n), theta=float(theta))
 
 
+def matern_MLEs_sets(handle, Ds, ys, nu, grid=96, lo=1e-3, hi=1e2):
+    """matern_MLEs for C designs of one shape in lockstep, on the analytic gradient of the Matern(nu) family
+    (OPT_FAMILY_FUSED_GRAD, which this function sets for its own calls: d = 1, n <= 32).
+
+    1. ONE profile_batch_sets(grad=True) call with C x grid rows: matern_MLEs' own grid for every set (log-spaced, scaled
+       by the set's range).  2. Per set the grid's best point and its two neighbours are three starts of
+    design.minimize_starts in log theta, each under the bracket [left neighbour, right neighbour] as its own box; the
+    objective is -l_p and its gradient -g_theta theta (chain rule to log theta; g_theta is the gradient at the point's own
+    (beta, sigma2): envelope theorem).  All sets run in lockstep: each step is ONE sets call carrying every start still
+    running.  3. One final sets call at the C best points.  A start's trajectory depends on its own evaluations only and a
+    row's bits on its own set only, so a set's result is the one it has alone.
+
+    Returns, per set, dict(beta, sigma2, theta, loglik, calls) -- loglik the profiled log-likelihood l_p at theta, calls the
+    device calls the set took part in (grid and final call included); the group made max(calls) of them.  Sets of one
+    shape only (ValueError otherwise); a set whose likelihood fails on the whole grid raises RuntimeError."""
+    from .design import minimize_starts
+    from .rsurface import _FamilyHandle
+
+    Ds = [np.asarray(D, dtype=np.float64).reshape(-1, 1) for D in Ds]
+    ys = [np.asarray(y, dtype=np.float64).ravel() for y in ys]
+    C = len(Ds)
+    if C < 1 or len(ys) != C:
+        raise ValueError("matern_MLEs_sets: one response per design, at least one set")
+    if any(D.shape != Ds[0].shape for D in Ds) or any(y.shape[0] != Ds[0].shape[0] for y in ys):
+        raise ValueError("matern_MLEs_sets: the sets of one call have one shape")
+    grid = int(grid)
+    h = _FamilyHandle(handle, api.KERNEL_MATERN, float(nu), fused_grad=True)
+    Xs, Y = np.stack(Ds), np.stack(ys)
+
+    def profile(thetas, set_of):
+        rows = np.stack([np.ones_like(thetas), thetas], axis=1)
+        return h.profile_batch_sets(Xs, Y, 1, rows, np.asarray(set_of, dtype=np.int32), grad=True)
+
+    spans = np.array([max(float(D.max() - D.min()), 1e-12) for D in Ds])
+    th = spans[:, None] * np.exp(np.linspace(math.log(lo), math.log(hi), grid))[None, :]
+    ll, _, _, _, st = profile(th.ravel(), np.repeat(np.arange(C), grid))
+    f = np.where((st == 0) & np.isfinite(ll), -ll, np.nan).reshape(C, grid)
+    x0, lows, ups = [], [], []
+    for c in range(C):
+        if not np.isfinite(f[c]).any():
+            raise RuntimeError("matern_MLEs_sets: the likelihood failed at every scale parameter of the search grid of set %d" % c)
+        i = int(np.nanargmin(f[c]))
+        a, b = max(i - 1, 0), min(i + 1, grid - 1)
+        x0 += [math.log(th[c, i]), math.log(th[c, a]), math.log(th[c, b])]
+        lows += [math.log(th[c, a])] * 3
+        ups += [math.log(th[c, b])] * 3
+    owner = np.repeat(np.arange(C), 3)
+
+    def evaluate(logth, live):
+        theta = np.exp(logth[:, 0])
+        ll, _, _, g, st = profile(theta, owner[live])
+        return -ll, -(g[:, 1:] * theta[:, None]), st
+
+    def col(v):
+        return np.asarray(v, dtype=np.float64)[:, None]
+
+    res = minimize_starts(evaluate, col(x0), lowers=col(lows), uppers=col(ups), pass_live=True)
+    best = []
+    for c in range(C):
+        fs = res["f"][3 * c:3 * c + 3]
+        best.append(3 * c + int(np.argmin(np.where(np.isfinite(fs), fs, np.inf))))
+    thetas = np.exp(res["x"][best, 0])
+    ll, s2, beta, _, _ = profile(thetas, np.arange(C))
+    return [dict(beta=float(beta[c]), sigma2=float(s2[c]), theta=float(thetas[c]), loglik=float(ll[c]),
+                 calls=int(res["calls_per_start"][3 * c:3 * c + 3].max()) + 2) for c in range(C)]
+
+
 def kriging_starts(D_train, starts=8, rng=0, extra_starts=None):
     """The start points of ordinary_kriging_sigma2 as rows of log theta -- the same generator drawn in the same order: start 0
     is 1 / span^2, the others uniform(0.2, 5) / span^2 -- with `extra_starts` (rows of theta) appended."""
@@ -1237,17 +1304,18 @@ def ordinary_kriging_fit_device(handle, D_train, y_train, starts=8, rng=0, extra
     return ordinary_kriging_fit_device_sets(handle, [D_train], [y_train], starts, rng, extra_starts, on_device, seg)[0]
 
 
-def matern_profile(handle, D, y, nu, thetas):
+def matern_profile(handle, D, y, nu, thetas, fused_grad=False):
     """log.likeli of the 1-D scripts (D1:424-444) for an array of scale parameters in ONE value-only device call under the
     Matern(nu) family: log det R(theta) + n log sigma2.MLE(theta), with beta.MLE and sigma2.MLE (D1:411-415) at each theta.
-    Returns dict(loglikeli, beta, sigma2, status), NaN where the factorisation failed."""
+    fused_grad=True: the call runs with OPT_FAMILY_FUSED_GRAD on (n <= 32: the register-resident evaluator in place of the
+    blocked sweep, equal to rounding).  Returns dict(loglikeli, beta, sigma2, status), NaN where the factorisation failed."""
     from .rsurface import _FamilyHandle
 
     D = np.asarray(D, dtype=np.float64).reshape(-1, 1)
     y = np.asarray(y, dtype=np.float64).ravel()
     n = D.shape[0]
     thetas = np.atleast_1d(np.asarray(thetas, dtype=np.float64))
-    h = _FamilyHandle(handle, api.KERNEL_MATERN, float(nu))
+    h = _FamilyHandle(handle, api.KERNEL_MATERN, float(nu), fused_grad=fused_grad)
     ll, s2, beta, _, st = h.profile_batch(D, y, 1, np.stack([np.ones_like(thetas), thetas], axis=1), grad=False)
     return dict(loglikeli=-2.0 * ll - n * math.log(2.0 * math.pi) - n, beta=beta, sigma2=s2, status=st)
 

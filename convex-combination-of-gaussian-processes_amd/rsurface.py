@@ -44,16 +44,18 @@ class _FamilyHandle:
     mirroring different scripts can share one device handle.  fused: OPT_FAMILY_FUSED for this object's calls (the
     register-resident evaluator of the 1-D families at n <= 32, include/ccgp.h) -- set to the object's own value before
     every call and back to 0 after it, as the family is, so that it does not leak into the handle's other users.
-    fused_predict: OPT_FAMILY_FUSED_PREDICT (prediction and leave-one-out on that evaluator), treated the same way; the two
-    are independent."""
+    fused_predict: OPT_FAMILY_FUSED_PREDICT (prediction and leave-one-out on that evaluator), and fused_grad:
+    OPT_FAMILY_FUSED_GRAD (the analytic gradient and the profiled mode on it), treated the same way; the three are
+    independent."""
 
-    def __init__(self, handle, family, nu, fused=False, fused_predict=False):
+    def __init__(self, handle, family, nu, fused=False, fused_predict=False, fused_grad=False):
         self._handle, self._family, self._nu, self._fused = handle, family, nu, bool(fused)
         self._fused_predict = bool(fused_predict)
+        self._fused_grad = bool(fused_grad)
         # (a handle without options -- api.MultiHandle -- has no fused route to select)
         self._set_option = getattr(handle, "set_option", None)
-        if (self._fused or self._fused_predict) and self._set_option is None:
-            raise ValueError("fused=True / fused_predict=True needs a handle with set_option (api.Handle)")
+        if (self._fused or self._fused_predict or self._fused_grad) and self._set_option is None:
+            raise ValueError("fused=True / fused_predict=True / fused_grad=True needs a handle with set_option (api.Handle)")
 
     def __getattr__(self, name):
         attr = getattr(self._handle, name)
@@ -65,12 +67,14 @@ class _FamilyHandle:
             if self._set_option is not None:
                 self._set_option(api.OPT_FAMILY_FUSED, int(self._fused))
                 self._set_option(api.OPT_FAMILY_FUSED_PREDICT, int(self._fused_predict))
+                self._set_option(api.OPT_FAMILY_FUSED_GRAD, int(self._fused_grad))
             try:
                 return attr(*args, **kwargs)
             finally:
                 if self._set_option is not None:
                     self._set_option(api.OPT_FAMILY_FUSED, 0)
                     self._set_option(api.OPT_FAMILY_FUSED_PREDICT, 0)
+                    self._set_option(api.OPT_FAMILY_FUSED_GRAD, 0)
                 self._handle.set_kernel(api.KERNEL_GAUSS, 0.0)
         return call
 
@@ -397,21 +401,25 @@ class CombinedGP1D(CombinedGP):
     the likelihood, the sets calls, the chains and the Laplace search take the register-resident evaluator (one launch each,
     values equal to the blocked sweep's to rounding); everything else, and n > 32, is unchanged.  fused_predict=True: this
     object's calls run with OPT_FAMILY_FUSED_PREDICT on -- at n <= 32 prediction_table, prediction and leave_one_out (and
-    fit.compare_GP, fit.leave_one_out, fit.Combined_GP_fit, which call them) take that evaluator too; independent of fused."""
+    fit.compare_GP, fit.leave_one_out, fit.Combined_GP_fit, which call them) take that evaluator too; independent of fused.
+    fused_grad=True: this object's calls run with OPT_FAMILY_FUSED_GRAD on -- at n <= 32 the handle's loglik_grad_batch and
+    profile_batch(_sets) serve this family, gradient included; independent of the other two."""
 
-    def __init__(self, nu=5.0, handle=None, device=0, fused=False, fused_predict=False):
+    def __init__(self, nu=5.0, handle=None, device=0, fused=False, fused_predict=False, fused_grad=False):
         self.script = "D1"
         self.cfg = dict(aniso=False, prior=api.PRIOR_ISO, npar=3)
         self.nu = float(nu)
         self.fused = bool(fused)
         self.fused_predict = bool(fused_predict)
+        self.fused_grad = bool(fused_grad)
         base = handle if handle is not None else api.Handle(device)
-        self.h = _FamilyHandle(base, api.KERNEL_MATERN, self.nu, self.fused, self.fused_predict)
+        self.h = _FamilyHandle(base, api.KERNEL_MATERN, self.nu, self.fused, self.fused_predict, self.fused_grad)
 
     def _with(self, nu):
         if nu is None or float(nu) == self.nu:
             return self
-        return CombinedGP1D(nu, handle=self.h._handle, fused=self.fused, fused_predict=self.fused_predict)
+        return CombinedGP1D(nu, handle=self.h._handle, fused=self.fused, fused_predict=self.fused_predict,
+                            fused_grad=self.fused_grad)
 
     @staticmethod
     def _col(X):
@@ -490,17 +498,18 @@ class CombinedGP1DTwoFamilies(CombinedGP1D):
         gp.logpost(D_train, theta, y, sigma2, nu)                  # D1F:576-601
     """
 
-    def __init__(self, nu=5.0, handle=None, device=0, fused=False, fused_predict=False):
-        super().__init__(nu, handle, device, fused, fused_predict)
+    def __init__(self, nu=5.0, handle=None, device=0, fused=False, fused_predict=False, fused_grad=False):
+        super().__init__(nu, handle, device, fused, fused_predict, fused_grad)
         self.script = "D1"       # prior D1F:596 = D1:636
         self._base = self.h._handle
-        self._matern = CombinedGP1D(nu, handle=self._base, fused=fused, fused_predict=fused_predict)
-        self.h = _FamilyHandle(self._base, api.KERNEL_MATERN_SPLINE, self.nu, self.fused, self.fused_predict)
+        self._matern = CombinedGP1D(nu, handle=self._base, fused=fused, fused_predict=fused_predict, fused_grad=fused_grad)
+        self.h = _FamilyHandle(self._base, api.KERNEL_MATERN_SPLINE, self.nu, self.fused, self.fused_predict, self.fused_grad)
 
     def _with(self, nu):
         if nu is None or float(nu) == self.nu:
             return self
-        return CombinedGP1DTwoFamilies(nu, handle=self._base, fused=self.fused, fused_predict=self.fused_predict)
+        return CombinedGP1DTwoFamilies(nu, handle=self._base, fused=self.fused, fused_predict=self.fused_predict,
+                                       fused_grad=self.fused_grad)
 
     # single-family pieces
     def corr_matrix_Matern(self, nu, X, theta):

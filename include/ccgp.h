@@ -166,10 +166,24 @@ int ccgp_set_workspace_limit(ccgp_handle* h, size_t bytes);
  *                           rounding; a site's column does not depend on the other sites, a draw's row not on the other
  *                           draws; a failed pivot gives the 1-based index and NaN rows as on the Gaussian route.  Nothing else
  *                           moves: ccgp_factor_batch and factor sets, R.Inv, the gradient, the profiled mode, the device fits,
- *                           n > 32 and K > 3 keep their routes.  No effect under CCGP_KERNEL_GAUSS. */
+ *                           n > 32 and K > 3 keep their routes.  No effect under CCGP_KERNEL_GAUSS.
+ *   CCGP_OPT_FAMILY_FUSED_GRAD  NOT a same-bits switch, and independent of CCGP_OPT_FAMILY_FUSED and
+ *                           CCGP_OPT_FAMILY_FUSED_PREDICT.  0 (default) = the analytic gradient is refused under the two 1-D
+ *                           families (CCGP_EUNSUPPORTED) and their profiled mode runs on the blocked sweep; 1 = inside the
+ *                           domain of CCGP_OPT_FAMILY_FUSED (d = 1, n <= 32; K = 2 for the two-family kernel) the
+ *                           register-resident evaluator serves ccgp_loglik_grad_batch, ccgp_profile_batch with and without
+ *                           out_grad and ccgp_profile_batch_sets (with out_grad: one launch for all sets; without: set by set
+ *                           through the fused single call).  The theta columns are + sigma2 w_q^2 sum_ab M_ab d R_q,ab / d
+ *                           theta_q with the family's own derivative (Matern: z^(nu+1) K_(nu-1)(z) / (Gamma(nu) 2^(nu-1)
+ *                           theta), spline: -u f'(u) / theta), the entries ccgp_family_corr_dtheta returns.  A row of the
+ *                           sets call has the bits of the single-set call on its set; failures as on the Gaussian route
+ *                           (1-based pivot index and a NaN row, gradient included; Q == 0: +Inf, NaN gradient, status 0).
+ *                           Outside the domain (n = 33, d = 2, K = 3 under the two-family kernel) the gradient stays refused
+ *                           before anything is copied or launched.  Nothing else moves: the device fits, the _dev variants,
+ *                           R.Inv and ccgp_reserve keep their routes.  No effect under CCGP_KERNEL_GAUSS. */
 enum { CCGP_OPT_FUSE_DIAG = 2, CCGP_OPT_TAIL_STRIPS = 3, CCGP_OPT_WIDE_OFFSETS = 4, CCGP_OPT_SMALL_GRID16 = 5,
        CCGP_OPT_SCHED = 7, CCGP_OPT_SCHED_POLICY = 8, CCGP_OPT_PREDICT_FACTOR = 9, CCGP_OPT_FUSED_SOLVE = 10,
-       CCGP_OPT_FAMILY_FUSED = 11, CCGP_OPT_FAMILY_FUSED_PREDICT = 12 };
+       CCGP_OPT_FAMILY_FUSED = 11, CCGP_OPT_FAMILY_FUSED_PREDICT = 12, CCGP_OPT_FAMILY_FUSED_GRAD = 13 };
 int ccgp_set_option(ccgp_handle* h, int option, int value);
 /* pre-size scratch so that later _dev calls of this shape (or of fewer draws B or test sites m), under the kernel family,
  * options and workspace limit in force now, never allocate, synchronise or create a stream or an event.  Covers: the
@@ -188,6 +202,14 @@ int ccgp_corr_matrix(ccgp_handle* h, const double* X, int n, int d, const double
                      double* out_R);
 int ccgp_corr_cross(ccgp_handle* h, const double* Xnew, int m, const double* X, int n, int d,
                     const double* theta, double* out);
+
+/* build-defined extension: d R_q / d theta_q of component q (0-based) under the 1-D family in force (d = 1: X holds n
+ * coordinates), entry by entry -- the derivative the gradient under CCGP_OPT_FAMILY_FUSED_GRAD sums, out of the C ABI as the
+ * values are out of ccgp_corr_matrix.  params is ONE row (2 K doubles: weights, then thetas); out is n x n, symmetric,
+ * its diagonal exactly 0; a NaN coordinate gives a NaN row and column.  Any n; needs no option.  Host pointers; blocks.
+ * CCGP_EUNSUPPORTED under CCGP_KERNEL_GAUSS. */
+int ccgp_family_corr_dtheta(ccgp_handle* h, const double* X, int n, int K, const double* params /* one row */, int q,
+                            double* out /* n x n */);
 
 /* ---- a4/a5: convex-combination mix ---------------------------------------------------
  * Mixed.corr.matrix HX:408-415, ANI:399-406, ADV:414-421; Mixed.corr.vec HX:425-431,
@@ -217,7 +239,9 @@ int ccgp_loglik_batch_dev(ccgp_handle* h, const double* dX, int n, int d, const 
 /* build-defined extension (the reference has no analytic gradient; LearnBayes::laplace
  * differences numerically, HX:493): d loglik(mode 0, beta profiled) / d params[b, j],
  * out_grad is B x P column-major.  Any n: n <= 128 in LDS; larger n carries the identity as
- * extra tile rows of the blocked sweep and contracts R^-1 tiles with the kernel derivatives. */
+ * extra tile rows of the blocked sweep and contracts R^-1 tiles with the kernel derivatives.
+ * Gaussian family; CCGP_KERNEL_MATERN and CCGP_KERNEL_MATERN_SPLINE at d = 1, n <= 32 under CCGP_OPT_FAMILY_FUSED_GRAD
+ * (theta columns with respect to the family's theta); CCGP_EUNSUPPORTED otherwise, before anything is copied. */
 int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const double* y, int K,
                            const double* params, int B, double sigma2, double* out_loglik,
                            double* out_beta, double* out_grad, int* status);
@@ -230,8 +254,10 @@ int ccgp_loglik_grad_batch(ccgp_handle* h, const double* X, int n, int d, const 
  * (the 1-D scripts' log.likeli is log det M + n log sigma2 = -2 loglik - n log 2 pi - n), from ONE factorisation per
  * draw: sigma2 is formed on the device in the pass that forms Q.  out_grad (B x P column-major, may be NULL):
  * d loglik / d params[b, j] -- the gradient of the mode-0 likelihood at (beta, sigma2) of the draw (envelope theorem).
- * Host pointers; blocks.  Every family of ccgp_set_kernel without out_grad; with it the Gaussian family only
- * (CCGP_EUNSUPPORTED otherwise, and for d + K beyond the blocked contraction's LDS, as ccgp_loglik_grad_batch).
+ * Host pointers; blocks.  Every family of ccgp_set_kernel without out_grad; with it the Gaussian family, and the two
+ * 1-D families at d = 1, n <= 32 under CCGP_OPT_FAMILY_FUSED_GRAD (which also moves their value-only call from the sweep
+ * to the register-resident evaluator) -- CCGP_EUNSUPPORTED otherwise, and for d + K beyond the blocked contraction's
+ * LDS, as ccgp_loglik_grad_batch.
  * A failed factorisation: status[b] = 1-based pivot index, NaN in loglik, sigma2, beta and the gradient row; returns
  * the number of failed draws.  Q == 0 (y exactly constant): sigma2 = 0, loglik = +Inf, gradient row NaN, status 0.
  * out_beta / out_grad / status may be NULL. */
@@ -372,6 +398,8 @@ int ccgp_metro_segments_sets(ccgp_handle* h, const double* Xs, int n, int d, con
  *     is legal.  CCGP_EUNSUPPORTED exactly where the single-set call says it.
  *   Routes.  ccgp_profile_batch_sets with out_grad, Gaussian family, n <= 128 where the register-resident gradient instance
  *     fits (where ccgp_profile_batch's gradient runs in LDS as one workgroup per row): ONE launch per chunk for all rows.
+ *     So for the two 1-D families at d = 1, n <= 32 under CCGP_OPT_FAMILY_FUSED_GRAD; without that option their gradient is
+ *     refused as in ccgp_profile_batch.
  *     Every other shape and family the single-set call serves (n > 128, the in-LDS fallback, Matern and spline value-only):
  *     the rows are grouped by set and each group goes through ccgp_profile_batch.  The value-only form (out_grad == NULL)
  *     takes that grouped route at EVERY shape: a fit calls it once, and one-launch instances for it would be 42 more kernels
