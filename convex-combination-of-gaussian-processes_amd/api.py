@@ -85,6 +85,11 @@ SIGNATURES = {
                                          _dp, _ip, c_int]),
     "ccgp_cgp_state_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _ip, _dp, _dp, _dp, _dp,
                                           _ip]),
+    "ccgp_cgp_fit_rows": (c_int, [c_int]),
+    "ccgp_cgp_fit_eval_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _dp, _dp, c_double, _ip, c_int, _dp, _dp,
+                                       _ip]),
+    "ccgp_cgp_fit_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, c_int, _ip, _dp, c_double, _ip, c_int, _ip, _dp, _ip,
+                                  c_int]),
     "ccgp_grid_marginal": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_double, _dp, c_int, c_int,
                                    c_double, c_int, c_double, _dp, _ip, _dp]),
     "ccgp_mixed_logdet_designs": (c_int, [c_void_p, _dp, c_int, c_int, c_int, c_int, _dp, _dp, _ip]),
@@ -266,6 +271,14 @@ def fit_feed(state, f, g, ok=True):
     if rc < 0:
         raise CcgpError(rc, "ccgp_fit_feed")
     return rc
+
+
+def cgp_fit_rows(d):
+    """ccgp_cgp_fit_rows: the parameter rows of one evaluation of the CGP refinement, 1 + 2 (d + 3)."""
+    R = lib().ccgp_cgp_fit_rows(int(d))
+    if R < 0:
+        raise CcgpError(R, "ccgp_cgp_fit_rows")
+    return R
 
 
 def fit_trial(state):
@@ -971,6 +984,46 @@ class Handle:
         self._chk(lib().ccgp_cgp_state_batch_sets(self._h, _p(Xb), n, d, _p(yb), C, _p(params), _ipt(idx), B, _ipt(sk), _p(val),
                                                   _p(beta), _p(tau2), _p(loo), _ipt(st)))
         return val, beta, tau2, loo, st
+
+    def cgp_fit_eval_sets(self, Xs, ys, w, lower, upper, step, set_of):
+        """ccgp_cgp_fit_eval_sets: the CGP refinement's objective at the points w [B, d + 3] = (lambda, theta, kappa, bw), point b
+        on training set set_of[b] under its box lower[b], upper[b] ([B, d + 3]) -- f = the value at w (1e6 where it is not
+        finite), g by central differences of `step` clipped at the box -- the host twin of cgp_fit_sets' evaluation.  Returns
+        (f[B], g[B, d + 3], status[B]: the centre row's)."""
+        w = _f(np.atleast_2d(w))
+        B, P = w.shape
+        Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, B)
+        _check_columns(P, d + 3, "d + 3")
+        lo = _f(np.broadcast_to(np.asarray(lower, dtype=np.float64), (B, P)))
+        hi = _f(np.broadcast_to(np.asarray(upper, dtype=np.float64), (B, P)))
+        f, st = _outputs(B, 1)
+        g = np.empty((B, P), order="F")
+        self._chk(lib().ccgp_cgp_fit_eval_sets(self._h, _p(Xb), n, d, _p(yb), C, _p(w), _p(lo), _p(hi), float(step), _ipt(idx), B,
+                                               _p(f), _p(g), _ipt(st)))
+        return f, g, st
+
+    def cgp_fit_sets(self, Xs, ys, set_of, state, step, max_evals, look=16, trace=False, T=None):
+        """ccgp_cgp_fit_sets: A starts of the CGP refinement, start a on training set set_of[a], stepped on the device from state
+        [A, W] (api.fit_begin at (lambda, theta, kappa, bw) under the start's box) through up to max_evals[a] evaluations each:
+        rounds of two launches (evaluate, step), `look` of them between the host's looks at the gates.  Returns dict(state
+        [A, W], evals[A], failed: evaluations whose centre row failed, and with trace=True trace_f, trace_status [A, T],
+        T = max(max_evals) unless given)."""
+        state = np.ascontiguousarray(np.atleast_2d(np.asarray(state, dtype=np.float64))).copy()
+        A = state.shape[0]
+        Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, A)
+        max_evals = np.ascontiguousarray(np.broadcast_to(np.asarray(max_evals), (A,)).astype(np.int32))
+        if T is None:
+            T = int(max_evals.max()) if A else 0
+        if state.shape[1] != FIT_HEADER + 16 * (d + 3):
+            raise ValueError("state must be [A, %d] for d = %d (d + 3 variables)" % (FIT_HEADER + 16 * (d + 3), d))
+        evals = np.zeros(A, dtype=np.int32)
+        tr_f, tr_st = (np.full((A, T), np.nan), np.full((A, T), -1, dtype=np.int32)) if trace else (None, None)
+        failed = self._chk(lib().ccgp_cgp_fit_sets(self._h, _p(Xb), n, d, _p(yb), C, A, _ipt(idx), _p(state), float(step),
+                                                   _ipt(max_evals), int(look), _ipt(evals), _p(tr_f), _ipt(tr_st), int(T)))
+        out = dict(state=state, evals=evals, failed=failed)
+        if trace:
+            out.update(trace_f=tr_f, trace_status=tr_st)
+        return out
 
     def grid_marginal(self, X, y, sigma2, hyper, N, tau, take_log, aniso_lambda=-1.0, want_logs=False):
         X, y = _f(X), _f(np.ravel(y))

@@ -21,6 +21,12 @@ predictions by 0.01 rms on the Ground-Vibrations set (0.001 with 1e-5).  `step` 
 CGP_sets fits the models of many training sets of one shape in lockstep (a simulation study's comparator): the same three
 steps with the rows of every set in each device call (ccgp_cgp_state_batch_sets).
 
+on_device=True (CGP and CGP_sets, default off) keeps the refinement on the device (refine_starts_device over
+ccgp_cgp_fit_sets): rounds of two launches, the gated evaluation of every running start's 1 + 2 (p + 3) rows and one wave per
+start that differences them, steps the start (csrc/fit_logic.h) and writes its next rows, `look` rounds between the host's
+looks.  Every operation between stepper and evaluator is exactly rounded on both sides (csrc/cgp_fit_logic.h), so the fit is
+the default's bit for bit.
+
 The final optim run from `beststart` (GV:155-157) is not repeated: it starts where that start's refinement started, every
 evaluation depends on its own row only (not on the batch it travels in), so the lockstep run of that start IS that run.
 """
@@ -31,7 +37,7 @@ import time
 
 import numpy as np
 
-from .design import minimize_starts
+from .design import _FIT_MESSAGES, minimize_starts
 
 N_CANDIDATE_BASE = 500      # n_candidate = 500 + num_starts (GV:136)
 NONFINITE = 1e6             # GV:130-131
@@ -77,21 +83,25 @@ def lhd(N, k, rng):
     return (np.stack([rng.permutation(N) for _ in range(k)], axis=1) + 0.5) / N
 
 
-def CGP(handle, X, y, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, kappa_u=None, rng=0, step=1e-5):
+def CGP(handle, X, y, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, kappa_u=None, rng=0, step=1e-5,
+        on_device=False, look=16):
     """CGP(X, yobs, ...) of GV:58-236 -> dict with the reference's fields (lambda, theta, alpha, bandwidth, Sig_matrix: its
     diagonal, sf, res2, temp_matrix, mu, tau2, beststart, objval, rmscv, Yp_jackknife, X, yobs), the fit's bounds, and
     calls / evaluations: device calls and the parameter rows they carried (seconds: host clock around the three steps).  invQ
     is not returned: predict_CGP solves with the factor the device keeps.  It is _fit_sets' C = 1 case over
-    ccgp_cgp_state_batch."""
+    ccgp_cgp_state_batch.  on_device: the refinement through refine_starts_device (`look` rounds between the host's looks):
+    every field the same bits except calls, refinement_calls and seconds."""
     h = _plain(handle)
 
     def state(designs, Y, rows, set_of, skip):
         return h.cgp_state_batch(designs[0], Y[0], rows, skip=skip)
 
-    return _fit_sets("CGP", "", h, state, [X], [y], [rng], nugget_l, num_starts, theta_l, alpha_l, kappa_u, step)[0]
+    return _fit_sets("CGP", "", h, state, [X], [y], [rng], nugget_l, num_starts, theta_l, alpha_l, kappa_u, step, on_device,
+                     look)[0]
 
 
-def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, kappa_u=None, rngs=None, step=1e-5):
+def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l=None, kappa_u=None, rngs=None, step=1e-5,
+             on_device=False, look=16):
     """CGP for C training sets of one shape in lockstep -> a list with, per set, the dict CGP(handle, Xs[c], ys[c], ...,
     rng=rngs[c]) returns: every field bit for bit except calls, evaluations, refinement_calls and seconds.
 
@@ -103,21 +113,91 @@ def CGP_sets(handle, Xs, ys, nugget_l=0.001, num_starts=5, theta_l=None, alpha_l
       * the final state per set is ccgp_cgp_predict, unchanged.
     A start's trajectory depends on its own evaluations only and a row's bits on its own set only, so each set's fit is the
     fit it has alone.  calls and refinement_calls are the group's device calls (the same in every dict), evaluations the
-    rows of the set itself, seconds the group's."""
+    rows of the set itself, seconds the group's.  on_device: the refinement of all sets through refine_starts_device, as CGP's."""
     h = _plain(handle)
     rngs = [0] * len(Xs) if rngs is None else list(rngs)
 
     def state(designs, Y, rows, set_of, skip):
         return h.cgp_state_batch_sets(designs, Y, rows, set_of, skip=skip)
 
-    return _fit_sets("CGP_sets", " of set %d", h, state, Xs, ys, rngs, nugget_l, num_starts, theta_l, alpha_l, kappa_u, step)
+    return _fit_sets("CGP_sets", " of set %d", h, state, Xs, ys, rngs, nugget_l, num_starts, theta_l, alpha_l, kappa_u, step,
+                     on_device, look)
 
 
-def _fit_sets(who, of_set, h, state, Xs, ys, rngs, nugget_l, num_starts, theta_l, alpha_l, kappa_u, step):
+def refine_starts_device(handle, Xs, ys, starts, lowers, uppers, set_of, step, look=16, maxit=100, factr=1e7, pgtol=0.0,
+                         max_backtracks=30, on_device=True, seg=512, evaluate=None):
+    """minimize_starts for the CGP objective with the iteration itself on the device: start s = (lambda, theta, kappa, bw)
+    [S, p + 3] runs on the standardised training set set_of[s] of Xs [C, n, p], ys [C, n] under its own box lowers[s],
+    uppers[s], and one call of ccgp_cgp_fit_sets carries every running start through up to `seg` evaluations -- two launches
+    per evaluation, `look` evaluations between the host's looks -- until none is running.
+
+    x, f, converged, iterations, message and calls_per_start are, bit for bit, what minimize_starts returns over the
+    lockstep evaluator (central differences of `step` clipped at the box over ccgp_cgp_state_batch_sets).  `calls` counts
+    device calls: calls of ccgp_cgp_fit_sets, or on the twin the evaluator calls.
+
+    on_device=False drives the same states through the host twin -- every evaluation through ccgp_cgp_fit_eval_sets, every
+    step through ccgp_fit_feed -- and leaves the same states; the driver falls back to it by itself where the device call
+    says CCGP_EUNSUPPORTED (too many rows for one launch, a workspace limit the rows do not fit under).  Beyond 64 variables
+    no such state exists: minimize_starts runs over `evaluate` (minimize_starts' evaluator with pass_live), which the caller
+    then has to give."""
+    from . import api
+
+    starts = np.asarray(starts, dtype=np.float64)
+    S, nv = starts.shape
+    set_of = np.asarray(set_of, dtype=np.int64).reshape(S)
+    lowers = np.broadcast_to(np.asarray(lowers, dtype=np.float64), (S, nv))
+    uppers = np.broadcast_to(np.asarray(uppers, dtype=np.float64), (S, nv))
+    seg, look = int(seg), int(look)
+    if seg < 1 or seg > api.FIT_MAX_EVALS:
+        raise ValueError("refine_starts_device: seg must lie in 1 .. %d" % api.FIT_MAX_EVALS)
+    if look < 1 or look > 64:
+        raise ValueError("refine_starts_device: look must lie in 1 .. 64")
+    if nv > 64:   # the stepper's state ends at 64 variables (csrc/fit_logic.h): minimize_starts itself over the lockstep evaluator
+        if evaluate is None:
+            raise ValueError("refine_starts_device: more than 64 variables need minimize_starts' evaluator")
+        return minimize_starts(evaluate, starts, m=5, maxit=maxit, factr=factr, pgtol=pgtol, max_backtracks=max_backtracks,
+                               lowers=lowers, uppers=uppers, pass_live=True)
+    state = np.stack([api.fit_begin(starts[s], lowers[s], uppers[s], maxit, factr, pgtol, max_backtracks)
+                      for s in range(S)]) if S else np.zeros((0, api.FIT_HEADER + 16 * nv))
+    device = bool(on_device)
+    calls = 0
+    while True:
+        live = np.flatnonzero(state[:, api.FIT_CODE] == api.FIT_RUNNING)
+        if live.size == 0:
+            break
+        if device:
+            try:
+                r = handle.cgp_fit_sets(Xs, ys, set_of[live], state[live], step, seg, look)
+            except api.CcgpError as e:
+                if e.code != -4:   # CCGP_EUNSUPPORTED: these starts have no device refinement; the twin carries them
+                    raise
+                device = False
+                continue
+            state[live] = r["state"]
+            calls += 1
+        else:
+            for _ in range(seg):
+                run = live[state[live, api.FIT_CODE] == api.FIT_RUNNING]
+                if run.size == 0:
+                    break
+                f, g, st = handle.cgp_fit_eval_sets(Xs, ys, api.fit_trial(state[run]), lowers[run], uppers[run], step, set_of[run])
+                calls += 1
+                for k, a in enumerate(run):
+                    api.fit_feed(state[a], f[k], np.asarray(g[k]).ravel(), st[k] == 0)
+    code = state[:, api.FIT_CODE].astype(np.int64)
+    return dict(x=api.fit_x(state), f=state[:, api.FIT_F].copy(),
+                converged=(code == api.FIT_CONV_REDUCTION) | (code == api.FIT_CONV_PROJ_GRAD),
+                iterations=state[:, api.FIT_ITERATIONS].astype(np.int64), message=[_FIT_MESSAGES[c] for c in code],
+                calls=calls, calls_per_start=state[:, api.FIT_EVALS].astype(np.int64))
+
+
+def _fit_sets(who, of_set, h, state, Xs, ys, rngs, nugget_l, num_starts, theta_l, alpha_l, kappa_u, step, on_device=False,
+              look=16):
     """The fit of C sets of one shape in lockstep: candidates, refinement, jackknife, final state.  state(designs[C, n, p],
     Y[C, n], rows, set_of, skip) -> (val, ..., loo, status) evaluates row b on set set_of[b]; skip is None except in the
     jackknife.  who and of_set (a format of the set's index, or empty) word the errors, those about the arguments' shapes
-    included.  Returns one dict per set."""
+    included.  on_device: the refinement runs through refine_starts_device on h instead of minimize_starts over `state`; the
+    rows it evaluates are counted from the starts' evaluation counts.  Returns one dict per set."""
     DDs = [np.asarray(X, dtype=np.float64) for X in Xs]
     yobs = [np.asarray(y, dtype=np.float64).ravel() for y in ys]
     C = len(DDs)
@@ -168,7 +248,13 @@ def _fit_sets(who, of_set, h, state, Xs, ys, rngs, nugget_l, num_starts, theta_l
         g = (f[:, 1::2] - f[:, 2::2]) / (hi - lo)
         return f[:, 0], g, st.reshape(k, -1)[:, 0]
 
-    res = minimize_starts(evaluate, np.concatenate(Starts), lowers=lowers, uppers=uppers, pass_live=True)   # GV:152-154
+    if on_device:
+        res = refine_starts_device(h, XS, Y, np.concatenate(Starts), lowers, uppers, owner, step, look, evaluate=evaluate)
+        if n_par <= 64:   # (beyond it `evaluate` ran and counted for itself)
+            count["calls"] += res["calls"]
+            np.add.at(count["rows"], owner, res["calls_per_start"] * (1 + 2 * n_par))
+    else:
+        res = minimize_starts(evaluate, np.concatenate(Starts), lowers=lowers, uppers=uppers, pass_live=True)   # GV:152-154
     clock.append(time.perf_counter())
     fitted = []
     for c in range(C):

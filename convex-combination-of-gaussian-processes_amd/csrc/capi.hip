@@ -16,6 +16,7 @@
 #include "call_stage.h"
 #include "ccgp_internal.h"
 #include "chain_terms.h"
+#include "cgp_fit_logic.h"
 #include "fit_logic.h"
 #include "nm_logic.h"
 #include "special_math.h"
@@ -1855,6 +1856,146 @@ int ccgp_design_fit(ccgp_handle* h, const double* D_old, int n_fixed, int n, int
     ScopedTimer t(h, CCGP_T_FUSED);
     launch_small_reg_design_fit(h->stream, n, d, dv, n_fixed, A, io);
     CCGP_LAUNCH_CHECK();
+  }
+  std::vector<int> cnt(2 * sA);
+  if (int rc = pull(h, {piece(io.state, state, sA * W), piece(dcnt, cnt.data(), 2 * sA), piece(io.tr_f, trace_f, tr ? sT : 0),
+                        piece(io.tr_status, trace_status, tr ? sT : 0)}))
+    return rc;
+  int failed = 0;
+  for (int a = 0; a < A; ++a) {
+    out_evals[a] = cnt[a];
+    failed += cnt[sA + a];
+  }
+  return failed;
+} CCGP_GUARD_END(h)
+
+// ---- the CGP refinement on the device (ccgp.h) -----------------------------------------------------------------------------------
+int ccgp_cgp_fit_rows(int d) { return d >= 1 && d <= (1 << 20) ? cgp_fit_rows(d) : CCGP_EINVAL; }
+
+// the host twin of the refinement's evaluation: ccgp_cgp_state_batch_sets on the B R rows around the B points (cgp_fit_logic.h),
+// then f = F_0, g_j from rows 1 + 2 j and 2 + 2 j, status = the centre row's
+int ccgp_cgp_fit_eval_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, const double* w,
+                           const double* lo, const double* hi, double step, const int* set, int B, double* out_f,
+                           double* out_g, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (n < 1 || d < 1 || !w || !lo || !hi || !out_f || !out_g || !fit_finite(step) || !(step > 0.0) ||
+      !sets_args_ok(Xs, ys, nullptr, false, C, set, B, 0))
+    return fail(h, CCGP_EINVAL, "ccgp_cgp_fit_eval_sets: bad argument");
+  if (int rc = cgp_shape(h, "ccgp_cgp_fit_eval_sets", n, d)) return rc;
+  if (B == 0) return CCGP_OK;
+  const int P = cgp_fit_vars(d), R = cgp_fit_rows(d), NC = cgp_fit_cols(d);
+  const size_t sB = B, nr = sB * R;
+  if (nr > (size_t)0x7fffffff) return fail(h, CCGP_EUNSUPPORTED, "ccgp_cgp_fit_eval_sets: B (1 + 2 (d + 3)) rows exceed an int");
+  std::vector<double> rows(nr * NC), val(nr), wv(P), lov(P), hiv(P);
+  std::vector<int> row_set(nr), st(nr);
+  for (size_t b = 0; b < sB; ++b) {
+    for (int j = 0; j < P; ++j) {
+      wv[j] = w[b + (size_t)j * sB];
+      lov[j] = lo[b + (size_t)j * sB];
+      hiv[j] = hi[b + (size_t)j * sB];
+    }
+    for (int r = 0; r < R; ++r) {
+      row_set[b * R + r] = set[b];
+      for (int c = 0; c < NC; ++c)
+        rows[b * R + r + (size_t)c * nr] = cgp_fit_row_entry(wv.data(), lov.data(), hiv.data(), step, d, r, c);
+    }
+  }
+  const int rc = ccgp_cgp_state_batch_sets(h, Xs, n, d, ys, C, rows.data(), row_set.data(), (int)nr, nullptr, val.data(), nullptr,
+                                           nullptr, nullptr, st.data());
+  if (rc < 0) return rc;
+  int failed = 0;
+  for (size_t b = 0; b < sB; ++b) {
+    out_f[b] = cgp_fit_value(val[b * R]);
+    if (status) status[b] = st[b * R];
+    failed += st[b * R] != 0;
+    for (int j = 0; j < P; ++j)
+      out_g[b + (size_t)j * sB] = cgp_fit_grad(val[b * R + 1 + 2 * j], val[b * R + 2 + 2 * j], w[b + (size_t)j * sB], step,
+                                               lo[b + (size_t)j * sB], hi[b + (size_t)j * sB]);
+  }
+  return failed;
+} CCGP_GUARD_END(h)
+
+int ccgp_cgp_fit_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int A, const int* set,
+                      double* state, double step, const int* max_evals, int look, int* out_evals, double* trace_f,
+                      int* trace_status, int T) try {
+  if (!h) return CCGP_EINVAL;
+  bool ok = n >= 1 && d >= 1 && A >= 0 && T >= 0 && look >= 1 && look <= 64 && fit_finite(step) && step > 0.0 &&
+            state && max_evals && out_evals && (trace_f != nullptr) == (trace_status != nullptr) &&
+            sets_args_ok(Xs, ys, nullptr, false, C, set, A, 0);
+  const bool steppable = ok && d <= kMaxD - 3;   // beyond 64 variables no state exists to check: refused below
+  const int P = steppable ? cgp_fit_vars(d) : 0, W = steppable ? fit_state_doubles(P) : 0;
+  const int cap = T < 4096 ? T : 4096;
+  int longest = 0;
+  for (int a = 0; ok && a < A; ++a) {
+    ok = max_evals[a] >= 0 && max_evals[a] <= cap && (!steppable || fit_state_ok(state + (size_t)a * W, P));
+    longest = std::max(longest, max_evals[a]);
+  }
+  if (!ok) return fail(h, CCGP_EINVAL, "ccgp_cgp_fit_sets: bad argument");
+  if (int rc = cgp_shape(h, "ccgp_cgp_fit_sets", n, d)) return rc;
+  if (!steppable || (long long)A * cgp_fit_rows(d) > 65535)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_cgp_fit_sets: the refinement runs on the device for at most 64 variables and "
+                                      "65535 rows per round; keep it on ccgp_cgp_fit_eval_sets");
+  const int R = cgp_fit_rows(d), NC = cgp_fit_cols(d);
+  const size_t sA = A, sT = (size_t)A * T, nr = sA * R;
+  const bool tr = trace_f != nullptr && T > 0;
+  double *dXs, *dys;
+  int *dset, *dmax, *dcnt;
+  CgpFitIO io{};
+  io.W = W; io.T = T; io.step = step; io.ldp = (int)nr;
+  // inputs back to back, then results back to back: each side crosses PCIe as one span (the state is both); behind them what
+  // never leaves the device: gates, rows and the round's results
+  auto lay = [&](Layout& c) {
+    dXs = c.take<double>((size_t)C * n * d);
+    dys = c.take<double>((size_t)C * n);
+    dset = c.take<int>(sA);
+    dmax = c.take<int>(sA);
+    io.state = c.take<double>(sA * W);
+    dcnt = c.take<int>(2 * sA);   // evaluations | centre rows failed
+    io.tr_f = tr ? c.take<double>(sT) : nullptr;
+    io.tr_status = tr ? c.take<int>(sT) : nullptr;
+    io.gate = c.take<int>(sA);
+    io.row_set = c.take<int>(nr);
+    io.rows = c.take<double>(nr * NC);
+    io.val = c.take<double>(nr);
+    io.beta = c.take<double>(nr);
+    io.tau2 = c.take<double>(nr);
+    io.status = c.take<int>(nr);
+  };
+  if (layout_bytes(lay) > h->ws_limit)
+    return fail(h, CCGP_EUNSUPPORTED, "ccgp_cgp_fit_sets: rows, results and states do not fit under the workspace limit in one "
+                                      "piece; keep the refinement on ccgp_cgp_fit_eval_sets, whose call chunks");
+  if (A == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  if (int rc = stage(h, lay)) return rc;
+  io.set = dset;
+  io.max_evals = dmax;
+  io.evals = dcnt;
+  io.nfail = dcnt + sA;
+  if (int prc = push(h, {piece(dXs, Xs, (size_t)C * n * d), piece(dys, ys, (size_t)C * n), piece(dset, set, sA),
+                         piece(dmax, max_evals, sA), piece(io.state, state, sA * W)}))
+    return prc;
+  if (tr) {   // a start that stops early leaves the rest of its trace as it is: NaN / -1, not what the buffer held
+    CCGP_HIP(hipMemsetAsync(io.tr_f, 0xFF, Layout::al(sT * sizeof(double)) + Layout::al(sT * sizeof(int)), h->stream));
+  }
+  launch_cgp_fit_step(h->stream, d, A, io, true);
+  CCGP_LAUNCH_CHECK();
+  // `look` rounds of (gated evaluation, step) back to back, then the A gate words: the host looks only there.  A start makes
+  // at most max_evals[a] evaluations, so `longest` rounds close every gate
+  std::vector<int> gate(sA);
+  for (int made = 0; made < longest;) {
+    const int rounds = std::min(look, longest - made);
+    {
+      ScopedTimer t(h, CCGP_T_FUSED);
+      for (int k = 0; k < rounds; ++k) {
+        launch_cgp_state_gated(h->stream, dXs, n, d, dys, io, A);
+        launch_cgp_fit_step(h->stream, d, A, io, false);
+      }
+      CCGP_LAUNCH_CHECK();
+    }
+    made += rounds;
+    if (made >= longest) break;
+    if (int rc = pull(h, {piece(io.gate, gate.data(), sA)})) return rc;
+    if (std::none_of(gate.begin(), gate.end(), [](int g) { return g != 0; })) break;
   }
   std::vector<int> cnt(2 * sA);
   if (int rc = pull(h, {piece(io.state, state, sA * W), piece(dcnt, cnt.data(), 2 * sA), piece(io.tr_f, trace_f, tr ? sT : 0),

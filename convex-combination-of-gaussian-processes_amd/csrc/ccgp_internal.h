@@ -326,6 +326,31 @@ void launch_cgp_state(hipStream_t s, const double* X, int n, int d, const double
 void launch_cgp_state_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set,
                            const double* params, int ldp, int nb, const int* skip, double* val, double* beta, double* tau2,
                            double* loo, int* status);
+// the CGP refinement on the device (ccgp_cgp_fit_sets): what the two launches of a round read and leave, every pointer a device
+// pointer.  With P = d + 3 variables and R = 1 + 2 P rows per start: state [A][W] in and out (fit_logic.h with d = P),
+// max_evals / evals / nfail / set / gate [A], the trace [A][T], both or none; rows A R x (2 d + 2) column-major with leading
+// dimension ldp = A R, row_set / val / beta / tau2 / status [A R]: start a's evaluation is rows a R .. a R + R - 1
+struct CgpFitIO {
+  double* state;
+  int W, T;
+  const int* max_evals;
+  int *evals, *nfail;
+  double* tr_f;
+  int* tr_status;
+  const int* set;
+  int* gate;
+  double step;
+  double* rows;
+  int ldp;
+  int* row_set;
+  double *val, *beta, *tau2;
+  int* status;
+};
+// the gated sets evaluation of the A R rows at io.rows: a workgroup whose start's gate is closed leaves at once
+void launch_cgp_state_gated(hipStream_t s, const double* Xs, int n, int d, const double* ys, const CgpFitIO& io, int A);
+// one wave per start: gradient from the round's values, the step of ccgp_fit_feed, the trace, the next rows or the gate closed.
+// init: before the first evaluation -- counters zeroed, first rows written, gates set
+void launch_cgp_fit_step(hipStream_t s, int d, int A, const CgpFitIO& io, bool init);
 // predict.CGP (GV:287-307) at m sites from a kept state; row: that state's parameter row, contiguous; out m x 6 column-major
 void launch_cgp_predict(hipStream_t s, const double* X, int n, int d, const double* row, const double* Xtest, int m,
                         const double* keep, const int* status, double* out);

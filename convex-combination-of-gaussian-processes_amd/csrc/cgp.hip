@@ -29,6 +29,7 @@
 // temp, s, e^2 and five scalars).  q'Q^-1 q comes from a forward substitution of q through the kept factor, columns streamed
 // from L2 one step ahead, never from an inverse.
 #include "ccgp_internal.h"
+#include "cgp_fit_logic.h"
 
 namespace ccgp {
 
@@ -45,6 +46,8 @@ struct CgpStateArgs {
   int* status;
   double* keep;           // CgpKeep(n) of evaluation 0, or nullptr
   const int* set;         // SETS: evaluation b belongs to training set set[b]: X + set[b] n d, y + set[b] n
+  const int* gate;        // GATED: evaluation b runs only where gate[b / gate_rows] != 0
+  int gate_rows;
 };
 
 __device__ inline double cgp_wave_sum(double v) {
@@ -74,8 +77,14 @@ __device__ __forceinline__ double cgp_dist_to(const double* xs, int ldx, int j, 
 // from its set, everything after the loads is the single-set instance's code, hence its bits.  A template parameter, not a
 // branch, for the reason small_reg.hip gives for PROF and SETS: the single-set instance compiles from unchanged code.  The
 // sets form keeps no state (`keep` does not exist there).
-template <bool SETS>
+// GATED: the evaluations of the refinement on the device (ccgp_cgp_fit_sets): gate_rows consecutive evaluations belong to one
+// start, and a workgroup whose start has stopped leaves at once -- before any LDS write or barrier, the whole workgroup on one
+// word.  A workgroup that stays runs the sets instance's code.  A second switch for the same reason as the first.
+template <bool SETS, bool GATED = false>
 __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
+  if constexpr (GATED) {
+    if (a.gate[blockIdx.x / a.gate_rows] == 0) return;   // uniform: every thread reads the same word
+  }
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int n0 = a.n, d = a.d;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -383,6 +392,61 @@ __global__ __launch_bounds__(256) void cgp_predict_kernel(CgpPredictArgs a) {
   }
 }
 
+// The step of the refinement on the device (ccgp_cgp_fit_sets): one wave per start, behind the gated evaluation of the start's
+// R = 1 + 2 P rows in the same stream.  The state comes to LDS; lane j < P forms g_j from the values of rows 1 + 2 j and
+// 2 + 2 j (cgp_fit_logic.h) and leaves it in LDS; lane 0 runs fit_feed on the state with f = F_0 and the centre row's status
+// and appends both to the trace; the state goes back.  Where the start is still running and has evaluations left, the lanes
+// write its next R parameter rows (and the rows' set); otherwise its gate closes and neither kernel touches the start again.
+// init: no evaluation has been made yet -- the counters are zeroed and the first rows written.  No path waits on another
+// workgroup: the order of evaluation and step is the stream's.
+__global__ __launch_bounds__(64) void cgp_fit_step_kernel(CgpFitIO io, int d, int init) {
+  extern __shared__ __attribute__((aligned(16))) double fsm[];
+  const int a = blockIdx.x, lane = threadIdx.x;
+  if (!init && io.gate[a] == 0) return;   // uniform
+  const int P = cgp_fit_vars(d), R = cgp_fit_rows(d), NC = cgp_fit_cols(d), W = io.W;
+  double* sg = io.state + (size_t)a * W;
+  double *st = fsm, *g = fsm + W, *cnt = fsm + W + P;
+  for (int e = lane; e < W; e += 64) st[e] = sg[e];
+  __syncthreads();
+  const size_t b0 = (size_t)a * R;
+  const double *w = fit_trial(st, P), *lo = fit_lo(st, P), *hi = fit_hi(st, P);
+  if (!init) {
+    for (int j = lane; j < P; j += 64)
+      g[j] = cgp_fit_grad(io.val[b0 + 1 + 2 * j], io.val[b0 + 2 + 2 * j], w[j], io.step, lo[j], hi[j]);
+    __syncthreads();
+    if (lane == 0) {
+      const double f = cgp_fit_value(io.val[b0]);
+      const int bad = io.status[b0];
+      const int t = io.evals[a];   // < max_evals[a] <= T: the gate was open
+      if (io.tr_f) {
+        const size_t at = (size_t)a * io.T + t;
+        io.tr_f[at] = f;
+        io.tr_status[at] = bad;
+      }
+      fit_feed(st, f, g, bad == 0);
+      io.evals[a] = t + 1;
+      io.nfail[a] += bad != 0;
+      cnt[0] = (double)(t + 1);
+    }
+    __syncthreads();
+    for (int e = lane; e < W; e += 64) sg[e] = st[e];
+  } else if (lane == 0) {
+    io.evals[a] = 0;
+    io.nfail[a] = 0;
+  }
+  const int made = init ? 0 : (int)cnt[0];
+  const bool go = st[kFitCode] == (double)kFitRunning && made < io.max_evals[a];   // uniform
+  if (go) {
+    const int st_a = io.set[a];
+    for (int e = lane; e < R * NC; e += 64) {
+      const int r = e % R, c = e / R;
+      io.rows[b0 + r + (size_t)c * io.ldp] = cgp_fit_row_entry(w, lo, hi, io.step, d, r, c);
+    }
+    for (int r = lane; r < R; r += 64) io.row_set[b0 + r] = st_a;
+  }
+  if (lane == 0) io.gate[a] = go ? 1 : 0;
+}
+
 }  // namespace
 
 void launch_cgp_state(hipStream_t st, const double* X, int n, int d, const double* y, const double* params, int ldp, int nb,
@@ -404,6 +468,23 @@ void launch_cgp_state_sets(hipStream_t st, const double* Xs, int n, int d, const
   a.X = Xs; a.y = ys; a.n = n; a.d = d; a.params = params; a.ldp = ldp; a.skip = skip; a.set = set;
   a.val = val; a.beta = beta; a.tau2 = tau2; a.loo = loo; a.status = status;
   hipLaunchKernelGGL(cgp_state_kernel<true>, dim3(nb), dim3(256), sizeof(double) * CgpCarve(n, d).total, st, a);
+}
+
+void launch_cgp_state_gated(hipStream_t st, const double* Xs, int n, int d, const double* ys, const CgpFitIO& io, int A) {
+  static unsigned long long attr_mask = 0;
+  once_per_device(attr_mask,
+                  [] { raise_lds_limit((const void*)cgp_state_kernel<true, true>, "cgp_state_kernel<sets, gated>"); });
+  CgpStateArgs a{};
+  a.X = Xs; a.y = ys; a.n = n; a.d = d; a.params = io.rows; a.ldp = io.ldp; a.set = io.row_set;
+  a.val = io.val; a.beta = io.beta; a.tau2 = io.tau2; a.status = io.status;
+  a.gate = io.gate; a.gate_rows = cgp_fit_rows(d);
+  hipLaunchKernelGGL((cgp_state_kernel<true, true>), dim3(A * cgp_fit_rows(d)), dim3(256),
+                     sizeof(double) * CgpCarve(n, d).total, st, a);
+}
+
+void launch_cgp_fit_step(hipStream_t st, int d, int A, const CgpFitIO& io, bool init) {
+  const size_t lds = sizeof(double) * ((size_t)io.W + cgp_fit_vars(d) + 1);
+  hipLaunchKernelGGL(cgp_fit_step_kernel, dim3(A), dim3(64), lds, st, io, d, init ? 1 : 0);
 }
 
 void launch_cgp_predict(hipStream_t st, const double* X, int n, int d, const double* row, const double* Xtest, int m,

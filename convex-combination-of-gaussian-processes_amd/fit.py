@@ -861,24 +861,33 @@ def _add_single_columns(table, gp, D_test, alpha, D_train, y_train, single):
     return table
 
 
-def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=None, exact=False, cgp=False, single=False):
+def _cgp_on_device(cgp, device_cgp):
+    """The cgp argument with device_cgp folded in: a fit that is still to be made gets on_device=True."""
+    if not device_cgp or not cgp or (isinstance(cgp, dict) and "est" in cgp):
+        return cgp
+    return dict(cgp if isinstance(cgp, dict) else {}, on_device=True)
+
+
+def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=None, exact=False, cgp=False, single=False,
+               device_cgp=False):
     """HX:713-725 + prediction HX:686-703 (GV:620-646 adds Quant.Combined): one row per test point
     (y.hat.Combined, Quant.Combined, LL.Combined, UL.Combined, y.true).  exact=True takes Quant and the interval from
     the exact posterior predictive on the device (gp.prediction) instead of sampling one variate per draw: rng is
     ignored, the tables stay on the device, and the keys are the same without mean / var.  cgp (default off; True, or a dict
     of cgp.CGP's keyword arguments) adds the table's CGP model (GV:654-660): y_hat_CGP, LL_CGP, UL_CGP and the fit as CGP;
-    cgp=dict(est=<a dict of cgp.CGP or cgp.CGP_sets>) takes a fitted model instead of fitting.
+    cgp=dict(est=<a dict of cgp.CGP or cgp.CGP_sets>) takes a fitted model instead of fitting.  device_cgp (default off): that
+    fit's refinement runs on the device (cgp.CGP(on_device=True)): the same model bit for bit.
     single (default off) adds the ordinary-kriging model: True fits it on the device (ordinary_kriging_fit; for a 1-D gp
     matern_MLEs), a dict(theta=..., sigma2=...) or dict(est=<a dict of ordinary_kriging_fit>) takes a given model, and
     further keys go to the fit.  It adds y_hat_single,
     LL_single, UL_single = y_hat -+ qt(1 - alpha / 2, n - 1) sqrt(max(var, 0)) -- var in the plug-in form for the 2-D /
     emulator scripts, in the unbiased form (and returned as single_var) for the 1-D scripts -- and the model as single."""
     if single:
-        table = compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng, exact, cgp)
+        table = compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng, exact, cgp, device_cgp=device_cgp)
         return _add_single_columns(table, gp, D_test, alpha, D_train, y_train, single)
     if cgp:
         table = compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng, exact)
-        return _add_cgp_columns(table, gp, D_test, D_train, y_train, cgp)
+        return _add_cgp_columns(table, gp, D_test, D_train, y_train, _cgp_on_device(cgp, device_cgp))
     if exact:
         r = gp.prediction(D_test, alpha, draws, D_train, sigma2, y_train)
         return dict(y_hat=r["y_hat"], quant=r["Quant"], LL=r["LL"], UL=r["UL"],
@@ -1408,7 +1417,7 @@ def stack_tables(tables):
 def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size=None, start=None, sigma2s=None,
           theta1_pars=None, theta2_pars=None, rngs=None, max_proposals=None, speculate=0, laplace=None, cgp=False,
           single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None, lockstep_fits=True,
-          device_chains=False, device_fits=False, device_laplace=False):
+          device_chains=False, device_fits=False, device_laplace=False, device_cgp=False):
     """The reference's simulation study (GV:689-762 declares nine training sets and fits one): every set of `sets` -- a list
     of (D_train, y_train, D_test, y_test) -- fitted and compared, the sets of one shape (n, d) in lockstep.  Per group:
     sigma2 per set from ordinary_kriging_fit (or sigma2s[i] as given), then laplace_sets and Metro_sets with one generator
@@ -1435,6 +1444,8 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     device_laplace (default off): the Laplace stage of each group goes through laplace_device_sets -- the Nelder-Mead search
     resident on the device, every set's search in one launch, over the twin evaluator.  Its estimates are laplace_sets' over
     that evaluator bit for bit, so with device_chains=True the tables are those of device_chains=True alone.
+    device_cgp (default off): the CGP fits' refinement runs on the device (cgp.CGP_sets / cgp.CGP with on_device=True): the
+    same models bit for bit, so the tables are those of device_cgp=False.
     Returns dict(tables, summaries, pooled: comparison_summary of the stacked tables, sigma2, draws, beta, chains,
     groups: {(n, d): indices}, calls and seconds: device calls and wall time of the sigma2, single, cgp, laplace, metro and
     predict parts; per set the single and cgp fits happen inside compare_GP, so their seconds are part of predict's and
@@ -1444,6 +1455,7 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     sets = list(sets)
     if not sets:
         raise ValueError("study: no sets")
+    cgp = _cgp_on_device(cgp, device_cgp)
     C = len(sets)
     groups = group_sets(sets)
     net = net_samp_size or samp_size

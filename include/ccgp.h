@@ -756,6 +756,48 @@ int ccgp_design_fit(ccgp_handle* h, const double* D_old, int n_fixed, int n, int
                     double ld_offset, int A, double* state /* A x W(nv), in and out */, const int* max_evals,
                     int* out_evals, double* trace_f, int* trace_status /* A x T, both or neither */, int T);
 
+/* ---- the CGP refinement on the device: evaluate and step launches, no host trips (CGP's optim calls, GV:152-154) ------------------
+ * A start's variables are w = (lambda, theta_1 .. theta_d, kappa, bw), P = d + 3, in its box [lo, hi]; the gradient is by central
+ * differences of step `step` clipped at the box: up_j = min(w_j + step, hi_j), dn_j = max(w_j - step, lo_j).  One evaluation is
+ * R = ccgp_cgp_fit_rows(d) = 1 + 2 P rows of ccgp_cgp_state_batch_sets: row 0 the centre, row 1 + 2 j variable j at up_j, row
+ * 2 + 2 j at dn_j, each as the device row (v_0, v_1 .. v_d, v_k + v_{d+1}, v_{d+2}).  F = val where val is finite, else 1e6
+ * (GV:130-131); f = F_0, g_j = (F_{1+2j} - F_{2+2j}) / (up_j - dn_j), status = the centre row's.  Every operation between the
+ * stepper and the evaluator is exactly rounded (csrc/cgp_fit_logic.h), so host and device form the same rows and gradients.
+ * The state of a start is ccgp_fit_begin's with d = P (W = ccgp_fit_state_doubles(P)); lo and hi are read from it.
+ * ccgp_cgp_fit_eval_sets is the evaluation of B points (w, lo, hi, out_g: B x P column-major) on the host side of
+ * ccgp_cgp_state_batch_sets: it forms the B R rows, calls ccgp_cgp_state_batch_sets with that call's checks, routes and
+ * chunking, and transforms the results.  ccgp_cgp_fit_sets runs A starts, start a on training set set[a], on the device: it
+ * stages the sets and states once, writes the first rows, and queues rounds of two launches on the handle's stream -- the gated
+ * evaluation of every running start's R rows, then one wave per start that forms the gradient, takes the step of ccgp_fit_feed
+ * and writes the start's next rows or closes its gate -- `look` rounds back to back before the host reads the A gate words,
+ * until no gate is open.  It writes the states back, so the next call continues them.  out_evals[a] is the number of
+ * evaluations made.  The trace (both or neither, [a T + t]): f and the centre row's pivot status of evaluation t of this call;
+ * NaN / -1 beyond out_evals[a].
+ *   Bits.  Every row evaluated inside ccgp_cgp_fit_sets has the bits ccgp_cgp_state_batch_sets gives it on its set.  A start
+ *     driven evaluation by evaluation through ccgp_cgp_fit_eval_sets and ccgp_fit_feed leaves the same state and trace, bit for
+ *     bit.
+ *   Independence.  A start depends on its own state, its set and `step` only: not on A, its position, the other starts' sets,
+ *     `look`, how its evaluations are cut into calls by max_evals, or what the handle's buffers held before.
+ *   Failure.  A failed centre row is an infeasible trial: the line search backs off and the start goes on; a failed differenced
+ *     row shows through the 1e6 only.  A start whose first point fails ends with code 5, its neighbours untouched.  The return
+ *     value is the number of evaluations whose centre row failed, over all starts (all points).
+ *   Arguments.  CCGP_EINVAL before anything is copied or launched, outputs and ccgp_workspace_bytes unchanged: bad shapes,
+ *     C < 1, A < 0 (B < 0), T < 0, look outside 1 .. 64, step not finite or <= 0, set[a] outside 0 .. C-1, max_evals[a] outside
+ *     0 .. min(T, 4096), a partial trace, a NULL required pointer (everything but the trace and ccgp_cgp_fit_eval_sets' status),
+ *     a state whose recorded d is not P.  CCGP_EUNSUPPORTED, outputs untouched: where ccgp_cgp_state_batch_sets refuses; and for
+ *     ccgp_cgp_fit_sets alone more than 64 variables (the stepper's state ends there), A R > 65535, or rows, results and states
+ *     that do not fit under the workspace limit in one piece -- the twin serves these, its call chunks.  A == 0 (B == 0) returns
+ *     CCGP_OK.  A start that is not running, or whose max_evals is 0, is returned as it came.
+ * Host pointers only, blocking; ccgp_reserve does not cover the staging.  Not in this version: an analytic gradient, _dev
+ * variants, a ccgp_multi wrapper, an R shim. */
+int ccgp_cgp_fit_rows(int d);
+int ccgp_cgp_fit_eval_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C,
+                           const double* w /* B x P */, const double* lo, const double* hi /* B x P */, double step,
+                           const int* set /* B */, int B, double* out_f, double* out_g /* B x P */, int* status /* NULL ok */);
+int ccgp_cgp_fit_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int A, const int* set /* A */,
+                      double* state /* A x W(P), in and out */, double step, const int* max_evals /* A */, int look,
+                      int* out_evals /* A */, double* trace_f, int* trace_status /* A x T, both or neither */, int T);
+
 /* ---- several GPUs behind ONE host process (csrc/multi.cpp) ------------------------------
  * The drop-in host is R: one single-threaded process.  A ccgp_multi owns one handle per device; the three
  * batched entry points below take the same arguments as their single-device forms, cut the batch into

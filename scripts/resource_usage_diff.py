@@ -5,7 +5,8 @@ Input: the remark output of each build, e.g. for csrc/small_reg.hip
 demangled name; a template argument the new build appended with its default value (`, false` at the end of
 small_reg_kernel's list) is dropped for the match, so an instance that existed before is compared with itself; likewise a
 kernel the new build turned into a template over switches (cgp_state_kernel<false>) matches the parent's plain kernel where
-every switch is `false`.  Prints every
+every switch is `false`, and a template over switches that gained further ones (cgp_state_kernel<true, false>) matches the
+parent's instance with the leading switches (cgp_state_kernel<true>) where the added ones are `false`.  Prints every
 difference, the counts, and the kernels only the new build has -- each beside the pre-existing instance with the same
 leading arguments.  Needs c++filt.  Exit status 1 when a pre-existing kernel differs.
     python scripts/resource_usage_diff.py parent.txt new.txt [--appended 1]"""
@@ -53,6 +54,12 @@ def main():
         m = re.match(r"void (.*?)<((?:true|false)(?:, (?:true|false))*)>(\(.*)", name)
         if m and m.group(1) + m.group(3) in parent_names:   # a plain kernel of the parent that became a template over switches
             return m.group(1) + m.group(3), "true" in m.group(2)
+        m = re.match(r"(.*?<)((?:true|false)(?:, (?:true|false))+)(>.*)", name)
+        if m and "small_reg_kernel<" not in name:   # a template over switches that gained some (cgp_state_kernel's GATED)
+            a = m.group(2).split(", ")
+            for cut in range(1, len(a)):
+                if m.group(1) + ", ".join(a[:len(a) - cut]) + m.group(3) in parent_names:
+                    return m.group(1) + ", ".join(a[:len(a) - cut]) + m.group(3), "true" in a[len(a) - cut:]
         m = re.match(r"(.*?<)([^>]*)(>.*)", name)
         if not m or "small_reg_kernel<" not in name:
             return name, False
