@@ -85,6 +85,13 @@ SIGNATURES = {
                                          _dp, _ip, c_int]),
     "ccgp_cgp_state_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _ip, _dp, _dp, _dp, _dp,
                                           _ip]),
+    "ccgp_predict_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, _ip, c_int, _dp, c_int, _dp, _dp,
+                                        _dp, _ip]),
+    "ccgp_krige_predict_batch_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, c_int, _dp, _ip, c_int, _dp, c_int, _dp,
+                                              c_int, _dp, _dp, _dp, _dp, _ip]),
+    "ccgp_predict_summary_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, _dp, c_int, c_int, _dp, _ip, c_int, _dp, c_int, _dp,
+                                          c_int, _dp, _dp, _dp, _ip]),
+    "ccgp_cgp_predict_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _ip, c_int, _dp, c_int, _dp, _dp, _ip]),
     "ccgp_cgp_fit_rows": (c_int, [c_int]),
     "ccgp_cgp_fit_eval_sets": (c_int, [c_void_p, _dp, c_int, c_int, _dp, c_int, _dp, _dp, _dp, c_double, _ip, c_int, _dp, _dp,
                                        _ip]),
@@ -984,6 +991,83 @@ class Handle:
         self._chk(lib().ccgp_cgp_state_batch_sets(self._h, _p(Xb), n, d, _p(yb), C, _p(params), _ipt(idx), B, _ipt(sk), _p(val),
                                                   _p(beta), _p(tau2), _p(loo), _ipt(st)))
         return val, beta, tau2, loo, st
+
+    def _sets_sites(self, Xs, ys, sigma2s, K, params, set_of, Xtests):
+        """What the three Gaussian sets predictions share: _sets, the B x (K + K d) rows and the sets' test sites [C, m, d] as
+        C column-major blocks."""
+        params = _f(np.atleast_2d(params))
+        B, P = params.shape
+        Xb, yb, s2, idx, C, n, d = self._sets(Xs, ys, sigma2s, set_of, B)
+        _check_columns(P, K + K * d, "K + K*d")
+        Xt = np.asarray(Xtests, dtype=np.float64)
+        if Xt.ndim != 3 or Xt.shape[0] != C or Xt.shape[2] != d:
+            raise ValueError("Xtests must be [C, m, d]: the sets of one call have as many test sites each")
+        return Xb, yb, s2, idx, C, n, d, params, B, np.ascontiguousarray(np.transpose(Xt, (0, 2, 1))), Xt.shape[1]
+
+    def predict_batch_sets(self, Xs, ys, sigma2s, K, params, set_of, Xtests):
+        """ccgp_predict_batch_sets: row b of params on training set set_of[b] of the C sets Xs [C, n, d], ys [C, n], sigma2s [C],
+        predicted at that set's own test sites Xtests [C, m, d].  Returns what predict_batch returns -- (mean[B, m], var[B, m],
+        beta[B], status[B]) -- each row with the bits predict_batch gives it on its set alone."""
+        Xb, yb, s2, idx, C, n, d, params, B, Xtb, m = self._sets_sites(Xs, ys, sigma2s, K, params, set_of, Xtests)
+        mean, var = np.empty((B, m), order="F"), np.empty((B, m), order="F")
+        beta, st = _outputs(B, 1)
+        self._chk(lib().ccgp_predict_batch_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, K, _p(params), _ipt(idx), B, _p(Xtb), m,
+                                                _p(mean), _p(var), _p(beta), _ipt(st)))
+        return mean, var, beta, st
+
+    def krige_predict_batch_sets(self, Xs, ys, K, params, set_of, sigma2, Xtests, form):
+        """ccgp_krige_predict_batch_sets: row b of params is one fitted single-GP model of training set set_of[b] with its own
+        sigma2[b] (None for VAR_UNBIASED), predicted at that set's test sites Xtests [C, m, d].  Returns what
+        krige_predict_batch returns -- (mean[B, m], var[B, m], beta[B], q[B], status[B]) -- each row with its bits there."""
+        Xb, yb, _, idx, C, n, d, params, B, Xtb, m = self._sets_sites(Xs, ys, None, K, params, set_of, Xtests)
+        s2 = None if sigma2 is None else _f(np.broadcast_to(np.asarray(sigma2, dtype=np.float64), (B,)).copy())
+        mean, var = np.empty((B, m), order="F"), np.empty((B, m), order="F")
+        beta, q, st = _outputs(B, 2)
+        self._chk(lib().ccgp_krige_predict_batch_sets(self._h, _p(Xb), n, d, _p(yb), C, K, _p(params), _ipt(idx), B, _p(s2),
+                                                      int(form), _p(Xtb), m, _p(mean), _p(var), _p(beta), _p(q), _ipt(st)))
+        return mean, var, beta, q, st
+
+    def predict_summary_sets(self, Xs, ys, sigma2s, K, params, set_of, Xtests, probs, ys_at=None):
+        """ccgp_predict_summary_sets: prediction()'s per-site summaries per training set -- set c's from the rows with
+        set_of[b] == c -- at that set's own test sites Xtests [C, m, d]; ys_at [C, m] adds cdf_at.  Returns a list of C dicts
+        as predict_summary returns them (beta, status: the set's rows in their order; n_failed: the set's), each with the bits
+        predict_summary gives on that set's rows alone; a set without rows is NaN throughout."""
+        Xb, yb, s2, idx, C, n, d, params, B, Xtb, m = self._sets_sites(Xs, ys, sigma2s, K, params, set_of, Xtests)
+        probs = _probs(probs)
+        yat = None if ys_at is None else np.ascontiguousarray(np.asarray(ys_at, dtype=np.float64).reshape(C, m))
+        out = np.empty((C, 4 + probs.size, m))
+        beta, st = _outputs(B, 1)
+        self._chk(lib().ccgp_predict_summary_sets(self._h, _p(Xb), n, d, _p(yb), _p(s2), C, K, _p(params), _ipt(idx), B, _p(Xtb),
+                                                  m, _p(probs), probs.size, _p(yat), _p(out), _p(beta), _ipt(st)))
+        res = []
+        for c in range(C):
+            rows = np.flatnonzero(idx == c)
+            res.append(_summary_dict(np.asfortranarray(out[c].T), int(np.count_nonzero(st[rows])), beta[rows], st[rows]))
+        return res
+
+    def cgp_predict_sets(self, Xs, ys, params, set_of, Xtests):
+        """ccgp_cgp_predict_sets: the final CGP state at row b of params [B, 2 d + 2] on training set set_of[b] of the C sets
+        Xs [C, n, d], ys [C, n], and predict.CGP(PI = TRUE) at that set's own test sites Xtests [C, m, d] (m may be 0), all
+        rows in one call.  Returns (out[B, m, 6], keeps: per row what cgp_predict returns -- dict(s, res2, temp, sf, beta, tau2)
+        or None where the row's state failed --, status[B]), each row with the bits cgp_predict gives it on its set alone."""
+        params = _f(np.atleast_2d(params))
+        B, P = params.shape
+        Xb, yb, _, idx, C, n, d = self._sets(Xs, ys, None, set_of, B)
+        _check_columns(P, 2 * d + 2, "2 d + 2")
+        Xt = np.asarray(Xtests, dtype=np.float64)
+        if Xt.ndim != 3 or Xt.shape[0] != C or Xt.shape[2] != d:
+            raise ValueError("Xtests must be [C, m, d]: the sets of one call have as many test sites each")
+        m = Xt.shape[1]
+        Xtb = np.ascontiguousarray(np.transpose(Xt, (0, 2, 1)))
+        blocks = np.empty((B, 6, m))
+        state = np.empty((B, 3 * n + 3))
+        st = np.zeros(B, dtype=np.int32)
+        self._chk(lib().ccgp_cgp_predict_sets(self._h, _p(Xb), n, d, _p(yb), C, _p(params), _ipt(idx), B, _p(Xtb) if m else None,
+                                              m, _p(blocks) if m else None, _p(state), _ipt(st)))
+        keeps = [None if st[b] else dict(s=state[b, :n].copy(), res2=state[b, n:2 * n].copy(), temp=state[b, 2 * n:3 * n].copy(),
+                                         sf=float(state[b, 3 * n]), beta=float(state[b, 3 * n + 1]),
+                                         tau2=float(state[b, 3 * n + 2])) for b in range(B)]
+        return np.transpose(blocks, (0, 2, 1)), keeps, st
 
     def cgp_fit_eval_sets(self, Xs, ys, w, lower, upper, step, set_of):
         """ccgp_cgp_fit_eval_sets: the CGP refinement's objective at the points w [B, d + 3] = (lambda, theta, kappa, bw), point b

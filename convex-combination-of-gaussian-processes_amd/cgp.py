@@ -319,3 +319,33 @@ def predict_CGP(handle, est, newdata, PI=False):
     if not PI:
         return dict(Yp=out[:, 0], gp=out[:, 1], lp=np.zeros(U.shape[0]), v=out[:, 3], Y_low=None, Y_up=None)
     return dict(Yp=out[:, 0], gp=out[:, 1], lp=out[:, 2], v=out[:, 3], Y_low=out[:, 4], Y_up=out[:, 5])
+
+
+def predict_CGP_sets(handle, ests, newdatas, PI=False):
+    """predict_CGP for many fitted models at once: model i (a dict of CGP or CGP_sets) predicted at newdatas[i].  The models
+    whose design has one shape (n, d) and whose test sets have one size m go to the device in ONE call
+    (Handle.cgp_predict_sets), so ragged test sets make one call per m.  Returns the list of predict_CGP's dicts, in the
+    models' order, each equal to predict_CGP(handle, ests[i], newdatas[i], PI) bit for bit."""
+    ests = list(ests)
+    if len(ests) != len(newdatas):
+        raise ValueError("predict_CGP_sets: one newdata per model")
+    Us = [np.asarray(u, dtype=np.float64).reshape(-1, e["X"].shape[1]) for e, u in zip(ests, newdatas)]
+    groups = {}
+    for i, (e, U) in enumerate(zip(ests, Us)):
+        groups.setdefault(e["X"].shape + (U.shape[0],), []).append(i)
+    res = [None] * len(ests)
+    for (n, d, m), idx in groups.items():
+        out, _, status = _plain(handle).cgp_predict_sets(np.stack([ests[i]["X"] for i in idx]),
+                                                         np.stack([np.ravel(ests[i]["yobs"]) for i in idx]),
+                                                         np.stack([param_row(ests[i]) for i in idx]), np.arange(len(idx)),
+                                                         np.stack([Us[i] for i in idx]))
+        if status.any():
+            j = int(np.flatnonzero(status)[0])
+            raise RuntimeError("predict_CGP_sets: the state of model %d cannot be factorised (pivot %d)" % (idx[j], status[j]))
+        for j, i in enumerate(idx):
+            o = out[j]
+            if not PI:
+                res[i] = dict(Yp=o[:, 0], gp=o[:, 1], lp=np.zeros(m), v=o[:, 3], Y_low=None, Y_up=None)
+            else:
+                res[i] = dict(Yp=o[:, 0], gp=o[:, 1], lp=o[:, 2], v=o[:, 3], Y_low=o[:, 4], Y_up=o[:, 5])
+    return res

@@ -365,6 +365,152 @@ inline CgpSetsStage cgp_sets_stage(Layout& c, int n, int d, int C, int nb) {
   return s;
 }
 inline size_t cgp_sets_row_bytes(int d) { return sizeof(double) * (2 * (size_t)d + 2 + 4) + 3 * sizeof(int); }
+//   ccgp_cgp_predict_sets: Xs | ys | Xtests | set | params | out | state | status | res | keep
+// The sets' test sites (C blocks of m x d) go up with the sets.  Per row: its m x 6 block, the 3 n + 3 doubles of its state
+// that the caller may ask for (gathered on the device from its kept block, so that they come down beside `out` as one span),
+// val | beta | tau2 of the state launch (res, never pulled) and the kept block itself (keep_doubles each, never pulled).
+struct CgpPredictSetsStage {
+  double *Xs, *ys, *Xtests;
+  int* set;
+  double *params, *out, *state;
+  int* status;
+  double *res, *keep;
+  size_t nXs, nys, nXt, P, nout, nstate;
+  std::vector<Piece> inputs(bool first, const double* hXs, const double* hys, const double* hXtests, const int* hset,
+                            const double* hparams, int nb) const {
+    return {piece(Xs, first ? hXs : nullptr, nXs), piece(ys, first ? hys : nullptr, nys),
+            piece(Xtests, first ? hXtests : nullptr, nXt), piece(set, hset, (size_t)nb),
+            piece(params, hparams, (size_t)nb * P)};
+  }
+  // the status words follow state (pull_status); hstate == nullptr: the caller does not want the states
+  std::vector<Piece> results(double* hout, double* hstate, int nb) const {
+    return {piece(out, hout, (size_t)nb * nout), piece(state, hstate, (size_t)nb * nstate)};
+  }
+};
+inline CgpPredictSetsStage cgp_predict_sets_stage(Layout& c, int n, int d, int C, int m, size_t keep_doubles, int nb) {
+  CgpPredictSetsStage s;
+  s.nXs = (size_t)C * n * d; s.nys = (size_t)C * n; s.nXt = (size_t)C * m * d; s.P = 2 * (size_t)d + 2;
+  s.nout = (size_t)m * 6; s.nstate = 3 * (size_t)n + 3;
+  s.Xs = c.take<double>(s.nXs);
+  s.ys = c.take<double>(s.nys);
+  s.Xtests = c.take<double>(s.nXt);
+  s.set = c.take<int>(nb);
+  s.params = c.take<double>((size_t)nb * s.P);
+  s.out = c.take<double>((size_t)nb * s.nout);
+  s.state = c.take<double>((size_t)nb * s.nstate);
+  s.status = c.take<int>(nb);
+  s.res = c.take<double>(3 * (size_t)nb);
+  s.keep = c.take<double>((size_t)nb * keep_doubles);
+  return s;
+}
+inline size_t cgp_predict_sets_row_bytes(int n, int d, int m, size_t keep_doubles) {
+  return sizeof(double) * (2 * (size_t)d + 2 + 6 * (size_t)m + 3 * (size_t)n + 3 + 3 + keep_doubles) + 2 * sizeof(int);
+}
+
+// ---- the Combined GP's and the single GP's prediction over sets (ccgp_predict_batch_sets, ccgp_krige_predict_batch_sets,
+// ccgp_predict_summary_sets): per set with rows the pieces the single-set call stages, each with its alignment there, laid in
+// three passes so that both copies are one span --
+//   1. inputs, set by set:  X | y | params (nb x P) | Xtest | sigma2_row? | y_at?          (up)
+//   2. tables, set by set:  mean | var | idx? | count?        (down without a summary; with one they never leave the device)
+//   3. results, set by set: out? | beta | q? | status                                       (down)
+// A set no row refers to takes nothing (every pointer null, nb 0).  off: where the set's rows start among the grouped rows.
+struct SetPieces {
+  int nb, off;
+  double *X, *y, *Xt, *params, *s2row, *y_at;
+  double *mean, *var, *out, *beta, *q;
+  int *status, *idx, *count;
+};
+inline std::vector<SetPieces> predict_sets_stage(Layout& w, const std::vector<int>& nb_of, int n, int d, int P, int m, bool krige,
+                                                 bool s2row, bool summary, bool y_at, size_t nout) {
+  std::vector<SetPieces> sp(nb_of.size());
+  int off = 0;
+  for (size_t c = 0; c < sp.size(); ++c) {
+    SetPieces& s = sp[c];
+    s = SetPieces{};
+    s.nb = nb_of[c];
+    s.off = off;
+    off += s.nb;
+    if (!s.nb) continue;
+    const size_t nb = (size_t)s.nb;
+    s.X = w.take<double>((size_t)n * d);
+    s.y = w.take<double>(n);
+    s.params = w.take<double>(nb * P);
+    s.Xt = w.take<double>((size_t)m * d);
+    s.s2row = s2row ? w.take<double>(nb) : nullptr;
+    s.y_at = y_at ? w.take<double>(m) : nullptr;
+  }
+  for (SetPieces& s : sp) {
+    if (!s.nb) continue;
+    const size_t nb = (size_t)s.nb;
+    s.mean = w.take<double>(nb * m);
+    s.var = w.take<double>(nb * m);
+    if (summary) {
+      s.idx = w.take<int>(nb);
+      s.count = w.take<int>(1);
+    }
+  }
+  for (SetPieces& s : sp) {
+    if (!s.nb) continue;
+    const size_t nb = (size_t)s.nb;
+    if (summary) s.out = w.take<double>(nout);
+    s.beta = w.take<double>(nb);
+    s.q = krige ? w.take<double>(nb) : nullptr;
+    s.status = w.take<int>(nb);
+  }
+  return sp;
+}
+
+// The same three calls on their one-launch route (small_route_predict_sets == Reg): the rows are grouped by set (a set's rows
+// consecutive, in their order), so that one B x P parameter table, one set index per row and B x m tables serve every set:
+//   up:    Xs | ys | sigma2_set | Xtests | set | off | nb | params | s2row? | y_at?
+//   stay:  mean | var | idx? | count?          (down without a summary)
+//   down:  out? | beta | q? | status
+struct PredictSetsOneStage {
+  double *Xs, *ys, *sigma2_set, *Xtests;
+  int *set, *off, *nb;
+  double *params, *s2row, *y_at, *mean, *var;
+  int *idx, *count;
+  double *out, *beta, *q;
+  int* status;
+  size_t nXs, nys, C, nXt, B, nparams, nyat, ntab, nout;
+  std::vector<Piece> inputs(const double* hXs, const double* hys, const double* hs2set, const double* hXt, const int* hset,
+                            const int* hoff, const int* hnb, const double* hparams, const double* hs2row,
+                            const double* hyat) const {
+    return {piece(Xs, hXs, nXs), piece(ys, hys, nys), piece(sigma2_set, hs2set, C), piece(Xtests, hXt, nXt), piece(set, hset, B),
+            piece(off, hoff, C), piece(nb, hnb, C), piece(params, hparams, nparams), piece(s2row, hs2row, s2row ? B : 0),
+            piece(y_at, hyat, y_at ? nyat : 0)};
+  }
+  // hmean / hvar: nullptr for a summary (the tables stay); hout: nullptr without one
+  std::vector<Piece> results(double* hmean, double* hvar, double* hout, double* hbeta, double* hq, int* hstatus) const {
+    return {piece(mean, hmean, hmean ? ntab : 0), piece(var, hvar, hvar ? ntab : 0), piece(out, hout, out ? nout : 0),
+            piece(beta, hbeta, B), piece(q, hq, q ? B : 0), piece(status, hstatus, B)};
+  }
+};
+inline PredictSetsOneStage predict_sets_one_stage(Layout& w, int n, int d, int P, int C, int B, int m, bool krige, bool s2row,
+                                                  bool summary, bool y_at, size_t nout_per_set) {
+  PredictSetsOneStage s;
+  s.nXs = (size_t)C * n * d; s.nys = (size_t)C * n; s.C = C; s.nXt = (size_t)C * m * d; s.B = B; s.nparams = (size_t)B * P;
+  s.nyat = (size_t)C * m; s.ntab = (size_t)B * m; s.nout = (size_t)C * nout_per_set;
+  s.Xs = w.take<double>(s.nXs);
+  s.ys = w.take<double>(s.nys);
+  s.sigma2_set = w.take<double>(C);
+  s.Xtests = w.take<double>(s.nXt);
+  s.set = w.take<int>(B);
+  s.off = w.take<int>(C);
+  s.nb = w.take<int>(C);
+  s.params = w.take<double>(s.nparams);
+  s.s2row = s2row ? w.take<double>(B) : nullptr;
+  s.y_at = y_at ? w.take<double>(s.nyat) : nullptr;
+  s.mean = w.take<double>(s.ntab);
+  s.var = w.take<double>(s.ntab);
+  s.idx = summary ? w.take<int>(B) : nullptr;
+  s.count = summary ? w.take<int>(C) : nullptr;
+  s.out = summary ? w.take<double>(s.nout) : nullptr;
+  s.beta = w.take<double>(B);
+  s.q = krige ? w.take<double>(B) : nullptr;
+  s.status = w.take<int>(B);
+  return s;
+}
 
 // the staging ccgp_reserve(n, d, K, B, m) provides: the host-pointer likelihood and, with test sites, the prediction
 // (without its tail) and the tables of ccgp_predict_summary_dev

@@ -1484,6 +1484,50 @@ int ccgp_cgp_predict(ccgp_handle* h, const double* X, int n, int d, const double
   return rc;
 } CCGP_GUARD_END(h)
 
+// ccgp_cgp_predict over many training sets: one state launch and one site launch per chunk of rows, every row on its own kept
+// block.  The sets, their responses and their test sites go up with the first chunk only.
+int ccgp_cgp_predict_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, const double* params,
+                          const int* set, int B, const double* Xtests, int m, double* out, double* out_state,
+                          int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (n < 1 || d < 1 || m < 0 || !params || (m > 0 && (!Xtests || !out)) ||
+      !sets_args_ok(Xs, ys, nullptr, false, C, set, B, 0))
+    return fail(h, CCGP_EINVAL, "ccgp_cgp_predict_sets: bad argument");
+  if (int rc = cgp_shape(h, "ccgp_cgp_predict_sets", n, d)) return rc;
+  if (B == 0) return CCGP_OK;
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = 2 * d + 2;
+  const CgpKeep kp(n);
+  const size_t ns = 3 * (size_t)n + 3;   // s | res2 | temp | sf, beta, tau2: contiguous in the kept block from kp.s on
+  return run_chunked(
+      h, cgp_predict_sets_row_bytes(n, d, m, kp.total), params, B, P, nullptr,
+      [&](Layout& w, int nb) { return cgp_predict_sets_stage(w, n, d, C, m, kp.total, nb); },
+      [&](const CgpPredictSetsStage& s, int b0, int nb, const double* rows, double*) -> int {
+        if (int prc = push(h, s.inputs(b0 == 0, Xs, ys, Xtests, set + b0, rows, nb))) return prc;
+        {
+          ScopedTimer t(h, CCGP_T_FUSED);
+          launch_cgp_state_sets_keep(h->stream, s.Xs, n, d, s.ys, s.set, s.params, nb, nb, s.res, s.res + nb,
+                                     s.res + 2 * (size_t)nb, s.status, s.keep);
+          if (m > 0)
+            launch_cgp_predict_sets(h->stream, s.Xs, n, d, s.set, s.params, nb, nb, s.Xtests, m, s.keep, s.status, s.out);
+        }
+        CCGP_LAUNCH_CHECK();
+        if (out_state)   // a failed row kept nothing: what is gathered for it is overwritten below
+          CCGP_HIP(hipMemcpy2DAsync(s.state, sizeof(double) * ns, s.keep + kp.s, sizeof(double) * kp.total, sizeof(double) * ns,
+                                    (size_t)nb, hipMemcpyDeviceToDevice, h->stream));
+        std::vector<int> st(nb);
+        const int rc = pull_status(h, s.results(m > 0 ? out + (size_t)b0 * m * 6 : nullptr,
+                                                out_state ? out_state + b0 * ns : nullptr, nb), s.status, nb, st.data());
+        if (rc < 0) return rc;
+        for (int r = 0; r < nb; ++r) {
+          if (status) status[b0 + r] = st[r];
+          if (st[r] && out_state)
+            for (size_t i = 0; i < ns; ++i) out_state[(b0 + r) * ns + i] = std::nan("");
+        }
+        return rc;
+      });
+} CCGP_GUARD_END(h)
+
 // ---- a8: logpost ------------------------------------------------------------------------------
 // the argument checks ccgp_logpost and ccgp_logpost_batch share; `who` is the name the message carries
 static int logpost_args(ccgp_handle* h, const char* who, bool shapes_ok, int d, int prior_id, const double* prior_pars) {
@@ -2537,6 +2581,245 @@ int ccgp_predict_summary(ccgp_handle* h, const double* X, int n, int d, const do
                          s.t.count, s.out);
   CCGP_LAUNCH_CHECK();
   return pull_status(h, s.results(out, out_beta), s.status, S, status);
+} CCGP_GUARD_END(h)
+
+// ---- the Combined GP's and the single GP's prediction over many training sets of one shape (ccgp.h) ---------------------------
+// One call for the rows of C sets: every set's design, responses, test sites and rows go up in ONE span, the single-set
+// launches (predict_run: whichever route the single-set call takes for the set's rows) run set after set on the resident
+// inputs with no host copy between them, and the results come down in ONE span.  (predict_run itself may synchronise: it
+// grows the workspace where the kept-factor scratch needs it -- once, the sets have one shape -- and forks and joins the
+// second stream per set as the single-set call does.)  A set's rows are staged in their order as the nb x P table the
+// single-set call stages, each piece with the alignment it has there, so the launches of set c are those of the single-set
+// call on its rows: hence the bits.  The staging (call_stage.h: predict_sets_stage) holds every set's inputs and tables at
+// once and is not cut over rows: the workspace limit governs predict_run's scratch, not this buffer.
+enum class SetsOp { Predict, Krige, Summary };
+
+// The one-launch route of the three calls (small_route_predict_sets == Reg, CCGP_OPT_PREDICT_FACTOR on, scratch to be had): the
+// rows grouped by set go up with every set's design, responses and test sites in ONE span; per chunk of rows (the kept-factor
+// scratch, capped as in kept_factor_ws_bytes) ONE factorisation launch, one correlation launch and one site launch serve the
+// rows of all sets; a summary then runs its (site, set) grids on the whole tables; ONE span comes down.  *ran = false: the
+// scratch could not be had and nothing was done -- the caller takes the grouped route.
+static int predict_sets_one_launch(ccgp_handle* h, SetsOp op, const double* Xs, int n, int d, const double* ys,
+                                   const double* sigma2, int C, int K, const double* params,
+                                   const std::vector<std::vector<int>>& rows_of, int B, const double* sigma2_row, int var_form,
+                                   const double* Xtests, int m, const double* probs, int n_probs, const double* ys_at,
+                                   double* out_mean, double* out_var, double* out_summary, double* out_beta, double* out_q,
+                                   int* status, bool* ran) {
+  *ran = false;
+  const size_t want = kept_factor_ws_bytes(h, true, n, d, K, B, m);
+  if (!want || ensure(h, h->ws, kWorkspace, want) != CCGP_OK || h->ws.bytes < small_reg_sites_scratch(n, d, K, m)) return CCGP_OK;
+  *ran = true;
+  const int P = K + K * d;
+  const bool summary = op == SetsOp::Summary, krige = op == SetsOp::Krige;
+  const bool s2row = !krige || sigma2_row != nullptr;   // the Combined GP's sigma2 is its set's: one per row on the device
+  const size_t nout = summary ? (size_t)m * (4 + n_probs) : 0;
+  PredictSetsOneStage s;
+  if (int rc = stage(h, [&](Layout& w) {
+        s = predict_sets_one_stage(w, n, d, P, C, B, m, krige, s2row, summary, summary && ys_at, nout);
+      }))
+    return rc;
+  // the grouped host images
+  std::vector<int> order, hset(B), hoff(C), hnb(C);
+  order.reserve(B);
+  bool any_staged = false, any_streamed = false;
+  for (int c = 0; c < C; ++c) {
+    hoff[c] = (int)order.size();
+    hnb[c] = (int)rows_of[c].size();
+    if (hnb[c]) (hnb[c] <= kSummaryLdsDraws ? any_staged : any_streamed) = true;
+    for (int b : rows_of[c]) { hset[order.size()] = c; order.push_back(b); }
+  }
+  std::vector<double> hp((size_t)B * P), hs2(s2row ? B : 0), hs2set(C, 1.0);
+  for (int j = 0; j < P; ++j)
+    for (int r = 0; r < B; ++r) hp[r + (size_t)j * B] = params[order[r] + (size_t)j * B];
+  for (int r = 0; r < B && s2row; ++r) hs2[r] = krige ? sigma2_row[order[r]] : sigma2[hset[r]];
+  if (!krige)
+    for (int c = 0; c < C; ++c) hs2set[c] = sigma2[c];
+  DrawView dv;
+  if (int frc = draw_view(h, h->fam, s.params, B, K, d, &dv)) return frc;
+  if (int prc = push(h, s.inputs(Xs, ys, hs2set.data(), Xtests, hset.data(), hoff.data(), hnb.data(), hp.data(),
+                                 s2row ? hs2.data() : nullptr, ys_at)))
+    return prc;
+  {
+    ScopedTimer t(h, CCGP_T_FUSED);
+    (void)ensure_aux(h);
+    const VarForm vf{s.s2row, krige ? var_form : VarForm{}.form, s.q};
+    launch_small_reg_predict_sets(h->stream, s.Xs, n, d, s.ys, s.sigma2_set, s.set, dv, B, s.Xtests, m, s.mean, s.var, s.beta,
+                                  s.status, h->ws.ptr, h->ws.bytes, h->aux_stream, h->aux_fork, h->aux_join, vf);
+  }
+  CCGP_LAUNCH_CHECK();
+  if (summary) {
+    launch_predict_summary_sets(h->stream, s.mean, s.var, s.status, B, m, C, s.off, s.nb, any_staged, any_streamed, probs,
+                                n_probs, s.y_at, s.idx, s.count, s.out);
+    CCGP_LAUNCH_CHECK();
+  }
+  std::vector<double> hmean(summary ? 0 : (size_t)B * m), hvar(summary ? 0 : (size_t)B * m), hbeta(B), hq(krige ? B : 0);
+  std::vector<int> hst(B);
+  if (int rc = pull(h, s.results(summary ? nullptr : hmean.data(), summary ? nullptr : hvar.data(), out_summary, hbeta.data(),
+                                 krige ? hq.data() : nullptr, hst.data())))
+    return rc;
+  int failed = 0;
+  for (int c = 0; c < C && summary; ++c)
+    if (!hnb[c])   // no row: the S' = 0 rule of the single-set summary (the kernels leave the block alone)
+      for (size_t e = 0; e < nout; ++e) out_summary[(size_t)c * nout + e] = std::nan("");
+  for (int r = 0; r < B; ++r) {
+    const int b = order[r];
+    if (!summary)
+      for (int t = 0; t < m; ++t) {
+        out_mean[b + (size_t)t * B] = hmean[r + (size_t)t * B];
+        out_var[b + (size_t)t * B] = hvar[r + (size_t)t * B];
+      }
+    if (out_beta) out_beta[b] = hbeta[r];
+    if (out_q) out_q[b] = hq[r];
+    if (status) status[b] = hst[r];
+    failed += hst[r] != 0;
+  }
+  return failed;
+}
+
+static int predict_sets_call(ccgp_handle* h, SetsOp op, const double* Xs, int n, int d, const double* ys,
+                             const double* sigma2, int C, int K, const double* params, const int* set, int B,
+                             const double* sigma2_row, int var_form, const double* Xtests, int m, const double* probs,
+                             int n_probs, const double* ys_at, double* out_mean, double* out_var, double* out_summary,
+                             double* out_beta, double* out_q, int* status) {
+  CCGP_HIP(hipSetDevice(h->device));
+  const int P = K + K * d;
+  const bool summary = op == SetsOp::Summary, krige = op == SetsOp::Krige;
+  const size_t nout = summary ? (size_t)m * (4 + n_probs) : 0;
+  std::vector<std::vector<int>> rows_of(C);
+  for (int b = 0; b < B; ++b) rows_of[set[b]].push_back(b);
+  if (h->fam.id == 0 && h->opt_predict_factor && small_route_predict_sets(true, n, d, K) == Route::Reg) {
+    bool ran = false;
+    const int rc = predict_sets_one_launch(h, op, Xs, n, d, ys, sigma2, C, K, params, rows_of, B, sigma2_row, var_form, Xtests, m,
+                                           probs, n_probs, ys_at, out_mean, out_var, out_summary, out_beta, out_q, status, &ran);
+    if (ran || rc < 0) return rc;
+  }
+  // the grouped route: set after set through the single-set launches
+  std::vector<int> nb_of(C);
+  for (int c = 0; c < C; ++c) nb_of[c] = (int)rows_of[c].size();
+  std::vector<SetPieces> sp;
+  if (int rc = stage(h, [&](Layout& w) {
+        sp = predict_sets_stage(w, nb_of, n, d, P, m, krige, krige && sigma2_row, summary, summary && ys_at, nout);
+      }))
+    return rc;
+  // the grouped host images: a set's rows as an nb x P column-major table, its per-row sigma2
+  std::vector<double> hp((size_t)B * P), hs2(krige && sigma2_row ? B : 0);
+  std::vector<Piece> up;
+  for (int c = 0; c < C; ++c) {
+    const SetPieces& s = sp[c];
+    if (!s.nb) continue;
+    double* rows = hp.data() + (size_t)s.off * P;
+    for (int j = 0; j < P; ++j)
+      for (int i = 0; i < s.nb; ++i) rows[i + (size_t)j * s.nb] = params[rows_of[c][i] + (size_t)j * B];
+    for (int i = 0; i < s.nb && !hs2.empty(); ++i) hs2[s.off + i] = sigma2_row[rows_of[c][i]];
+    up.push_back(piece(s.X, Xs + (size_t)c * n * d, (size_t)n * d));
+    up.push_back(piece(s.y, ys + (size_t)c * n, n));
+    up.push_back(piece(s.params, rows, (size_t)s.nb * P));
+    up.push_back(piece(s.Xt, Xtests + (size_t)c * m * d, (size_t)m * d));
+    if (s.s2row) up.push_back(piece(s.s2row, hs2.data() + s.off, (size_t)s.nb));
+    if (s.y_at) up.push_back(piece(s.y_at, ys_at + (size_t)c * m, m));
+  }
+  if (int prc = push(h, up)) return prc;
+  for (int c = 0; c < C; ++c) {
+    const SetPieces& s = sp[c];
+    if (!s.nb) continue;
+    DrawView dv;
+    if (int frc = draw_view(h, h->fam, s.params, s.nb, K, d, &dv)) return frc;
+    const VarForm vf = krige ? VarForm{s.s2row, var_form, s.q} : VarForm{};
+    if (int rc = predict_run(h, s.X, n, d, s.y, dv, s.Xt, m, krige ? 1.0 : sigma2[c], s.mean, s.var, s.beta, s.status, vf))
+      return rc;
+    if (summary) {
+      launch_predict_summary(h->stream, s.mean, s.var, s.status, s.nb, m, probs, n_probs, s.y_at, s.idx, s.count, s.out);
+      CCGP_LAUNCH_CHECK();
+    }
+  }
+  // one span down, into grouped host images; then every row to its place among the B
+  const bool tables = !summary;
+  std::vector<double> hmean(tables ? (size_t)B * m : 0), hvar(tables ? (size_t)B * m : 0), hbeta(B), hq(krige ? B : 0);
+  std::vector<int> hst(B);
+  std::vector<Piece> down;
+  for (int c = 0; c < C; ++c) {
+    const SetPieces& s = sp[c];
+    if (!s.nb) continue;
+    const size_t nb = (size_t)s.nb;
+    if (tables) {
+      down.push_back(piece(s.mean, hmean.data() + (size_t)s.off * m, nb * m));
+      down.push_back(piece(s.var, hvar.data() + (size_t)s.off * m, nb * m));
+    } else {
+      down.push_back(piece(s.out, out_summary + (size_t)c * nout, nout));
+    }
+    down.push_back(piece(s.beta, hbeta.data() + s.off, nb));
+    if (krige) down.push_back(piece(s.q, hq.data() + s.off, nb));
+    down.push_back(piece(s.status, hst.data() + s.off, nb));
+  }
+  if (int rc = pull(h, down)) return rc;
+  int failed = 0;
+  for (int c = 0; c < C; ++c) {
+    const SetPieces& s = sp[c];
+    if (!s.nb) {   // no row: the S' = 0 rule of the single-set summary
+      for (size_t e = 0; e < nout; ++e) out_summary[(size_t)c * nout + e] = std::nan("");
+      continue;
+    }
+    for (int i = 0; i < s.nb; ++i) {
+      const int b = rows_of[c][i];
+      if (tables)
+        for (int t = 0; t < m; ++t) {
+          out_mean[b + (size_t)t * B] = hmean[(size_t)s.off * m + i + (size_t)t * s.nb];
+          out_var[b + (size_t)t * B] = hvar[(size_t)s.off * m + i + (size_t)t * s.nb];
+        }
+      if (out_beta) out_beta[b] = hbeta[s.off + i];
+      if (out_q) out_q[b] = hq[s.off + i];
+      if (status) status[b] = hst[s.off + i];
+      failed += hst[s.off + i] != 0;
+    }
+  }
+  return failed;
+}
+
+int ccgp_predict_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                            int K, const double* params, const int* set, int B, const double* Xtests, int m,
+                            double* out_mean, double* out_var, double* out_beta, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || m < 1 || !params || !Xtests || !out_mean || !out_var ||
+      !sets_args_ok(Xs, ys, sigma2, true, C, set, B, 1))
+    return fail(h, CCGP_EINVAL, "ccgp_predict_batch_sets: bad argument");
+  return predict_sets_call(h, SetsOp::Predict, Xs, n, d, ys, sigma2, C, K, params, set, B, nullptr, 0,
+                           Xtests, m, nullptr, 0, nullptr, out_mean, out_var, nullptr, out_beta, nullptr, status);
+} CCGP_GUARD_END(h)
+
+int ccgp_krige_predict_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int K,
+                                  const double* params, const int* set, int B, const double* sigma2_row, int var_form,
+                                  const double* Xtests, int m, double* out_mean, double* out_var, double* out_beta,
+                                  double* out_q, int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || m < 1 || !params || !Xtests || !out_mean || !out_var ||
+      !sets_args_ok(Xs, ys, nullptr, false, C, set, B, 1))
+    return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch_sets: bad argument");
+  // what ccgp_krige_predict_batch refuses
+  if (var_form != CCGP_VAR_ORDINARY && var_form != CCGP_VAR_PLUGIN && var_form != CCGP_VAR_UNBIASED)
+    return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch_sets: unknown var_form");
+  const bool own_s2 = var_form != CCGP_VAR_UNBIASED;
+  if (!own_s2 && n < 2) return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch_sets: CCGP_VAR_UNBIASED divides by n - 1");
+  if (own_s2) {
+    if (!sigma2_row) return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch_sets: this var_form needs sigma2");
+    for (int b = 0; b < B; ++b)
+      if (!(std::isfinite(sigma2_row[b]) && sigma2_row[b] >= 0.0))
+        return fail(h, CCGP_EINVAL, "ccgp_krige_predict_batch_sets: every sigma2 must be finite and >= 0");
+  }
+  return predict_sets_call(h, SetsOp::Krige, Xs, n, d, ys, nullptr, C, K, params, set, B,
+                           own_s2 ? sigma2_row : nullptr, var_form, Xtests, m, nullptr, 0, nullptr, out_mean, out_var, nullptr,
+                           out_beta, out_q, status);
+} CCGP_GUARD_END(h)
+
+int ccgp_predict_summary_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2, int C,
+                              int K, const double* params, const int* set, int B, const double* Xtests, int m,
+                              const double* probs, int n_probs, const double* ys_at, double* out, double* out_beta,
+                              int* status) try {
+  if (!h) return CCGP_EINVAL;
+  if (bad_shape(n, d, K) || !params || !Xtests || !out || !sets_args_ok(Xs, ys, sigma2, true, C, set, B, 1))
+    return fail(h, CCGP_EINVAL, "ccgp_predict_summary_sets: bad argument");
+  if (int rc = check_summary_args(h, m, probs, n_probs)) return rc;
+  return predict_sets_call(h, SetsOp::Summary, Xs, n, d, ys, sigma2, C, K, params, set, B, nullptr, 0,
+                           Xtests, m, probs, n_probs, ys_at, nullptr, nullptr, out, out_beta, nullptr, status);
 } CCGP_GUARD_END(h)
 
 // ---- leave-one-out cross-validation of the Combined GP: the closed form from ONE factorisation per draw ---------------

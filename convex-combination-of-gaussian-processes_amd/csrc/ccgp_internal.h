@@ -173,6 +173,14 @@ constexpr int kSummaryLdsDraws = 2048;
 void launch_predict_summary(hipStream_t s, const double* d_mean, const double* d_var, const int* d_status, int S, int m,
                             const double* probs, int n_probs, const double* d_y_at, int* d_idx, int* d_count,
                             double* d_out);
+// the sets form (ccgp_predict_summary_sets): C sets in one grid of (site, set).  d_mean / d_var: B x m column-major with the
+// rows grouped by set; d_off / d_nb (C ints each): a set's first row and its number of rows; d_idx (B ints) and d_count
+// (C ints) are scratch; d_y_at: C blocks of m or nullptr; d_out: C blocks of m x (4 + n_probs) -- the block of a set
+// without rows is not written.  any_staged / any_streamed: some set has at most / more than kSummaryLdsDraws rows.
+void launch_predict_summary_sets(hipStream_t s, const double* d_mean, const double* d_var, const int* d_status, int B, int m,
+                                 int C, const int* d_off, const int* d_nb, bool any_staged, bool any_streamed,
+                                 const double* probs, int n_probs, const double* d_y_at, int* d_idx, int* d_count,
+                                 double* d_out);
 
 // ---- small.hip -----------------------------------------------------------------------
 // In-LDS evaluator, one workgroup per (draw, chunk of unit rows): explicit inverse (solve(R), HX:454) and gradient for the
@@ -289,6 +297,13 @@ void launch_small_reg_nm_sets(hipStream_t s, const double* Xs, int n, int d, con
 // vf.sigma2_row (indexed by draw) replaces, vf.q (may be nullptr) receives Q per draw
 void launch_small_reg_loo(hipStream_t s, const double* X, int n, int d, const double* y, DrawView dv, int B, double sigma2,
                           VarForm vf, double* mean, double* var, double* beta, int* status);
+// the sets form of launch_small_reg_predict's kept-factor scheme (ccgp_predict_batch_sets and its kin): row b on set set[b],
+// its own sigma2 at vf.sigma2_row[b] (never null), mean / var B x m column-major; scratch: small_reg_sites_scratch() bytes
+// per row of a chunk, at least one row
+void launch_small_reg_predict_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2_set,
+                                   const int* set, DrawView dv, int B, const double* Xtests, int m, double* mean, double* var,
+                                   double* beta, int* status, void* scratch, size_t scratch_bytes, hipStream_t aux,
+                                   hipEvent_t ev_fork, hipEvent_t ev_join, VarForm vf);
 
 // ---- cgp.hip: the composite GP comparator (CGP / predict.CGP, GV:58-317), n <= 128 -------------------------------------
 // LDS carve of cgp_state_kernel, in doubles:
@@ -326,6 +341,11 @@ void launch_cgp_state(hipStream_t s, const double* X, int n, int d, const double
 void launch_cgp_state_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set,
                            const double* params, int ldp, int nb, const int* skip, double* val, double* beta, double* tau2,
                            double* loo, int* status);
+// the sets form that keeps (ccgp_cgp_predict_sets): as launch_cgp_state_sets without held-out rows, and EVERY evaluation
+// leaves its state: evaluation b at keep + b CgpKeep(n).total
+void launch_cgp_state_sets_keep(hipStream_t s, const double* Xs, int n, int d, const double* ys, const int* set,
+                                const double* params, int ldp, int nb, double* val, double* beta, double* tau2, int* status,
+                                double* keep);
 // the CGP refinement on the device (ccgp_cgp_fit_sets): what the two launches of a round read and leave, every pointer a device
 // pointer.  With P = d + 3 variables and R = 1 + 2 P rows per start: state [A][W] in and out (fit_logic.h with d = P),
 // max_evals / evals / nfail / set / gate [A], the trace [A][T], both or none; rows A R x (2 d + 2) column-major with leading
@@ -354,6 +374,11 @@ void launch_cgp_fit_step(hipStream_t s, int d, int A, const CgpFitIO& io, bool i
 // predict.CGP (GV:287-307) at m sites from a kept state; row: that state's parameter row, contiguous; out m x 6 column-major
 void launch_cgp_predict(hipStream_t s, const double* X, int n, int d, const double* row, const double* Xtest, int m,
                         const double* keep, const int* status, double* out);
+// its sets form behind launch_cgp_state_sets_keep: row r of the nb (grid y) on set set[r] -- design Xs + set[r] n d, sites
+// Xtests + set[r] m d -- from the state at keep + r CgpKeep(n).total and row r of params (nb x (2 d + 2) column-major, leading
+// dimension ldp); status[r] != 0: NaN; out: nb blocks of m x 6 column-major
+void launch_cgp_predict_sets(hipStream_t s, const double* Xs, int n, int d, const int* set, const double* params, int ldp,
+                             int nb, const double* Xtests, int m, const double* keep, const int* status, double* out);
 
 // ---- blocked.hip ---------------------------------------------------------------------
 struct BlockedWs {

@@ -28,6 +28,13 @@
 // cgp_predict_kernel: one wave per test site against the state a `keep` evaluation left in HBM (the normalised factor, Q^-1 1,
 // temp, s, e^2 and five scalars).  q'Q^-1 q comes from a forward substitution of q through the kept factor, columns streamed
 // from L2 one step ahead, never from an inverse.
+//
+// Over many training sets of one shape (ccgp_cgp_predict_sets): cgp_state_kernel<sets, keep> leaves the state of EVERY row,
+// each on its own set, and cgp_predict_kernel<sets> serves rows x sites from them, each row at its own set's test sites.  Both
+// are template instances beside the single-set ones and run the single-set code behind their loads: a row has the bits of
+// ccgp_cgp_predict on its set alone.
+#include <type_traits>
+
 #include "ccgp_internal.h"
 #include "cgp_fit_logic.h"
 
@@ -76,12 +83,19 @@ __device__ __forceinline__ double cgp_dist_to(const double* xs, int ldx, int j, 
 // SETS: many training sets of one shape in one launch (ccgp_cgp_state_batch_sets): the evaluation's design and responses come
 // from its set, everything after the loads is the single-set instance's code, hence its bits.  A template parameter, not a
 // branch, for the reason small_reg.hip gives for PROF and SETS: the single-set instance compiles from unchanged code.  The
-// sets form keeps no state (`keep` does not exist there).
+// sets form of the fits keeps no state (`keep` does not exist there).
+// KEEP: the sets form of the prediction (ccgp_cgp_predict_sets): EVERY evaluation leaves its CgpKeep(n) block, evaluation b at
+// keep + b CgpKeep(n).total, for cgp_predict_kernel<sets> behind it in the stream.  A third switch for the same reason: what it
+// adds (Q^-1 1 in the last back substitution, the epilogue) is the single-set instance's code for its evaluation 0.
 // GATED: the evaluations of the refinement on the device (ccgp_cgp_fit_sets): gate_rows consecutive evaluations belong to one
 // start, and a workgroup whose start has stopped leaves at once -- before any LDS write or barrier, the whole workgroup on one
 // word.  A workgroup that stays runs the sets instance's code.  A second switch for the same reason as the first.
-template <bool SETS, bool GATED = false>
+template <bool SETS, bool GATED = false, bool KEEP = false>
 __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
+  static_assert(!KEEP || (SETS && !GATED), "the keeping sets instance is the plain sets instance plus the kept state");
+  // the instances that can leave a state.  They form Q^-1 1 in EVERY evaluation once `keep` is set, although the single-set
+  // instance keeps evaluation 0 only: the u chain shares nothing with the others, so no bit depends on it
+  constexpr bool kKeeps = !SETS || KEEP;
   if constexpr (GATED) {
     if (a.gate[blockIdx.x / a.gate_rows] == 0) return;   // uniform: every thread reads the same word
   }
@@ -189,7 +203,7 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
       // A[k + i ld] / d_i, i < k) carries it into the entries above
       double t0 = r0 * rd0, t1 = r1 * rd1;          // temp
       double u0 = z10 * rd0, u1 = z11 * rd1;        // Q^-1 1 (kept state only)
-      const bool want_u = !SETS && last && a.keep != nullptr;
+      const bool want_u = kKeeps && last && a.keep != nullptr;
       for (int k = n - 1; k > 0; --k) {
         const double xk = __shfl(k < 64 ? t0 : t1, k & 63, 64);
         const double c0 = i0 < k ? A[k + (size_t)i0 * ld] * rd0 : 0.0;
@@ -283,9 +297,9 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
       a.status[b] = bad;
     }
   }
-  if (!SETS && a.keep && b == 0 && !bad) {
+  if (kKeeps && a.keep && (KEEP || b == 0) && !bad) {
     const CgpKeep kp(n);
-    double* K = a.keep;
+    double* K = a.keep + (KEEP ? (size_t)b * kp.total : 0);
     for (int e = tid; e < n * n; e += 256) {
       const int i = e % n, k = e / n;
       double v = 0.0;
@@ -319,8 +333,31 @@ struct CgpPredictArgs {
   double* out;            // m x 6 column-major: Yp gp lp v Y_low Y_up
 };
 
-// one wave per site; lane l owns design points l and l + 64
-__global__ __launch_bounds__(256) void cgp_predict_kernel(CgpPredictArgs a) {
+// the sets form (ccgp_cgp_predict_sets): row r = blockIdx.y of the call has its own kept state (keep + r CgpKeep(n).total),
+// parameter row (row + r, leading dimension ldp), status word and output block (out + r 6 m), and reads the design and the
+// test sites of its set: X and Xtest are then the C blocks of all sets
+struct CgpPredictSetsArgs : CgpPredictArgs {
+  const int* set;         // rows
+  int ldp;
+};
+
+// one wave per site; lane l owns design points l and l + 64.  SETS is a template parameter, not a branch, as in
+// cgp_state_kernel: the single-set instance compiles from unchanged code, and the sets instance narrows its arguments to its
+// row and then runs that code, hence its bits.
+template <bool SETS>
+__global__ __launch_bounds__(256) void cgp_predict_kernel(std::conditional_t<SETS, CgpPredictSetsArgs, CgpPredictArgs> a) {
+  if constexpr (SETS) {
+    const int r = blockIdx.y;
+    const int st = __builtin_amdgcn_readfirstlane(a.set[r]);   // wave-uniform: the addresses stay in scalar registers
+    a.X += (size_t)st * a.n * a.d;
+    a.Xtest += (size_t)st * a.m * a.d;
+    a.row += r;
+    a.keep += (size_t)r * CgpKeep(a.n).total;
+    a.status += r;
+    a.out += (size_t)r * a.m * 6;
+  }
+  size_t ldp = 1;   // entry j of the parameter row is row[j ldp]: contiguous, or a row of the column-major table
+  if constexpr (SETS) ldp = (size_t)a.ldp;
   const int n = a.n, d = a.d, m = a.m;
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -333,12 +370,12 @@ __global__ __launch_bounds__(256) void cgp_predict_kernel(CgpPredictArgs a) {
   const CgpKeep kp(n);
   const double* K = a.keep;
   const double* F = K + kp.F;
-  const double lam = a.row[0], bw = a.row[1 + 2 * d];
+  const double lam = a.row[0], bw = a.row[(1 + 2 * d) * ldp];
   const int i0 = lane, i1 = lane + 64;
   const bool h0 = i0 < n, h1 = i1 < n;
   double dt0 = 0.0, dt1 = 0.0, da0 = 0.0, da1 = 0.0;
   for (int k = 0; k < d; ++k) {
-    const double xt = a.Xtest[t + (size_t)k * m], thk = a.row[1 + k], alk = a.row[1 + d + k];
+    const double xt = a.Xtest[t + (size_t)k * m], thk = a.row[(1 + k) * ldp], alk = a.row[(1 + d + k) * ldp];
     if (h0) { const double df = a.X[i0 + (size_t)k * n] - xt; dt0 = fma(df * df, thk, dt0); da0 = fma(df * df, alk, da0); }
     if (h1) { const double df = a.X[i1 + (size_t)k * n] - xt; dt1 = fma(df * df, thk, dt1); da1 = fma(df * df, alk, da1); }
   }
@@ -470,6 +507,18 @@ void launch_cgp_state_sets(hipStream_t st, const double* Xs, int n, int d, const
   hipLaunchKernelGGL(cgp_state_kernel<true>, dim3(nb), dim3(256), sizeof(double) * CgpCarve(n, d).total, st, a);
 }
 
+void launch_cgp_state_sets_keep(hipStream_t st, const double* Xs, int n, int d, const double* ys, const int* set,
+                                const double* params, int ldp, int nb, double* val, double* beta, double* tau2, int* status,
+                                double* keep) {
+  static unsigned long long attr_mask = 0;
+  once_per_device(attr_mask,
+                  [] { raise_lds_limit((const void*)cgp_state_kernel<true, false, true>, "cgp_state_kernel<sets, keep>"); });
+  CgpStateArgs a{};
+  a.X = Xs; a.y = ys; a.n = n; a.d = d; a.params = params; a.ldp = ldp; a.set = set;
+  a.val = val; a.beta = beta; a.tau2 = tau2; a.status = status; a.keep = keep;
+  hipLaunchKernelGGL((cgp_state_kernel<true, false, true>), dim3(nb), dim3(256), sizeof(double) * CgpCarve(n, d).total, st, a);
+}
+
 void launch_cgp_state_gated(hipStream_t st, const double* Xs, int n, int d, const double* ys, const CgpFitIO& io, int A) {
   static unsigned long long attr_mask = 0;
   once_per_device(attr_mask,
@@ -490,7 +539,13 @@ void launch_cgp_fit_step(hipStream_t st, int d, int A, const CgpFitIO& io, bool 
 void launch_cgp_predict(hipStream_t st, const double* X, int n, int d, const double* row, const double* Xtest, int m,
                         const double* keep, const int* status, double* out) {
   CgpPredictArgs a{X, n, d, row, Xtest, m, keep, status, out};
-  hipLaunchKernelGGL(cgp_predict_kernel, dim3((m + 3) / 4), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(cgp_predict_kernel<false>, dim3((m + 3) / 4), dim3(256), 0, st, a);
+}
+
+void launch_cgp_predict_sets(hipStream_t st, const double* Xs, int n, int d, const int* set, const double* params, int ldp,
+                             int nb, const double* Xtests, int m, const double* keep, const int* status, double* out) {
+  CgpPredictSetsArgs a{{Xs, n, d, params, Xtests, m, keep, status, out}, set, ldp};
+  hipLaunchKernelGGL(cgp_predict_kernel<true>, dim3((m + 3) / 4, nb), dim3(256), 0, st, a);
 }
 
 }  // namespace ccgp

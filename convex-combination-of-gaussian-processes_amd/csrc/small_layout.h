@@ -248,6 +248,17 @@ inline bool small_reg_sets_supported(int n, int d, int K) {
 inline Route small_route_sets(bool gauss, int n, int d, int K) {
   return gauss && small_reg_sets_supported(n, d, K) ? Route::Reg : Route::Blocked;
 }
+// The predictions over sets (ccgp_predict_batch_sets, ccgp_krige_predict_batch_sets, ccgp_predict_summary_sets).  Reg: ONE set
+// of launches per chunk of rows for all sets -- the factor-keeping sets instance (FAC + SETS), site_corr_kernel<K, true> with a
+// set per row, site_solve_kernel, and for the summary the (site, set) grids of summary.hip -- exactly where the single-set
+// call takes the kept-factor scheme on the Gaussian family (small_reg_sites_supported: n <= 104, K <= 3) and the sets
+// instance's carve fits (on the 8 x 8 grid it keeps a design per matrix).  capi.hip adds what only the handle knows:
+// CCGP_OPT_PREDICT_FACTOR and whether the scratch could be had.  Blocked: the rows are grouped by set and every group goes
+// through the single-set launches, whatever route they take (105 <= n <= 128, K > 3, n > 128, the Matern and spline families
+// with or without option 12).  The kept-factor and extra-row schemes have the same bits, so the contract does not depend on it.
+inline Route small_route_predict_sets(bool gauss, int n, int d, int K) {
+  return gauss && small_reg_sites_supported(n, d, K) && small_reg_sets_supported(n, d, K) ? Route::Reg : Route::Blocked;
+}
 // Metropolis chains on the device (ccgp_metro_segments_sets): the CHAIN instances are the sets likelihood instances of the
 // 16 x 16 grid, one workgroup per chain, with the chain's own words behind the instance's carve: the two 256-entry tables
 // of the portable exp (chain_terms.h), state, candidate, l / ljac / lprior / beta, and the two words of the decision (go on, accepted)

@@ -222,6 +222,9 @@ __device__ __forceinline__ void mat_sync() {
 // right-hand side and sigma2 come from its set, everything after the loads is the code of the single-set instances in the
 // same order, hence their bits.  A template parameter for the same reason as PROF.  G = 16 has one matrix per workgroup, so
 // the set's design goes into the shared xs slot; G = 8 keeps one copy per matrix where the per-design form keeps it.
+// FAC with SETS (ccgp_predict_batch_sets, ccgp_krige_predict_batch_sets, ccgp_predict_summary_sets): the plain-likelihood sets
+// instance that writes its FacLayout block as the FAC instance does, on both grids, so that one factorisation launch serves
+// the rows of all training sets of a prediction; a template combination, not a branch, for the same reason.
 // INV = 2 with PROF and SETS (ccgp_profile_batch_sets): the ordinary-kriging fits of many sets in lockstep.  The gradient
 // epilogue takes its differences from xs and its right-hand side from zb, so it is the single-set instance's code as it is.
 // CHAIN: a Metropolis chain per workgroup (ccgp_metro_segments_sets): the sets likelihood instance evaluating again and
@@ -283,8 +286,8 @@ void small_reg_kernel(RegArgs a) {
   static_assert(!INV || (G == 16 && NE == NB + 1 && !FULL), "the inverse / gradient runs one matrix per workgroup with n identity rows");
   static_assert(!FAC || (NE == 1 && !FULL && !INV), "the factor is kept by the plain likelihood instantiation");
   static_assert(!PROF || ((NE == 1 || INV == 2) && INV != 1 && INV != 3 && !FAC), "sigma2 is concentrated out of the likelihood and of its gradient only");
-  static_assert(!SETS || (!FAC && ((NE == 1 && !INV && !PROF) || (INV == 2 && PROF))),
-                "the sets form exists for the plain likelihood and for the profiled gradient only");
+  static_assert(!SETS || ((NE == 1 && !INV && !PROF) || (INV == 2 && PROF && !FAC)),
+                "the sets form exists for the plain likelihood (with or without the kept factor) and for the profiled gradient only");
   static_assert(!CHAIN || (SETS && G == 16 && NE == 1 && !INV && !PROF && !FAC), "a chain is the sets likelihood instance on the 16 x 16 grid");
   static_assert(!FIT || (SETS && PROF && INV == 2 && !CHAIN), "a fit is the profiled-gradient sets instance");
   static_assert(!NM || CHAIN, "a Laplace search is a chain instance with another step");
@@ -1258,6 +1261,13 @@ void launch_one(hipStream_t s, const RegArgs& a) {
       });
       if (a.n == G * NB) kernel = small_reg_kernel<G, NB, NE, true, 0, false, false, true>;
       else kernel = small_reg_kernel<G, NB, NE, false, 0, false, false, true>;
+      if (a.fac) {   // the sets form of the instance that keeps its factor (ccgp_predict_batch_sets and its kin)
+        static unsigned long long sets_fac_mask = 0;
+        once_per_device(sets_fac_mask, [] {
+          raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false, 0, true, false, true>, "small_reg_kernel<fac, sets>");
+        });
+        kernel = small_reg_kernel<G, NB, NE, false, 0, true, false, true>;
+      }
     } else if (a.fac) {   // the likelihood instantiation that keeps its factor for site_solve_kernel
       static unsigned long long fac_mask = 0;
       once_per_device(fac_mask, [] { raise_lds_limit((const void*)small_reg_kernel<G, NB, NE, false, 0, true>, "small_reg_kernel<fac>"); });
@@ -1329,13 +1339,17 @@ struct SiteArgs {
   double* rs;              // per (draw, 64-site batch) NPF x 64 doubles: the correlation vectors, lane-major
   int nbatch, npf;         // ceil(m / 64); n rounded up to a multiple of 8
   VarForm vf;              // per-draw sigma2 indexed by the global draw (nullptr: sigma2), the variance form; Q comes from the factor header
+  const int* set;          // site_corr_kernel<K, true>: draw gb belongs to training set set[gb]: X + set[gb] n d, Xt + set[gb] m d
 };
 
 // r_i(x_t) = Mixed.corr.vec (HX:425-431) in corr.vec's operation order (HX:373: (theta'x^2 - 2 X Theta x) + u_i) for one draw and
 // up to four batches of 64 test sites (one wave each): the scaled training coordinates x_ik theta_qk and u_qi = sum_k theta_qk
 // x_ik^2 are formed once per workgroup in LDS and read by broadcast; a lane's site coordinates sit in LDS too ([k][lane]).
 // Needs nothing from the factorisation: runs beside it.
-template <int KC>
+// SETS (ccgp_predict_batch_sets and its kin): the draw's design and test sites are those of its training set; a template
+// parameter, not a branch, as in small_reg_kernel: the single-set instance compiles from unchanged code, and the arithmetic
+// per (draw, site) and its order are the same.  site_solve_kernel reads neither and serves both forms as it is.
+template <int KC, bool SETS = false>
 __global__ __launch_bounds__(256, 4) void site_corr_kernel(SiteArgs a) {
   constexpr int RB = 8;
   typedef double d2v __attribute__((ext_vector_type(2)));
@@ -1345,6 +1359,11 @@ __global__ __launch_bounds__(256, 4) void site_corr_kernel(SiteArgs a) {
   const int b = blockIdx.y, nbatch = a.nbatch, npf = a.npf;
   const int batch = blockIdx.x * (nthr >> 6) + wave;
   const int n = a.n, d = a.d, m = a.m, gb = a.draw0 + b;
+  if constexpr (SETS) {
+    const int st = __builtin_amdgcn_readfirstlane(a.set[gb]);   // uniform over the workgroup: the addresses stay scalar
+    a.X += (size_t)st * n * d;
+    a.Xt += (size_t)st * m * d;
+  }
   const SiteCorrCarve cv(npf, d, KC, nthr >> 6);
   double *th = smem + cv.th, *w2 = smem + cv.w2, *us = smem + cv.us, *xs = smem + cv.xs;
   double* xw = smem + cv.xw + (size_t)wave * d * 64; // this wave's test sites, [k][lane]
@@ -1603,6 +1622,18 @@ static void launch_site_corr(hipStream_t s, const SiteArgs& a, int ns, const Ker
     raise_lds_limit((const void*)site_corr_kernel<2>, "site_corr_kernel");
     raise_lds_limit((const void*)site_corr_kernel<3>, "site_corr_kernel");
   });
+  if (a.set) {
+    static unsigned long long sets_mask = 0;
+    once_per_device(sets_mask, [] {
+      raise_lds_limit((const void*)site_corr_kernel<1, true>, "site_corr_kernel<sets>");
+      raise_lds_limit((const void*)site_corr_kernel<2, true>, "site_corr_kernel<sets>");
+      raise_lds_limit((const void*)site_corr_kernel<3, true>, "site_corr_kernel<sets>");
+    });
+    if (a.K == 1) hipLaunchKernelGGL((site_corr_kernel<1, true>), grid, block, lds, s, a);
+    else if (a.K == 2) hipLaunchKernelGGL((site_corr_kernel<2, true>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((site_corr_kernel<3, true>), grid, block, lds, s, a);
+    return;
+  }
   if (a.K == 1) hipLaunchKernelGGL(site_corr_kernel<1>, grid, block, lds, s, a);
   else if (a.K == 2) hipLaunchKernelGGL(site_corr_kernel<2>, grid, block, lds, s, a);
   else hipLaunchKernelGGL(site_corr_kernel<3>, grid, block, lds, s, a);
@@ -1939,7 +1970,8 @@ void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, cons
     double* rs = fac + (size_t)chunk * fl.total;
     for (int s0 = 0; s0 < S; s0 += chunk) {
       const int ns = std::min(chunk, S - s0);
-      SiteArgs sa{fac, (size_t)fl.total, X, dv.params, dv.ldp, n, d, dv.K, Xtest, m, S, s0, sigma2, mean, var, rs, nbatch, fl.npf, vf};
+      SiteArgs sa{fac, (size_t)fl.total, X, dv.params, dv.ldp, n, d, dv.K, Xtest, m, S, s0, sigma2, mean, var, rs, nbatch, fl.npf, vf,
+                  nullptr};
       // the correlation vectors need nothing from the factorisation: on the second stream beside it (the factorisation is ONE
       // wave per draw -- 1000 draws leave three quarters of the wave slots empty -- and runs at the latency of its n columns)
       if (aux && ev_fork && ev_join) {
@@ -1964,6 +1996,45 @@ void launch_small_reg_predict(hipStream_t s, const double* X, int n, int d, cons
   // (a 1-D family never comes here: predict_run secures the scratch before it takes this route, and launch_one has no
   // extra-row instance to give it)
   dispatch<kPredictNE>(s, a);
+}
+
+// predict.post for B rows over C training sets of one shape in ONE set of launches per chunk of rows (ccgp_predict_batch_sets
+// and its kin on the kept-factor scheme): row b on set set[b] -- design Xs + set[b] n d, responses ys + set[b] n, test sites
+// Xtests + set[b] m d -- with its own sigma2 (vf.sigma2_row, indexed by the row; never null here).  mean / var are B x m
+// column-major.  scratch holds small_reg_sites_scratch() bytes per row of a chunk, at least one row.  The launches are those
+// of launch_small_reg_predict's kept-factor branch with the sets instances: factorisation (FAC + SETS), correlation vectors
+// (site_corr_kernel<K, true>, beside it on the second stream) and site_solve_kernel as it is.
+void launch_small_reg_predict_sets(hipStream_t s, const double* Xs, int n, int d, const double* ys, const double* sigma2_set,
+                                   const int* set, DrawView dv, int B, const double* Xtests, int m, double* mean, double* var,
+                                   double* beta, int* status, void* scratch, size_t scratch_bytes, hipStream_t aux,
+                                   hipEvent_t ev_fork, hipEvent_t ev_join, VarForm vf) {
+  RegArgs a = reg_args(Xs, n, d, ys, dv);
+  a.vf = vf; a.beta = beta; a.status = status; a.S = B; a.set = set; a.sigma2_set = sigma2_set;
+  const size_t per = small_reg_sites_scratch(n, d, dv.K, m);
+  const FacLayout fl(n);
+  const int nbatch = (m + 63) / 64;
+  const int chunk = (int)std::min<size_t>((size_t)B, std::min<size_t>(scratch_bytes / per, 32768));
+  double* fac = static_cast<double*>(scratch);
+  double* rs = fac + (size_t)chunk * fl.total;
+  for (int s0 = 0; s0 < B; s0 += chunk) {
+    const int ns = std::min(chunk, B - s0);
+    SiteArgs sa{fac, (size_t)fl.total, Xs, dv.params, dv.ldp, n, d, dv.K, Xtests, m, B, s0, 1.0, mean, var, rs, nbatch, fl.npf, vf, set};
+    if (aux && ev_fork && ev_join) {
+      (void)hipEventRecord(ev_fork, s);
+      (void)hipStreamWaitEvent(aux, ev_fork, 0);
+      launch_site_corr(aux, sa, ns, dv.fam);
+      (void)hipEventRecord(ev_join, aux);
+    } else {
+      launch_site_corr(s, sa, ns, dv.fam);
+    }
+    RegArgs f = a;
+    f.draw0 = s0; f.B = ns;
+    f.fac = fac - (size_t)s0 * fl.total;     // the kernel indexes the block by the row's global number
+    f.fac_stride = (size_t)fl.total;
+    dispatch_sets(s, f);
+    if (aux && ev_fork && ev_join) (void)hipStreamWaitEvent(s, ev_join, 0);
+    launch_site_solve(s, sa, ns);
+  }
 }
 
 }  // namespace ccgp

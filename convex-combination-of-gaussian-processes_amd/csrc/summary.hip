@@ -10,6 +10,7 @@
 // column of the tables.  Both tails go through erfc: levels <= 1/2 are solved on F, levels > 1/2 on 1 - F.
 #include <cfloat>
 #include <cmath>
+#include <type_traits>
 
 #include "ccgp_internal.h"
 
@@ -30,7 +31,19 @@ constexpr double kFarZ = 64.0;   // stands for (q - mu) / 0: erfc(kFarZ / sqrt 2
 
 // the indices of the draws with status == 0, in order, and their number: ONE workgroup, so the order is the draws' own.
 // A failed draw thereby leaves every sum exactly as if the call had not contained it.
-__global__ __launch_bounds__(kThreads) void summary_valid_kernel(const int* status, int S, int* idx, int* count) {
+// SETS (ccgp_predict_summary_sets): one workgroup per training set (blockIdx.x); the rows of set c are the nb[c] consecutive
+// rows from off[c] of tables whose rows are grouped by set, its indices (relative to off[c]) go to idx + off[c] and its
+// number to count[c].  A template parameter, not a branch: the single-set instance compiles from unchanged code.
+struct SetRows {
+  const int *off, *nb;   // per set: first row and number of rows
+};
+template <bool SETS>
+__global__ __launch_bounds__(kThreads) void summary_valid_kernel(const int* status, int S, int* idx, int* count, SetRows sr) {
+  if constexpr (SETS) {
+    const int c = blockIdx.x, o = sr.off[c];
+    status += o; idx += o; count += c;
+    S = sr.nb[c];
+  }
   __shared__ int wave_n[kWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int base = 0;
@@ -58,6 +71,13 @@ struct SummaryArgs {
   double* out;          // m x (4 + n_probs) column-major
   int S, m, n_probs;
   double probs[CCGP_SUMMARY_MAX_PROBS];
+};
+// the sets form: a grid of (site, set).  mean / var are B x m with the rows grouped by set (S is their leading dimension B),
+// idx / count as summary_valid_kernel<true> leaves them, y_at C blocks of m (or nullptr), out C blocks of m x (4 + n_probs).
+// want_staged: this launch serves the sets whose rows fit the staged route (nb <= kSummaryLdsDraws) or those that do not --
+// a set takes the route the single-set call takes for its rows; a workgroup of another set's kind leaves at once.
+struct SummarySetsArgs : SummaryArgs {
+  SetRows sr;
 };
 
 struct SumOp { __device__ static double f(double a, double b) { return a + b; } };
@@ -187,11 +207,18 @@ __device__ inline void root_update(Root& r, double tail, double dens) {
   root_next(r);
 }
 
-template <int NL, bool STAGED>
-__global__ __launch_bounds__(kThreads) void predict_summary_kernel(SummaryArgs g) {
+template <int NL, bool STAGED, bool SETS = false>
+__global__ __launch_bounds__(kThreads) void predict_summary_kernel(std::conditional_t<SETS, SummarySetsArgs, SummaryArgs> g) {
   __shared__ double smu[STAGED ? kSummaryLdsDraws : 1];
   __shared__ double sis[STAGED ? kSummaryLdsDraws : 1];
   __shared__ double red[kWaves * 2 * (NL > 2 ? NL : 2)];
+  if constexpr (SETS) {
+    const int c = blockIdx.y, nb = g.sr.nb[c], o = g.sr.off[c];
+    if (nb == 0 || (nb <= kSummaryLdsDraws) != STAGED) return;   // uniform over the workgroup, before any barrier
+    g.mean += o; g.var += o; g.idx += o; g.count += c;
+    if (g.y_at) g.y_at += (size_t)c * g.m;
+    g.out += (size_t)c * g.m * (4 + g.n_probs);
+  }
   const int t = blockIdx.x, tid = threadIdx.x;
   const int Sv = *g.count, ncol = 4 + g.n_probs;
   if (Sv == 0) {
@@ -294,7 +321,7 @@ void launch_nl(hipStream_t s, const SummaryArgs& g, bool staged) {
 void launch_predict_summary(hipStream_t s, const double* d_mean, const double* d_var, const int* d_status, int S, int m,
                             const double* probs, int n_probs, const double* d_y_at, int* d_idx, int* d_count,
                             double* d_out) {
-  hipLaunchKernelGGL(summary_valid_kernel, dim3(1), dim3(kThreads), 0, s, d_status, S, d_idx, d_count);
+  hipLaunchKernelGGL(summary_valid_kernel<false>, dim3(1), dim3(kThreads), 0, s, d_status, S, d_idx, d_count, SetRows{});
   SummaryArgs g{};
   g.mean = d_mean; g.var = d_var; g.idx = d_idx; g.count = d_count; g.y_at = d_y_at; g.out = d_out;
   g.S = S; g.m = m; g.n_probs = n_probs;
@@ -305,6 +332,38 @@ void launch_predict_summary(hipStream_t s, const double* d_mean, const double* d
   else if (n_probs <= 2) launch_nl<2>(s, g, staged);
   else if (n_probs <= 4) launch_nl<4>(s, g, staged);
   else launch_nl<8>(s, g, staged);
+}
+
+namespace {
+template <int NL>
+void launch_nl_sets(hipStream_t s, const SummarySetsArgs& g, int C, bool staged) {
+  if (staged) hipLaunchKernelGGL((predict_summary_kernel<NL, true, true>), dim3(g.m, C), dim3(kThreads), 0, s, g);
+  else hipLaunchKernelGGL((predict_summary_kernel<NL, false, true>), dim3(g.m, C), dim3(kThreads), 0, s, g);
+}
+}  // namespace
+
+// the sets form: C sets in one grid.  d_mean / d_var: B x m column-major, rows grouped by set; d_off / d_nb (C ints each):
+// a set's first row and its rows; d_idx (B ints) and d_count (C ints) are scratch; d_y_at: C blocks of m or nullptr; d_out:
+// C blocks of m x (4 + n_probs), the block of a set without rows is not written.  any_staged / any_streamed: whether some set
+// has at most / more than kSummaryLdsDraws rows (the host knows): one launch per kind that occurs.
+void launch_predict_summary_sets(hipStream_t s, const double* d_mean, const double* d_var, const int* d_status, int B, int m,
+                                 int C, const int* d_off, const int* d_nb, bool any_staged, bool any_streamed,
+                                 const double* probs, int n_probs, const double* d_y_at, int* d_idx, int* d_count,
+                                 double* d_out) {
+  const SetRows sr{d_off, d_nb};
+  hipLaunchKernelGGL(summary_valid_kernel<true>, dim3(C), dim3(kThreads), 0, s, d_status, 0, d_idx, d_count, sr);
+  SummarySetsArgs g{};
+  g.mean = d_mean; g.var = d_var; g.idx = d_idx; g.count = d_count; g.y_at = d_y_at; g.out = d_out;
+  g.S = B; g.m = m; g.n_probs = n_probs; g.sr = sr;
+  for (int j = 0; j < n_probs; ++j) g.probs[j] = probs[j];
+  for (int kind = 0; kind < 2; ++kind) {
+    const bool staged = kind == 0;
+    if (!(staged ? any_staged : any_streamed)) continue;
+    if (n_probs <= 1) launch_nl_sets<1>(s, g, C, staged);
+    else if (n_probs <= 2) launch_nl_sets<2>(s, g, C, staged);
+    else if (n_probs <= 4) launch_nl_sets<4>(s, g, C, staged);
+    else launch_nl_sets<8>(s, g, C, staged);
+  }
 }
 
 }  // namespace ccgp

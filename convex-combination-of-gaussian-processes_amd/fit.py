@@ -904,6 +904,72 @@ def compare_GP(gp, D_test, alpha, y_test, draws, D_train, sigma2, y_train, rng=N
                 mean=mean, var=var)
 
 
+def _fitted(arg):
+    """The fitted model in a comparator argument of compare_GP (dict(est=...)), or None."""
+    return arg["est"] if isinstance(arg, dict) and "est" in arg else None
+
+
+def compare_GP_sets(gp, D_tests, alpha, y_tests, draws, D_trains, sigma2s, y_trains, cgp=None, single=None, counts=None):
+    """compare_GP(..., exact=True, cgp=..., single=...) for many training sets at once: the list of its tables, set by set,
+    equal in every key and bit.  The sets are grouped by (n, d, m) -- ragged test sets make one call per m -- and a group's
+    Combined-GP columns come from ONE device call (gp.prediction_sets), its single-GP columns from one
+    (krige_predict_batch_sets) and its CGP columns from one (cgp.predict_CGP_sets).  cgp / single: per-set lists of fitted
+    models, dict(est=<a dict of cgp.CGP / cgp.CGP_sets>) and dict(est=<a dict of ordinary_kriging_fit>) -- nothing is fitted
+    here; None (or a list of None) leaves the columns out, and a set whose entry is anything else (True, fit keywords)
+    falls back to compare_GP for that set.  counts (a dict, optional): counts["calls"] receives the device calls made."""
+    from . import cgp as cgp_mod
+    C = len(D_trains)
+    cgp = list(cgp) if cgp is not None else [None] * C
+    single = list(single) if single is not None else [None] * C
+    base = getattr(gp.h, "_handle", gp.h)
+    tables, calls = [None] * C, 0
+    groups = {}
+    for i in range(C):
+        ready = all(not arg or _fitted(arg) is not None for arg in (cgp[i], single[i]))
+        if not ready or hasattr(gp, "nu"):   # a model still to be fitted, or a 1-D gp: the per-set path
+            tables[i] = compare_GP(gp, D_tests[i], alpha, y_tests[i], draws[i], D_trains[i], sigma2s[i], y_trains[i], exact=True,
+                                   cgp=cgp[i] or False, single=single[i] or False)
+            calls += 1 + bool(cgp[i]) + bool(single[i])
+            continue
+        key = np.shape(D_trains[i]) + (np.atleast_2d(np.asarray(D_tests[i], dtype=np.float64)).shape[0],)
+        groups.setdefault(key, []).append(i)
+    for (n, d, m), idx in groups.items():
+        Dt = [np.asarray(D_tests[i], dtype=np.float64).reshape(m, d) for i in idx]
+        Dn = [np.asarray(D_trains[i], dtype=np.float64) for i in idx]
+        yn = [np.asarray(y_trains[i], dtype=np.float64).ravel() for i in idx]
+        pred = gp.prediction_sets(Dt, alpha, [draws[i] for i in idx], Dn, [sigma2s[i] for i in idx], yn)
+        calls += 1
+        for i, r in zip(idx, pred):
+            tables[i] = dict(y_hat=r["y_hat"], quant=r["Quant"], LL=r["LL"], UL=r["UL"],
+                             y_true=np.asarray(y_tests[i], dtype=np.float64))
+        # the comparators in compare_GP's order: CGP first, then the single GP
+        with_cgp = [j for j, i in enumerate(idx) if cgp[i]]
+        if with_cgp:
+            ests = [_fitted(cgp[idx[j]]) for j in with_cgp]
+            preds = cgp_mod.predict_CGP_sets(gp.h, ests, [Dt[j] for j in with_cgp], PI=True)
+            calls += 1   # the group's models have one shape and one m: predict_CGP_sets makes one call
+            for j, est, p in zip(with_cgp, ests, preds):
+                tables[idx[j]].update(y_hat_CGP=p["Yp"], LL_CGP=p["Y_low"], UL_CGP=p["Y_up"], CGP=est)
+        with_single = [j for j, i in enumerate(idx) if single[i]]
+        if with_single:
+            models = [_fitted(single[idx[j]]) for j in with_single]
+            rows = np.stack([np.concatenate([[1.0], np.asarray(mo["theta"], dtype=np.float64).ravel()]) for mo in models])
+            mean, var, _, _, st = base.krige_predict_batch_sets(np.stack([Dn[j] for j in with_single]),
+                                                                np.stack([yn[j] for j in with_single]), 1, rows,
+                                                                np.arange(len(models)), [mo["sigma2"] for mo in models],
+                                                                np.stack([Dt[j] for j in with_single]), api.VAR_PLUGIN)
+            calls += 1
+            if st.any():
+                raise RuntimeError("compare_GP_sets: the single GP's correlation matrix could not be factorised (pivot %d)"
+                                   % st[np.flatnonzero(st)[0]])
+            for k, (j, mo) in enumerate(zip(with_single, models)):
+                lo, hi = _t_interval(mean[k], var[k], alpha, n)
+                tables[idx[j]].update(y_hat_single=mean[k].copy(), LL_single=lo, UL_single=hi, single=mo)
+    if counts is not None:
+        counts["calls"] = counts.get("calls", 0) + calls
+    return tables
+
+
 def _add_single_loo_columns(table, gp, alpha, D_train, y_train, single):
     """leave_one_out's single-GP columns: the model as _add_single_columns takes or fits it (ONCE, on all n points: the
     parameters stay fixed across the folds, as for the Combined GP's draws), then one ccgp_loo_batch row with K = 1 -- the
@@ -1417,7 +1483,7 @@ def stack_tables(tables):
 def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size=None, start=None, sigma2s=None,
           theta1_pars=None, theta2_pars=None, rngs=None, max_proposals=None, speculate=0, laplace=None, cgp=False,
           single=False, out_dir=None, input_names=None, logpost_sets_fn=None, compare_fn=None, lockstep_fits=True,
-          device_chains=False, device_fits=False, device_laplace=False, device_cgp=False):
+          device_chains=False, device_fits=False, device_laplace=False, device_cgp=False, lockstep_predict=False):
     """The reference's simulation study (GV:689-762 declares nine training sets and fits one): every set of `sets` -- a list
     of (D_train, y_train, D_test, y_test) -- fitted and compared, the sets of one shape (n, d) in lockstep.  Per group:
     sigma2 per set from ordinary_kriging_fit (or sigma2s[i] as given), then laplace_sets and Metro_sets with one generator
@@ -1446,6 +1512,13 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     that evaluator bit for bit, so with device_chains=True the tables are those of device_chains=True alone.
     device_cgp (default off): the CGP fits' refinement runs on the device (cgp.CGP_sets / cgp.CGP with on_device=True): the
     same models bit for bit, so the tables are those of device_cgp=False.
+    lockstep_predict (default off): the prediction stage runs in lockstep as well -- without compare_fn and for a gp that is
+    not 1-D, the tables come from compare_GP_sets: per group of sets of one shape (n, d, m) one device call for the Combined
+    GP, one for the single GP and one for the CGP, a comparator going that way only when its model is already fitted (in
+    lockstep, or given); any other set falls back to compare_GP.  calls["predict"] counts the prediction calls on the device
+    in either mode: per set one per model of its table, per group one per model with lockstep_predict.  (This changes what the
+    default reports: it used to count one per set whatever the comparators; with a compare_fn it still does.)  Tables,
+    summaries and result files are those of lockstep_predict=False bit for bit.
     Returns dict(tables, summaries, pooled: comparison_summary of the stacked tables, sigma2, draws, beta, chains,
     groups: {(n, d): indices}, calls and seconds: device calls and wall time of the sigma2, single, cgp, laplace, metro and
     predict parts; per set the single and cgp fits happen inside compare_GP, so their seconds are part of predict's and
@@ -1467,6 +1540,8 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
         start = np.concatenate([[1.0, 1.0, 0.0], np.zeros(npar - 3)])
     starts = np.broadcast_to(np.asarray(start, dtype=np.float64), (C, np.shape(start)[-1]))
     lockstep = bool(lockstep_fits) and compare_fn is None and logpost_sets_fn is None and not hasattr(gp, "nu")
+    predict_sets = bool(lockstep_predict) and compare_fn is None and not hasattr(gp, "nu")
+    own_compare = compare_fn is None   # compare_GP itself: one device call per model of the table
     compare_fn = compare_fn or compare_GP
     fit_sets = ordinary_kriging_fit_device_sets if device_fits else ordinary_kriging_fit_sets
     fit_one = ordinary_kriging_fit_device if device_fits else ordinary_kriging_fit
@@ -1570,11 +1645,17 @@ def study(gp, sets, alpha, N, samp_size, batch_size, alpha_geweke, net_samp_size
     draws = [transformed_to_draws(ch["sample"][keep]) for ch in chains]
     betas = [ch["beta"][keep] for ch in chains]
     t0 = time.perf_counter()
+    if predict_sets:
+        made = {}
+        tables = compare_GP_sets(gp, [s[2] for s in sets], alpha, [s[3] for s in sets], draws, [s[0] for s in sets], s2,
+                                 [s[1] for s in sets], cgp=cgp_of, single=single_of, counts=made)
+        calls["predict"] = made["calls"]
     for i, (D_train, y_train, D_test, y_test) in enumerate(sets):
-        tables[i] = compare_fn(gp, D_test, alpha, y_test, draws[i], D_train, s2[i], y_train, exact=True, cgp=cgp_of[i],
-                               single=single_of[i])
+        if not predict_sets:
+            tables[i] = compare_fn(gp, D_test, alpha, y_test, draws[i], D_train, s2[i], y_train, exact=True, cgp=cgp_of[i],
+                                   single=single_of[i])
+            calls["predict"] += 1 + (bool(cgp_of[i]) + bool(single_of[i]) if own_compare else 0)
         summaries[i] = comparison_summary(tables[i])
-        calls["predict"] += 1
         # the fits compare_GP made itself
         if not lockstep and single and isinstance(tables[i].get("single"), dict):
             calls["single"] += int(tables[i]["single"].get("calls", 0))

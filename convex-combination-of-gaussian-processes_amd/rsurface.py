@@ -358,6 +358,21 @@ class CombinedGP:
         return dict(y_hat=r["y_hat"], Quant=r["quant"], LL=r["quantiles"][:, 0], UL=r["quantiles"][:, 1],
                     pred_var=r["pred_var"], cdf_at=r["cdf_at"], beta=r["beta"], status=r["status"])
 
+    def prediction_sets(self, D_tests, alpha, draws, D_trains, sigma2s, y_trains, y_tests=None):
+        """prediction() for many training sets of one shape in ONE device call (ccgp_predict_summary_sets): set i's draws
+        draws[i] on D_trains[i], y_trains[i], sigma2s[i], summarised at its own test sites D_tests[i] (as many sites for
+        every set).  Returns the list of prediction()'s dicts, each equal to the per-set call bit for bit."""
+        params = [self.draws_to_params(D, dr) for D, dr in zip(D_trains, draws)]
+        set_of = np.concatenate([np.full(len(p), i) for i, p in enumerate(params)])
+        at = None if y_tests is None else np.stack([np.asarray(y, dtype=np.float64).ravel() for y in y_tests])
+        res = self.h.predict_summary_sets(np.stack([np.asarray(D, dtype=np.float64) for D in D_trains]),
+                                          np.stack([np.asarray(y, dtype=np.float64).ravel() for y in y_trains]),
+                                          np.asarray(sigma2s, dtype=np.float64), 2, np.concatenate(params), set_of,
+                                          np.stack([np.asarray(D, dtype=np.float64) for D in D_tests]),
+                                          (alpha / 2.0, 1.0 - alpha / 2.0), at)
+        return [dict(y_hat=r["y_hat"], Quant=r["quant"], LL=r["quantiles"][:, 0], UL=r["quantiles"][:, 1],
+                     pred_var=r["pred_var"], cdf_at=r["cdf_at"], beta=r["beta"], status=r["status"]) for r in res]
+
     def leave_one_out(self, alpha, draws, D_train, sigma2, y_train):
         """Leave-one-out cross-validation of the posterior sample, the counterpart of prediction() with the training
         points as sites: per point i the exact posterior predictive of y_i given the n - 1 OTHER points -- per draw

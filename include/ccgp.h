@@ -416,6 +416,73 @@ int ccgp_cgp_state_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, co
                               const double* params /* B x (2d+2) */, const int* set, int B, const int* skip /* B or NULL */,
                               double* out_val, double* out_beta, double* out_tau2, double* out_loo, int* status);
 
+/* ---- the Combined GP's and the single GP's prediction over many training sets of one shape ----------------------------------
+ * The sets forms of ccgp_predict_batch, ccgp_krige_predict_batch and ccgp_predict_summary: row b of params is a draw (a fitted
+ * model) of training set set[b] and is predicted at that set's own test sites, so that the prediction stage of a study is one
+ * call per model and shape instead of one per set.  Xs, ys, sigma2 (one per set), set as in ccgp_loglik_batch_sets; Xtests
+ * holds C blocks of m x d column-major, m common to the sets of a call; params, sigma2_row, var_form, probs and the NULLs of
+ * the outputs as in the single-set call.  out_mean / out_var: B x m column-major, [b + t B].  ccgp_predict_summary_sets: ys_at
+ * (may be NULL) holds C blocks of m; out holds C blocks of m x (4 + n_probs) column-major, block c summarising the rows with
+ * set[b] == c and status 0 in increasing b; a set with no such row is NaN throughout.
+ *   Bits.  Row b (for the summary: set c's block) has exactly the bits the single-set entry point returns on that set alone
+ *     with its rows in their order: they do not depend on C, B, the row's position, the order of `set`, the workspace limit
+ *     or what the handle ran before.
+ *   Failure.  As in the single-set calls: status[b] is the 1-based pivot and row b is NaN; a failed row is left out of its
+ *     set's summary; other rows and other sets are untouched; the return value is the number of failed rows.
+ *   Arguments.  C < 1, B < 1, m < 1, a set[b] outside 0 .. C-1, a NULL required pointer, a var_form or a sigma2_row that
+ *     ccgp_krige_predict_batch refuses, or probs that ccgp_predict_summary refuses return CCGP_EINVAL before anything is copied
+ *     or launched, outputs untouched.  A set no row refers to is legal.
+ *   Routes.  ONE set of launches per chunk of rows, for the rows of all sets, exactly where the single-set call takes the
+ *     kept-factor scheme: Gaussian family, n <= 104 and K <= 3 with the carves that fit (the sets instance keeps a design per
+ *     matrix on the 8 x 8 grid), CCGP_OPT_PREDICT_FACTOR on and the scratch to be had.  The rows are grouped by set and go up
+ *     with every set's design, responses and test sites in one span; a factor-keeping sets instance of the small-n evaluator,
+ *     the correlation kernel with a set per row and the site kernel serve a chunk -- as many rows as the kept-factor scratch
+ *     holds under the workspace limit, at least 64; a cut may fall inside a set --; the summary then runs its (site, set)
+ *     grids on the whole tables, which never leave the device; one span comes down.
+ *     Everything else -- 105 <= n <= 128, K > 3, n > 128, the option off, the Matern and spline families with or without
+ *     option 12 -- is grouped by set: the single-set launches run set after set on resident inputs with no host copy between
+ *     them, whatever route they take.  The kept-factor and extra-row schemes have the same bits, so the contract does not
+ *     depend on the route.  All inputs and tables of a call are staged at once: the workspace limit governs the kept-factor
+ *     scratch, not the staging.
+ * Host pointers only, blocking; ccgp_reserve does not cover the staging.  Not in this version: _dev variants, ccgp_multi
+ * wrappers, an R shim. */
+int ccgp_predict_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2 /* C */,
+                            int C, int K, const double* params /* B x P */, const int* set, int B,
+                            const double* Xtests /* C blocks m x d */, int m, double* out_mean, double* out_var /* B x m */,
+                            double* out_beta /* NULL ok */, int* status /* NULL ok */);
+int ccgp_krige_predict_batch_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C, int K,
+                                  const double* params, const int* set, int B,
+                                  const double* sigma2_row /* B; NULL ok for CCGP_VAR_UNBIASED */, int var_form,
+                                  const double* Xtests, int m, double* out_mean, double* out_var, double* out_beta,
+                                  double* out_q, int* status);
+int ccgp_predict_summary_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, const double* sigma2 /* C */,
+                              int C, int K, const double* params, const int* set, int B, const double* Xtests, int m,
+                              const double* probs, int n_probs, const double* ys_at /* C blocks of m, NULL ok */,
+                              double* out /* C blocks of m x (4 + n_probs) */, double* out_beta /* B */, int* status /* B */);
+
+/* ---- the CGP comparator's prediction over many training sets of one shape: the CGP columns of a study's tables in one call ----
+ * The sets form of ccgp_cgp_predict: row b of params is a fitted model of training set set[b] and is predicted at that set's
+ * own test sites.  Xs, ys, set as in ccgp_loglik_batch_sets; Xtests holds C blocks of m x d column-major, m common to the
+ * sets of a call (m may be 0: states only).  out: B blocks of m x 6 column-major, block b as ccgp_cgp_predict's out;
+ * out_state (may be NULL): B blocks of 3 n + 3 as ccgp_cgp_predict's out_state; status (may be NULL): B.
+ *   Bits.  Block b of out and of out_state has exactly the bits ccgp_cgp_predict returns for that row on set set[b] alone
+ *     with that set's test sites: they do not depend on C, B, the row's position, the order of `set`, where the workspace
+ *     limit or the 65535-workgroup grid cuts the call, or what the handle ran before.
+ *   Failure.  As in ccgp_cgp_predict, per row: status[b] is the 1-based pivot, blocks b of out and out_state are NaN; the
+ *     other rows are untouched; the return value is the number of failed rows.
+ *   Arguments.  C < 1, B < 0, m < 0, a set[b] outside 0 .. C-1 or a NULL required pointer (everything but out_state and
+ *     status; Xtests and out only where m > 0) return CCGP_EINVAL before anything is copied or launched, outputs untouched.
+ *     B == 0 returns CCGP_OK.  A set no row refers to is legal.  CCGP_EUNSUPPORTED exactly where ccgp_cgp_predict says it.
+ *   Route.  One state launch (every row keeps its factor, Q^-1 1 and temp on the device) and one site launch (row x site) per
+ *     chunk, for every supported shape; a chunk is as many rows as the workspace limit allows (n^2 + 7 n + 6 m + 2 d + 16
+ *     doubles each).
+ * Host pointers only, blocking; the sets and their test sites go up once per call, not once per chunk; ccgp_reserve does not
+ * cover the staging.  Not in this version: a _dev variant, a ccgp_multi wrapper, an R shim. */
+int ccgp_cgp_predict_sets(ccgp_handle* h, const double* Xs, int n, int d, const double* ys, int C,
+                          const double* params /* B x (2d+2) */, const int* set, int B,
+                          const double* Xtests /* C blocks m x d */, int m /* may be 0 */, double* out /* B blocks of m x 6 */,
+                          double* out_state /* B blocks of 3n+3, NULL ok */, int* status /* B, NULL ok */);
+
 /* ---- the ordinary-kriging fits on the device: every start in one launch (mlegp(...)$sig2, HX:759-760) ----------------------------
  * The quasi-Newton iteration of a start (box-constrained L-BFGS, memory 5, projected Armijo search: design._Start of the
  * Python package) restated from exactly rounded operations (csrc/fit_logic.h), so that host and device step a start to the

@@ -34,8 +34,11 @@ def parse(path):
 
 
 def demangle(names):
+    """demangled names; an argument type chosen by a switch, std::conditional<false, A, B>::type, is written as the type it
+    is (B), so a kernel that became a template over such a switch (cgp_predict_kernel<false>) matches the parent's plain one"""
     r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
-    return dict(zip(names, r.stdout.split("\n")))
+    cond = re.compile(r"std::conditional<(true|false), ([^<>,]+), ([^<>,]+)>::type")
+    return {k: cond.sub(lambda m: m.group(2 if m.group(1) == "true" else 3), v) for k, v in zip(names, r.stdout.split("\n"))}
 
 
 def main():
@@ -51,9 +54,24 @@ def main():
 
     def split(name):
         """(name without the appended arguments, True when they are not all `false`)"""
+        # a switch appended behind non-boolean template arguments (site_corr_kernel<1, false>, predict_summary_kernel<2, true,
+        # false>): the parent's instance where it is `false`, a new instance beside it where it is `true`
+        m = re.match(r"(.*?<[^>]*?), (true|false)(>.*)", name)
+        if m and "small_reg_kernel<" not in name and m.group(1) + m.group(3) in parent_names:
+            return m.group(1) + m.group(3), m.group(2) == "true"
+        # a plain kernel that became a template over one switch AND gained a last parameter for it (summary_valid_kernel<false>)
+        m = re.match(r"void (.*?)<(true|false)>(\(.*), [^,()]*(?:\([^()]*\))?[^,()]*\)$", name)
+        if m and m.group(1) + m.group(3) + ")" in parent_names:
+            return m.group(1) + m.group(3) + ")", m.group(2) == "true"
         m = re.match(r"void (.*?)<((?:true|false)(?:, (?:true|false))*)>(\(.*)", name)
         if m and m.group(1) + m.group(3) in parent_names:   # a plain kernel of the parent that became a template over switches
             return m.group(1) + m.group(3), "true" in m.group(2)
+        m = re.match(r"void (.*?)<true>(\(.*)", name)
+        if m and any(v.startswith("void " + m.group(1) + "<false>(") for v in dn.values()):
+            # the `true` sibling of a kernel that became a template over ONE switch, with an argument type of its own
+            # (cgp_predict_kernel<true>): new, shown beside the parent's plain kernel
+            base = [p for p in parent_names if p.startswith(m.group(1) + "(")]
+            return (base[0] if base else name), True
         m = re.match(r"(.*?<)((?:true|false)(?:, (?:true|false))+)(>.*)", name)
         if m and "small_reg_kernel<" not in name:   # a template over switches that gained some (cgp_state_kernel's GATED)
             a = m.group(2).split(", ")
