@@ -62,6 +62,15 @@ __device__ inline double cgp_wave_sum(double v) {
   return __shfl(v, 0, 64);
 }
 
+// exp(-dist) with a range select.  exp_cov_poly's reduction has no meaning once n no longer resolves x: dist = +Inf gives
+// fma(-ln2, -Inf, -Inf) = NaN, a finite dist beyond ~1e45 a garbage r whose polynomial overflows -- where exp(-dist) is 0 (base R:
+// exp(-Inf) = 0).  Such a dist is a rate that overflows against a coordinate difference: outside every fit's bounds, not outside
+// the raw entry points.  Beyond 750 exp_cov_poly's ldexp already returns 0 (2^-1082 p is under half the smallest subnormal), so
+// every argument that had the right value keeps its bits; a NaN dist fails the compare and stays NaN.  Here and not inside
+// exp_cov_poly: there the select cost the register-resident small-n evaluators 1.7 % (cfg2) and 4.8 % (cfg3) against a
+// run-to-run spread of 0.1 % (profiles/exp_poly_range_select.md).
+__device__ __forceinline__ double cgp_exp(double dist) { return dist > 750.0 ? 0.0 : exp_cov_poly(dist); }
+
 // sum_k rate_k (a_k - b_k)^2 from the direct differences, as Stand_PSI forms it (GV:96-99): exactly 0 for coincident points
 __device__ __forceinline__ double cgp_dist(const double* xs, int ldx, int i, int j, const double* rate, int d) {
   double s = 0.0;
@@ -153,12 +162,12 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
         } else if (i < n) {
           double g;
           if (rep == 0) {
-            g = exp_cov_poly(cgp_dist(xs, n0, i, j, th, d));
+            g = cgp_exp(cgp_dist(xs, n0, i, j, th, d));
             A[j + (size_t)i * ld] = g;
           } else {
             g = A[j + (size_t)i * ld];
           }
-          const double l = exp_cov_poly(cgp_dist(xs, n0, i, j, al, d));
+          const double l = cgp_exp(cgp_dist(xs, n0, i, j, al, d));
           v = fma(lam, (rs[i] * l) * rsj, g);
         } else {
           v = i == n ? yv[j] : 1.0;
@@ -242,7 +251,7 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
     for (int i = wave; i < n; i += 4) {
       double num = 0.0, den = 0.0;
       for (int j = lane; j < n; j += 64) {
-        const double gb = exp_cov_poly(cgp_dist(xs, n0, i, j, tb, d));
+        const double gb = cgp_exp(cgp_dist(xs, n0, i, j, tb, d));
         num = fma(gb, e2[j], num);
         den += gb;
       }
@@ -273,7 +282,7 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
       // predict.CGP's arithmetic for the held-out point (GV:191-197): e^2 and sf are the fourth pass's, s the final one
       double num = 0.0, den = 0.0;
       for (int j = lane; j < n; j += 64) {
-        const double gb = exp_cov_poly(cgp_dist_to(xs, n0, j, x0, tb, d));
+        const double gb = cgp_exp(cgp_dist_to(xs, n0, j, x0, tb, d));
         num = fma(gb, e2[j], num);
         den += gb;
       }
@@ -283,8 +292,8 @@ __global__ __launch_bounds__(256) void cgp_state_kernel(CgpStateArgs a) {
       const double lsv = lam * sqrt(v);
       double acc = 0.0;
       for (int j = lane; j < n; j += 64) {
-        const double g = exp_cov_poly(cgp_dist_to(xs, n0, j, x0, th, d));
-        const double l = exp_cov_poly(cgp_dist_to(xs, n0, j, x0, al, d));
+        const double g = cgp_exp(cgp_dist_to(xs, n0, j, x0, th, d));
+        const double l = cgp_exp(cgp_dist_to(xs, n0, j, x0, al, d));
         acc = fma(fma(lsv * rs[j], l, g), tv[j], acc);
       }
       loo = beta + cgp_wave_sum(acc);
@@ -380,9 +389,9 @@ __global__ __launch_bounds__(256) void cgp_predict_kernel(std::conditional_t<SET
     if (h1) { const double df = a.X[i1 + (size_t)k * n] - xt; dt1 = fma(df * df, thk, dt1); da1 = fma(df * df, alk, da1); }
   }
   // g, gbw, l against the n design points (GV:288-292)
-  const double g0 = h0 ? exp_cov_poly(dt0) : 0.0, g1 = h1 ? exp_cov_poly(dt1) : 0.0;
-  const double b0 = h0 ? exp_cov_poly(dt0 * bw) : 0.0, b1 = h1 ? exp_cov_poly(dt1 * bw) : 0.0;
-  const double l0 = h0 ? exp_cov_poly(da0) : 0.0, l1 = h1 ? exp_cov_poly(da1) : 0.0;
+  const double g0 = h0 ? cgp_exp(dt0) : 0.0, g1 = h1 ? cgp_exp(dt1) : 0.0;
+  const double b0 = h0 ? cgp_exp(dt0 * bw) : 0.0, b1 = h1 ? cgp_exp(dt1 * bw) : 0.0;
+  const double l0 = h0 ? cgp_exp(da0) : 0.0, l1 = h1 ? cgp_exp(da1) : 0.0;
   const double e20 = h0 ? K[kp.res2 + i0] : 0.0, e21 = h1 ? K[kp.res2 + i1] : 0.0;
   const double tp0 = h0 ? K[kp.temp + i0] : 0.0, tp1 = h1 ? K[kp.temp + i1] : 0.0;
   const double rs0 = h0 ? sqrt(K[kp.s + i0]) : 0.0, rs1 = h1 ? sqrt(K[kp.s + i1]) : 0.0;
