@@ -475,7 +475,12 @@ inline void once_per_device(unsigned long long& mask, F set_attributes) {
 // instructions per entry were exp).  Error: <= 1.3 ulp over 2 * 10^5 arguments in [-700, 0] against a 50-digit
 // exp (exact-FMA emulation; the library routine: < 1 ulp); tests hold 1e-13 on entries.
 // The argument is clamped at -1000 for the index computation only (the magic-number trick needs |n| < 2^31); r is
-// formed from the ORIGINAL x, so a NaN distance stays NaN, and v_ldexp_f64 underflows gradually to 0.
+// formed from the ORIGINAL x, so a NaN distance stays NaN, and v_ldexp_f64 underflows gradually to 0 -- down to dist = 750.
+// Beyond the floor the reduction no longer cancels: r ~ -dist, the quartic grows like dist^4 / 24 against the fixed 2^-1443 of
+// the clamped index, so the unselected value is 0 only up to dist ~ 1e28, then positive (2^95 -> 5e-322, 2^200 -> 1.4e-195)
+// and +Inf from ~1e78 and at dist = +Inf, where exp(-dist) is 0 (base R: exp(-Inf) = 0).  Hence the closing range select:
+// dist > 750 returns exactly 0 (2^-1082 is under half the smallest subnormal, so every argument that had the right value
+// keeps its bits), and a NaN dist fails the compare and stays NaN ("Beyond exp's range").
 static __device__ const unsigned long long kExpTableBits[kExpTableDoubles] = CCGP_EXP_TABLE_BITS;
 
 // cooperative copy of the table into LDS (call before a barrier that precedes the first exp_cov)
@@ -511,7 +516,7 @@ __device__ __forceinline__ double exp_cov(double dist, const double* tab) {
   const double q = r * p;                                               // e^r - 1
   double v;
   asm("v_fma_f64 %0, %1, %2, %1" : "=v"(v) : "v"(tj), "v"(q));         // T + T (e^r - 1)
-  return __builtin_amdgcn_ldexp(v, n >> 8);
+  return dist > 750.0 ? 0.0 : __builtin_amdgcn_ldexp(v, n >> 8);
 #endif
 }
 
@@ -594,6 +599,28 @@ __device__ __forceinline__ double exp_small(double dist, const double* tab) {
 #endif
 }
 
+// exp(-dist) with a range select.  exp_cov_poly's reduction has no meaning once n no longer resolves x: dist = +Inf gives
+// fma(-ln2, -Inf, -Inf) = NaN, a finite dist beyond ~1e45 a garbage r whose polynomial overflows -- where exp(-dist) is 0 (base R:
+// exp(-Inf) = 0).  Such a dist is a rate that overflows against a coordinate difference: outside every fit's bounds, not outside
+// the raw entry points.  Beyond 750 exp_cov_poly's ldexp already returns 0 (2^-1082 p is under half the smallest subnormal), so
+// every argument that had the right value keeps its bits; a NaN dist fails the compare and stays NaN.  Here and not inside
+// exp_cov_poly: there the select cost the register-resident small-n evaluators 1.7 % (cfg2) and 4.8 % (cfg3) against a
+// run-to-run spread of 0.1 % (profiles/exp_poly_range_select.md).  Callers: the CGP kernels (cgp.hip) and every CROSS-correlation
+// vector of the small-n evaluators (test site x training points: small_reg_kernel's extra rows, site_corr_kernel) -- a cross
+// vector passes no pivot test, so a wrong exponential there would reach a mean and a variance with status 0.  The matrix
+// generation loops of small_reg.hip / small.hip call exp_small unselected; their domain is stated in include/ccgp.h.
+template <bool SC = false>
+__device__ __forceinline__ double exp_poly_ranged(double dist) { return dist > 750.0 ? 0.0 : exp_cov_poly<SC>(dist); }
+template <bool SC = false>
+__device__ __forceinline__ double exp_small_ranged(double dist, const double* tab) {
+#if CCGP_SMALL_EXP_TABLE
+  return exp_cov(dist, tab);   // selects itself
+#else
+  (void)tab;
+  return exp_poly_ranged<SC>(dist);
+#endif
+}
+
 // ---- correlation families ---------------------------------------------------------------------------
 // Every kernel forms the weighted squared distance  dist = sum_k rate_k (x_ik - x_jk)^2  and then the correlation:
 // the Gaussian family in the reference's expanded form, the 1-D families from the direct difference x_i - x_j, as
@@ -632,6 +659,10 @@ __device__ __forceinline__ double spline_corr(double u2) {
 __device__ inline double matern_corr(const KernelFamily& f, double z2) {
   if (!(z2 > 9e-20)) return z2 == z2 ? 1.0 : z2;
   if (z2 <= 1e-10 && f.nu >= 1.5) return 1.0 - z2 / (4.0 * (f.nu - 1.0));
+  // z > 1e6: exactly 0, as the rule's last factor exp(nu log z - z) already is there (nu log z - z < -745 for every nu below
+  // 7e4) -- stated ahead of the rule because z2 = +Inf (z beyond 1.3e154, whose square overflows) makes the step 0 and the
+  // first term's exponent Inf * 0 = NaN, where base R's z^nu K_nu(z) is 0 (tests/test_gpu_far_arguments.py)
+  if (z2 > 1e12) return 0.0;
   const double z = sqrt(z2);
   const double hs = 0.15 / fmax(1.0, sqrt(z));
   double s = 0.5;
@@ -670,6 +701,7 @@ __device__ __forceinline__ double spline_corr_grad(double u2, double theta, doub
 // tests/test_gpu_family_fused_grad.py (this code) against a 40-digit evaluation.
 __device__ inline double matern_corr_grad(const KernelFamily& f, double z2, double theta, double* dth) {
   if (!(z2 > 9e-20)) { *dth = z2 == z2 ? 0.0 : z2; return z2 == z2 ? 1.0 : z2; }
+  if (z2 > 1e12) { *dth = 0.0; return 0.0; }   // matern_corr's early return: both exp() factors are 0 beyond z = 1e6, and z2 = +Inf gave NaN
   const bool series = z2 <= 1e-10 && f.nu >= 1.5;
   const double z = sqrt(z2);
   const double hs = 0.15 / fmax(1.0, sqrt(z));

@@ -62,14 +62,8 @@ __device__ inline double cgp_wave_sum(double v) {
   return __shfl(v, 0, 64);
 }
 
-// exp(-dist) with a range select.  exp_cov_poly's reduction has no meaning once n no longer resolves x: dist = +Inf gives
-// fma(-ln2, -Inf, -Inf) = NaN, a finite dist beyond ~1e45 a garbage r whose polynomial overflows -- where exp(-dist) is 0 (base R:
-// exp(-Inf) = 0).  Such a dist is a rate that overflows against a coordinate difference: outside every fit's bounds, not outside
-// the raw entry points.  Beyond 750 exp_cov_poly's ldexp already returns 0 (2^-1082 p is under half the smallest subnormal), so
-// every argument that had the right value keeps its bits; a NaN dist fails the compare and stays NaN.  Here and not inside
-// exp_cov_poly: there the select cost the register-resident small-n evaluators 1.7 % (cfg2) and 4.8 % (cfg3) against a
-// run-to-run spread of 0.1 % (profiles/exp_poly_range_select.md).
-__device__ __forceinline__ double cgp_exp(double dist) { return dist > 750.0 ? 0.0 : exp_cov_poly(dist); }
+// every exponential of this file: exp(-dist) with the range select (ccgp_internal.h exp_poly_ranged), exactly 0 beyond exp's range
+__device__ __forceinline__ double cgp_exp(double dist) { return exp_poly_ranged(dist); }
 
 // sum_k rate_k (a_k - b_k)^2 from the direct differences, as Stand_PSI forms it (GV:96-99): exactly 0 for coincident points
 __device__ __forceinline__ double cgp_dist(const double* xs, int ldx, int i, int j, const double* rate, int d) {

@@ -541,6 +541,15 @@ chain_next:
       }
     }
   }
+  // The exp of a matrix entry.  The extra-row prediction instances (NE > 1, no INV) take it through the range select: their
+  // 12 x 11 lattice at n = 128 reaches exponents of 2^148.8, beyond the unselected polynomial's domain (below 2^148.47: include/ccgp.h), where rates of
+  // 2^140 must still give R = I (tests/test_gpu_far_arguments.py).  Every other instance -- the likelihood, gradient, profile,
+  // sets, chain and fit instances that the select was measured on and rejected for (profiles/exp_poly_range_select.md) -- keeps
+  // exp_small as it was: the constexpr folds, and their code is the parent's.
+  auto gen_exp = [&](double dist) {
+    if constexpr (NE > 1 && !INV) return exp_small_ranged<!FULL>(dist, etab);
+    else return exp_small<!FULL>(dist, etab);
+  };
   for (int q = 0; q < (FAM ? 0 : K); ++q) {
     const double wq = w2[q];
 #pragma unroll
@@ -584,13 +593,13 @@ chain_next:
             // every (r, c) is a matrix entry; entries above the diagonal of the diagonal blocks (aa == bb, ty < tx)
             // are computed too and zeroed below -- cheaper than a divergent branch
             const double dist = (us[q * NP + r] + us[q * NP + c]) + (-2.0 * sdot[aa][j]);
-            M[aa][bb] = fma(wq, exp_small<!FULL>(dist, etab), M[aa][bb]);
+            M[aa][bb] = fma(wq, gen_exp(dist), M[aa][bb]);
             // pin the finished entry here: without the branch the compiler sinks the tail of every exp (ldexp + mix)
             // to the end of the component loop and keeps two temporaries per entry alive until then (580 B of scratch)
             asm volatile("" : "+v"(M[aa][bb]));
           } else if (r < n && c < n && r >= c) {
             const double dist = (us[q * NP + r] + us[q * NP + c]) + (-2.0 * sdot[aa][j]);
-            M[aa][bb] = fma(wq, exp_small<!FULL>(dist, etab), M[aa][bb]);
+            M[aa][bb] = fma(wq, gen_exp(dist), M[aa][bb]);
           }
         }
       }
@@ -620,7 +629,7 @@ chain_next:
             double sd = 0.0;
             for (int k = 0; k < d; ++k) sd = fma(xs[k * n + c] * th[q * d + k], xt[k * XR + ridx], sd);
             const double dist = (ut[q * XR + ridx] - 2.0 * sd) + us[q * NP + c];
-            acc = fma(w2[q], exp_small<!FULL>(dist, etab), acc);
+            acc = fma(w2[q], exp_small_ranged<!FULL>(dist, etab), acc);   // a cross vector passes no pivot test
           }
           v = acc / sw;
         }
@@ -1424,7 +1433,7 @@ __global__ __launch_bounds__(256, 4) void site_corr_kernel(SiteArgs a) {
 #pragma unroll
         for (int q = 0; q < KC; ++q) {
           const double dist = (ut[q] - 2.0 * sd[q][j]) + us[q * npf + i0 + j];
-          acc = fma(w2[q], exp_small<true>(dist, nullptr), acc);
+          acc = fma(w2[q], exp_small_ranged<true>(dist, nullptr), acc);   // a cross vector passes no pivot test
         }
         rs[(size_t)(i0 + j) * 64] = acc / sw;
       }

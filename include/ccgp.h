@@ -29,6 +29,21 @@
  *     the batch whose factorisation met a non-positive pivot.  Per-evaluation
  *     status[b] = 0 or 1-based index of the first bad pivot; such an evaluation
  *     returns NaN -- the reference's NA from try(solve(R)) (HX:454-455).
+ *   - domain of the rates: base R has exp(-x) = 0 for every x beyond 745, +Inf
+ *     included.  The raw correlation entry points, everything computed on the blocked
+ *     sweep (n > 128 and the n <= 128 shapes routed there) and every cross-correlation
+ *     vector (test site x training points) on every route return exactly 0 for such an
+ *     exponent at ANY finite magnitude and at +Inf (NaN stays NaN), and so does the
+ *     extra-row prediction of the register-resident evaluator (n > 104, K > 3 or
+ *     CCGP_OPT_PREDICT_FACTOR = 0), matrix and cross rows alike.  The matrix
+ *     generation of the other register- and LDS-resident n <= 128 evaluators is exact in
+ *     that sense for exponents below 2^148.47 (3.3e44), a worst-case bound: its reduced
+ *     argument is the rounding residue of n = rint(x log2 e), up to ulp(n) ln 2 / 2, and
+ *     the degree-11 polynomial overflows from 2^95.4, i.e. possibly from n = 2^149; beyond
+ *     that -- rates of 2^140 on an integer lattice wider than 11 x 10 -- an evaluation is
+ *     either still right or FAILS under the contract above (status = a pivot index,
+ *     NaN outputs, counted in the return value) -- never a finite wrong value, never
+ *     a non-finite value with status 0.  Such rates lie outside every fit's bounds.
  *   - "_dev" entry points take DEVICE pointers and only enqueue work on the
  *     handle's stream (no allocation, no synchronisation once the workspace has
  *     been sized by ccgp_reserve); the others take HOST pointers and block.

@@ -14,7 +14,8 @@ sum w^2 and the normalisation are powers of two.
 
 Why exact: every product and sum of the expanded exponent u_a + u_b - 2 sum_k theta_k x_ak x_bk is an integer below 2^53,
 so it is the same number in any order.  Distinct points have exponent <= -2048 -> exp gives exactly 0 (the device's
-polynomial and table exp underflow gradually to 0 there, as libm does); coincident points have exponent exactly 0 ->
+polynomial and table exp have underflowed to 0 there, as libm has; how far beyond that each stays 0 is what the FAR
+magnitudes below are for); coincident points have exponent exactly 0 ->
 exactly 1.  R is the identity plus ones at the coincident pairs, to the bit.
 
 So a draw that zeroes the separators J fails with a pivot of exactly 0 at 1-based index min_{j in J} (p_j + 1) -- under
@@ -36,6 +37,15 @@ from oracle import ccgp_oracle as orc
 
 EPS = float(np.finfo(np.float64).eps)
 THETA = (2048.0, 4096.0)
+# Magnitudes beyond exp's range (tests/test_gpu_far_arguments.py, tests/test_far_arguments_host.py): component rates
+# (2^k, 2^(k+1)) in place of THETA.  k = 95: the first argument at which the unselected table exp is not 0; 140: the last
+# at which the polynomial exp is still right; 200: the polynomial is +-Inf, the table 1e-195; 260: the table is +Inf; 1000:
+# the largest that overflows nothing (coordinates <= 18, so u <= 2^1000 * 650 < 2^1010).  The exactness argument below carries
+# over: each term of a component's expanded exponent is an integer below 2^53 times ONE power of two, so it is the same
+# number in every order.  One magnitude per component: 2^k and 2^11 inside a component would not cancel in u_i + u_i - 2 s_ii.
+FAR_K = (95, 140, 200, 260, 1000)
+FAR = [(2.0 ** k, 2.0 ** (k + 1)) for k in FAR_K]
+SLOW = 2.0 ** -4          # the dyadic rate of the two-scale mix's healthy component: exponents are multiples of 1/16
 
 
 def mode1_sigma2(K):
@@ -69,12 +79,13 @@ class ExactDesign:
         self.y = np.sin(0.7 * i) + 0.3 * np.cos(2.1 * i) + 0.5
 
     # ---- draws ------------------------------------------------------------------------------------------------------
-    def row(self, K, zero=()):
-        """One parameter row (w_1..w_K, theta_1,1..d, ..., theta_K,1..d) that zeroes the separators in `zero`."""
+    def row(self, K, zero=(), theta=THETA):
+        """One parameter row (w_1..w_K, theta_1,1..d, ..., theta_K,1..d) that zeroes the separators in `zero`; theta = (a, b):
+        the rate of the even and of the odd components (default THETA; FAR: beyond exp's range)."""
         assert K in (1, 2, 4, 8)
         th = np.empty((K, self.d))
         for c in range(K):
-            th[c] = THETA[c % 2]
+            th[c] = theta[c % 2]
             for j in zero:
                 th[c, 2 + j] = 0.0
         return np.concatenate([np.ones(K), th.ravel()])
@@ -82,9 +93,9 @@ class ExactDesign:
     def expected(self, zero):
         return min((self.seps[j] for j in zero), default=0)
 
-    def draws(self, K, zero_sets):
+    def draws(self, K, zero_sets, theta=THETA):
         """(rows[B, K + K d], expected status[B]) for a list of separator subsets."""
-        rows = np.stack([self.row(K, z) for z in zero_sets])
+        rows = np.stack([self.row(K, z, theta) for z in zero_sets])
         return rows, np.array([self.expected(z) for z in zero_sets], dtype=np.int32)
 
     def mixed(self):
@@ -128,7 +139,94 @@ class ExactDesign:
         return Xt, on
 
 
-def duplicate_designs(n=20):
+class TwoScaleDesign:
+    """K = 2, unit weights, on the integer lattice of ExactDesign (no separators; n_pad all-zero dimensions): component 0 has a
+    far rate (or THETA[0], its stand-in) on every dimension, so R_0 = I to the bit; component 1 has the dyadic rate SLOW =
+    2^-4, whose exponents are multiples of 1/16 below 2^53 / 16 and exact in every order.  Base R's matrix is (I + R2) / 2 at
+    every far magnitude: non-trivial, eigenvalues in [1/2, (1 + n) / 2].  rows(): the stand-in first, then one row per
+    FAR magnitude -- every row of a call on them must equal row 0."""
+
+    def __init__(self, n, n_pad=0):
+        self.n, self.d, self.K = int(n), 2 + int(n_pad), 2
+        self.W = int(math.ceil(math.sqrt(n)))
+        i = np.arange(n)
+        self.X = np.zeros((n, self.d))
+        self.X[:, 0], self.X[:, 1] = i % self.W, i // self.W
+        self.y = np.sin(0.7 * i) + 0.3 * np.cos(2.1 * i) + 0.5
+
+    def row(self, a=THETA[0]):
+        return np.concatenate([np.ones(2), np.full(self.d, float(a)), np.full(self.d, SLOW)])
+
+    def rows(self):
+        return np.stack([self.row()] + [self.row(a) for a, _ in FAR])
+
+    def sites(self, m):
+        """Integer points (exact exponents in both components): even columns on a training point, odd ones off the lattice."""
+        Xt = np.zeros((m, self.d))
+        on = np.full(m, -1)
+        for t in range(m):
+            if t % 2 == 0:
+                on[t] = (5 + 11 * t) % self.n
+                Xt[t] = self.X[on[t]]
+            else:
+                Xt[t, 0], Xt[t, 1] = -(1.0 + t), -1.0
+        return Xt, on
+
+    def matrix(self, a=THETA[0]):
+        """The fp64 oracle's normalised mixed matrix of row(a)."""
+        return orc.mixed_corr_matrix_general(self.X, *orc.unpack_params(self.row(a), 2, self.d))
+
+    def guard(self):
+        """The oracle's matrix is (I + R2) / 2 to the bit at every magnitude, and well conditioned (returns cond1)."""
+        R2 = orc.corr_matrix(self.X, np.full(self.d, SLOW))
+        want = (np.eye(self.n) + R2) / 2.0
+        for a in [THETA[0]] + [a for a, _ in FAR]:
+            assert np.array_equal(self.matrix(a), want), a
+        return orc.cond1(want, np.linalg.inv(want))
+
+
+class FarSiteDesign:
+    """A far test site on a VALID factor.  One active dimension (the other d - 1 are all-zero padding), K = 1, rate 2^k on
+    every dimension, training coordinates i 2^-(k // 2): theta x_i^2 = s i^2 and theta x_i x_j = s i j with s = 1 (k even) or
+    2 (k odd), so the training exponents s (i - j)^2 are exact integers and R = exp(-s (i - j)^2) is the same well-conditioned
+    matrix at every k.  The sites sit at coordinates -1, -2, ...: their exponent 2^k (t + x_i)^2 >= 2^k under any rounding
+    (it is not exact and need not be), so r = 0, mean = beta and var = sigma2 (1 + 1 / 1'R^-1 1).  (-1 and not +1: at the
+    stand-ins k = 11, 12 the training coordinates i / 32, i / 64 of n = 108 points reach +1 themselves.)  stand_in(): the
+    design of the same parity at k = 11 (rate 2048) or 12 (rate 4096)."""
+
+    def __init__(self, n, k, d=1):
+        self.n, self.k, self.d, self.K = int(n), int(k), int(d), 1
+        self.theta = 2.0 ** k
+        i = np.arange(n)
+        self.X = np.zeros((n, d))
+        self.X[:, 0] = i * 2.0 ** -(k // 2)
+        self.y = np.sin(0.7 * i) + 0.3 * np.cos(2.1 * i) + 0.5
+        s = self.theta * self.X[1, 0] ** 2 if n > 1 else 1.0
+        assert s in (1.0, 2.0) and np.array_equal(self.theta * self.X[:, 0] ** 2, s * i.astype(np.float64) ** 2)
+        self.s = s
+
+    def stand_in(self):
+        return FarSiteDesign(self.n, 11 + (self.k + 1) % 2, self.d)
+
+    def row(self):
+        return np.concatenate([np.ones(1), np.full(self.d, self.theta)])
+
+    def sites(self, m):
+        Xt = np.zeros((m, self.d))
+        Xt[:, 0] = -(1.0 + np.arange(m))
+        return Xt
+
+    def guard(self):
+        """The oracle's training matrix is exp(-s (i - j)^2) to the bit, every cross entry is 0; returns cond1."""
+        i = np.arange(self.n, dtype=np.float64)
+        want = np.exp(-self.s * (i[:, None] - i[None, :]) ** 2)
+        assert np.array_equal(orc.corr_matrix(self.X, np.full(self.d, self.theta)), want)
+        for x in self.sites(3):
+            assert not orc.corr_vec(x, self.X, np.full(self.d, self.theta)).any()
+        return orc.cond1(want, np.linalg.inv(want))
+
+
+def duplicate_designs(n=20, theta=THETA):
     """B = 5 candidate designs of n points in d = 2 that share one parameter row: TRUE duplicates instead of separators
     (here the designs differ and the row is shared).  Duplicates at 1-based rows 2 / none / n / 2 again (the first design
     twice) / both 2 and n.  Returns (designs[5, n, 2], K, row, expected status)."""
@@ -138,7 +236,7 @@ def duplicate_designs(n=20):
     dup2[1] = dup2[0]
     dupn[n - 1] = dupn[n - 2]
     both[1], both[n - 1] = both[0], both[n - 2]
-    row = np.concatenate([np.ones(2), np.full(2, THETA[0]), np.full(2, THETA[1])])
+    row = np.concatenate([np.ones(2), np.full(2, theta[0]), np.full(2, theta[1])])
     return np.stack([dup2, base, dupn, dup2.copy(), both]), 2, row, np.array([2, 0, n, 2, 2], dtype=np.int32)
 
 
